@@ -2,6 +2,7 @@
 """bench.py -- throughput of the MI355X LZ4 block codec on BASELINE.json's configs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--dist text|...]
+                    [--dump-outputs DIR]
 
 Default workload = BASELINE.json configs[1]: 65 536 independent 64 KiB blocks (4 GiB),
 compressDefault, then decompressSafe of the result (the metric is "block
@@ -17,6 +18,12 @@ The JSON line also carries
                 against the 8 TB/s HBM3E peak;
   cpu_baseline  oracle/ (C restatement of the reference, "port") timed on this box's host
                 cores on a bounded sample of the same blocks (rank 0, N == 1 only).
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's shard) as DIR/<name>.npy, float32
+or float64, 64 MB at most: the size every call returned, and the bytes of a fixed, seeded sample of the blocks
+(for cfg5, of frame positions).  Bytes at or past a block's returned length are written as 0; the call leaves them
+undefined.  The inputs depend only on the arguments, so two builds run with the same arguments can be compared file by
+file.
 """
 import argparse
 import ctypes as C
@@ -34,10 +41,36 @@ import torch
 
 HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 GIB = float(1 << 30)
+DUMP_LIMIT = 64 * 10**6        # --dump-outputs: bytes of array data at most
+DUMP_SAMPLE = 4 << 20          # --dump-outputs: uncompressed bytes of the sampled blocks (16 MiB as float32)
+DUMP_SEED = 20261015
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def sample_blocks(nblocks, block_size):
+    """The fixed, seeded choice of blocks whose bytes --dump-outputs writes (sorted block indices)."""
+    n = max(1, min(nblocks, DUMP_SAMPLE // block_size))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(nblocks, n, replace=False))
+
+
+def valid_bytes(rows, lengths):
+    """rows [n, width] uint8, lengths [n] as returned by the calls (negative = error code, no bytes) -> float32 on the
+    host, with the undefined bytes at or past each length set to 0."""
+    keep = torch.arange(rows.shape[1], device=rows.device).unsqueeze(0) < lengths.clamp(min=0).unsqueeze(1)
+    return torch.where(keep, rows, torch.zeros_like(rows)).cpu().numpy().astype(np.float32)
+
+
+def write_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("[rank 0] wrote %d outputs (%.1f MB) to %s" % (len(arrays), total / 1e6, path))
 
 
 def make_device_blocks(dist, nblocks, block_size, dev, seed):
@@ -185,7 +218,10 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-sample-mib", type=int, default=0)
     ap.add_argument("--level", type=int, default=9, help="compressHC level for cfg4 (2..12)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks here.  Nothing above has touched the GPU
@@ -247,7 +283,7 @@ def main():
         out = torch.empty(total_n, dtype=torch.uint8, device=dev)
         L = zl.lib()
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        fsize = [0]
+        fsize, dlen = [0], [0]
 
         # One logical frame of world x nblocks blocks: rank r holds blocks [r*nblocks, (r+1)*nblocks) (shard.shard_range)
         # and produces / decodes its own segment of the frame; rank 0's segment starts with the frame header, the last
@@ -264,6 +300,17 @@ def main():
             r = L.zlz4f_decompress_frame_segment_device(st, C.c_void_p(frame.data_ptr()), fsize[0], C.c_void_p(out.data_ptr()),
                                                         total_n, C.byref(prefs), seg_flags)
             assert r == total_n, "decompressFrame failed: %s" % zl.error_name(r)
+            dlen[0] = r
+
+        def outputs():
+            sel = sample_blocks(nblocks, block)
+            pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, fsize[0], min(fsize[0], DUMP_SAMPLE // 2)))
+            return {"frame_size": np.array([fsize[0]], dtype=np.float64),
+                    "frame_byte_index": pos.astype(np.float64),
+                    "frame_bytes": frame[torch.from_numpy(pos).to(dev)].cpu().numpy().astype(np.float32),
+                    "decompressed_size": np.array([dlen[0]], dtype=np.float64),
+                    "block_index": sel.astype(np.float64),
+                    "decompressed_bytes": out.view(nblocks, block)[torch.from_numpy(sel).to(dev)].cpu().numpy().astype(np.float32)}
 
         do_compress()
         do_decompress()
@@ -309,6 +356,13 @@ def main():
         def do_decompress():
             zl.batch_decompress_safe(comp, slot_off, clen32, out, in_off, in_len, dsize)
 
+        def outputs():
+            sel = sample_blocks(nblocks, block)
+            s = torch.from_numpy(sel).to(dev)
+            return {"block_index": sel.astype(np.float64),
+                    "decompressed_size": dsize.cpu().numpy().astype(np.float64),
+                    "decompressed_bytes": valid_bytes(out[s], dsize[s])}
+
         do_decompress()
         torch.cuda.synchronize()
         assert bool((dsize == block).all()), "decompress size mismatch"
@@ -347,6 +401,15 @@ def main():
 
         def do_decompress():
             zl.batch_decompress_safe(comp, slot_off, clen[0], out, in_off, in_len, dsize)
+
+        def outputs():
+            sel = sample_blocks(nblocks, block)
+            s = torch.from_numpy(sel).to(dev)
+            return {"block_index": sel.astype(np.float64),
+                    "compressed_size": csize.cpu().numpy().astype(np.float64),
+                    "compressed_bytes": valid_bytes(comp.view(nblocks, slot)[s], csize[s]),
+                    "decompressed_size": dsize.cpu().numpy().astype(np.float64),
+                    "decompressed_bytes": valid_bytes(out[s], dsize[s])}
 
         # untimed first pass: produces the compressed batch and checks the round trip
         do_compress()
@@ -399,6 +462,8 @@ def main():
         elapsed = float(t.item())
     tc_ms = float(np.mean([ev[k][0].elapsed_time(ev[k][1]) for k in range(args.steps)]))
     td_ms = float(np.mean([ev[k][1].elapsed_time(ev[k][2]) for k in range(args.steps)]))
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, outputs())
 
     if rank == 0:
         value = world * total_n * args.steps / elapsed / GIB
