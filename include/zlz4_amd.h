@@ -127,6 +127,19 @@ int64_t zlz4_decompress_safe(const uint8_t *src, size_t src_len, uint8_t *dst, s
 int64_t zlz4_decompress_safe_partial(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                      size_t target_output_size);
 
+/* replaces lz4.decompressSafeUsingDict, src/lz4.zig:960-962: decompressGeneric (:89-251) with the external dictionary
+ * `dict` in front of dst.  A match whose offset reaches in front of dst reads dict ++ dst (:181-225); CorruptedData iff
+ * offset > op + dict_len (:189-192), checked after the match's OutputTooSmall (:174).  An empty dictionary (dict_len == 0,
+ * dict may be NULL) gives exactly zlz4_decompress_safe.  Only the last min(dict_len, 65536) bytes are staged (offsets
+ * are <= 65535).  dict must not overlap dst.  dict == NULL with dict_len > 0 -> InvalidState. */
+int64_t zlz4_decompress_safe_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                        const uint8_t *dict, size_t dict_len);
+
+/* replaces lz4.decompressSafePartialUsingDict, src/lz4.zig:967-969: the same with target_output_size as the output
+ * limit (:99, :109), as zlz4_decompress_safe_partial. */
+int64_t zlz4_decompress_safe_partial_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                                size_t target_output_size, const uint8_t *dict, size_t dict_len);
+
 /* replaces lz4.sizeofState, src/lz4.zig:524-526 (= @sizeOf(HashTable) = 16384) */
 size_t  zlz4_sizeof_state(void);
 
@@ -166,6 +179,16 @@ int32_t zlz4_batch_decompress_safe(void *stream,
                                    const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
                                    uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                    int64_t *d_result, uint32_t nblocks);
+
+/* decompressSafeUsingDict (src/lz4.zig:960-962) per block: block i reads the dictionary d_dict + d_dict_off[i]
+ * (d_dict_len[i] bytes, any length; only its last 65536 bytes can be reached).  A dictionary shared by every block is
+ * one copy with the same offset for all.  Dictionaries are read-only and must not overlap any output slot.  Same
+ * contract as zlz4_batch_decompress_safe: device pointers, asynchronous, no allocation (graph-capturable). */
+int32_t zlz4_batch_decompress_safe_using_dict(void *stream,
+                                              const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                              uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                              const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                              const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks);
 
 /* workspace for the HC path: bytes needed for `nblocks` blocks of at most `max_in_len` bytes (448 KiB per 64 KiB block
  * up to 8192 blocks = 3.5 GiB, about 6 GiB at most for large blocks; longer batches are processed in rounds) */

@@ -62,11 +62,14 @@ SYMBOLS = {
     "zlz4_compress_hc_ext_state": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _I32]),
     "zlz4_decompress_safe": (_I64, [_VP, _SZ, _VP, _SZ]),
     "zlz4_decompress_safe_partial": (_I64, [_VP, _SZ, _VP, _SZ, _SZ]),
+    "zlz4_decompress_safe_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ]),
+    "zlz4_decompress_safe_partial_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _SZ, _VP, _SZ]),
     "zlz4_sizeof_state": (_SZ, []),
     "zlz4_compress_fast_ext_state": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _U32]),
     "zlz4_compress_dest_size": (_I64, [_VP, _VP, _SZ, C.POINTER(C.c_size_t)]),
     "zlz4_batch_compress_fast": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_decompress_safe": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_batch_decompress_safe_using_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_compress_hc_workspace": (_SZ, [_U32, _U32]),
     "zlz4_batch_compress_hc": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _I32, _VP, _SZ]),
     "zlz4_batch_verify": (_I64, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
@@ -187,6 +190,18 @@ def decompressSafePartial(src, dst_cap, target_output_size):
     return _run(lib().zlz4_decompress_safe_partial, src, dst_cap, target_output_size)
 
 
+def decompressSafeUsingDict(src, dst_cap, dict):
+    """lz4.decompressSafeUsingDict(src, dst, dict), src/lz4.zig:960-962; dst_cap == dst.len."""
+    dk, dn = _in(dict)
+    return _run(lib().zlz4_decompress_safe_using_dict, src, dst_cap, C.addressof(dk), dn)
+
+
+def decompressSafePartialUsingDict(src, dst_cap, target_output_size, dict):
+    """lz4.decompressSafePartialUsingDict(src, dst, targetOutputSize, dict), src/lz4.zig:967-969."""
+    dk, dn = _in(dict)
+    return _run(lib().zlz4_decompress_safe_partial_using_dict, src, dst_cap, target_output_size, C.addressof(dk), dn)
+
+
 def sizeofState():
     """lz4.sizeofState, src/lz4.zig:524-526."""
     return lib().zlz4_sizeof_state()
@@ -279,6 +294,14 @@ def batch_compress_fast(d_in, in_off, in_len, d_out, out_off, out_cap, result, m
 def batch_decompress_safe(d_in, in_off, in_len, d_out, out_off, out_cap, result):
     _check(lib().zlz4_batch_decompress_safe(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
                                             _ptr(out_off), _ptr(out_cap), _ptr(result), in_len.numel()))
+
+
+def batch_decompress_safe_using_dict(d_in, in_off, in_len, d_out, out_off, out_cap, d_dict, dict_off, dict_len, result):
+    """zlz4_batch_decompress_safe_using_dict: as batch_decompress_safe, block i with the dictionary
+    d_dict[dict_off[i] .. + dict_len[i]) (int64 offsets / int32 lengths; a shared dictionary = equal offsets)."""
+    _check(lib().zlz4_batch_decompress_safe_using_dict(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
+                                                       _ptr(out_off), _ptr(out_cap), _ptr(d_dict), _ptr(dict_off),
+                                                       _ptr(dict_len), _ptr(result), in_len.numel()))
 
 
 def batch_compress_hc_workspace(nblocks, max_in_len):

@@ -44,6 +44,15 @@ inline Result decompressSafe(const std::uint8_t *src, std::size_t n, std::uint8_
 inline Result decompressSafePartial(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap, std::size_t target) {
     return wrap(zlz4_decompress_safe_partial(src, n, dst, cap, target));
 }
+// lz4.decompressSafeUsingDict / decompressSafePartialUsingDict, src/lz4.zig:960-969 (dict must not overlap dst)
+inline Result decompressSafeUsingDict(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                                      const std::uint8_t *dict, std::size_t dict_len) {
+    return wrap(zlz4_decompress_safe_using_dict(src, n, dst, cap, dict, dict_len));
+}
+inline Result decompressSafePartialUsingDict(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                                             std::size_t target, const std::uint8_t *dict, std::size_t dict_len) {
+    return wrap(zlz4_decompress_safe_partial_using_dict(src, n, dst, cap, target, dict, dict_len));
+}
 // lz4.sizeofState / compressFastExtState / compressDestSize, src/lz4.zig:524-616
 inline std::size_t sizeofState() { return zlz4_sizeof_state(); }
 inline Result compressFastExtState(void *state, std::size_t state_len, const std::uint8_t *src, std::size_t n,
@@ -78,6 +87,14 @@ inline Result compressFastBatch(void *stream, const Blocks &b, std::uint32_t max
 }
 inline Result decompressSafeBatch(void *stream, const Blocks &b) {
     return wrap(zlz4_batch_decompress_safe(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks));
+}
+// per-block dictionaries: block i reads dict + dict_off[i] (dict_len[i] bytes); shared = the same offset everywhere
+struct DictBlocks {
+    const std::uint8_t *dict; const std::uint64_t *dict_off; const std::uint32_t *dict_len;
+};
+inline Result decompressSafeUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d) {
+    return wrap(zlz4_batch_decompress_safe_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
+                                                      d.dict_off, d.dict_len, b.result, b.nblocks));
 }
 inline std::size_t compressHCWorkspace(std::uint32_t nblocks, std::uint32_t max_in_len) {
     return zlz4_batch_compress_hc_workspace(nblocks, max_in_len);

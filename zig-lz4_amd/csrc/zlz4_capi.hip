@@ -17,6 +17,9 @@
 // kernel launchers (one per .hip file)
 extern "C" int zlz4_launch_decompress_safe(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
                                            const uint64_t *, const uint32_t *, int64_t *, uint32_t);
+extern "C" int zlz4_launch_decompress_safe_using_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
+                                                      uint8_t *, const uint64_t *, const uint32_t *, int64_t *, uint32_t,
+                                                      const uint8_t *, const uint64_t *, const uint32_t *);
 extern "C" int zlz4_launch_compress_fast(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
                                          const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
 extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
@@ -49,11 +52,12 @@ bool device_ok() {
 using zlz4host::DevBuf;
 using zlz4host::DeviceCall;
 
-enum class Op { Fast, Hc, Decompress };
+enum class Op { Fast, Hc, Decompress, DecompressDict };
 
-// One block, host pointers: stage -> kernel -> copy back.
+// One block, host pointers: stage -> kernel -> copy back.  Op::DecompressDict stages the last min(dict_len, 65536)
+// bytes of `dict` (offsets are at most 65535: nothing in front of that tail can be reached, src/lz4.zig:189-192).
 int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t accel,
-                   int32_t level) {
+                   int32_t level, const uint8_t *dict = nullptr, size_t dict_len = 0) {
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     if (src_len > 0xFFFFFFFFull) return op == Op::Decompress ? ZLZ4_ERR_CORRUPTED_DATA : ZLZ4_ERR_INPUT_TOO_LARGE;
     // the kernels index with 32 bits; a destination larger than 4 GiB-1 is clamped (never reached:
@@ -66,12 +70,17 @@ int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size
     hipStream_t st = nullptr;
     DeviceCall dc(st);
     const size_t ws = op == Op::Hc ? zlz4_hc_workspace_bytes(1, len32) : 0;
-    DevBuf d_in(src_len, &dc), d_out(cap32, &dc), d_meta(64, &dc), d_ws(ws, &dc);
-    if (!d_in.p || !d_out.p || !d_meta.p || !d_ws.p) return ZLZ4_ERR_ALLOCATION_FAILED;
-    struct Meta { uint64_t in_off; uint64_t out_off; int64_t result; uint32_t in_len; uint32_t out_cap; } m;
-    m.in_off = 0; m.out_off = 0; m.result = 0; m.in_len = len32; m.out_cap = cap32;
+    const size_t dtail = op == Op::DecompressDict ? (dict_len < 65536u ? dict_len : 65536u) : 0;
+    DevBuf d_in(src_len, &dc), d_out(cap32, &dc), d_meta(64, &dc), d_ws(ws, &dc), d_dict(dtail, &dc);
+    if (!d_in.p || !d_out.p || !d_meta.p || !d_ws.p || !d_dict.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    struct Meta {
+        uint64_t in_off; uint64_t out_off; int64_t result; uint32_t in_len; uint32_t out_cap; uint64_t dict_off; uint32_t dict_len;
+    } m;
+    m.in_off = 0; m.out_off = 0; m.result = 0; m.in_len = len32; m.out_cap = cap32; m.dict_off = 0; m.dict_len = (uint32_t)dtail;
     dc.launched();
     if (src_len && hipMemcpyAsync(d_in.p, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (dtail && hipMemcpyAsync(d_dict.p, dict + (dict_len - dtail), dtail, hipMemcpyHostToDevice, st) != hipSuccess)
+        return ZLZ4_ERR_DEVICE;
     if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
     auto *dm = d_meta.as<uint8_t>();
     const uint64_t *p_in_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off));
@@ -86,9 +95,14 @@ int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size
     } else if (op == Op::Hc) {
         rc = zlz4_launch_compress_hc(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
                                      p_out_cap, p_res, 1, len32, level, d_ws.p, ws);
-    } else {
+    } else if (op == Op::Decompress) {
         rc = zlz4_launch_decompress_safe(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
                                          p_out_cap, p_res, 1);
+    } else {
+        rc = zlz4_launch_decompress_safe_using_dict(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(),
+                                                    p_out_off, p_out_cap, p_res, 1, d_dict.as<uint8_t>(),
+                                                    reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off)),
+                                                    reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)));
     }
     if (rc != 0) return rc;
     int64_t result = 0;
@@ -99,6 +113,38 @@ int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size
         if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
     }
     return result;
+}
+
+// decompressGeneric with targetOutputSize == 0 and a non-empty dst (src/lz4.zig:111-174): no byte can be produced, the
+// result is decided by the first sequence header alone -- nothing to run on the device.  Every exit comes before the
+// match-source tests (:181-192), so it holds with and without a dictionary.
+int64_t partial_target_zero(const uint8_t *src, size_t n) {
+    size_t ip = 0;
+    const uint8_t token = src[ip++];
+    size_t lit = token >> 4;
+    if (lit == 15) {
+        for (;;) {
+            if (ip >= n) return ZLZ4_ERR_CORRUPTED_DATA;            // :125
+            const uint8_t s = src[ip++];
+            lit += s;
+            if (s != 255) break;
+        }
+    }
+    if (lit > 0) {
+        if (ip + lit > n) return ZLZ4_ERR_CORRUPTED_DATA;           // :136
+        return ZLZ4_ERR_OUTPUT_TOO_SMALL;                           // :137 (op + lit > 0)
+    }
+    if (ip >= n) return 0;                                          // :146
+    if (ip + 2 > n) return ZLZ4_ERR_CORRUPTED_DATA;                 // :149
+    if ((src[ip] | (src[ip + 1] << 8)) == 0) return ZLZ4_ERR_CORRUPTED_DATA;   // :154
+    ip += 2;
+    if ((token & 15) == 15) {
+        for (;;) {
+            if (ip >= n) return ZLZ4_ERR_CORRUPTED_DATA;            // :162
+            if (src[ip++] != 255) break;
+        }
+    }
+    return ZLZ4_ERR_OUTPUT_TOO_SMALL;                               // :174 (op + matchLength > 0)
 }
 
 // src/lz4hc.zig:1445 + :1464-1466 level normalisation, strategy table :72-86
@@ -185,34 +231,25 @@ int64_t zlz4_decompress_safe_partial(const uint8_t *src, size_t n, uint8_t *dst,
     if (cap == 0) return 0;                                         // :98
     if (target > cap) return ZLZ4_ERR_OUTPUT_TOO_SMALL;             // :99
     if (target > 0) return run_single(Op::Decompress, src, n, dst, target, 0, 0);   // oend = targetOutputSize (:109)
-    // target == 0 with a non-empty dst: no byte can be produced, the result is decided by the first sequence
-    // header alone (:111-174) -- nothing to run on the device
-    size_t ip = 0;
-    const uint8_t token = src[ip++];
-    size_t lit = token >> 4;
-    if (lit == 15) {
-        for (;;) {
-            if (ip >= n) return ZLZ4_ERR_CORRUPTED_DATA;            // :125
-            const uint8_t s = src[ip++];
-            lit += s;
-            if (s != 255) break;
-        }
-    }
-    if (lit > 0) {
-        if (ip + lit > n) return ZLZ4_ERR_CORRUPTED_DATA;           // :136
-        return ZLZ4_ERR_OUTPUT_TOO_SMALL;                           // :137 (op + lit > 0)
-    }
-    if (ip >= n) return 0;                                          // :146
-    if (ip + 2 > n) return ZLZ4_ERR_CORRUPTED_DATA;                 // :149
-    if ((src[ip] | (src[ip + 1] << 8)) == 0) return ZLZ4_ERR_CORRUPTED_DATA;   // :154
-    ip += 2;
-    if ((token & 15) == 15) {
-        for (;;) {
-            if (ip >= n) return ZLZ4_ERR_CORRUPTED_DATA;            // :162
-            if (src[ip++] != 255) break;
-        }
-    }
-    return ZLZ4_ERR_OUTPUT_TOO_SMALL;                               // :174 (op + matchLength > 0)
+    return partial_target_zero(src, n);
+}
+
+int64_t zlz4_decompress_safe_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const uint8_t *dict,
+                                        size_t dict_len) {                   // src/lz4.zig:960-962
+    if (n == 0) return 0;                                           // :97
+    if (cap == 0) return 0;                                         // :98
+    if (!dict && dict_len) return ZLZ4_ERR_INVALID_STATE;
+    return run_single(Op::DecompressDict, src, n, dst, cap, 0, 0, dict, dict_len);
+}
+
+int64_t zlz4_decompress_safe_partial_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t target,
+                                                const uint8_t *dict, size_t dict_len) {   // src/lz4.zig:967-969
+    if (n == 0) return 0;                                           // :97
+    if (cap == 0) return 0;                                         // :98
+    if (target > cap) return ZLZ4_ERR_OUTPUT_TOO_SMALL;             // :99
+    if (!dict && dict_len) return ZLZ4_ERR_INVALID_STATE;
+    if (target > 0) return run_single(Op::DecompressDict, src, n, dst, target, 0, 0, dict, dict_len);
+    return partial_target_zero(src, n);
 }
 
 size_t zlz4_sizeof_state(void) { return 4096 * sizeof(uint32_t); }  // src/lz4.zig:524-526, :263-265
@@ -333,6 +370,15 @@ int32_t zlz4_batch_decompress_safe(void *stream, const uint8_t *d_in, const uint
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     return zlz4_launch_decompress_safe((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
                                        d_result, nblocks);
+}
+
+int32_t zlz4_batch_decompress_safe_using_dict(void *stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                              const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                              const uint32_t *d_out_cap, const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                              const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks) {
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_decompress_safe_using_dict((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off,
+                                                  d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len);
 }
 
 size_t zlz4_batch_compress_hc_workspace(uint32_t nblocks, uint32_t max_in_len) {

@@ -2,7 +2,8 @@
 //
 // Replaces lz4.decompressSafe (reference src/lz4.zig:257-259), i.e.
 // decompressGeneric (src/lz4.zig:89-251) with lowPrefix == dst.ptr and no
-// dictionary.  The decision order and the error returned at every exit follow
+// dictionary, and (kDict) decompressSafe[Partial]UsingDict (:960-969), the same
+// with an external dictionary in front of dst.  The decision order and the error returned at every exit follow
 // SURVEY.md Appendix C exactly; `dst` contents after an error are unspecified
 // (as in the reference).
 //
@@ -56,11 +57,19 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
 // (the decoder is bound by vector issue and lives on occupancy: eight wavefronts per SIMD = at most 64 VGPRs.  The copy
 //  phases brought the lane-copy build to 66 and the seventh-of-eight cost D-text 7 %; it is back at 62 since the lane
 //  copy keeps two rounds of registers instead of three.)
-template <bool kWrite, bool kLaneCopy = false, bool kPhases = kLaneCopy>
-__global__ __launch_bounds__(256) void k_decompress_safe(
+// kDict: decompressSafeUsingDict (src/lz4.zig:960-969): a match whose offset reaches in front of dst reads the virtual
+// buffer dict ++ dst (:181-225).  Only the last min(dict.len, 65536) bytes can be reached (offset <= 65535), so dend /
+// dlen below are that tail; the dictionary is read-only and must not overlap dst.  The dictionary arguments come last so
+// that the kernel-argument layout of the no-dict instantiations is unchanged.  The dict instantiations are held to eight
+// wavefronts per SIMD (64 VGPRs; the lane-copy build would take 67 and spills two to scratch instead): measured on
+// MI355X, 7 -> 8 wavefronts beat the spill on every case of tools/time_dict_decompress.py (configs[1] with an empty
+// dictionary 10.96 -> 10.46 ms); the no-dict instantiations are compiled exactly as before.
+template <bool kWrite, bool kLaneCopy = false, bool kPhases = kLaneCopy, bool kDict = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 : 1))) void k_decompress_safe(
     const uint8_t *__restrict__ d_in, const uint64_t *__restrict__ d_in_off,
     const uint32_t *__restrict__ d_in_len, uint8_t *d_out, const uint64_t *__restrict__ d_out_off,
-    const uint32_t *__restrict__ d_out_cap, int64_t *__restrict__ d_result, uint32_t nblocks, uint32_t min_phase_tokens) {
+    const uint32_t *__restrict__ d_out_cap, int64_t *__restrict__ d_result, uint32_t nblocks, uint32_t min_phase_tokens,
+    const uint8_t *__restrict__ d_dict, const uint64_t *__restrict__ d_dict_off, const uint32_t *__restrict__ d_dict_len) {
     constexpr uint32_t short_max = kLaneCopy ? 32u : 0u;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t blk = rfl(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
@@ -70,6 +79,16 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
     uint8_t *dst = d_out + d_out_off[blk];
     const uint32_t iend = rfl(d_in_len[blk]);   // src.len
     const uint32_t oend = rfl(d_out_cap[blk]);  // dst.len == targetOutputSize
+    // dictionary end and reachable length (kDict only).  Hand-issued dictionary loads use the scalar base dend - 65536 and
+    // the 32-bit offset 65536 - (bytes in front of dend), which is >= 65536 - dlen >= 0.
+    const uint8_t *dend = nullptr, *dbase = nullptr;
+    uint32_t dlen = 0;
+    if constexpr (kDict) {
+        const uint32_t dl = rfl(d_dict_len[blk]);
+        dend = d_dict + d_dict_off[blk] + dl;
+        dbase = dend - 65536;
+        dlen = dl < 65536u ? dl : 65536u;
+    }
 
     int64_t res = 0;
     uint32_t ip = 0, op = 0;
@@ -103,7 +122,8 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
                 //  spends vector instructions on 64-bit pointer arithmetic)
                 if (pml >= 16u) {
                     st128(dst + po, pa);
-                    for (uint32_t k = 16u; k + 16u <= pml; k += 16u) st128(dst + (po + k), ld128(dst + (po - pof + k)));
+                    for (uint32_t k = 16u; k + 16u <= pml; k += 16u)
+                        st128(dst + (po + k), ld128(kDict && po < pof ? dend - (pof - po) + k : dst + (po - pof + k)));
                     st128(dst + (po + pml - 16u), pb);
                 } else if (pml >= 8u) {
                     // exact-size copies without partial-word stores: the last piece overlaps the first
@@ -273,6 +293,13 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
                     // matches: end the phase in front of the first such sequence
                     const uint32_t lit0 = rdlane(lit, 0);
                     viol_err = off > op0 + relv + lit;
+                    if constexpr (kDict) {
+                        // a match wholly inside the dictionary reads memory no batch writes: it is always taken, as long
+                        // as it passes :190 and the 16-byte loads of the sequence-lane copy stay inside the dictionary
+                        // (the lane copy reads exact pieces).  Spanning matches and :190 errors go to the single path.
+                        const uint32_t pr = op0 + relv + lit, need = kLaneCopy ? ml : (ml > 16u ? ml : 16u);
+                        viol_err = viol_err && (off - pr < need || off - pr > dlen);
+                    }
                     bool viol = viol_err;
                     if (kWrite) viol = viol || (off + lit0 < relv + ol);
                     const uint64_t vm = ballot(real0 && viol);
@@ -335,9 +362,19 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
                     [[maybe_unused]] const bool shortm = real && ml <= short_max;
                     if (!kLaneCopy || ballot(real && ml > short_max)) {   // long matches: 16-byte pieces per sequence lane
                         if (real && ml > short_max) {
-                            asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pa) : "v"(mo_t), "s"(dst) : "memory");
-                            if (ml >= 16u)
-                                asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pb) : "v"(mo_t + ml - 16u), "s"(dst) : "memory");
+                            if constexpr (kDict) {
+                                // one load per piece from a per-lane address: the source is wholly in the dictionary
+                                // (see viol_err) or wholly in dst (two exec-masked loads would write pa twice in flight)
+                                const uint64_t ma = off > po_t ? (uint64_t)(uintptr_t)dbase + (mo_t + 65536u)
+                                                               : (uint64_t)(uintptr_t)dst + mo_t;
+                                asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(pa) : "v"(ma) : "memory");
+                                if (ml >= 16u)
+                                    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(pb) : "v"(ma + (ml - 16u)) : "memory");
+                            } else {
+                                asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pa) : "v"(mo_t), "s"(dst) : "memory");
+                                if (ml >= 16u)
+                                    asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pb) : "v"(mo_t + ml - 16u), "s"(dst) : "memory");
+                            }
                             pml = ml; po = po_t; pof = off;
                         }
                     }
@@ -360,7 +397,12 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
                             const bool act = g0 + grp < ns && k4 < g_ml;
                             const uint32_t pk = k4 + 4u <= g_ml ? k4 : g_ml - 4u;       // the last piece overlaps the one before
                             if (act) {
-                                asm volatile("global_load_dword %0, %1, %2" : "+v"(pd) : "v"(g_mo + pk), "s"(dst) : "memory");
+                                if constexpr (kDict) {              // (per-lane address, as for the 16-byte pieces)
+                                    const uint64_t ga = g_po < (g_om & 0xFFFFu) ? (uint64_t)(uintptr_t)dbase + (g_mo + pk + 65536u)
+                                                                                : (uint64_t)(uintptr_t)dst + (g_mo + pk);
+                                    asm volatile("global_load_dword %0, %1, off" : "+v"(pd) : "v"(ga) : "memory");
+                                } else
+                                    asm volatile("global_load_dword %0, %1, %2" : "+v"(pd) : "v"(g_mo + pk), "s"(dst) : "memory");
                                 pdo = g_po + pk;
                             }
                         };
@@ -438,7 +480,9 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
                     if (offset == 0) { res = kErrCorrupted; break; }                     // :154
                     const uint32_t ml = mlc + kMinMatch;                                 // :171 (4..18)
                     if (ml > oend - op) { res = kErrOutputTooSmall; break; }             // :174
-                    if (offset > op) { res = kErrCorrupted; break; }                     // :181-186 / :231
+                    if (offset > op) {                                                   // :181-186 / :231
+                        if (!kDict || offset - op > dlen) { res = kErrCorrupted; break; }   // (dict: :189-192)
+                    }
                     if (kWrite) {
                         const uint8_t *m = dst + (op - offset);
                         // out[op+k] = out[op-offset + (k mod offset)]; ml <= 18 lanes, one load + one store
@@ -447,7 +491,12 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
                             if (offset == 1u) k = 0;
                             else { while (k >= offset) k -= offset; }
                         }
-                        if (lane < ml) dst[op + lane] = m[k];
+                        if constexpr (kDict) {
+                            // the same identity over dict ++ dst (:199-225): op + k < offset is a dictionary byte
+                            if (lane < ml) dst[op + lane] = op + k < offset ? *(dend - (offset - op - k)) : dst[op + k - offset];
+                        } else {
+                            if (lane < ml) dst[op + lane] = m[k];
+                        }
                     }
                     op += ml;
                     continue;
@@ -504,7 +553,19 @@ __global__ __launch_bounds__(256) void k_decompress_safe(
             }
             ml += kMinMatch;                                        // :171
             if (ml > oend - op) { res = kErrOutputTooSmall; break; }   // :174
-            if (offset > op) { res = kErrCorrupted; break; }        // :181-186 (no dict) / :231
+            if (offset > op) {                                      // :181-186 (no dict) / :231
+                if (!kDict || offset - op > dlen) { res = kErrCorrupted; break; }   // (dict: :189-192)
+            }
+            if constexpr (kDict) {
+                if (offset > op) {
+                    // :199-225: the dictionary part first; what is left of a match that spans the dictionary end is
+                    // dst[0..] with period offset, i.e. an in-block match at op == offset, copied below
+                    const uint32_t a = offset - op, n1 = a < ml ? a : ml;
+                    if (kWrite) copy_bytes(dst + op, dend - a, n1, lane);
+                    op += n1;
+                    ml -= n1;
+                }
+            }
             const uint8_t *m = dst + (op - offset);
             uint8_t *o = dst + op;
             if (!kWrite) {
@@ -716,13 +777,41 @@ extern "C" int zlz4_launch_decompress_safe(hipStream_t stream, const uint8_t *d_
     static const uint32_t min_phase_tokens = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_PHASE_MIN"); return e ? (uint32_t)atoi(e) : 3u; }();
     if (short_max && no_phases)
         hipLaunchKernelGGL((zlz4::k_decompress_safe<true, true, false>), dim3(grid), dim3(64 * waves_per_wg), dyn_lds, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens);
+                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
+                           nullptr, nullptr, nullptr);
     else if (short_max)
         hipLaunchKernelGGL((zlz4::k_decompress_safe<true, true>), dim3(grid), dim3(64 * waves_per_wg), dyn_lds, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens);
+                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
+                           nullptr, nullptr, nullptr);
     else
         hipLaunchKernelGGL((zlz4::k_decompress_safe<true, false>), dim3(grid), dim3(64 * waves_per_wg), dyn_lds, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens);
+                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
+                           nullptr, nullptr, nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+// decompressSafeUsingDict over a batch: the grid and the build choice of zlz4_launch_decompress_safe (16 bytes per
+// sequence lane below kLaneCopyMinBlocks blocks, lane copy with phases from there on); block i reads the dictionary
+// d_dict[d_dict_off[i] .. + d_dict_len[i]) (any length; only its last 65536 bytes can be reached).  The tuning knobs of
+// the no-dict launcher (lane decoder, phases off, LDS) do not apply here.
+extern "C" int zlz4_launch_decompress_safe_using_dict(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                      const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                                      const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks,
+                                                      const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                      const uint32_t *d_dict_len) {
+    if (nblocks == 0) return 0;
+    static const uint32_t waves_per_wg = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_WPW"); const uint32_t v = e ? (uint32_t)atoi(e) : 4u;
+                                              return (v == 1u || v == 2u || v == 4u) ? v : 4u; }();
+    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
+    static const uint32_t min_phase_tokens = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_PHASE_MIN"); return e ? (uint32_t)atoi(e) : 3u; }();
+    if (nblocks >= kLaneCopyMinBlocks)
+        hipLaunchKernelGGL((zlz4::k_decompress_safe<true, true, true, true>), dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in,
+                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
+                           d_dict, d_dict_off, d_dict_len);
+    else
+        hipLaunchKernelGGL((zlz4::k_decompress_safe<true, false, false, true>), dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in,
+                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
+                           d_dict, d_dict_off, d_dict_len);
     return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 
@@ -734,7 +823,7 @@ extern "C" int zlz4_launch_decompress_sizes(hipStream_t stream, const uint8_t *d
     const uint32_t waves_per_wg = 4;
     const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
     hipLaunchKernelGGL((zlz4::k_decompress_safe<false, false>), dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in, d_in_off,
-                       d_in_len, (uint8_t *)nullptr, d_out_off, d_out_cap, d_result, nblocks, 0u);
+                       d_in_len, (uint8_t *)nullptr, d_out_off, d_out_cap, d_result, nblocks, 0u, nullptr, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 

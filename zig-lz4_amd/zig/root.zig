@@ -15,6 +15,8 @@ extern "c" fn zlz4_compress_fast(src: [*]const u8, src_len: usize, dst: [*]u8, d
 extern "c" fn zlz4_compress_hc(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, level: i32) i64;
 extern "c" fn zlz4_decompress_safe(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize) i64;
 extern "c" fn zlz4_decompress_safe_partial(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, target: usize) i64;
+extern "c" fn zlz4_decompress_safe_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4_decompress_safe_partial_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, target: usize, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4_sizeof_state() usize;
 extern "c" fn zlz4_compress_fast_ext_state(state: [*]u8, state_len: usize, src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, acceleration: u32) i64;
 extern "c" fn zlz4_compress_dest_size(src: [*]const u8, dst: [*]u8, dst_cap: usize, src_size: *usize) i64;
@@ -24,6 +26,7 @@ extern "c" fn zlz4_compress_hc_ext_state(state: [*]u8, state_len: usize, src: [*
 // the data-parallel hot path: device pointers, one wavefront (HC: one workgroup) per block, results per block
 extern "c" fn zlz4_batch_compress_fast(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_decompress_safe(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
+extern "c" fn zlz4_batch_decompress_safe_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: [*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
 extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) usize;
 extern "c" fn zlz4_batch_compress_hc(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_verify(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_comp: [*]const u8, d_comp_off: [*]const u64, d_comp_result: [*]const i64, d_verify: [*]i64, nblocks: u32) i64;
@@ -96,6 +99,15 @@ pub fn decompressSafe(src: []const u8, dst: []u8) Error!usize {
 pub fn decompressSafePartial(src: []const u8, dst: []u8, targetOutputSize: usize) Error!usize {
     return mapBlock(zlz4_decompress_safe_partial(src.ptr, src.len, dst.ptr, dst.len, targetOutputSize));
 }
+/// reference src/lz4.zig:960-962: `dict` is the data in front of dst (only its last 64 KiB can be referenced);
+/// it must not overlap dst
+pub fn decompressSafeUsingDict(src: []const u8, dst: []u8, dict: []const u8) Error!usize {
+    return mapBlock(zlz4_decompress_safe_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len));
+}
+/// reference src/lz4.zig:967-969
+pub fn decompressSafePartialUsingDict(src: []const u8, dst: []u8, targetOutputSize: usize, dict: []const u8) Error!usize {
+    return mapBlock(zlz4_decompress_safe_partial_using_dict(src.ptr, src.len, dst.ptr, dst.len, targetOutputSize, dict.ptr, dict.len));
+}
 /// reference src/lz4.zig:524-526
 pub fn sizeofState() usize {
     return zlz4_sizeof_state();
@@ -134,6 +146,8 @@ pub const lz4 = struct {
     pub const compressDestSize = root.compressDestSize;
     pub const decompressSafe = root.decompressSafe;
     pub const decompressSafePartial = root.decompressSafePartial;
+    pub const decompressSafeUsingDict = root.decompressSafeUsingDict;
+    pub const decompressSafePartialUsingDict = root.decompressSafePartialUsingDict;
     pub const sizeofState = root.sizeofState;
     pub const compressFastExtState = root.compressFastExtState;
 };
@@ -161,6 +175,8 @@ pub const device = struct {
         result: [*]i64, // per block: bytes written or -(lz4.Error index)
         nblocks: u32,
     };
+    pub const DictBlocks = root.DictBlocks;
+    pub const decompressSafeUsingDictBatch = root.decompressSafeUsingDictBatch;
     fn mapLaunch(rc: i32) Error!void {
         if (rc == 0) return;
         _ = try mapBlock(rc);
@@ -186,6 +202,18 @@ pub const device = struct {
         return mapBlock(zlz4_batch_verify(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.result, verify, b.nblocks));
     }
 };
+
+/// Per-block dictionaries of `device.decompressSafeUsingDictBatch` (device memory, like `device.Blocks`): block i reads
+/// dict[dict_off[i] ..][0..dict_len[i]].  A shared dictionary is one copy with the same offset for every block.
+pub const DictBlocks = struct {
+    dict: [*]const u8, // dictionary arena
+    dict_off: [*]const u64, // per block: offset into `dict`
+    dict_len: [*]const u32, // per block: bytes (any length; only the last 64 KiB can be referenced)
+};
+/// batch form of decompressSafeUsingDict (src/lz4.zig:960-962); dictionaries are read-only and must not overlap `b.out`
+pub fn decompressSafeUsingDictBatch(stream: ?*anyopaque, b: device.Blocks, d: DictBlocks) Error!void {
+    return device.mapLaunch(zlz4_batch_decompress_safe_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict, d.dict_off, d.dict_len, b.result, b.nblocks));
+}
 
 /// Mirror of the `lz4f` namespace (reference src/lz4f.zig); enum/struct shapes as in :64-122.
 pub const lz4f = struct {
