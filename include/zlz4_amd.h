@@ -64,6 +64,7 @@ extern "C" {
 #define ZLZ4HC_CLEVEL_DEFAULT    9
 #define ZLZ4HC_CLEVEL_MAX        12
 #define ZLZ4F_MAGICNUMBER        0x184D2204u     /* src/lz4f.zig:12 */
+#define ZLZ4_STREAM_TABLE_ENTRIES 4096u          /* Stream.hashTable, src/lz4.zig:752 (LZ4_HASH_SIZE_U32, :33) */
 
 /* ======================================================================
  * 1. Single-buffer entry points, HOST pointers -- the names root.zig binds.
@@ -140,6 +141,25 @@ int64_t zlz4_decompress_safe_using_dict(const uint8_t *src, size_t src_len, uint
 int64_t zlz4_decompress_safe_partial_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                                 size_t target_output_size, const uint8_t *dict, size_t dict_len);
 
+/* Streaming compression, lz4.Stream (src/lz4.zig:751-866).  `table` is Stream.hashTable: ZLZ4_STREAM_TABLE_ENTRIES
+ * u32 in HOST memory, staged with the data (correct, not fast -- the batch calls of section 2 are the fast path).  The
+ * rest of the Stream struct (dictionary slice, dictSize, currentOffset, saveDict) is host bookkeeping in the bindings.
+ *
+ * zlz4_stream_load_dict replaces Stream.loadDict (:798-820): the table is reset, then
+ * table[hash4(rd32(tail + i))] = i for i in [0, dictSize - 5] of tail = the last dictSize = min(dict_len, 65536)
+ * bytes (last writer wins; 4 bytes or fewer hash nothing).  Returns dictSize (0 for an empty dictionary).
+ *
+ * zlz4_stream_compress_fast_continue replaces Stream.compressFastContinue (:822-836): compressFast's loop starting from
+ * `table`, which receives the final table on success.  InputTooLarge, 0 bytes, 1..12 bytes (compressAsLiterals) and
+ * any error leave the table unchanged.
+ * The reference reads every table entry as a position in the CURRENT src (:656-659), so a loaded dictionary only
+ * changes which in-block matches the greedy parse finds; no output block refers to the dictionary, every block
+ * decodes with plain decompressSafe, and the ratio gains nothing from it.  This is reproduced byte for byte.
+ * table == NULL, or dict == NULL with dict_len > 0 -> InvalidState. */
+int64_t zlz4_stream_load_dict(uint32_t *table, const uint8_t *dict, size_t dict_len);
+int64_t zlz4_stream_compress_fast_continue(uint32_t *table, const uint8_t *src, size_t src_len, uint8_t *dst,
+                                           size_t dst_cap, uint32_t acceleration);
+
 /* replaces lz4.sizeofState, src/lz4.zig:524-526 (= @sizeOf(HashTable) = 16384) */
 size_t  zlz4_sizeof_state(void);
 
@@ -189,6 +209,29 @@ int32_t zlz4_batch_decompress_safe_using_dict(void *stream,
                                               uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                               const uint8_t *d_dict, const uint64_t *d_dict_off,
                                               const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks);
+
+/* Stream.loadDict (src/lz4.zig:798-820) per dictionary: table i (d_tables + i * ZLZ4_STREAM_TABLE_ENTRIES u32) receives
+ * the table of dictionary i = d_dict + d_dict_off[i] (d_dict_len[i] bytes); d_result[i] = its return value, dictSize.
+ * d_tables must be 16-byte aligned (as every table of zlz4_batch_compress_fast_continue), else InvalidState. */
+int32_t zlz4_batch_load_dict(void *stream, const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                             uint32_t *d_tables, int64_t *d_result, uint32_t ndicts);
+
+/* Stream.compressFastContinue (src/lz4.zig:822-836) per block: block i starts from table d_table_idx[i] of d_table_in
+ * (d_table_idx == NULL: table i) and its final table goes to table i of d_table_out (NULL: not written).  Tables are
+ * ZLZ4_STREAM_TABLE_ENTRIES u32 each; d_table_in and d_table_out must be 16-byte aligned (the kernel moves tables in
+ * 16-byte vectors), else the call returns InvalidState and launches nothing.  d_table_out[i] always holds what the reference's Stream.hashTable holds after the
+ * call: the input table where the block did not compress (InputTooLarge, InvalidState, 0..12 bytes, OutputTooSmall).
+ * A shared dictionary = one loaded table every block points at; a chained stream step = identity indexing with
+ * d_table_out == d_table_in (in place; anything else that overlaps, or in place with an index array, is not allowed:
+ * the latter returns InvalidState).  Same contract as zlz4_batch_compress_fast otherwise (max_in_len, asynchronous,
+ * no allocation).  Blocks compress exactly as in zlz4_stream_compress_fast_continue above: no ratio gain from a
+ * dictionary. */
+int32_t zlz4_batch_compress_fast_continue(void *stream,
+                                          const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                          uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                          const uint32_t *d_table_in, const uint32_t *d_table_idx, uint32_t *d_table_out,
+                                          int64_t *d_result, uint32_t nblocks, uint32_t max_in_len,
+                                          uint32_t acceleration);
 
 /* workspace for the HC path: bytes needed for `nblocks` blocks of at most `max_in_len` bytes (448 KiB per 64 KiB block
  * up to 8192 blocks = 3.5 GiB, about 6 GiB at most for large blocks; longer batches are processed in rounds) */

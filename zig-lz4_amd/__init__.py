@@ -64,12 +64,16 @@ SYMBOLS = {
     "zlz4_decompress_safe_partial": (_I64, [_VP, _SZ, _VP, _SZ, _SZ]),
     "zlz4_decompress_safe_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ]),
     "zlz4_decompress_safe_partial_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _SZ, _VP, _SZ]),
+    "zlz4_stream_load_dict": (_I64, [_VP, _VP, _SZ]),
+    "zlz4_stream_compress_fast_continue": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _U32]),
     "zlz4_sizeof_state": (_SZ, []),
     "zlz4_compress_fast_ext_state": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _U32]),
     "zlz4_compress_dest_size": (_I64, [_VP, _VP, _SZ, C.POINTER(C.c_size_t)]),
     "zlz4_batch_compress_fast": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_decompress_safe": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_decompress_safe_using_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_batch_load_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_batch_compress_fast_continue": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_compress_hc_workspace": (_SZ, [_U32, _U32]),
     "zlz4_batch_compress_hc": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _I32, _VP, _SZ]),
     "zlz4_batch_verify": (_I64, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
@@ -202,6 +206,93 @@ def decompressSafePartialUsingDict(src, dst_cap, target_output_size, dict):
     return _run(lib().zlz4_decompress_safe_partial_using_dict, src, dst_cap, target_output_size, C.addressof(dk), dn)
 
 
+STREAM_TABLE_ENTRIES = 4096                           # Stream.hashTable, src/lz4.zig:752 (LZ4_HASH_SIZE_U32, :33)
+
+
+class Stream:
+    """lz4.Stream, the streaming compressor (src/lz4.zig:751-866).  `hashTable` is a numpy uint32[4096]; loadDict and
+    compressFastContinue compute it on the device (zlz4_stream_load_dict / zlz4_stream_compress_fast_continue), the rest
+    is host bookkeeping with the reference's field names.  `dictionary` keeps a copy of the loaded tail (the reference
+    borrows the caller's slice).  The reference reads every table entry as a position in the CURRENT block, so a loaded
+    dictionary only changes which in-block matches are found: no block refers to it and every block decodes with plain
+    decompressSafe (reproduced, not a defect of this binding)."""
+    byU32, byU16, byPtr = 1, 2, 3                     # TableType, src/lz4.zig:744-748
+
+    def __init__(self):                               # Stream.init, :776-786
+        import numpy as np
+        self.hashTable = np.zeros(STREAM_TABLE_ENTRIES, dtype=np.uint32)
+        self.dictionary = None
+        self.dictCtx = None
+        self.currentOffset = 0
+        self.tableType = Stream.byU32
+        self.dictSize = 0
+
+    @classmethod
+    def create(cls):                                  # :761-766
+        return cls()
+
+    def destroy(self):                                # :769-773
+        pass
+
+    @classmethod
+    def init(cls):
+        return cls()
+
+    def resetFast(self):                              # :789-795
+        self.hashTable[:] = 0
+        self.dictionary = None
+        self.dictCtx = None
+        self.currentOffset = 0
+        self.dictSize = 0
+
+    def _table(self):
+        return C.c_void_p(self.hashTable.ctypes.data)
+
+    def loadDict(self, dict):
+        """Stream.loadDict (:798-820) -> dictSize = min(len(dict), 65536)."""
+        self.resetFast()                              # :799
+        dk, dn = _in(dict)
+        size = _check(lib().zlz4_stream_load_dict(self._table(), C.addressof(dk), dn))
+        if size:
+            self.dictionary = bytes(dict)[dn - size:]  # :805-806
+            self.dictSize = size                      # :807
+        return size
+
+    def compressFastContinue(self, src, acceleration=1, dst_cap=None):
+        """Stream.compressFastContinue (:822-836) -> the compressed block; the table is updated only when a block of 13
+        or more bytes compresses (errors raise Lz4Error and leave it unchanged)."""
+        cap = compressBound(len(src)) if dst_cap is None else dst_cap
+        out = _run(lambda sp, n, dp, c: lib().zlz4_stream_compress_fast_continue(self._table(), sp, n, dp, c, acceleration),
+                   src, cap)
+        if len(src) >= 13:                            # :833 (:824-827 return before it)
+            self.currentOffset = min(self.currentOffset + len(src), 0xFFFFFFFF)
+        return out
+
+    def saveDict(self, safeBuffer, maxDictSize):
+        """Stream.saveDict (:839-855): copies the tail of the LOADED dictionary (not the compressed history) to the front
+        of the writable buffer `safeBuffer`; returns the number of bytes copied."""
+        if maxDictSize == 0:                          # :840
+            return 0
+        if self.dictionary is None:                   # :841
+            return 0
+        d = self.dictionary
+        size = min(min(len(d), maxDictSize), 64 * 1024)   # :844
+        if size > len(safeBuffer):                    # :846-850
+            size = min(size, len(safeBuffer))
+        safeBuffer[0:size] = d[len(d) - size:]        # :848 / :852
+        return size
+
+
+def createStream():
+    """lz4.createStream, src/lz4.zig:858-860."""
+    return Stream.create()
+
+
+def freeStream(stream):
+    """lz4.freeStream, src/lz4.zig:863-865."""
+    stream.destroy()
+
+
 def sizeofState():
     """lz4.sizeofState, src/lz4.zig:524-526."""
     return lib().zlz4_sizeof_state()
@@ -302,6 +393,24 @@ def batch_decompress_safe_using_dict(d_in, in_off, in_len, d_out, out_off, out_c
     _check(lib().zlz4_batch_decompress_safe_using_dict(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
                                                        _ptr(out_off), _ptr(out_cap), _ptr(d_dict), _ptr(dict_off),
                                                        _ptr(dict_len), _ptr(result), in_len.numel()))
+
+
+def batch_load_dict(d_dict, dict_off, dict_len, tables, result):
+    """zlz4_batch_load_dict: table i (tables.view(-1, 4096)[i], int32/uint32) = Stream.loadDict of dictionary
+    d_dict[dict_off[i] .. + dict_len[i]); result[i] (int64) = dictSize."""
+    _check(lib().zlz4_batch_load_dict(_stream(), _ptr(d_dict), _ptr(dict_off), _ptr(dict_len), _ptr(tables), _ptr(result),
+                                      dict_len.numel()))
+
+
+def batch_compress_fast_continue(d_in, in_off, in_len, d_out, out_off, out_cap, table_in, table_idx, table_out, result,
+                                 max_in_len, acceleration=1):
+    """zlz4_batch_compress_fast_continue: as batch_compress_fast, block i starting from table table_idx[i] of table_in
+    (table_idx None = table i); its final table goes to table i of table_out (None = not written; table_out may be
+    table_in itself when table_idx is None)."""
+    _check(lib().zlz4_batch_compress_fast_continue(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
+                                                   _ptr(out_off), _ptr(out_cap), _ptr(table_in), _ptr(table_idx),
+                                                   _ptr(table_out), _ptr(result), in_len.numel(), max_in_len,
+                                                   acceleration))
 
 
 def batch_compress_hc_workspace(nblocks, max_in_len):

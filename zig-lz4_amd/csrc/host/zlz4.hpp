@@ -53,6 +53,45 @@ inline Result decompressSafePartialUsingDict(const std::uint8_t *src, std::size_
                                              std::size_t target, const std::uint8_t *dict, std::size_t dict_len) {
     return wrap(zlz4_decompress_safe_partial_using_dict(src, n, dst, cap, target, dict, dict_len));
 }
+// lz4.Stream, src/lz4.zig:751-866: the table lives on the host and is computed on the device by loadDict /
+// compressFastContinue; the rest is bookkeeping.  A loaded dictionary only changes which in-block matches are found (the
+// reference reads table entries as positions in the current block): no block refers to it, and saveDict copies the
+// loaded dictionary, not the compressed history.
+struct Stream {
+    std::uint32_t hashTable[ZLZ4_STREAM_TABLE_ENTRIES] = {};
+    const std::uint8_t *dictionary = nullptr;   // borrowed, as in the reference
+    std::size_t dictionaryLen = 0;
+    std::uint32_t currentOffset = 0;
+    std::uint32_t dictSize = 0;
+
+    void resetFast() {                                              // :789-795
+        for (auto &e : hashTable) e = 0;
+        dictionary = nullptr; dictionaryLen = 0; currentOffset = 0; dictSize = 0;
+    }
+    // :798-820; a negative value = the device call failed (the reference returns usize)
+    std::int64_t loadDict(const std::uint8_t *dict, std::size_t len) {
+        resetFast();
+        const std::int64_t r = zlz4_stream_load_dict(hashTable, dict, len);
+        if (r > 0) { dictionary = dict + (len - (std::size_t)r); dictionaryLen = (std::size_t)r; dictSize = (std::uint32_t)r; }
+        return r;
+    }
+    // :822-836
+    Result compressFastContinue(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap, std::uint32_t accel = 1) {
+        const Result r = wrap(zlz4_stream_compress_fast_continue(hashTable, src, n, dst, cap, accel));
+        if (r.ok() && n >= 13) currentOffset = currentOffset + n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (std::uint32_t)(currentOffset + n);
+        return r;
+    }
+    // :839-855
+    std::size_t saveDict(std::uint8_t *safeBuffer, std::size_t safeLen, std::size_t maxDictSize) const {
+        if (maxDictSize == 0 || !dictionary) return 0;
+        std::size_t size = dictionaryLen < maxDictSize ? dictionaryLen : maxDictSize;
+        if (size > 65536) size = 65536;
+        if (size > safeLen) size = safeLen;
+        for (std::size_t i = 0; i < size; i++) safeBuffer[i] = dictionary[dictionaryLen - size + i];
+        return size;
+    }
+};
+
 // lz4.sizeofState / compressFastExtState / compressDestSize, src/lz4.zig:524-616
 inline std::size_t sizeofState() { return zlz4_sizeof_state(); }
 inline Result compressFastExtState(void *state, std::size_t state_len, const std::uint8_t *src, std::size_t n,
@@ -95,6 +134,20 @@ struct DictBlocks {
 inline Result decompressSafeUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d) {
     return wrap(zlz4_batch_decompress_safe_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
                                                       d.dict_off, d.dict_len, b.result, b.nblocks));
+}
+// Stream.loadDict per dictionary (table i of d_tables, ZLZ4_STREAM_TABLE_ENTRIES u32 each; result[i] = dictSize)
+inline Result loadDictBatch(void *stream, const DictBlocks &d, std::uint32_t *d_tables, std::int64_t *d_result, std::uint32_t ndicts) {
+    return wrap(zlz4_batch_load_dict(stream, d.dict, d.dict_off, d.dict_len, d_tables, d_result, ndicts));
+}
+// Stream.compressFastContinue per block: block i starts from table table_idx[i] of table_in (nullptr = table i), its
+// final table goes to table i of table_out (nullptr = not written; in place only without table_idx)
+struct StreamTables {
+    const std::uint32_t *table_in; const std::uint32_t *table_idx; std::uint32_t *table_out;
+};
+inline Result compressFastContinueBatch(void *stream, const Blocks &b, const StreamTables &t, std::uint32_t max_in_len,
+                                        std::uint32_t accel = 1) {
+    return wrap(zlz4_batch_compress_fast_continue(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, t.table_in,
+                                                  t.table_idx, t.table_out, b.result, b.nblocks, max_in_len, accel));
 }
 inline std::size_t compressHCWorkspace(std::uint32_t nblocks, std::uint32_t max_in_len) {
     return zlz4_batch_compress_hc_workspace(nblocks, max_in_len);

@@ -22,6 +22,11 @@ extern "C" int zlz4_launch_decompress_safe_using_dict(hipStream_t, const uint8_t
                                                       const uint8_t *, const uint64_t *, const uint32_t *);
 extern "C" int zlz4_launch_compress_fast(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
                                          const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
+extern "C" int zlz4_launch_compress_fast_continue(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
+                                                  uint8_t *, const uint64_t *, const uint32_t *, const uint32_t *,
+                                                  const uint32_t *, uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
+extern "C" int zlz4_launch_load_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint32_t *,
+                                     int64_t *, uint32_t);
 extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
                                        const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, int32_t,
                                        void *, size_t);
@@ -147,6 +152,54 @@ int64_t partial_target_zero(const uint8_t *src, size_t n) {
     return ZLZ4_ERR_OUTPUT_TOO_SMALL;                               // :174 (op + matchLength > 0)
 }
 
+// Stream.loadDict / compressFastContinue on a HOST table of 4096 u32: the table is staged with the data, the kernel
+// updates it in place on the device, and it is copied back.  src == nullptr: loadDict of `dict` (its last
+// min(dict_len, 65536) bytes are staged); else compressFastContinue of src[0..src_len).
+int64_t run_stream_single(uint32_t *table, const uint8_t *dict, size_t dict_len, const uint8_t *src, size_t src_len,
+                          uint8_t *dst, size_t dst_cap, uint32_t accel) {
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const bool load = src == nullptr;
+    const size_t in_len = load ? (dict_len < 65536u ? dict_len : 65536u) : src_len;
+    const uint8_t *in = load ? dict + (dict_len - in_len) : src;
+    const uint32_t cap32 = dst_cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dst_cap;
+    const size_t tbytes = ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t);
+    hipStream_t st = nullptr;
+    DeviceCall dc(st);
+    DevBuf d_in(in_len, &dc), d_out(load ? 0 : cap32, &dc), d_meta(64, &dc), d_tab(tbytes, &dc);
+    if (!d_in.p || !d_out.p || !d_meta.p || !d_tab.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    struct Meta { uint64_t in_off; uint64_t out_off; int64_t result; uint32_t in_len; uint32_t out_cap; } m;
+    m.in_off = 0; m.out_off = 0; m.result = 0; m.in_len = (uint32_t)in_len; m.out_cap = cap32;
+    dc.launched();
+    if (in_len && hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (!load && hipMemcpyAsync(d_tab.p, table, tbytes, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    auto *dm = d_meta.as<uint8_t>();
+    const uint64_t *p_in_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off));
+    const uint32_t *p_in_len = reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len));
+    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
+    int rc;
+    if (load) {
+        rc = zlz4_launch_load_dict(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_tab.as<uint32_t>(), p_res, 1);
+    } else {
+        rc = zlz4_launch_compress_fast_continue(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(),
+                                                reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
+                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)),
+                                                d_tab.as<uint32_t>(), nullptr, d_tab.as<uint32_t>(), p_res, 1,
+                                                (uint32_t)in_len, accel);
+    }
+    if (rc != 0) return rc;
+    int64_t result = 0;
+    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
+    if (!load && result > 0) {
+        if ((uint64_t)result > dst_cap) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
+        if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    }
+    // the table is the reference's after the call on every exit (unchanged ones included)
+    if (hipMemcpy(table, d_tab.p, tbytes, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return result;
+}
+
 // src/lz4hc.zig:1445 + :1464-1466 level normalisation, strategy table :72-86
 int32_t normalise_hc_level(int32_t level) {
     if (level < ZLZ4HC_CLEVEL_MIN) level = ZLZ4HC_CLEVEL_DEFAULT;
@@ -250,6 +303,19 @@ int64_t zlz4_decompress_safe_partial_using_dict(const uint8_t *src, size_t n, ui
     if (!dict && dict_len) return ZLZ4_ERR_INVALID_STATE;
     if (target > 0) return run_single(Op::DecompressDict, src, n, dst, target, 0, 0, dict, dict_len);
     return partial_target_zero(src, n);
+}
+
+int64_t zlz4_stream_load_dict(uint32_t *table, const uint8_t *dict, size_t dict_len) {   // src/lz4.zig:798-820
+    if (!table || (!dict && dict_len)) return ZLZ4_ERR_INVALID_STATE;
+    return run_stream_single(table, dict, dict_len, nullptr, 0, nullptr, 0, 0);
+}
+
+int64_t zlz4_stream_compress_fast_continue(uint32_t *table, const uint8_t *src, size_t n, uint8_t *dst, size_t cap,
+                                           uint32_t accel) {                  // src/lz4.zig:822-836
+    if (!table) return ZLZ4_ERR_INVALID_STATE;
+    if (n > ZLZ4_MAX_INPUT_SIZE) return ZLZ4_ERR_INPUT_TOO_LARGE;   // :823 (table untouched)
+    if (n == 0) return 0;                                           // :824
+    return run_stream_single(table, nullptr, 0, src, n, dst, cap, accel);
 }
 
 size_t zlz4_sizeof_state(void) { return 4096 * sizeof(uint32_t); }  // src/lz4.zig:524-526, :263-265
@@ -379,6 +445,31 @@ int32_t zlz4_batch_decompress_safe_using_dict(void *stream, const uint8_t *d_in,
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     return zlz4_launch_decompress_safe_using_dict((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off,
                                                   d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len);
+}
+
+int32_t zlz4_batch_load_dict(void *stream, const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                             uint32_t *d_tables, int64_t *d_result, uint32_t ndicts) {
+    if (ndicts == 0) return 0;
+    if (!d_dict_off || !d_dict_len || !d_tables || !d_result) return ZLZ4_ERR_INVALID_STATE;
+    if ((uintptr_t)d_tables & 15u) return ZLZ4_ERR_INVALID_STATE;   // the header's 16-byte table alignment
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_load_dict((hipStream_t)stream, d_dict, d_dict_off, d_dict_len, d_tables, d_result, ndicts);
+}
+
+int32_t zlz4_batch_compress_fast_continue(void *stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                          const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                          const uint32_t *d_out_cap, const uint32_t *d_table_in,
+                                          const uint32_t *d_table_idx, uint32_t *d_table_out, int64_t *d_result,
+                                          uint32_t nblocks, uint32_t max_in_len, uint32_t acceleration) {
+    if (nblocks == 0) return 0;
+    if (!d_table_in) return ZLZ4_ERR_INVALID_STATE;
+    if (d_table_idx && d_table_out == d_table_in) return ZLZ4_ERR_INVALID_STATE;   // in place needs identity indexing
+    // the kernel moves tables in 16-byte vectors (k_compress_fast, kSeed)
+    if (((uintptr_t)d_table_in | (uintptr_t)d_table_out) & 15u) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_compress_fast_continue((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
+                                              d_table_in, d_table_idx, d_table_out, d_result, nblocks, max_in_len,
+                                              acceleration);
 }
 
 size_t zlz4_batch_compress_hc_workspace(uint32_t nblocks, uint32_t max_in_len) {

@@ -103,12 +103,32 @@ __device__ __forceinline__ uint32_t extend_match(const uint8_t *__restrict__ src
 // bytes from memory (on text more than half of all candidates are false: 4096 slots, 64 Ki positions).  A tag mismatch
 // implies a 4-byte mismatch, so no decision changes.  1 = a separate u8 array beside the u16 table (12 KiB per
 // wavefront), 2 = packed into bits 24..31 of a u32 entry (positions < 2^24), 0 = none.
-template <typename T, int kTag>
+//
+// kSeed: Stream.compressFastContinue (src/lz4.zig:822-836).  compressFastWithHashTable (:624-748) is compressFast's
+// loop with the table starting from the stream's state instead of zeros, so the only differences are here:
+//   * block i starts from table d_table_in + idx[i] * 4096 (idx = d_table_idx, NULL = identity).  Every entry is read
+//     as a position in the CURRENT block (:656-659), so an entry v >= L = srcSize - 12 cannot pass `match < ip`
+//     (ip <= L) and is loaded as 0 (empty): no decision changes, and every loaded entry fits the u16 table and the
+//     24-bit positions of the kTag == 2 table.  (No block ever refers to the dictionary: a loaded dictionary only
+//     changes which in-block matches the greedy parse finds.)
+//   * table values are no longer always earlier positions: the window path tests `old < pos` as well (the generic
+//     path always did).
+//   * the final table goes to d_table_out + i * 4096 (NULL = not written): out[h] = final[h] if it differs from what
+//     was loaded, else the input value (re-read from memory).  A slot that differs was put by this block (a position
+//     below srcSize); an equal one is untouched or a re-put of the same position; position 0 is never put (Q1).  So
+//     entries this block could not use pass through unchanged.  Every exit that does not compress (InputTooLarge,
+//     InvalidState, 0..12 bytes, OutputTooSmall) passes the whole input table through, as the reference returns
+//     before its store (:823-827, :831).
+// The launcher never picks kTag == 1 (its tag array is left uninitialised) for seeded calls; kTag == 2 entries get the
+// tag of the current block's bytes at the loaded position.  d_table_in / d_table_out may be the same table (identity
+// indexing): each lane reads an entry before it writes it.
+template <typename T, int kTag, bool kSeed = false>
 __global__ __launch_bounds__(256) void k_compress_fast(
     const uint8_t *__restrict__ d_in, const uint64_t *__restrict__ d_in_off,
     const uint32_t *__restrict__ d_in_len, uint8_t *__restrict__ d_out,
     const uint64_t *__restrict__ d_out_off, const uint32_t *__restrict__ d_out_cap,
-    int64_t *__restrict__ d_result, uint32_t nblocks, uint32_t acceleration, uint32_t max_in_len) {
+    int64_t *__restrict__ d_result, uint32_t nblocks, uint32_t acceleration, uint32_t max_in_len,
+    const uint32_t *d_table_in, const uint32_t *__restrict__ d_table_idx, uint32_t *d_table_out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_in_wg = threadIdx.x >> 6;
@@ -141,12 +161,29 @@ __global__ __launch_bounds__(256) void k_compress_fast(
     } else if (src_size < kMfLimit + 1u) {                              // :302-304
         res = emit_last_literals(dst, dst_len, 0, src, src_size, lane);
     } else {
+        if constexpr (kSeed) {
+            // the stream's table (:830), entries >= L loaded as empty (see above)
+            const uint32_t L = src_size - kMfLimit;
+            const uint32_t tix = d_table_idx ? rfl(d_table_idx[blk]) : blk;
+            const u32x4 *seed4 = reinterpret_cast<const u32x4 *>(d_table_in + (uint64_t)tix * 4096u);
+            for (uint32_t k = lane; k < 1024u; k += 64u) {
+                const u32x4 v = seed4[k];
+                uint32_t e[4] = {v.x < L ? v.x : 0u, v.y < L ? v.y : 0u, v.z < L ? v.z : 0u, v.w < L ? v.w : 0u};
+                if (kTag == 2) {
+                    for (int q = 0; q < 4; q++)
+                        if (e[q]) e[q] |= ((ld32(src + e[q]) * kHashMul) >> 12 & 0xFFu) << 24;   // v < L: in bounds
+                }
+                for (int q = 0; q < 4; q++) table[4u * k + q] = (T)e[q];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        } else {
         // HashTable.init(): zero fill (:266-268)
         {
             u32x4 z = {0, 0, 0, 0};
             u32x4 *t4 = reinterpret_cast<u32x4 *>(lds_raw) + wave_in_wg * (4096u * sizeof(T) / 16u);
             const uint32_t n16 = 4096u * sizeof(T) / 16u;
             for (uint32_t k = lane; k < n16; k += 64u) t4[k] = z;
+        }
         }
         const uint32_t accel = acceleration < 1u ? 1u : (acceleration > 65537u ? 65537u : acceleration);   // :321
         const uint32_t cbase = accel > 64u ? accel : 64u;
@@ -205,10 +242,10 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 }
                 if (kTag == 2) told = old_e >> 24;
                 const uint32_t old = old_e & kPosMask;
-                // pre-window candidates: the old table value passes `match > 0`, `match < ip` (always) and
+                // pre-window candidates: the old table value passes `match > 0`, `match < ip` (always, unless seeded) and
                 // the distance test (:345-347); its bytes are gathered once for the whole window.  The gather is
                 // issued right away so that its latency overlaps the speculative put / read-back below.
-                const bool old_ok = wr && old > 0 && (old + kMaxDist >= pos) && (kTag == 0 || told == tg);
+                const bool old_ok = wr && old > 0 && (!kSeed || old < pos) && (old + kMaxDist >= pos) && (kTag == 0 || told == tg);
                 u32x4 cold = {0, 0, 0, 0};
                 if (old_ok) cold = ld128(src + old);
                 // the second compare level (bytes 16..47, below) is a round trip of its own behind the first -- unless it is
@@ -644,7 +681,14 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     found = true;
                     break;
                 }
-                if (bail_mask) { bailed = true; break; }                // :335-338 -> finishCompression
+                if (bail_mask) {                                        // :335-338 -> finishCompression
+                    if constexpr (kSeed) {
+                        // the final table is an output here: the last lane of every duplicate group holds the slot
+                        if (active && ((grp & ~lanes_below & ~lane_bit) == 0) && grp != lane_bit) table[h] = (T)mine;
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    }
+                    bailed = true; break;
+                }
                 // no match in 64 probes: all puts stand; fix duplicate groups so the last lane's position is stored
                 if (active && ((grp & ~lanes_below & ~lane_bit) == 0)) {
                     if (grp != lane_bit) table[h] = (T)mine;
@@ -682,14 +726,77 @@ __global__ __launch_bounds__(256) void k_compress_fast(
             if (end < L) { has_ins = true; F0 = end + 1u; }
             else { has_ins = false; F0 = L; }
         }
+        if constexpr (kSeed) {
+            // a match that ends at L - 1 leaves its put(anchor) (:732-736) pending when the loop ends (F0 = L): the final
+            // table is an output here, so it is applied
+            if (!failed && has_ins && F0 >= L && lane == 0) {
+                const uint32_t prod = ld32(src + anchor) * kHashMul;
+                table[prod >> 20] = (T)(kTag == 2 ? (anchor | ((prod >> 12 & 0xFFu) << 24)) : anchor);
+            }
+        }
         res = failed ? kErrOutputTooSmall
                      : emit_last_literals(dst, dst_len, op, src + anchor, src_size - anchor, lane);   // :337, :446
         STAMP(7);   // tail
         STAMP_FLUSH;
     }
+    if constexpr (kSeed) {
+        // Stream.hashTable after the call (:830-833): merged where this block compressed, else the input table
+        if (d_table_out) {
+            const uint32_t tix = d_table_idx ? rfl(d_table_idx[blk]) : blk;
+            const uint32_t *seed = d_table_in + (uint64_t)tix * 4096u;
+            uint32_t *out = d_table_out + (uint64_t)blk * 4096u;
+            const bool merged = src_size >= kMfLimit + 1u && src_size <= max_in_len && src_size <= kMaxInput && res >= 0;
+            if (merged) {
+                const uint32_t L = src_size - kMfLimit;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                for (uint32_t k = lane; k < 4096u; k += 64u) {
+                    const uint32_t v = seed[k];
+                    const uint32_t loaded = v < L ? v : 0u;
+                    const uint32_t f = (uint32_t)table[k] & kPosMask;
+                    out[k] = f != loaded ? f : v;
+                }
+            } else if (out != seed) {
+                const u32x4 *s4 = reinterpret_cast<const u32x4 *>(seed);
+                u32x4 *o4 = reinterpret_cast<u32x4 *>(out);
+                for (uint32_t k = lane; k < 1024u; k += 64u) o4[k] = s4[k];
+            }
+        }
+    }
     if (lane == 0) d_result[blk] = res;
 }
 
+// Stream.loadDict (src/lz4.zig:798-820), one workgroup per dictionary: the table of the last min(len, 64 KiB) bytes,
+// table[hash4(rd32(tail + i))] = i for i in [0, dictSize - 5] (:810-815; a dictionary of 4 bytes or fewer hashes
+// nothing).  "Last writer wins" is an LDS atomicMax per position (position 0 stores 0 = what the reference stores).  A
+// lane whose right neighbour has the same hash leaves the slot to it (the neighbour's position is larger), so a run of
+// one repeated byte, whose 64 Ki positions all share one slot, costs one atomic per wavefront instead of 64.
+__global__ __launch_bounds__(256) void k_load_dict(const uint8_t *__restrict__ d_dict, const uint64_t *__restrict__ d_dict_off,
+                                                   const uint32_t *__restrict__ d_dict_len, uint32_t *__restrict__ d_tables,
+                                                   int64_t *__restrict__ d_result, uint32_t ndicts) {
+    __shared__ uint32_t t[4096];
+    const uint32_t d = blockIdx.x;
+    if (d >= ndicts) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t len = d_dict_len[d];
+    const uint32_t size = len < 65536u ? len : 65536u;                  // :804
+    const uint8_t *tail = d_dict + d_dict_off[d] + (len - size);        // :805
+    for (uint32_t k = threadIdx.x; k < 4096u; k += blockDim.x) t[k] = 0;   // resetFast (:799)
+    __syncthreads();
+    if (size >= kMinMatch) {                                            // :810
+        const uint32_t n = size - kMinMatch;                            // :812  i < dictSize - MINMATCH
+        for (uint32_t base = threadIdx.x - lane; base < n; base += blockDim.x) {   // wave-uniform trip count
+            const uint32_t i = base + lane;
+            const bool act = i < n;
+            const uint32_t h = act ? hash4(ld32(tail + i)) : 0xFFFFFFFFu;  // :813
+            const uint32_t hr = shfl(h, lane + 1u);                     // (lane 63 reads lane 0: ignored below)
+            if (act && !(lane < 63u && hr == h)) atomicMax(&t[h], i);    // :814
+        }
+    }
+    __syncthreads();
+    uint32_t *out = d_tables + (uint64_t)d * 4096u;
+    for (uint32_t k = threadIdx.x; k < 4096u; k += blockDim.x) out[k] = t[k];
+    if (threadIdx.x == 0) d_result[d] = (int64_t)size;                  // :818
+}
 
 }  // namespace zlz4
 
@@ -709,7 +816,7 @@ extern "C" int zlz4_launch_compress_fast(hipStream_t stream, const uint8_t *d_in
 #define ZLZ4_LAUNCH_FAST(KERN, T, TAG, WPW, LDS)                                                                      \
     hipLaunchKernelGGL((zlz4::KERN<T, TAG>), dim3((nblocks + (WPW) - 1) / (WPW)), dim3(64 * (WPW)), (LDS),              \
                        stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, acceleration,  \
-                       max_in_len)
+                       max_in_len, nullptr, nullptr, nullptr)
     if (max_in_len <= 65536u + 11u) {
         // 8 KiB of table (+ 4 KiB of tags) per wavefront in LDS -> 20 (13) wavefronts per CU whatever the workgroup size;
         // one-wave workgroups measured 5 % faster than four-wave ones on MI355X (44.1 / 45.0 / 46.6 ms for 1 / 2 / 4 on
@@ -724,6 +831,34 @@ extern "C" int zlz4_launch_compress_fast(hipStream_t stream, const uint8_t *d_in
         else ZLZ4_LAUNCH_FAST(k_compress_fast, uint32_t, 0, wpw, wpw * 4096 * sizeof(uint32_t) + lds_pad);
     }
 #undef ZLZ4_LAUNCH_FAST
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+// Stream.compressFastContinue per block (see k_compress_fast, kSeed).  The same table widths as the launcher above, with
+// the tag packed into u32 entries; never the u16 table with a separate tag array (kTag == 1).
+extern "C" int zlz4_launch_compress_fast_continue(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                  const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                                  const uint32_t *d_out_cap, const uint32_t *d_table_in,
+                                                  const uint32_t *d_table_idx, uint32_t *d_table_out, int64_t *d_result,
+                                                  uint32_t nblocks, uint32_t max_in_len, uint32_t acceleration) {
+    if (nblocks == 0) return 0;
+    static const int tune_tag = [] { const char *e = zlz4_tune_env("ZLZ4_TUNE_TAG"); return e ? atoi(e) : -1; }();
+#define ZLZ4_LAUNCH_SEEDED(T, TAG)                                                                                      \
+    hipLaunchKernelGGL((zlz4::k_compress_fast<T, TAG, true>), dim3(nblocks), dim3(64), 4096 * sizeof(T), stream, d_in,   \
+                       d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, acceleration, max_in_len,      \
+                       d_table_in, d_table_idx, d_table_out)
+    if (max_in_len <= 65536u + 11u) ZLZ4_LAUNCH_SEEDED(uint16_t, 0);
+    else if (tune_tag != 0 && max_in_len <= (1u << 24)) ZLZ4_LAUNCH_SEEDED(uint32_t, 2);
+    else ZLZ4_LAUNCH_SEEDED(uint32_t, 0);
+#undef ZLZ4_LAUNCH_SEEDED
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_load_dict(hipStream_t stream, const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                     const uint32_t *d_dict_len, uint32_t *d_tables, int64_t *d_result, uint32_t ndicts) {
+    if (ndicts == 0) return 0;
+    hipLaunchKernelGGL(zlz4::k_load_dict, dim3(ndicts), dim3(256), 0, stream, d_dict, d_dict_off, d_dict_len, d_tables,
+                       d_result, ndicts);
     return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 

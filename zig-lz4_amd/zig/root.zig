@@ -17,6 +17,8 @@ extern "c" fn zlz4_decompress_safe(src: [*]const u8, src_len: usize, dst: [*]u8,
 extern "c" fn zlz4_decompress_safe_partial(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, target: usize) i64;
 extern "c" fn zlz4_decompress_safe_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4_decompress_safe_partial_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, target: usize, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4_stream_load_dict(table: *[LZ4_HASH_SIZE_U32]u32, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4_stream_compress_fast_continue(table: *[LZ4_HASH_SIZE_U32]u32, src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, acceleration: u32) i64;
 extern "c" fn zlz4_sizeof_state() usize;
 extern "c" fn zlz4_compress_fast_ext_state(state: [*]u8, state_len: usize, src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, acceleration: u32) i64;
 extern "c" fn zlz4_compress_dest_size(src: [*]const u8, dst: [*]u8, dst_cap: usize, src_size: *usize) i64;
@@ -27,6 +29,8 @@ extern "c" fn zlz4_compress_hc_ext_state(state: [*]u8, state_len: usize, src: [*
 extern "c" fn zlz4_batch_compress_fast(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_decompress_safe(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
 extern "c" fn zlz4_batch_decompress_safe_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: [*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
+extern "c" fn zlz4_batch_load_dict(stream: ?*anyopaque, d_dict: [*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_tables: [*]u32, d_result: [*]i64, ndicts: u32) i32;
+extern "c" fn zlz4_batch_compress_fast_continue(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_table_in: [*]const u32, d_table_idx: ?[*]const u32, d_table_out: ?[*]u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) usize;
 extern "c" fn zlz4_batch_compress_hc(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_verify(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_comp: [*]const u8, d_comp_off: [*]const u64, d_comp_result: [*]const i64, d_verify: [*]i64, nblocks: u32) i64;
@@ -56,6 +60,8 @@ pub const LZ4_DISTANCE_MAX = 65535;
 pub const LZ4HC_CLEVEL_MIN = 2;
 pub const LZ4HC_CLEVEL_DEFAULT = 9;
 pub const LZ4HC_CLEVEL_MAX = 12;
+/// Stream.hashTable entries (reference src/lz4.zig:33, :752)
+pub const LZ4_HASH_SIZE_U32 = 4096;
 
 /// reference src/lz4.zig:48-55 plus the two device-side additions
 pub const Error = error{
@@ -133,6 +139,103 @@ pub fn compressHCExtState(ctx: []u8, src: []const u8, dst: []u8, compressionLeve
     return mapBlock(zlz4_compress_hc_ext_state(ctx.ptr, ctx.len, src.ptr, src.len, dst.ptr, dst.len, compressionLevel));
 }
 
+/// reference src/lz4.zig:744-748 (carried, never read, as in the reference)
+const TableType = enum(u32) {
+    byU32 = 1,
+    byU16 = 2,
+    byPtr = 3,
+};
+
+/// The streaming compressor, reference src/lz4.zig:751-856: same fields and methods.  loadDict and compressFastContinue
+/// compute the table on the device (zlz4_stream_load_dict / zlz4_stream_compress_fast_continue); the rest is host
+/// bookkeeping.  The reference reads every table entry as a position in the CURRENT block (:656-659), so a loaded
+/// dictionary only changes which in-block matches are found: no block refers to it, every block decodes with plain
+/// decompressSafe, and saveDict copies the loaded dictionary, not the compressed history.  Reproduced as is.
+pub const Stream = struct {
+    hashTable: [LZ4_HASH_SIZE_U32]u32,
+    dictionary: ?[]const u8,
+    dictCtx: ?*const Stream,
+    currentOffset: u32,
+    tableType: TableType,
+    dictSize: u32,
+    allocator: ?std.mem.Allocator,
+
+    /// reference :761-766
+    pub fn create(allocator: std.mem.Allocator) Error!*Stream {
+        const stream = allocator.create(Stream) catch return error.AllocationFailed;
+        stream.* = init();
+        stream.allocator = allocator;
+        return stream;
+    }
+    /// reference :769-773
+    pub fn destroy(self: *Stream) void {
+        if (self.allocator) |alloc| {
+            alloc.destroy(self);
+        }
+    }
+    /// reference :776-786
+    pub fn init() Stream {
+        return .{
+            .hashTable = [_]u32{0} ** LZ4_HASH_SIZE_U32,
+            .dictionary = null,
+            .dictCtx = null,
+            .currentOffset = 0,
+            .tableType = .byU32,
+            .dictSize = 0,
+            .allocator = null,
+        };
+    }
+    /// reference :789-795
+    pub fn resetFast(self: *Stream) void {
+        @memset(&self.hashTable, 0);
+        self.dictionary = null;
+        self.dictCtx = null;
+        self.currentOffset = 0;
+        self.dictSize = 0;
+    }
+    /// reference :798-820.  The signature has no error union; a missing device is a loud failure, never a silently
+    /// empty table.
+    pub fn loadDict(self: *Stream, dict: []const u8) usize {
+        self.resetFast();
+        const r = zlz4_stream_load_dict(&self.hashTable, dict.ptr, dict.len);
+        if (r < 0) @panic("Stream.loadDict: libzlz4_amd has no usable gfx950 device");
+        const dictSize: usize = @intCast(r);
+        if (dictSize > 0) {
+            self.dictionary = dict[dict.len - dictSize ..];
+            self.dictSize = @intCast(dictSize);
+        }
+        return dictSize;
+    }
+    /// reference :822-836: the table changes only when a block of 13 or more bytes compresses
+    pub fn compressFastContinue(self: *Stream, src: []const u8, dst: []u8, acceleration: u32) Error!usize {
+        const result = try mapBlock(zlz4_stream_compress_fast_continue(&self.hashTable, src.ptr, src.len, dst.ptr, dst.len, acceleration));
+        if (src.len >= 13) self.currentOffset +|= @intCast(src.len);
+        return result;
+    }
+    /// reference :839-855
+    pub fn saveDict(self: *Stream, safeBuffer: []u8, maxDictSize: usize) usize {
+        if (maxDictSize == 0) return 0;
+        if (self.dictionary == null) return 0;
+        const dict = self.dictionary.?;
+        const dictSize = @min(@min(dict.len, maxDictSize), 64 * 1024);
+        if (dictSize > safeBuffer.len) {
+            const copySize = @min(dictSize, safeBuffer.len);
+            @memcpy(safeBuffer[0..copySize], dict[dict.len - copySize ..]);
+            return copySize;
+        }
+        @memcpy(safeBuffer[0..dictSize], dict[dict.len - dictSize ..]);
+        return dictSize;
+    }
+};
+/// reference src/lz4.zig:858-860
+pub fn createStream(allocator: std.mem.Allocator) Error!*Stream {
+    return Stream.create(allocator);
+}
+/// reference src/lz4.zig:863-865
+pub fn freeStream(stream: *Stream) void {
+    stream.destroy();
+}
+
 /// `@import("lz4").lz4.compressDefault(...)` and `.lz4hc.compressHC(...)` keep working (reference src/root.zig:3-5)
 const root = @This();
 pub const lz4 = struct {
@@ -150,6 +253,10 @@ pub const lz4 = struct {
     pub const decompressSafePartialUsingDict = root.decompressSafePartialUsingDict;
     pub const sizeofState = root.sizeofState;
     pub const compressFastExtState = root.compressFastExtState;
+    pub const LZ4_HASH_SIZE_U32 = root.LZ4_HASH_SIZE_U32;
+    pub const Stream = root.Stream;
+    pub const createStream = root.createStream;
+    pub const freeStream = root.freeStream;
 };
 pub const lz4hc = struct {
     pub const LZ4HC_CLEVEL_MIN = 2;
@@ -188,6 +295,22 @@ pub const device = struct {
     /// batch form of decompressSafe (src/lz4.zig:257-259)
     pub fn decompressSafeBatch(stream: ?*anyopaque, b: Blocks) Error!void {
         return mapLaunch(zlz4_batch_decompress_safe(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks));
+    }
+    /// batch form of Stream.loadDict (src/lz4.zig:798-820): table i of `tables` (LZ4_HASH_SIZE_U32 u32 each) receives
+    /// the table of dict[dict_off[i] ..][0..dict_len[i]]; result[i] = dictSize
+    pub fn loadDictBatch(stream: ?*anyopaque, dict: [*]const u8, dict_off: [*]const u64, dict_len: [*]const u32, tables: [*]u32, result: [*]i64, ndicts: u32) Error!void {
+        return mapLaunch(zlz4_batch_load_dict(stream, dict, dict_off, dict_len, tables, result, ndicts));
+    }
+    /// Stream tables of `compressFastContinueBatch`: block i starts from table table_idx[i] of table_in (null = table i)
+    /// and its final table goes to table i of table_out (null = not written; may equal table_in when table_idx is null)
+    pub const StreamTables = struct {
+        table_in: [*]const u32,
+        table_idx: ?[*]const u32 = null,
+        table_out: ?[*]u32 = null,
+    };
+    /// batch form of Stream.compressFastContinue (src/lz4.zig:822-836); every in_len[i] <= max_in_len
+    pub fn compressFastContinueBatch(stream: ?*anyopaque, b: Blocks, t: StreamTables, max_in_len: u32, acceleration: u32) Error!void {
+        return mapLaunch(zlz4_batch_compress_fast_continue(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, t.table_in, t.table_idx, t.table_out, b.result, b.nblocks, max_in_len, acceleration));
     }
     pub fn compressHCWorkspace(nblocks: u32, max_in_len: u32) usize {
         return zlz4_batch_compress_hc_workspace(nblocks, max_in_len);
