@@ -27,9 +27,11 @@ stamps: $(HIPSRC) $(CSRC)/zlz4_device.hpp $(CSRC)/zlz4_host.hpp include/zlz4_amd
 oracle:
 	$(MAKE) -C oracle
 
-# audit of the decoder's hand-issued loads (see tools/check_decoder_asm.py); run after any toolchain / flag change
+# audit of the hand-issued loads of the decoder and of the fast compressor's input ring (tools/check_decoder_asm.py,
+# tools/check_compress_ring_asm.py); run after any toolchain / flag change
 check-asm:
 	python3 tools/check_decoder_asm.py
+	python3 tools/check_compress_ring_asm.py
 
 clean:
 	rm -f $(LIB) $(TUNELIB)

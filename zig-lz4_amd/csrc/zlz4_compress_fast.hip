@@ -203,9 +203,83 @@ __global__ __launch_bounds__(256) void k_compress_fast(
         // a window keeps going to its last lane (handing over to the next window earlier, once it holds a match, was
         // measured at every lane: 49 -> 55.6 ms, 64 -> 46.8 ms on configs[1]; any choice gives the same bytes)
         uint32_t guard = 0;      // every round of this loop consumes at least one input byte
-        // forward bytes of the next window, loaded as soon as its anchor is known (before the emission and the table
-        // fix-up of the current window, which hide the load)
+
+        // Input ring of the window path: register k, lane l holds the dword at src + rbase + 256k + 4l (ring_q: at the end
+        // of the block).  r0 and r1 cover [rbase, rbase + 512), r2 the next 256 bytes and is in flight.  A window
+        // at A reads [A, A + 111) (16 forward bytes and 32 more for the second compare level, lanes 0..63); with
+        // A - rbase < 256 that lies in r0 / r1, and it lies below src_size because the window path stops at A + 192 >= L.
+        // The ring moves by 256 bytes when A - rbase reaches 256 (a window advances ~72 bytes, so r2 was issued three
+        // or more windows earlier) and is reloaded when A has jumped further or the generic path ran in between.
+        // (the 16 forward bytes of every window used to be a load of their own at its top: a trip through the CU's
+        //  vector-memory address path behind the other wavefronts' gathers, on the chain that leads to the hash)
+        // (the ring's offset lives in a VGPR, lane l = rbase + 4l, its own dword's offset: the scalar registers are full)
+        // Only the u16 builds (blocks <= 65 547 bytes, 20 wavefronts per CU) have it.  The u32 builds run larger blocks
+        // at as little as one wavefront per SIMD, where the permutes are latency that nothing overlaps: 1024 x 4 MiB
+        // took 4.8 % longer with the ring (their second level is already fetched early, kGuess2 below).
+        constexpr bool kRing = sizeof(T) == 2;
+        uint32_t rpos = 0x80000000u + 4u * lane;                        // A - rbase >= 512 for every A: empty
+        uint32_t r0 = 0, r1 = 0, r2 = 0;
+        // lane's dword at q; a lane whose dword would reach past src_size reads the block's last dword instead (never
+        // used: a window only reads below A + 111)
+        // (the bound src_size - 4 is kept in a VGPR: as a loop invariant the compiler would give it a scalar register)
+        uint32_t ring_lim = 0;
+        if constexpr (kRing) asm volatile("v_mov_b32 %0, %1" : "=v"(ring_lim) : "s"(src_size - 4u));
+        auto ring_q = [&](uint32_t q) -> uint32_t { return q < ring_lim ? q : ring_lim; };
+        // W: lane l = the dword at src + (A & ~3) + 4l, i.e. the window's bytes from 4-byte-aligned A on (one select and
+        // one ds_bpermute over r0 / r1; moves or reloads the ring first)
+        auto ring_win = [&](uint32_t A) -> uint32_t {
+            uint32_t rel = rfl(A - rpos);                               // A - rbase (lane 0)
+            if (rel >= 256u) {
+                // The ring's loads are issued by hand, move and reload in one statement: the compiler carries the ring
+                // around the loop with copies, and waits for a load at the first copy of its register, i.e. at once.
+                // Here r2 stays in its register until the next statement's wait (tools/check_compress_ring_asm.py
+                // audits that no instruction reads, copies or spills it on any path before a wait that covers it).
+                // A reload waits for r0 / r1 on the spot: where long matches make the anchor jump past the ring at
+                // most windows (D-reptext) that wait is not hidden, and the ring costs 2.8 % there
+                // (profiles/r06_compress_ring.md: the variants that hid it lost more elsewhere).
+                const bool reload = rel >= 512u;
+                const uint32_t nb = reload ? (A & ~127u) + 4u * lane : rpos + 256u;
+                asm volatile("s_waitcnt vmcnt(0)\n\t"               // the previous r2
+                             "s_cmpk_lt_u32 %[rel], 0x200\n\t"   // move
+                             "s_cbranch_scc1 1f\n\t"
+                             "global_load_dword %[r0], %[q0], %[src]\n\t"
+                             "global_load_dword %[r1], %[q1], %[src]\n\t"
+                             "s_waitcnt vmcnt(0)\n\t"
+                             "s_branch 2f\n"
+                             "1:\n\t"
+                             "v_mov_b32 %[r0], %[r1]\n\t"
+                             "v_mov_b32 %[r1], %[r2]\n"
+                             "2:\n\t"
+                             "global_load_dword %[r2], %[q2], %[src]"
+                             : [r0] "+v"(r0), [r1] "+v"(r1), [r2] "+v"(r2)
+                             : [rel] "s"(rel), [q0] "v"(ring_q(nb)), [q1] "v"(ring_q(nb + 256u)), [q2] "v"(ring_q(nb + 512u)),
+                               [src] "s"(src)
+                             : "scc", "memory");
+                rpos = nb;
+                rel = reload ? A & 127u : rel - 256u;
+            }
+            const uint32_t s0 = rel >> 2;
+            return shfl(lane >= s0 ? r0 : r1, (s0 + lane) & 63u);
+        };
+        // dwords k0 .. k0+n-1 of the bytes at A + lane (+ 4 k), from the window register W of A
+        auto win_bytes = [&](uint32_t W, uint32_t A, uint32_t k0, uint32_t *out, uint32_t n) {
+            const uint32_t o = (A & 3u) + lane, jw = (o >> 2) + k0;   // jw + n <= 16 + 4 + 8 < 64
+            uint32_t lo = shfl(W, jw);
+            for (uint32_t k = 0; k < n; k++) {
+                const uint32_t hi = shfl(W, jw + k + 1u);
+                out[k] = __builtin_amdgcn_alignbyte(hi, lo, o & 3u);
+                lo = hi;
+            }
+        };
+        auto ring_fwd = [&](uint32_t W, uint32_t A) -> u32x4 {
+            uint32_t d[4];
+            win_bytes(W, A, 0u, d, 4u);
+            return u32x4{d[0], d[1], d[2], d[3]};
+        };
+        // forward bytes of the next window, taken from the ring (u32: loaded) as soon as its anchor is known (before the
+        // emission and the table fix-up of the current window, which hide the permutes)
         u32x4 fwd_pf = {0, 0, 0, 0};
+        uint32_t w_pf = 0;
         uint32_t pf_anchor = 0xFFFFFFFFu;
         while (F0 < L) {                                                // :320
             if (++guard > src_size) { failed = true; break; }           // unreachable; never spin on the GPU
@@ -215,8 +289,9 @@ __global__ __launch_bounds__(256) void k_compress_fast(
             // Window path (acceleration 1, away from the end of the block): lane i <-> position
             // anchor + i.  Every search that starts inside the window probes consecutive positions
             // (the first 66 probes of a search have stride 1), so all sequences that begin in these
-            // 64 positions are resolved from registers: one 16-byte forward load per lane, one table
-            // read / speculative put / read-back, one candidate gather -- then one short loop
+            // 64 positions are resolved from registers: 16 forward bytes per lane from the input ring
+            // (u16; six ds_bpermute, no memory) or one 16-byte load (u32), one table read / speculative put /
+            // read-back, one candidate gather -- then one short loop
             // iteration per sequence.  `ins` = lanes the serial loop would have put() so far; a lane's
             // table read is its nearest earlier `ins` lane with the same hash, else the pre-window
             // value.  At the end lanes not in `ins` put their old value back.
@@ -228,7 +303,12 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 const uint32_t A = anchor;
                 const uint32_t pos = A + lane;
                 const bool wr = has_ins || lane > 0;                    // position 0 is never inserted (Q1)
-                const u32x4 fwd = (pf_anchor == A) ? fwd_pf : ld128(src + pos);
+                if (kRing && pf_anchor != A) {
+                    w_pf = ring_win(A);
+                    fwd_pf = ring_fwd(w_pf, A);
+                }
+                const uint32_t W = w_pf;
+                const u32x4 fwd = (kRing || pf_anchor == A) ? fwd_pf : ld128(src + pos);
                 const uint32_t prod = fwd.x * kHashMul;
                 const uint32_t h = prod >> 20;                          // :341
                 const uint32_t tg = (prod >> 12) & 0xFFu;
@@ -255,13 +335,14 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 // (blocks > 64 KiB only: few large blocks leave the chip to one wavefront per SIMD, where the round trip is
                 //  what counts -- 1024 x 4 MiB 121.5 -> 118.9 ms; with 20 wavefronts per CU the extra requests cost more
                 //  than the round trip, configs[1] 41.3 -> 41.6 ms, D-reptext 58.9 -> 60.3 ms)
+                // (u16: the forward side, bytes 16..47 at pos, comes from the input ring when it is needed)
                 constexpr bool kGuess2 = sizeof(T) == 4;
                 const uint32_t old12 = kGuess2 ? shfl(old, (lane + 12u) & 63u) : 0u;
                 const bool pred2 = kGuess2 && old_ok && lane < 52u && old12 == old + 12u;
                 u32x4 f2 = {0, 0, 0, 0}, c2 = f2, f3 = f2, c3 = f2;
                 if (pred2) {
-                    f2 = ld128(src + pos + 16u); c2 = ld128(src + old + 16u);
-                    f3 = ld128(src + pos + 32u); c3 = ld128(src + old + 32u);
+                    if (!kRing) { f2 = ld128(src + pos + 16u); f3 = ld128(src + pos + 32u); }
+                    c2 = ld128(src + old + 16u); c3 = ld128(src + old + 32u);
                 }
                 STAMP(3);
                 if (wr) table[h] = (T)mine;                             // :350 (speculative)
@@ -293,9 +374,15 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 // second level: the few lanes whose 16 bytes all match compare 16 more (matches of 16..31 bytes are a
                 // fifth of all sequences on text; without this each of them costs an exact step and its own emission)
                 const bool need2 = vo && mlo == 12u;
-                if (need2 && !pred2) {                        // (all four loads in one round trip)
-                    f2 = ld128(src + pos + 16u); c2 = ld128(src + old + 16u);
-                    f3 = ld128(src + pos + 32u); c3 = ld128(src + old + 32u);
+                if (need2 && !pred2) {                        // (all loads in one round trip)
+                    if (!kRing) { f2 = ld128(src + pos + 16u); f3 = ld128(src + pos + 32u); }
+                    c2 = ld128(src + old + 16u); c3 = ld128(src + old + 32u);
+                }
+                if (kRing && ballot(need2)) {                 // (wave-uniform: the permutes read every lane of W)
+                    uint32_t d[8];
+                    win_bytes(W, A, 4u, d, 8u);
+                    f2 = u32x4{d[0], d[1], d[2], d[3]};
+                    f3 = u32x4{d[4], d[5], d[6], d[7]};
                 }
                 if (need2) {
                     const uint32_t d2 = first_diff16_sel(f2, c2);
@@ -532,7 +619,12 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 const bool next_win = !continue_generic && !failed && a != 0u && (uint64_t)A + a + 192u < L;
                 if (next_win) {
                     pf_anchor = A + a;
-                    fwd_pf = ld128(src + pf_anchor + lane);
+                    if constexpr (kRing) {
+                        w_pf = ring_win(pf_anchor);
+                        fwd_pf = ring_fwd(w_pf, pf_anchor);
+                    } else {
+                        fwd_pf = ld128(src + pf_anchor + lane);
+                    }
                 }
                 if (mm_run && !failed) flush_run();
                 anchor = A + a;
@@ -726,6 +818,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
             if (end < L) { has_ins = true; F0 = end + 1u; }
             else { has_ins = false; F0 = L; }
         }
+        if constexpr (kRing) asm volatile("s_waitcnt vmcnt(0)" : "+v"(r2));   // (the ring's last load, before the wave can end)
         if constexpr (kSeed) {
             // a match that ends at L - 1 leaves its put(anchor) (:732-736) pending when the loop ends (F0 = L): the final
             // table is an output here, so it is applied
