@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "liblz4_oracle.so")
 
 UNSUPPORTED_LEVEL = -1005
+OUTPUT_TOO_SMALL = -1                  # ZO_ERR_OUTPUT_TOO_SMALL (lz4_oracle.h)
 
 
 class Prefs(C.Structure):
@@ -87,9 +88,15 @@ def compress_bound(n):
     return lib().zo_compress_bound(n)
 
 
+def _slack(cap):
+    """destination bytes allocated for a limit of `cap`: the restated compressHashChain / compressMID / compressOptimal
+    write the final run's length-extension bytes past `cap` unchecked (DESIGN.md section 2), at most cap // 255 + 1"""
+    return cap + cap // 255 + 64
+
+
 def _call(fn, src, cap, *extra):
     s, n = _buf(src)
-    d = (C.c_uint8 * max(1, cap))()
+    d = (C.c_uint8 * _slack(cap))()
     r = fn(C.addressof(s), n, C.addressof(d), cap, *extra)
     if r < 0:
         return r
@@ -109,6 +116,17 @@ def compress_fast(src, accel, cap=None):
 def compress_hc(src, level, cap=None):
     cap = compress_bound(len(src)) if cap is None else cap
     return _call(lib().zo_compress_hc, src, cap, level)
+
+
+def compress_hc_expected(src, level, cap=None):
+    """what compressHC(src, dst[:cap], level) returns on this project: the restatement's result, except that a result
+    longer than `cap` (the reference overran dst with the final run's length-extension bytes) is OutputTooSmall,
+    as the kernels return"""
+    r = compress_hc(src, level, cap)
+    cap = compress_bound(len(src)) if cap is None else cap
+    if not isinstance(r, int) and len(r) > cap:
+        return OUTPUT_TOO_SMALL
+    return r
 
 
 def hc_reference_ub(reset=True):

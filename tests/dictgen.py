@@ -119,25 +119,23 @@ def crafted_cases():
     return cases
 
 
-def run_batch(zl, items, caps, dicts, dict_index, dev):
+def run_batch(zl, items, caps, dicts, dict_index, dev, layout=None):
     """zlz4_batch_decompress_safe_using_dict on one batch: block i decodes items[i] into a slot of capacity caps[i]
     with the dictionary dicts[dict_index[i]] (dicts are stored once each: equal indices share one copy).  Checks that
-    no slot is written past its capacity and that the dictionary arena is unchanged.  -> [(result, bytes)]"""
+    no slot is written past its capacity and that the input and dictionary arenas are unchanged.  `layout`
+    (gpu_harness.Packed) packs the streams, the dictionaries and the output slots at unaligned offsets.
+    -> [(result, bytes)]"""
     import numpy as np
     import torch
     import gpu_harness as gh
-    buf, offs, lens = gh._pack(items)
-    dbuf, doffs, dlens = gh._pack(dicts)
+    buf, offs, lens = gh._pack(items, layout=layout)
+    dbuf, doffs, dlens = gh._pack(dicts, layout=layout)
     caps = np.asarray(caps, dtype=np.int64)
-    out_offs = np.zeros(len(items), dtype=np.int64)
-    pos = 0
-    for i, c in enumerate(caps):
-        out_offs[i] = pos
-        pos += (int(c) + 15) // 16 * 16 + 64
+    out_offs, guard_ends, total = gh._out_slots(caps, layout)
     idx = np.asarray(dict_index, dtype=np.int64)
     d_in = torch.from_numpy(buf).to(dev)
     d_dict = torch.from_numpy(dbuf).to(dev)
-    d_out = torch.full((max(pos, 16),), 0xA5, dtype=torch.uint8, device=dev)
+    d_out = torch.full((total,), 0xA5, dtype=torch.uint8, device=dev)
     res = torch.full((len(items),), -999, dtype=torch.int64, device=dev)
     u32 = lambda a: torch.from_numpy(np.asarray(a).astype(np.uint32).view(np.int32)).to(dev)
     zl.batch_decompress_safe_using_dict(d_in, torch.from_numpy(offs).to(dev), u32(lens), d_out,
@@ -145,12 +143,5 @@ def run_batch(zl, items, caps, dicts, dict_index, dev):
                                         torch.from_numpy(doffs[idx]).to(dev), u32(dlens[idx]), res)
     torch.cuda.synchronize()
     assert (d_dict.cpu().numpy() == dbuf).all(), "the dictionary arena changed"
-    r = res.cpu().numpy()
-    o = d_out.cpu().numpy()
-    outs = []
-    for i in range(len(items)):
-        n = int(r[i])
-        guard = o[out_offs[i] + int(caps[i]): out_offs[i] + (int(caps[i]) + 15) // 16 * 16 + 64]
-        assert (guard == 0xA5).all(), "block %d wrote past its capacity" % i
-        outs.append((n, bytes(o[out_offs[i]: out_offs[i] + n]) if n > 0 else b""))
-    return outs
+    assert (d_in.cpu().numpy() == buf).all(), "the input arena changed"
+    return gh._collect(res, d_out, out_offs, guard_ends, caps)

@@ -4,7 +4,6 @@ offsets with the last one ending at the end of the input buffer, sizes around th
 blocks > 64 KiB (u32 table with tags), and seeded stream blocks."""
 import numpy as np
 import pytest
-import torch
 
 import datagen as dg
 import gpu_harness as gh
@@ -17,39 +16,8 @@ GENS = (dg.text_bytes, dg.reptext_bytes, dg.mixed_bytes, dg.zero_bytes, dg.rando
 
 def _compress_tight(zl, items, dev, caps=None, seed=0):
     """batch_compress_fast over blocks packed back to back at odd offsets (gaps of 1..3 bytes), the input tensor ending
-    exactly where the last block ends; output slots with 64-byte guard bands.  -> [(status, bytes)]"""
-    rng = np.random.default_rng(seed)
-    caps = [zl.compressBound(len(b)) for b in items] if caps is None else caps
-    offs, pos = [], 1
-    for b in items:
-        offs.append(pos)
-        pos += len(b) + int(rng.integers(1, 4))
-    offs_a = np.array(offs, dtype=np.int64)
-    total = offs[-1] + len(items[-1])
-    buf = np.zeros(total, dtype=np.uint8)
-    for o, b in zip(offs, items):
-        buf[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
-    out_offs, opos = [], 0
-    for c in caps:
-        out_offs.append(opos)
-        opos += (c + 15) // 16 * 16 + 64
-    d_in = torch.from_numpy(buf).to(dev)
-    d_out = torch.full((max(opos, 16),), 0xA5, dtype=torch.uint8, device=dev)
-    lens = np.array([len(b) for b in items], dtype=np.uint32).view(np.int32)
-    res = torch.full((len(items),), -999, dtype=torch.int64, device=dev)
-    zl.batch_compress_fast(d_in, torch.from_numpy(offs_a).to(dev), torch.from_numpy(lens).to(dev), d_out,
-                           torch.from_numpy(np.array(out_offs, dtype=np.int64)).to(dev),
-                           torch.from_numpy(np.array(caps, dtype=np.uint32).view(np.int32)).to(dev), res,
-                           max(len(b) for b in items), 1)
-    torch.cuda.synchronize()
-    r, o = res.cpu().numpy(), d_out.cpu().numpy()
-    outs = []
-    for i, c in enumerate(caps):
-        g = o[out_offs[i] + c: out_offs[i] + (c + 15) // 16 * 16 + 64]
-        assert (g == 0xA5).all(), "block %d wrote past its capacity" % i
-        n = int(r[i])
-        outs.append((n, bytes(o[out_offs[i]: out_offs[i] + n]) if n > 0 else b""))
-    return outs
+    exactly where the last block ends; output slots with guard bands (gpu_harness.Packed).  -> [(status, bytes)]"""
+    return gh.compress_fast(zl, items, dev, caps=caps, layout=gh.Packed(seed, gaps=(1, 3)))
 
 
 def _cmp(got, want, names):
