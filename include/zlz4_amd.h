@@ -308,6 +308,45 @@ int64_t zlz4f_decompress_frame_segment_device(void *stream, const uint8_t *d_src
                                               uint8_t *d_dst, size_t dst_cap, const zlz4f_prefs *prefs,
                                               uint32_t segment_flags);
 
+/* Batch frames, DEVICE pointers: N independent frames in one launch sequence.  Frame f reads d_src + d_src_off[f]
+ * (d_src_len[f] bytes) and writes d_dst + d_dst_off[f] (capacity d_dst_cap[f]); d_result[f] receives what
+ * zlz4f_compress_frame_device / zlz4f_decompress_frame_device return for that frame alone (frame size, decompressed
+ * size or the frame's error code).  Same contract as the block batch calls of section 2: all pointers are device
+ * pointers, kernels are enqueued on `stream` and the call returns without synchronising; nothing is allocated and
+ * nothing is read back, so both calls can be captured into a hipGraph.  Return: 0, ZLZ4_ERR_DEVICE, or
+ * ZLZ4_ERR_INVALID_STATE when the workspace is smaller than its size function says (then nothing is launched).
+ * Output slots must not overlap each other or any source.  Bytes inside a failed frame's slot are unspecified; no byte
+ * outside [d_dst_off[f], d_dst_off[f] + d_dst_cap[f]) is ever written.
+ *
+ * max_blocks is the capacity of the block table that all frames share.  Blocks are numbered in frame order; a frame
+ * with blocks whose numbers do not all fall below max_blocks gets ZLZ4_ERR_INVALID_STATE and nothing is written for
+ * it (a frame without blocks needs no entries).  Earlier frames are unaffected.  Compress: a frame has
+ * ceil(src_len[f] / block size) blocks.  Decompress: what the frame's block chain holds, found on the device.
+ *
+ * Compress: `prefs` is shared by the batch (block size, checksums, dict_id, level routing of compressFrame: fast with
+ * acceleration 1 for level <= 0, compressHC with the level clamped otherwise).  Without ZLZ4F_BATCH_CONTENT_SIZE
+ * prefs->content_size goes into every header as given; with it prefs->content_size must be 0 (else
+ * ZLZ4F_ERR_PARAMETER_INVALID) and frame f carries src_len[f] as its content size (none for an empty frame).  A frame
+ * whose d_dst_cap[f] < zlz4f_compress_frame_bound(src_len[f], prefs) gets ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL
+ * (src/lz4f.zig:363-366).  The workspace holds the block table, a compressBound-sized slot per entry and, for
+ * compression_level > 0, the HC workspace of max_blocks blocks.
+ * Decompress: every parameter comes from the frame's own header, so one batch may mix frames of any block size and
+ * checksum flags (compressFrame, the lz4 CLI); error order of src/lz4f.zig:541-638 per frame. */
+#define ZLZ4F_BATCH_CONTENT_SIZE 1u   /* batch_flags: frame f's header carries src_len[f] as its content size */
+size_t  zlz4f_batch_compress_frame_workspace(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs);
+int32_t zlz4f_batch_compress_frame(void *stream,
+                                   const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                   uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                                   int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                   const zlz4f_prefs *prefs, uint32_t batch_flags, void *d_workspace,
+                                   size_t workspace_bytes);
+size_t  zlz4f_batch_decompress_frame_workspace(uint32_t nframes, uint32_t max_blocks);
+int32_t zlz4f_batch_decompress_frame(void *stream,
+                                     const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                     uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                                     int64_t *d_result, uint32_t nframes, uint32_t max_blocks, void *d_workspace,
+                                     size_t workspace_bytes);
+
 /* ======================================================================
  * 4. Introspection
  * ====================================================================== */

@@ -85,6 +85,10 @@ SYMBOLS = {
     "zlz4f_decompress_frame_device": (_I64, [_VP, _VP, _SZ, _VP, _SZ]),
     "zlz4f_compress_frame_segment_device": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _PP, _U32]),
     "zlz4f_decompress_frame_segment_device": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _PP, _U32]),
+    "zlz4f_batch_compress_frame_workspace": (_SZ, [_U32, _U32, _PP]),
+    "zlz4f_batch_compress_frame": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _PP, _U32, _VP, _SZ]),
+    "zlz4f_batch_decompress_frame_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_decompress_frame": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -363,6 +367,124 @@ class lz4f:
     def decompressFrameSegmentDevice(d_seg, seg_len, d_dst, prefs, seg_flags):
         return _check(lib().zlz4f_decompress_frame_segment_device(_stream(), _ptr(d_seg), seg_len, _ptr(d_dst), d_dst.numel(),
                                                                   C.byref(prefs) if prefs is not None else None, seg_flags))
+
+    # batch frames (include/zlz4_amd.h section 3): N independent frames per call, device descriptors, asynchronous
+    BATCH_CONTENT_SIZE = 1
+    BLOCK_SIZES = {0: 64 << 10, 4: 64 << 10, 5: 256 << 10, 6: 1 << 20, 7: 4 << 20}     # BlockSizeID.toBlockSize
+
+    @staticmethod
+    def compressFrameBatchWorkspace(nframes, max_blocks, prefs=None):
+        return lib().zlz4f_batch_compress_frame_workspace(nframes, max_blocks, C.byref(prefs) if prefs is not None else None)
+
+    @staticmethod
+    def decompressFrameBatchWorkspace(nframes, max_blocks):
+        return lib().zlz4f_batch_decompress_frame_workspace(nframes, max_blocks)
+
+    @staticmethod
+    def compressFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, prefs=None, batch_flags=0,
+                           max_blocks=None, workspace=None):
+        """zlz4f_batch_compress_frame on torch CUDA tensors: d_src / d_dst uint8, src_off / src_len / dst_off / dst_cap
+        int64 (one entry per frame), result int64 (frame size or the frame's error code).  max_blocks defaults to the
+        total block count of the lengths (read back once), workspace to a fresh buffer of the size the library asks for.
+        Enqueued on the current stream; nothing is synchronised."""
+        import torch
+        if max_blocks is None:
+            bs = lz4f.BLOCK_SIZES.get(prefs.block_size_id if prefs is not None else 0, 64 << 10)
+            max_blocks = int(((src_len.cpu() + bs - 1) // bs).sum()) if src_len.numel() else 0
+        pp = C.byref(prefs) if prefs is not None else None
+        if workspace is None:
+            workspace = torch.empty(max(1, lib().zlz4f_batch_compress_frame_workspace(src_len.numel(), max_blocks, pp)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_compress_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(), max_blocks,
+                                                pp, batch_flags, _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def decompressFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, max_blocks=None, workspace=None):
+        """zlz4f_batch_decompress_frame on torch CUDA tensors (layout as compressFrameBatch; result = decompressed size or
+        the frame's error code).  The block count of a frame is only known on the device, so the default max_blocks is
+        one entry per started 256 frame bytes (reads the lengths back once): enough for frames whose blocks average 256
+        bytes or more; pass the real count for anything denser, else such frames report InvalidState."""
+        import torch
+        if max_blocks is None:
+            max_blocks = int((src_len.cpu() // 256 + 1).sum()) if src_len.numel() else 0
+        if workspace is None:
+            workspace = torch.empty(max(1, lib().zlz4f_batch_decompress_frame_workspace(src_len.numel(), max_blocks)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_decompress_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                  _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(), max_blocks,
+                                                  _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def compressFrames(items, prefs=None, batch_flags=0, device="cuda"):
+        """Every byte string of `items` as its own frame, in one batch call -> list of frames (bytes) or error codes."""
+        import torch
+        lens = [len(b) for b in items]
+        caps = [lz4f.compressFrameBound(n, prefs) for n in lens]
+        d_src, src_off, src_len = _stage(items, device)
+        dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+        d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+        result = torch.empty(len(items), dtype=torch.int64, device=device)
+        lz4f.compressFrameBatch(d_src, src_off, src_len, d_dst, dst_off,
+                                torch.tensor(caps, dtype=torch.int64, device=device), result, prefs, batch_flags)
+        return _unstage(d_dst, _offsets(caps), result)
+
+    @staticmethod
+    def decompressFrames(frames, caps, device="cuda"):
+        """Every frame of `frames` decoded into a destination of caps[f] bytes, in one batch call -> list of contents
+        (bytes) or error codes."""
+        import torch
+        caps = list(caps)
+        d_src, src_off, src_len = _stage(frames, device)
+        dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+        d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+        result = torch.empty(len(frames), dtype=torch.int64, device=device)
+        lz4f.decompressFrameBatch(d_src, src_off, src_len, d_dst, dst_off,
+                                  torch.tensor(caps, dtype=torch.int64, device=device), result,
+                                  max_blocks=sum(_chain_blocks(bytes(f)) for f in frames))
+        return _unstage(d_dst, _offsets(caps), result)
+
+
+def _offsets(lens):
+    out, pos = [], 0
+    for n in lens:
+        out.append(pos)
+        pos += n
+    return out
+
+
+def _stage(items, device):
+    """Byte strings back to back in one device tensor -> (tensor, int64 offsets, int64 lengths)."""
+    import numpy as np
+    import torch
+    lens = [len(b) for b in items]
+    buf = np.frombuffer(b"".join(bytes(b) for b in items) or b"\0", dtype=np.uint8)
+    return (torch.from_numpy(buf.copy()).to(device), torch.tensor(_offsets(lens), dtype=torch.int64, device=device),
+            torch.tensor(lens, dtype=torch.int64, device=device))
+
+
+def _unstage(d_dst, offs, result):
+    res = result.cpu().tolist()                       # (synchronises the stream)
+    host = d_dst.cpu().numpy().tobytes()
+    return [host[o:o + r] if r >= 0 else r for o, r in zip(offs, res)]
+
+
+def _chain_blocks(f):
+    """Upper bound of the blocks the device walk of frame `f` finds (src/lz4f.zig:563-600): every block header before the
+    end mark or the end of the bytes, under the header size the FLG byte gives."""
+    if len(f) < 7 or int.from_bytes(f[:4], "little") != lz4f.MAGICNUMBER:
+        return 0
+    flg = f[4]
+    pos = 7 + (8 if flg & 0x08 else 0) + (4 if flg & 0x01 else 0)
+    extra = 4 if flg & 0x10 else 0
+    n = 0
+    while pos + 4 <= len(f):
+        h = int.from_bytes(f[pos:pos + 4], "little")
+        if h == 0:
+            break
+        n += 1
+        pos += 4 + (h & 0x7FFFFFFF) + extra
+    return n
 
 
 # ----------------------------------------------------------------------------- batch (device pointers)

@@ -181,6 +181,29 @@ inline Result compressFrameSegmentDevice(void *stream, const std::uint8_t *d_src
 inline Result decompressFrameSegmentDevice(void *stream, const std::uint8_t *d_src, std::size_t n, std::uint8_t *d_dst, std::size_t cap, const Preferences *p, std::uint32_t seg) {
     return wrap(zlz4f_decompress_frame_segment_device(stream, d_src, n, d_dst, cap, p, seg));
 }
+// batch frames (device pointers, asynchronous): frame f reads src + src_off[f] (src_len[f] bytes), writes dst + dst_off[f]
+// (capacity dst_cap[f]); result[f] = frame size / decompressed size or the frame's error code
+struct Frames {
+    const std::uint8_t *src; const std::uint64_t *src_off; const std::uint64_t *src_len;
+    std::uint8_t *dst; const std::uint64_t *dst_off; const std::uint64_t *dst_cap;
+    std::int64_t *result; std::uint32_t nframes;
+};
+constexpr std::uint32_t BATCH_CONTENT_SIZE = ZLZ4F_BATCH_CONTENT_SIZE;
+inline std::size_t compressFrameBatchWorkspace(std::uint32_t nframes, std::uint32_t max_blocks, const Preferences *p = nullptr) {
+    return zlz4f_batch_compress_frame_workspace(nframes, max_blocks, p);
+}
+inline Result compressFrameBatch(void *stream, const Frames &f, std::uint32_t max_blocks, const Preferences *p, std::uint32_t batch_flags,
+                                 void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_compress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes,
+                                           max_blocks, p, batch_flags, ws, ws_bytes));
+}
+inline std::size_t decompressFrameBatchWorkspace(std::uint32_t nframes, std::uint32_t max_blocks) {
+    return zlz4f_batch_decompress_frame_workspace(nframes, max_blocks);
+}
+inline Result decompressFrameBatch(void *stream, const Frames &f, std::uint32_t max_blocks, void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_decompress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes,
+                                             max_blocks, ws, ws_bytes));
+}
 }  // namespace lz4f
 
 }  // namespace zlz4

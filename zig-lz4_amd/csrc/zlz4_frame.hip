@@ -127,30 +127,33 @@ __host__ __device__ inline uint32_t xxh32(const uint8_t *p, uint64_t len, uint32
 // ------------------------------------------------------------------ frame header (host side, <= 19 bytes)
 struct HeaderBytes { uint8_t b[20]; uint32_t n; };
 
-// writeFrameHeader, src/lz4f.zig:304-351 (encodeFLG :152-184, encodeBD :224-232, headerChecksum :138-141)
-HeaderBytes encode_header(const zlz4f_prefs &p) {
+// writeFrameHeader, src/lz4f.zig:304-351 (encodeFLG :152-184, encodeBD :224-232, headerChecksum :138-141) with
+// `content_size` in place of p.content_size (the batch call can give every frame its own)
+__host__ __device__ inline HeaderBytes encode_header_cs(const zlz4f_prefs &p, uint64_t content_size) {
     HeaderBytes h;
-    std::memset(&h, 0, sizeof h);
+    for (uint32_t k = 0; k < sizeof h.b; k++) h.b[k] = 0;
     uint32_t pos = 0;
     const uint32_t magic = ZLZ4F_MAGICNUMBER;
-    std::memcpy(h.b, &magic, 4); pos = 4;
+    for (int k = 0; k < 4; k++) h.b[pos++] = (uint8_t)(magic >> (8 * k));
     uint8_t flg = 0x40;
     if (p.block_mode == 1) flg |= 0x20;
     if (p.block_checksum == 1) flg |= 0x10;
-    if (p.content_size != 0) flg |= 0x08;
+    if (content_size != 0) flg |= 0x08;
     if (p.content_checksum == 1) flg |= 0x04;
     if (p.dict_id != 0) flg |= 0x01;
     h.b[pos++] = flg;
     uint8_t bd = 4;
     if (p.block_size_id == 5) bd = 5; else if (p.block_size_id == 6) bd = 6; else if (p.block_size_id == 7) bd = 7;
     h.b[pos++] = (uint8_t)(bd << 4);
-    if (p.content_size != 0) { std::memcpy(h.b + pos, &p.content_size, 8); pos += 8; }
-    if (p.dict_id != 0) { std::memcpy(h.b + pos, &p.dict_id, 4); pos += 4; }
+    if (content_size != 0) for (int k = 0; k < 8; k++) h.b[pos++] = (uint8_t)(content_size >> (8 * k));
+    if (p.dict_id != 0) for (int k = 0; k < 4; k++) h.b[pos++] = (uint8_t)(p.dict_id >> (8 * k));
     h.b[pos] = (uint8_t)((xxh32(h.b + 4, pos - 4, 0) >> 8) & 0xFF);
     pos += 1;
     h.n = pos;
     return h;
 }
+
+HeaderBytes encode_header(const zlz4f_prefs &p) { return encode_header_cs(p, p.content_size); }
 
 struct ParsedHeader { int64_t size; uint8_t flg; size_t block_size; };
 
@@ -263,15 +266,12 @@ __global__ void k_block_xxh32(const uint8_t *__restrict__ src, const uint64_t *_
 }
 
 // one workgroup per block: header word, payload (compressed slot or raw source), optional checksum
-__global__ __launch_bounds__(256) void k_frame_scatter(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
-                                                        const uint8_t *__restrict__ slots,
-                                                        const uint64_t *__restrict__ slot_off,
-                                                        const uint32_t *__restrict__ hdr,
-                                                        const uint64_t *__restrict__ dst_off,
-                                                        const uint32_t *__restrict__ cks, uint32_t block_checksum,
-                                                        uint8_t *__restrict__ dst) {
-    const uint32_t i = blockIdx.x, t = threadIdx.x;
-    const uint32_t h = hdr[i];
+__device__ __forceinline__ void scatter_block(uint32_t i, const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                              const uint8_t *__restrict__ slots, const uint64_t *__restrict__ slot_off,
+                                              uint32_t h, const uint64_t *__restrict__ dst_off,
+                                              const uint32_t *__restrict__ cks, uint32_t block_checksum,
+                                              uint8_t *__restrict__ dst) {
+    const uint32_t t = threadIdx.x;
     const uint32_t n = h & 0x7FFFFFFFu;
     const uint8_t *p = (h & 0x80000000u) ? src + src_off[i] : slots + slot_off[i];
     uint8_t *o = dst + dst_off[i];
@@ -281,6 +281,16 @@ __global__ __launch_bounds__(256) void k_frame_scatter(const uint8_t *__restrict
     const uint32_t t0 = n & ~15u;
     if (t < 16u && t0 + t < n) o[t0 + t] = p[t0 + t];
     if (block_checksum && t < 4) o[n + t] = (uint8_t)(cks[i] >> (8u * t));        // :425
+}
+
+__global__ __launch_bounds__(256) void k_frame_scatter(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                                        const uint8_t *__restrict__ slots,
+                                                        const uint64_t *__restrict__ slot_off,
+                                                        const uint32_t *__restrict__ hdr,
+                                                        const uint64_t *__restrict__ dst_off,
+                                                        const uint32_t *__restrict__ cks, uint32_t block_checksum,
+                                                        uint8_t *__restrict__ dst) {
+    scatter_block(blockIdx.x, src, src_off, slots, slot_off, hdr[blockIdx.x], dst_off, cks, block_checksum, dst);
 }
 
 // one lane: frame header at dst[0..) (hb.n = 0: none), then -- for the segment that ends the frame -- the end mark and the
@@ -482,7 +492,7 @@ __global__ void k_content_check(const uint8_t *dst, const int64_t *total_p, cons
     if (xxh32(dst, total, 0) != zx_rd32(stored)) dplan[1] = ZLZ4F_ERR_CONTENT_CHECKSUM_INVALID;   // :631
 }
 
-int64_t map_block_error(int64_t e) {     // mapCompressionError, src/lz4f.zig:144-149
+__host__ __device__ inline int64_t map_block_error(int64_t e) {     // mapCompressionError, src/lz4f.zig:144-149
     if (e == ZLZ4_ERR_OUTPUT_TOO_SMALL) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
     if (e == ZLZ4_ERR_UNSUPPORTED || e == ZLZ4_ERR_DEVICE) return e;
     return ZLZ4F_ERR_GENERIC;
@@ -763,6 +773,591 @@ int64_t zlz4f_decompress_frame(const uint8_t *src, size_t n, uint8_t *dst, size_
     if ((uint64_t)r > cap) return ZLZ4_ERR_DEVICE;
     if (hipMemcpy(dst, d_dst.p, (size_t)r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
     return r;
+}
+
+}  // extern "C"
+
+// ====================================================================== batch frames: N independent frames per call
+// zlz4f_batch_compress_frame / zlz4f_batch_decompress_frame (include/zlz4_amd.h).  Frame f's
+// result is what compress_frame_impl / decompress_frame_impl return for it, but the whole batch is one fixed sequence of
+// kernels on the caller's stream: no allocation, no read-back, no synchronisation (so it can be captured into a graph).
+// The per-block work of every frame shares one block table of `max_blocks` entries: frame f owns the entries
+// [base_f, base_f + nb_f), base = the exclusive scan of the block counts in frame order.  A frame with blocks whose range
+// does not end at or below max_blocks gets ZLZ4_ERR_INVALID_STATE; every entry it would have owned, and every entry past
+// the last block, has length 0.  Per-frame serial steps (header, chain walk, dstPos plan, XXH32 of the content) run one
+// lane per frame; the block steps (compression, decoding, block checksums, copies) one entry per lane / wave / workgroup.
+namespace {
+
+constexpr uint32_t kNoFrame = 0xFFFFFFFFu;
+constexpr uint32_t kBlkStored = 1u, kBlkNoCks = 2u, kBlkCks = 4u;   // block flags (decompress table)
+
+struct BFrame {
+    uint64_t nb;        // block count: ceil(len / bs) (compress), what the block chain holds (decompress)
+    uint64_t base;      // first table entry (exclusive scan of nb)
+    int64_t status;     // compress: 0, DstMaxSizeTooSmall or SrcSizeTooLarge; decompress: header size or header error
+    uint64_t end;       // compress: frame bytes in front of the end mark; decompress: srcPos after the walk
+    int64_t err;        // compress: first failing block's code; decompress: the walk's error, then the plan's
+    uint64_t total;     // decompress: decoded bytes
+    uint64_t bs;        // decompress: block size from BD
+    uint32_t flg;       // decompress: FLG
+    uint32_t proven;    // decompress: 1 = the speculative layout is proven
+};
+
+__device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { return F.nb == 0 || F.base + F.nb <= max_blocks; }
+
+// exclusive scan of fr[].nb into fr[].base: one workgroup, thread t sums a contiguous run of frames, the 1024 run sums are
+// scanned in LDS, then every thread writes its run's bases
+__global__ __launch_bounds__(1024) void k_bf_scan(BFrame *__restrict__ fr, uint32_t nframes) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (nframes + 1023u) / 1024u;
+    const uint64_t b0 = (uint64_t)t * chunk;
+    const uint32_t lo = b0 < nframes ? (uint32_t)b0 : nframes;
+    const uint32_t hi = b0 + chunk < nframes ? (uint32_t)(b0 + chunk) : nframes;
+    uint64_t s = 0;
+    for (uint32_t f = lo; f < hi; f++) s += fr[f].nb;
+    part[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {
+        const uint64_t v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint64_t run = part[t] - s;
+    for (uint32_t f = lo; f < hi; f++) { fr[f].base = run; run += fr[f].nb; }
+}
+
+// ------------------------------------------------------------------ compress
+// one lane per frame: block count and the frame's capacity check (compress_frame_impl's order: :363-366 first)
+__global__ void k_bfc_count(const uint64_t *__restrict__ src_len, const uint64_t *__restrict__ dst_cap, uint32_t nframes,
+                            uint64_t bs, uint64_t per_block, uint64_t fixed, BFrame *__restrict__ fr) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const uint64_t n = src_len[f];
+    const uint64_t nb = n / bs + (n % bs != 0);
+    BFrame F = {};
+    F.nb = nb;
+    F.status = dst_cap[f] < fixed + nb * per_block ? ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL
+                                                    : (nb > 0x7FFFFFFFull ? ZLZ4F_ERR_SRC_SIZE_TOO_LARGE : 0);
+    fr[f] = F;
+}
+
+// one lane per table entry: its frame (the last frame whose base is <= i: frames without blocks share the next frame's
+// base), the block's source range and its workspace slot.  Entries of failed frames and unused entries get length 0.
+__global__ void k_bfc_desc(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                           const uint64_t *__restrict__ src_off, const uint64_t *__restrict__ src_len, uint64_t bs,
+                           uint64_t slot, uint64_t *__restrict__ in_off, uint32_t *__restrict__ in_len,
+                           uint64_t *__restrict__ out_off, uint32_t *__restrict__ out_cap, uint32_t *__restrict__ hdr) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = nframes;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            if (fr[mid].base <= i) lo = mid + 1u; else hi = mid;
+        }
+        uint64_t o = 0;
+        uint32_t len = 0;
+        if (lo > 0) {
+            const uint32_t f = lo - 1u;
+            const BFrame F = fr[f];
+            const uint64_t k = i - F.base;
+            if (k < F.nb && F.status == 0 && bf_fits(F, max_blocks)) {
+                const uint64_t n = src_len[f], b = k * bs;
+                len = (uint32_t)((n - b) < bs ? (n - b) : bs);
+                o = src_off[f] + b;
+            }
+        }
+        in_off[i] = o;
+        in_len[i] = len;
+        out_off[i] = (uint64_t)i * slot;
+        out_cap[i] = (uint32_t)slot;
+        hdr[i] = 0;
+    }
+}
+
+__device__ __forceinline__ uint32_t bf_header_size(const zlz4f_prefs &p, uint64_t content_size) {   // :304-351
+    return 7u + (content_size != 0 ? 8u : 0u) + (p.dict_id != 0 ? 4u : 0u);
+}
+
+// one wavefront per frame: k_frame_plan over the frame's entries, offsets absolute in dst; F.end = frame bytes in front
+// of the end mark, F.err = the first failing block's code
+__global__ __launch_bounds__(256) void k_bfc_plan(BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                                                  const int64_t *__restrict__ csize, const uint32_t *__restrict__ in_len,
+                                                  uint32_t block_checksum, zlz4f_prefs p, uint32_t cs_from_len,
+                                                  const uint64_t *__restrict__ src_len, const uint64_t *__restrict__ dst_off_f,
+                                                  uint64_t *__restrict__ dst_off, uint32_t *__restrict__ hdr) {
+    const uint32_t f = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    if (F.status != 0 || F.nb == 0 || !bf_fits(F, max_blocks)) return;
+    const uint32_t nb = (uint32_t)F.nb;
+    const uint64_t start = bf_header_size(p, cs_from_len ? src_len[f] : p.content_size);
+    uint64_t pos = dst_off_f[f] + start;
+    uint32_t bad = 0;
+    int64_t bad_code = 0;
+    for (uint32_t b0 = 0; b0 < nb; b0 += 64u) {
+        const uint32_t j = b0 + lane;
+        const uint64_t i = F.base + j;
+        uint64_t bytes = 0;
+        uint32_t h = 0;
+        bool err = false;
+        int64_t c = 0;
+        if (j < nb) {
+            c = csize[i];
+            const uint32_t len = in_len[i];
+            err = c < 0;
+            const bool stored = !err && (uint64_t)c >= len;           // :407
+            const uint32_t actual = stored ? len : (uint32_t)(err ? 0 : c);
+            h = actual | (stored ? 0x80000000u : 0u);                 // :411-414
+            bytes = 4u + (uint64_t)actual + (block_checksum ? 4u : 0u);
+        }
+        const uint64_t em = zlz4::ballot(err);
+        if (em && !bad) {
+            const uint32_t l = zlz4::first_lane(em);
+            bad = b0 + l + 1u;
+            bad_code = (int64_t)(int32_t)zlz4::rdlane((uint32_t)c, l);
+        }
+        uint64_t incl = bytes;
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t lo = __shfl_up((uint32_t)incl, d), hi = __shfl_up((uint32_t)(incl >> 32), d);
+            if (lane >= d) incl += ((uint64_t)hi << 32) | lo;
+        }
+        if (j < nb) { dst_off[i] = pos + incl - bytes; hdr[i] = h; }
+        const uint32_t tlo = zlz4::rdlane((uint32_t)incl, 63), thi = zlz4::rdlane((uint32_t)(incl >> 32), 63);
+        pos += ((uint64_t)thi << 32) | tlo;
+    }
+    if (lane == 0) { fr[f].end = pos - dst_off_f[f]; fr[f].err = bad ? bad_code : 0; }
+}
+
+// one workgroup per entry; entries without a block (hdr 0: every real block has a non-empty payload) write nothing
+__global__ __launch_bounds__(256) void k_bf_scatter(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                                     const uint8_t *__restrict__ slots, const uint64_t *__restrict__ slot_off,
+                                                     const uint32_t *__restrict__ hdr, const uint64_t *__restrict__ dst_off,
+                                                     const uint32_t *__restrict__ cks, uint32_t block_checksum,
+                                                     uint8_t *__restrict__ dst) {
+    const uint32_t h = hdr[blockIdx.x];
+    if (h == 0) return;
+    scatter_block(blockIdx.x, src, src_off, slots, slot_off, h, dst_off, cks, block_checksum, dst);
+}
+
+// one lane per frame: the frame's status, or header (:369), end mark (:433), content checksum (:437-441) and its size
+__global__ void k_bfc_head_tail(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks, zlz4f_prefs p,
+                                uint32_t cs_from_len, const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                const uint64_t *__restrict__ src_len, uint8_t *__restrict__ dst,
+                                const uint64_t *__restrict__ dst_off, int64_t *__restrict__ result) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    if (F.status != 0) { result[f] = F.status; return; }
+    if (!bf_fits(F, max_blocks)) { result[f] = ZLZ4_ERR_INVALID_STATE; return; }
+    if (F.nb && F.err) { result[f] = map_block_error(F.err); return; }                   // :398, :404
+    const uint64_t n = src_len[f];
+    const HeaderBytes hb = encode_header_cs(p, cs_from_len ? n : p.content_size);
+    uint8_t *o = dst + dst_off[f];
+    for (uint32_t k = 0; k < hb.n; k++) o[k] = hb.b[k];
+    uint64_t pos = F.nb ? F.end : hb.n;
+    for (int k = 0; k < 4; k++) o[pos + k] = 0;
+    pos += 4;
+    if (p.content_checksum == 1) {
+        const uint32_t c = xxh32(src + src_off[f], n, 0);
+        for (int k = 0; k < 4; k++) o[pos + k] = (uint8_t)(c >> (8 * k));
+        pos += 4;
+    }
+    result[f] = (int64_t)pos;
+}
+
+// ------------------------------------------------------------------ decompress
+__global__ void k_bfd_init(uint32_t *__restrict__ data_len, uint32_t *__restrict__ flags, uint32_t *__restrict__ fidx,
+                           uint32_t max_blocks) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        data_len[i] = 0; flags[i] = 0; fidx[i] = kNoFrame;
+    }
+}
+
+// one lane per frame: k_frame_walk's header parse (:547) and chain walk (:563-600).  The first pass counts (kRecord false),
+// the second records the blocks of every frame that fits the table at its base.
+template <bool kRecord>
+__global__ void k_bfd_walk(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                           const uint64_t *__restrict__ src_len, uint32_t nframes, uint32_t max_blocks,
+                           BFrame *__restrict__ fr, uint64_t *__restrict__ data_off, uint32_t *__restrict__ data_len,
+                           uint32_t *__restrict__ flags, uint64_t *__restrict__ cks_off, uint32_t *__restrict__ fidx) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const uint64_t so = src_off[f], n = src_len[f];
+    const uint8_t *s = src + so;
+    uint64_t pos, entry = 0;
+    uint32_t flg;
+    if (kRecord) {
+        const BFrame F = fr[f];
+        if (F.status < 0 || F.nb == 0 || !bf_fits(F, max_blocks)) return;
+        pos = (uint64_t)F.status;
+        flg = F.flg;
+        entry = F.base;
+    } else {
+        uint8_t head[19];
+        const uint32_t have = n < sizeof head ? (uint32_t)n : (uint32_t)sizeof head;
+        for (uint32_t k = 0; k < have; k++) head[k] = s[k];
+        const ParsedHeader ph = parse_header(head, have);
+        BFrame F = {};
+        F.status = ph.size;
+        F.flg = ph.flg;
+        F.bs = ph.block_size;
+        if (ph.size < 0) { fr[f] = F; return; }
+        fr[f] = F;
+        pos = (uint64_t)ph.size;
+        flg = ph.flg;
+    }
+    const bool bc = (flg & 0x10u) != 0;
+    const uint64_t nb_max = kRecord ? fr[f].nb : ~0ull;               // (the record pass never leaves the frame's range)
+    uint64_t nb = 0;
+    int64_t err = 0;
+    while (pos < n && nb < nb_max) {                                  // :563
+        if (pos + 4 > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }             // :565
+        const uint32_t h = zx_rd32(s + pos);
+        pos += 4;
+        if (h == 0) break;                                            // :573
+        const uint32_t sz = h & 0x7FFFFFFFu;
+        if (pos + sz > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }            // :582
+        const uint64_t off = pos;
+        pos += sz;
+        uint32_t fl = (h >> 31);
+        uint64_t co = 0;
+        if (bc) {                                                     // :590
+            if (pos + 4 > n) fl |= kBlkNoCks;                         // FrameSizeWrong when this block is reached
+            else { co = pos; pos += 4; fl |= kBlkCks; }
+        }
+        if (kRecord) {
+            const uint64_t i = entry + nb;
+            data_off[i] = so + off; data_len[i] = sz; flags[i] = fl; cks_off[i] = so + co; fidx[i] = f;
+        }
+        nb++;
+        if (fl & kBlkNoCks) break;
+    }
+    if (!kRecord) { fr[f].nb = nb; fr[f].end = pos; fr[f].err = err; }
+}
+
+// one lane per entry of a frame whose FLG asks for block checksums: k_block_verify (:594-598)
+__global__ void k_bfd_verify(const uint8_t *__restrict__ src, const uint64_t *__restrict__ data_off,
+                             const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags,
+                             const uint64_t *__restrict__ cks_off, uint32_t max_blocks, uint32_t *__restrict__ ok) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= max_blocks) return;
+    const uint32_t fl = flags[i];
+    if (fl & kBlkNoCks) { ok[i] = 2; return; }
+    if (!(fl & kBlkCks)) return;
+    ok[i] = xxh32(src + data_off[i], data_len[i], 0) == zx_rd32(src + cks_off[i]) ? 1u : 0u;
+}
+
+// k_dframe_spec per entry: block k of frame f -> dst_f + k * bs_f with the capacity left there (at most bs_f)
+__global__ void k_bfd_spec(const BFrame *__restrict__ fr, const uint32_t *__restrict__ fidx,
+                           const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags,
+                           const uint64_t *__restrict__ dst_off, const uint64_t *__restrict__ dst_cap, uint32_t max_blocks,
+                           uint64_t *__restrict__ out_off, uint32_t *__restrict__ out_cap, uint32_t *__restrict__ dec_len) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        const uint32_t f = fidx[i];
+        if (f == kNoFrame) { out_off[i] = 0; out_cap[i] = 0; dec_len[i] = 0; continue; }
+        const uint64_t bs = fr[f].bs, o = (i - fr[f].base) * bs, cap = dst_cap[f];
+        out_off[i] = dst_off[f] + (o < cap ? o : cap);
+        out_cap[i] = o >= cap ? 0u : (uint32_t)((cap - o) < bs ? (cap - o) : bs);
+        dec_len[i] = (flags[i] & kBlkStored) ? 0u : data_len[i];
+    }
+}
+
+// one workgroup per entry: raw copy of a stored block (:607) that fits its entry's capacity
+__global__ __launch_bounds__(256) void k_bf_copy_stored(const uint8_t *__restrict__ src, const uint64_t *__restrict__ data_off,
+                                                         const uint32_t *__restrict__ data_len,
+                                                         const uint32_t *__restrict__ flags,
+                                                         const uint64_t *__restrict__ out_off,
+                                                         const uint32_t *__restrict__ out_cap, uint8_t *__restrict__ dst) {
+    const uint32_t i = blockIdx.x, t = threadIdx.x;
+    if (!(flags[i] & kBlkStored)) return;
+    const uint32_t n = data_len[i];
+    if (n > out_cap[i]) return;                         // (speculative layout: the check kernel reports it)
+    const uint8_t *p = src + data_off[i];
+    uint8_t *o = dst + out_off[i];
+    for (uint32_t k = t * 16u; k + 16u <= n; k += 256u * 16u) zlz4::st128(o + k, zlz4::ld128(p + k));
+    const uint32_t t0 = n & ~15u;
+    if (t < 16u && t0 + t < n) o[t0 + t] = p[t0 + t];
+}
+
+// one wavefront per frame: k_dframe_check over the frame's entries -> F.proven, F.total
+__global__ __launch_bounds__(256) void k_bfd_check(BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                                                   const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags,
+                                                   const int64_t *__restrict__ sizes, const uint32_t *__restrict__ cks_ok,
+                                                   const uint32_t *__restrict__ out_cap) {
+    const uint32_t f = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    if (F.status < 0 || F.nb == 0 || !bf_fits(F, max_blocks)) return;
+    const bool bc = (F.flg & 0x10u) != 0;
+    bool ok = F.err == 0;
+    uint64_t last = 0;
+    for (uint64_t j = lane; j < F.nb; j += 64u) {
+        const uint64_t i = F.base + j;
+        if (bc && cks_ok[i] != 1u) ok = false;
+        uint64_t sz;
+        if (flags[i] & kBlkStored) { sz = data_len[i]; if (sz > out_cap[i]) ok = false; }
+        else { const int64_t r = sizes[i]; if (r < 0 || data_len[i] == 0) ok = false; sz = r < 0 ? 0 : (uint64_t)r; }
+        if (j + 1u < F.nb) { if (sz != F.bs) ok = false; }
+        else last = sz;
+    }
+    const bool all_ok = zlz4::ballot(!ok) == 0;
+    const uint32_t owner = (uint32_t)((F.nb - 1u) & 63u);
+    const uint64_t last_sz = ((uint64_t)zlz4::rdlane((uint32_t)(last >> 32), owner) << 32) | zlz4::rdlane((uint32_t)last, owner);
+    if (lane == 0) {
+        fr[f].proven = all_ok ? 1u : 0u;
+        fr[f].total = (F.nb - 1u) * F.bs + last_sz;
+    }
+}
+
+// exact path, per entry: only the blocks of frames that fit the table and are not proven take part (stored blocks as
+// empty inputs); everything else has length and capacity 0
+__global__ void k_bfd_mask(const BFrame *__restrict__ fr, const uint32_t *__restrict__ fidx,
+                           const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags, uint32_t max_blocks,
+                           uint64_t *__restrict__ x_off, uint32_t *__restrict__ x_cap, uint32_t *__restrict__ x_len) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        const uint32_t f = fidx[i];
+        const bool cand = f != kNoFrame && !fr[f].proven;
+        x_len[i] = cand && !(flags[i] & kBlkStored) ? data_len[i] : 0u;
+        x_off[i] = 0;
+        x_cap[i] = cand ? 0xFFFFFFFFu : 0u;
+    }
+}
+
+// exact path, one lane per unproven frame: k_dframe_plan (:602-621, the reference's error order) -> exact offsets and
+// capacities; a frame with an error decodes nothing
+__global__ void k_bfd_plan(BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                           const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags,
+                           const int64_t *__restrict__ sizes, const uint32_t *__restrict__ cks_ok,
+                           const uint64_t *__restrict__ dst_off, const uint64_t *__restrict__ dst_cap,
+                           uint64_t *__restrict__ x_off, uint32_t *__restrict__ x_cap, uint32_t *__restrict__ x_len) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    if (F.status < 0 || !bf_fits(F, max_blocks) || F.proven) return;
+    const bool bc = (F.flg & 0x10u) != 0;
+    const uint64_t cap = dst_cap[f];
+    uint64_t pos = 0;
+    int64_t err = 0;
+    for (uint64_t j = 0; j < F.nb; j++) {
+        const uint64_t i = F.base + j;
+        if (bc) {
+            if (cks_ok[i] == 2u) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }          // :591
+            if (cks_ok[i] == 0u) { err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID; break; }    // :596
+        }
+        const uint64_t rem = cap - pos;
+        uint64_t sz;
+        if (flags[i] & kBlkStored) {                                  // stored block :603-608
+            sz = data_len[i];
+            if (pos + sz > cap) { err = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL; break; }
+        } else {                                                      // :610
+            if (data_len[i] == 0 || rem == 0) sz = 0;                 // src/lz4.zig:97-98
+            else {
+                const int64_t s = sizes[i];
+                if (s < 0 || (uint64_t)s > rem) { err = ZLZ4F_ERR_DECOMPRESSION_FAILED; break; }   // :611
+                sz = (uint64_t)s;
+            }
+        }
+        x_off[i] = dst_off[f] + pos;
+        x_cap[i] = (uint32_t)sz;
+        pos += sz;
+    }
+    if (!err) err = F.err;
+    if (err)
+        for (uint64_t j = 0; j < F.nb; j++) { x_cap[F.base + j] = 0; x_len[F.base + j] = 0; }
+    fr[f].total = pos;
+    fr[f].err = err;
+}
+
+// one lane per frame: the status, or the content checksum check (:625-635) and the decoded size
+__global__ void k_bfd_finish(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                             const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                             const uint64_t *__restrict__ src_len, const uint8_t *__restrict__ dst,
+                             const uint64_t *__restrict__ dst_off, const uint64_t *__restrict__ dst_cap,
+                             int64_t *__restrict__ result) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    if (F.status < 0) { result[f] = F.status; return; }                                // :547
+    if (!bf_fits(F, max_blocks)) { result[f] = ZLZ4_ERR_INVALID_STATE; return; }
+    if (F.err) { result[f] = F.err; return; }              // (a proven frame has no error: its walk ended cleanly)
+    if (F.flg & 0x04u) {
+        if (F.end + 4 > src_len[f]) { result[f] = ZLZ4F_ERR_FRAME_SIZE_WRONG; return; }            // :626
+        if (F.total > dst_cap[f] ||
+            xxh32(dst + dst_off[f], F.total, 0) != zx_rd32(src + src_off[f] + F.end)) {             // :631
+            result[f] = ZLZ4F_ERR_CONTENT_CHECKSUM_INVALID;
+            return;
+        }
+    }
+    result[f] = (int64_t)F.total;
+}
+
+// ------------------------------------------------------------------ workspace layout
+struct BatchLayout {
+    size_t off[20];
+    size_t bytes = 0;
+    int n = 0;
+    size_t add(size_t b) { const size_t o = bytes; off[n++] = o; bytes = (o + b + 255) & ~(size_t)255; return o; }
+};
+
+int32_t bf_hc_level(const zlz4f_prefs &p) {   // compress_frame_impl's routing (:393-404, src/lz4hc.zig:1445)
+    if (p.compression_level <= 0) return 0;
+    return p.compression_level < 2 ? 9 : (p.compression_level > 12 ? 12 : p.compression_level);
+}
+
+uint64_t bf_slot(size_t bs) { return (zlz4_compress_bound(bs) + 15) & ~15ull; }
+
+// compress: frames | in_off out_off dst_off (u64) | in_len out_cap hdr cks (u32) | csize (i64) | slots | HC workspace
+BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p) {
+    const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
+    BatchLayout L;
+    L.add((size_t)nframes * sizeof(BFrame));
+    for (int k = 0; k < 3; k++) L.add(m * sizeof(uint64_t));
+    for (int k = 0; k < 4; k++) L.add(m * sizeof(uint32_t));
+    L.add(m * sizeof(int64_t));
+    L.add(m * bf_slot(bs));
+    L.add(bf_hc_level(p) ? zlz4_hc_workspace_bytes(max_blocks, (uint32_t)bs) : 0);
+    return L;
+}
+
+// decompress: frames | data_off cks_off out_off x_off (u64) | data_len flags fidx cks_ok out_cap dec_len x_cap x_len (u32)
+// | sizes (i64)
+BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks) {
+    const size_t m = max_blocks;
+    BatchLayout L;
+    L.add((size_t)nframes * sizeof(BFrame));
+    for (int k = 0; k < 4; k++) L.add(m * sizeof(uint64_t));
+    for (int k = 0; k < 8; k++) L.add(m * sizeof(uint32_t));
+    L.add(m * sizeof(int64_t));
+    return L;
+}
+
+inline uint32_t bf_grid(uint64_t items, uint32_t threads, uint32_t cap = 0xFFFFFFFFu) {
+    const uint64_t g = (items + threads - 1) / threads;
+    return g == 0 ? 1u : (g > cap ? cap : (uint32_t)g);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t zlz4f_batch_compress_frame_workspace(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs) {
+    return bfc_layout(nframes, max_blocks, prefs ? *prefs : kDefaultPrefs).bytes;
+}
+
+size_t zlz4f_batch_decompress_frame_workspace(uint32_t nframes, uint32_t max_blocks) {
+    return bfd_layout(nframes, max_blocks).bytes;
+}
+
+int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                   uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
+                                   uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                   void *d_workspace, size_t workspace_bytes) {
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    if (batch_flags & ~ZLZ4F_BATCH_CONTENT_SIZE) return ZLZ4F_ERR_PARAMETER_INVALID;
+    const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
+    if (cs_from_len && p.content_size != 0) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    const BatchLayout L = bfc_layout(nframes, max_blocks, p);
+    if (nframes == 0) return 0;
+    if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
+    hipStream_t st = (hipStream_t)stream_;
+    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
+    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
+    uint64_t *in_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *out_off = reinterpret_cast<uint64_t *>(ws + L.off[2]),
+             *dst_off = reinterpret_cast<uint64_t *>(ws + L.off[3]);
+    uint32_t *in_len = reinterpret_cast<uint32_t *>(ws + L.off[4]), *out_cap = reinterpret_cast<uint32_t *>(ws + L.off[5]),
+             *hdr = reinterpret_cast<uint32_t *>(ws + L.off[6]), *cks = reinterpret_cast<uint32_t *>(ws + L.off[7]);
+    int64_t *csize = reinterpret_cast<int64_t *>(ws + L.off[8]);
+    uint8_t *slots = ws + L.off[9];
+    void *hc_ws = ws + L.off[10];
+    const size_t hc_bytes = L.bytes - L.off[10];
+    const size_t bs = block_size_of(p.block_size_id);
+    const int32_t hc_level = bf_hc_level(p);
+    const uint32_t bc = p.block_checksum == 1 ? 1u : 0u;
+    const uint64_t slot = bf_slot(bs);
+    const uint64_t per_block = 4 + zlz4_compress_bound(bs) + (bc ? 4 : 0);       // zlz4f_compress_frame_bound
+    const uint64_t fixed = 19 + 4 + (p.content_checksum == 1 ? 4 : 0);
+    hipLaunchKernelGGL(k_bfc_count, dim3(bf_grid(nframes, 256)), dim3(256), 0, st, d_src_len, d_dst_cap, nframes,
+                       (uint64_t)bs, per_block, fixed, fr);
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
+    if (max_blocks) {
+        hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, fr, nframes, max_blocks,
+                           d_src_off, d_src_len, (uint64_t)bs, slot, in_off, in_len, out_off, out_cap, hdr);
+        int rc;
+        if (hc_level == 0)
+            rc = zlz4_launch_compress_fast(st, d_src, in_off, in_len, slots, out_off, out_cap, csize, max_blocks,
+                                           (uint32_t)bs, 1);                                               // :400-404
+        else
+            rc = zlz4_launch_compress_hc(st, d_src, in_off, in_len, slots, out_off, out_cap, csize, max_blocks,
+                                         (uint32_t)bs, hc_level, hc_ws, hc_bytes);                         // :394-398
+        if (rc != 0) return rc;
+        hipLaunchKernelGGL(k_bfc_plan, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, csize, in_len,
+                           bc, p, cs_from_len, d_src_len, d_dst_off, dst_off, hdr);
+        if (bc)
+            hipLaunchKernelGGL(k_block_xxh32, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, in_off, slots, out_off,
+                               hdr, max_blocks, cks);
+        hipLaunchKernelGGL(k_bf_scatter, dim3(max_blocks), dim3(256), 0, st, d_src, in_off, slots, out_off, hdr, dst_off,
+                           cks, bc, d_dst);
+    }
+    hipLaunchKernelGGL(k_bfc_head_tail, dim3(bf_grid(nframes, 64)), dim3(64), 0, st, fr, nframes, max_blocks, p,
+                       cs_from_len, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+int32_t zlz4f_batch_decompress_frame(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
+                                     const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                     const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                     void *d_workspace, size_t workspace_bytes) {
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    const BatchLayout L = bfd_layout(nframes, max_blocks);
+    if (nframes == 0) return 0;
+    if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
+    hipStream_t st = (hipStream_t)stream_;
+    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
+    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
+    uint64_t *data_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *cks_off = reinterpret_cast<uint64_t *>(ws + L.off[2]),
+             *out_off = reinterpret_cast<uint64_t *>(ws + L.off[3]), *x_off = reinterpret_cast<uint64_t *>(ws + L.off[4]);
+    uint32_t *data_len = reinterpret_cast<uint32_t *>(ws + L.off[5]), *flags = reinterpret_cast<uint32_t *>(ws + L.off[6]),
+             *fidx = reinterpret_cast<uint32_t *>(ws + L.off[7]), *cks_ok = reinterpret_cast<uint32_t *>(ws + L.off[8]),
+             *out_cap = reinterpret_cast<uint32_t *>(ws + L.off[9]), *dec_len = reinterpret_cast<uint32_t *>(ws + L.off[10]),
+             *x_cap = reinterpret_cast<uint32_t *>(ws + L.off[11]), *x_len = reinterpret_cast<uint32_t *>(ws + L.off[12]);
+    int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[13]);
+    const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
+    if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
+    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
+                       data_off, data_len, flags, cks_off, fidx);
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
+    if (max_blocks) {
+        hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
+                           data_off, data_len, flags, cks_off, fidx);
+        // speculative layout, proven per frame
+        hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, data_off, data_len, flags,
+                           cks_off, max_blocks, cks_ok);
+        hipLaunchKernelGGL(k_bfd_spec, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, d_dst_off, d_dst_cap, max_blocks,
+                           out_off, out_cap, dec_len);
+        int rc = zlz4_launch_decompress_safe(st, d_src, data_off, dec_len, d_dst, out_off, out_cap, sizes, max_blocks);
+        if (rc != 0) return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, out_off,
+                           out_cap, d_dst);
+        hipLaunchKernelGGL(k_bfd_check, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags,
+                           sizes, cks_ok, out_cap);
+        // exact path for the frames whose layout was not proven (always enqueued: the sequence does not depend on data)
+        hipLaunchKernelGGL(k_bfd_mask, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, max_blocks, x_off, x_cap, x_len);
+        rc = zlz4_launch_decompress_sizes(st, d_src, data_off, x_len, x_off, x_cap, sizes, max_blocks);
+        if (rc != 0) return ZLZ4_ERR_DEVICE;
+    }
+    hipLaunchKernelGGL(k_bfd_plan, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags, sizes, cks_ok,
+                       d_dst_off, d_dst_cap, x_off, x_cap, x_len);
+    if (max_blocks) {
+        const int rc = zlz4_launch_decompress_safe(st, d_src, data_off, x_len, d_dst, x_off, x_cap, sizes, max_blocks);
+        if (rc != 0) return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, x_off,
+                           x_cap, d_dst);
+    }
+    hipLaunchKernelGGL(k_bfd_finish, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, d_src, d_src_off, d_src_len, d_dst,
+                       d_dst_off, d_dst_cap, d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
 }  // extern "C"

@@ -52,6 +52,10 @@ extern "c" fn zlz4f_compress_frame_device(stream: ?*anyopaque, d_src: [*]const u
 extern "c" fn zlz4f_decompress_frame_device(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize) i64;
 extern "c" fn zlz4f_compress_frame_segment_device(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, segment_flags: u32) i64;
 extern "c" fn zlz4f_decompress_frame_segment_device(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, segment_flags: u32) i64;
+extern "c" fn zlz4f_batch_compress_frame_workspace(nframes: u32, max_blocks: u32, prefs: ?*const CPrefs) usize;
+extern "c" fn zlz4f_batch_compress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_decompress_frame_workspace(nframes: u32, max_blocks: u32) usize;
+extern "c" fn zlz4f_batch_decompress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 
 // ---- constants (reference src/lz4.zig:12-25, src/lz4hc.zig:28-31) ----
 pub const MINMATCH = 4;
@@ -450,5 +454,43 @@ pub const lz4f = struct {
     pub fn decompressFrameSegmentDevice(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, prefs: Preferences, segment_flags: u32) Error!usize {
         const c = toC(prefs);
         return mapFrame(zlz4f_decompress_frame_segment_device(stream, d_src, src_len, d_dst, dst_cap, &c, segment_flags));
+    }
+
+    /// Batch frames (include/zlz4_amd.h section 3): frame f reads src[src_off[f]..][0..src_len[f]] and writes
+    /// dst[dst_off[f]..][0..dst_cap[f]]; result[f] = what compressFrameDevice / decompressFrameDevice return for it
+    /// (size, or a negative code).  Device pointers; asynchronous on `stream`; `workspace` = device memory of the size the
+    /// workspace function gives.
+    pub const BATCH_CONTENT_SIZE: u32 = 1;
+    pub const Frames = struct {
+        src: [*]const u8,
+        src_off: [*]const u64,
+        src_len: [*]const u64,
+        dst: [*]u8,
+        dst_off: [*]const u64,
+        dst_cap: [*]const u64,
+        result: [*]i64,
+        nframes: u32,
+    };
+    fn mapBatch(rc: i32) (Error || root.Error)!void {
+        if (rc == 0) return;
+        if (rc == -104) return error.ParameterInvalid;
+        _ = try mapBlock(rc);
+    }
+    pub fn compressFrameBatchWorkspace(nframes: u32, max_blocks: u32, prefs: ?Preferences) usize {
+        if (prefs) |p| { const c = toC(p); return zlz4f_batch_compress_frame_workspace(nframes, max_blocks, &c); }
+        return zlz4f_batch_compress_frame_workspace(nframes, max_blocks, null);
+    }
+    pub fn compressFrameBatch(stream: ?*anyopaque, f: Frames, max_blocks: u32, prefs: ?Preferences, batch_flags: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        if (prefs) |p| {
+            const c = toC(p);
+            return mapBatch(zlz4f_batch_compress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, &c, batch_flags, workspace, workspace_bytes));
+        }
+        return mapBatch(zlz4f_batch_compress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, null, batch_flags, workspace, workspace_bytes));
+    }
+    pub fn decompressFrameBatchWorkspace(nframes: u32, max_blocks: u32) usize {
+        return zlz4f_batch_decompress_frame_workspace(nframes, max_blocks);
+    }
+    pub fn decompressFrameBatch(stream: ?*anyopaque, f: Frames, max_blocks: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, workspace, workspace_bytes));
     }
 };
