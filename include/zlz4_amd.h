@@ -242,6 +242,21 @@ int32_t zlz4_batch_compress_hc(void *stream,
                                int64_t *d_result, uint32_t nblocks, uint32_t max_in_len,
                                int32_t compression_level, void *d_workspace, size_t workspace_bytes);
 
+/* lz4.compressDestSize (src/lz4.zig:551-616) per block: d_in_len[i] is *srcSizePtr on entry and d_out_cap[i] is dst.len.
+ * d_result[i] and d_consumed[i] receive what zlz4_compress_dest_size returns and leaves in *src_size; bytes [0, result)
+ * of the output slot hold compressDefault of the consumed prefix (the best probe, as in the single call), bytes
+ * [result, cap) are not written.  A block longer than max_in_len gets InvalidState and consumed 0 (nothing written).
+ * Every block is compressed once at full length into the workspace (zlz4_batch_compress_dest_size_workspace bytes,
+ * 8-byte aligned, at least nblocks x compressBound(max_in_len)); the reference's search is then replayed on the device
+ * from that one stream.  A workspace that is too small, null or misaligned returns InvalidState and launches nothing.
+ * Same contract as zlz4_batch_compress_fast otherwise (asynchronous, no allocation, no read-back). */
+size_t  zlz4_batch_compress_dest_size_workspace(uint32_t nblocks, uint32_t max_in_len);
+int32_t zlz4_batch_compress_dest_size(void *stream,
+                                      const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                      uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                      int64_t *d_result, uint32_t *d_consumed, uint32_t nblocks, uint32_t max_in_len,
+                                      void *d_workspace, size_t workspace_bytes);
+
 /* Opt-in check for the levels whose output the reference itself does not always get right (10..12, see the HAZARD note
  * at zlz4_compress_hc): decodes every compressed block on the device and compares it with its input.
  *   d_comp_result[i] : what the compress call wrote for block i (size, or a negative code, which is passed through)

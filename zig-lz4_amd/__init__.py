@@ -76,6 +76,8 @@ SYMBOLS = {
     "zlz4_batch_compress_fast_continue": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_compress_hc_workspace": (_SZ, [_U32, _U32]),
     "zlz4_batch_compress_hc": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _I32, _VP, _SZ]),
+    "zlz4_batch_compress_dest_size_workspace": (_SZ, [_U32, _U32]),
+    "zlz4_batch_compress_dest_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
     "zlz4_batch_verify": (_I64, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4f_compress_frame_bound": (_SZ, [_SZ, _PP]),
     "zlz4f_compress_frame": (_I64, [_VP, _SZ, _VP, _SZ, _PP]),
@@ -543,6 +545,42 @@ def batch_compress_hc(d_in, in_off, in_len, d_out, out_off, out_cap, result, max
     _check(lib().zlz4_batch_compress_hc(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
                                         _ptr(out_off), _ptr(out_cap), _ptr(result), in_len.numel(), max_in_len,
                                         level, _ptr(workspace), workspace.numel()))
+
+
+def batch_compress_dest_size_workspace(nblocks, max_in_len):
+    return lib().zlz4_batch_compress_dest_size_workspace(nblocks, max_in_len)
+
+
+def batch_compress_dest_size(d_in, in_off, in_len, d_out, out_off, out_cap, result, consumed, max_in_len, workspace):
+    """zlz4_batch_compress_dest_size: lz4.compressDestSize per block (in_len[i] = bytes available, out_cap[i] = dst.len);
+    result[i] (int64) = compressed size or error code, consumed[i] (int32) = source bytes consumed.  `workspace` is a
+    uint8 tensor of at least batch_compress_dest_size_workspace(nblocks, max_in_len) bytes."""
+    _check(lib().zlz4_batch_compress_dest_size(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
+                                               _ptr(out_off), _ptr(out_cap), _ptr(result), _ptr(consumed),
+                                               in_len.numel(), max_in_len, _ptr(workspace),
+                                               workspace.numel() if workspace is not None else 0))
+
+
+def compressDestSizeBatch(items, caps, device="cuda"):
+    """lz4.compressDestSize of every byte string of `items` into a destination of caps[i] bytes, in one batch call
+    -> list of (compressed bytes, consumed source bytes); a block that fails gives (error code, 0)."""
+    import numpy as np
+    import torch
+    caps = list(caps)
+    n = len(items)
+    if n == 0:
+        return []
+    d_src, src_off, src_len = _stage(items, device)
+    max_in = max(len(b) for b in items)
+    dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+    d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+    result = torch.empty(n, dtype=torch.int64, device=device)
+    consumed = torch.empty(n, dtype=torch.int32, device=device)
+    ws = torch.empty(max(1, batch_compress_dest_size_workspace(n, max_in)), dtype=torch.uint8, device=device)
+    out_cap = torch.from_numpy(np.asarray(caps, dtype=np.uint32).view(np.int32)).to(device)
+    batch_compress_dest_size(d_src, src_off, src_len.to(torch.int32), d_dst, dst_off, out_cap, result, consumed, max_in, ws)
+    out = _unstage(d_dst, _offsets(caps), result)
+    return [(o, c if isinstance(o, bytes) else 0) for o, c in zip(out, consumed.cpu().tolist())]
 
 
 def batch_verify(d_in, in_off, in_len, d_comp, comp_off, comp_result, verify):

@@ -155,6 +155,15 @@ inline std::size_t compressHCWorkspace(std::uint32_t nblocks, std::uint32_t max_
 inline Result compressHCBatch(void *stream, const Blocks &b, std::uint32_t max_in_len, std::int32_t level, void *ws, std::size_t ws_bytes) {
     return wrap(zlz4_batch_compress_hc(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks, max_in_len, level, ws, ws_bytes));
 }
+inline std::size_t compressDestSizeWorkspace(std::uint32_t nblocks, std::uint32_t max_in_len) {
+    return zlz4_batch_compress_dest_size_workspace(nblocks, max_in_len);
+}
+// compressDestSize per block: in_len[i] = bytes available, out_cap[i] = dst.len; consumed[i] = source bytes consumed
+inline Result compressDestSizeBatch(void *stream, const Blocks &b, std::uint32_t *consumed, std::uint32_t max_in_len, void *ws,
+                                    std::size_t ws_bytes) {
+    return wrap(zlz4_batch_compress_dest_size(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, consumed,
+                                              b.nblocks, max_in_len, ws, ws_bytes));
+}
 }  // namespace device
 
 namespace lz4f {   // src/lz4f.zig

@@ -31,6 +31,11 @@ extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint6
                                        const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, int32_t,
                                        void *, size_t);
 extern "C" size_t zlz4_hc_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
+extern "C" int zlz4_launch_compress_dest_size(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
+                                              const uint64_t *, const uint32_t *, int64_t *, uint32_t *, uint32_t, uint32_t,
+                                              void *, const uint64_t *, const uint32_t *);
+extern "C" size_t zlz4_dest_size_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
+extern "C" uint32_t zlz4_dest_size_slot_cap(uint32_t max_in_len);
 
 namespace {
 
@@ -200,6 +205,56 @@ int64_t run_stream_single(uint32_t *table, const uint8_t *dict, size_t dict_len,
     return result;
 }
 
+// compressDestSize's search branch (src/lz4.zig:567-615) for 1 <= *src_size <= ZLZ4_MAX_INPUT_SIZE and dst_cap below
+// compressBound: the batch pipeline (zlz4_dest_size.hip) as a batch of one.  One upload (descriptors + input), two
+// launches, one read-back (output slot + results): the device does the whole search.
+int64_t dest_size_batch_of_one(const uint8_t *src, uint8_t *dst, size_t cap, size_t *src_size) {
+    const uint32_t n = (uint32_t)*src_size;
+    const uint32_t cap32 = (uint32_t)cap;                     // < compressBound(n) <= 2^31
+    struct Meta {
+        uint64_t in_off, out_off, slot_off; int64_t result; uint32_t in_len, out_cap, slot_cap, consumed;
+    };
+    const size_t out_bytes = ((size_t)cap32 + 15u) & ~(size_t)15u;   // [out | meta | input]
+    const size_t meta_bytes = (sizeof(Meta) + 15u) & ~(size_t)15u;
+    const size_t ws_bytes = zlz4_dest_size_workspace_bytes(1, n);
+    hipStream_t st = nullptr;
+    DeviceCall dc(st);
+    DevBuf d_buf(out_bytes + meta_bytes + n, &dc), d_ws(ws_bytes, &dc);
+    if (!d_buf.p || !d_ws.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    std::vector<uint8_t> h(meta_bytes + n);
+    Meta m;
+    std::memset(&m, 0, sizeof m);
+    m.in_off = meta_bytes;                                    // relative to the meta block
+    m.in_len = n;
+    m.out_off = 0;
+    m.out_cap = cap32;
+    m.slot_off = 0;
+    m.slot_cap = zlz4_dest_size_slot_cap(n);
+    std::memcpy(h.data(), &m, sizeof m);
+    std::memcpy(h.data() + meta_bytes, src, n);
+    uint8_t *dm = d_buf.as<uint8_t>() + out_bytes;
+    dc.launched();
+    if (hipMemcpyAsync(dm, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    const int rc = zlz4_launch_compress_dest_size(
+        st, dm, reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
+        reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)), d_buf.as<uint8_t>(),
+        reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
+        reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)), reinterpret_cast<int64_t *>(dm + offsetof(Meta, result)),
+        reinterpret_cast<uint32_t *>(dm + offsetof(Meta, consumed)), 1, n, d_ws.p,
+        reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, slot_off)),
+        reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, slot_cap)));
+    if (rc != 0) return rc;
+    std::vector<uint8_t> back(out_bytes + sizeof(Meta));
+    if (hipMemcpyAsync(back.data(), d_buf.p, back.size(), hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
+    std::memcpy(&m, back.data() + out_bytes, sizeof m);
+    if (m.result < 0) return m.result;
+    if ((uint64_t)m.result > cap || m.consumed > n) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
+    if (m.result > 0) std::memcpy(dst, back.data(), (size_t)m.result);
+    *src_size = m.consumed;
+    return m.result;
+}
+
 // src/lz4hc.zig:1445 + :1464-1466 level normalisation, strategy table :72-86
 int32_t normalise_hc_level(int32_t level) {
     if (level < ZLZ4HC_CLEVEL_MIN) level = ZLZ4HC_CLEVEL_DEFAULT;
@@ -354,11 +409,11 @@ int64_t zlz4_compress_dest_size(const uint8_t *src, uint8_t *dst, size_t cap, si
         return r;
     }
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    if (max_src > ZLZ4_MAX_INPUT_SIZE) {
-        // probes larger than the input limit fail with InputTooLarge in the reference (:594-607 -> `high = mid - 1`);
-        // the search below never needs more than this many source bytes on the device
-    }
-    const size_t stage = max_src > ZLZ4_MAX_INPUT_SIZE ? (size_t)ZLZ4_MAX_INPUT_SIZE : max_src;
+    if (max_src <= ZLZ4_MAX_INPUT_SIZE) return dest_size_batch_of_one(src, dst, cap, src_size);
+    // Inputs past the limit: the search runs on the host, one device compression per probe.  Probes larger than the
+    // limit fail with InputTooLarge in the reference (:594-607 -> `high = mid - 1`), so the device never needs more
+    // than ZLZ4_MAX_INPUT_SIZE source bytes.
+    const size_t stage = (size_t)ZLZ4_MAX_INPUT_SIZE;
     const uint32_t cap32 = cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap;
     DevBuf d_in(stage), d_out(cap32), d_meta(64);
     if (!d_in.p || !d_out.p || !d_meta.p) return ZLZ4_ERR_ALLOCATION_FAILED;
@@ -486,6 +541,23 @@ int32_t zlz4_batch_compress_hc(void *stream, const uint8_t *d_in, const uint64_t
         return ZLZ4_ERR_INVALID_STATE;
     return zlz4_launch_compress_hc((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
                                    d_result, nblocks, max_in_len, level, d_workspace, workspace_bytes);
+}
+
+size_t zlz4_batch_compress_dest_size_workspace(uint32_t nblocks, uint32_t max_in_len) {
+    return zlz4_dest_size_workspace_bytes(nblocks, max_in_len);
+}
+
+int32_t zlz4_batch_compress_dest_size(void *stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                      uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                      int64_t *d_result, uint32_t *d_consumed, uint32_t nblocks, uint32_t max_in_len,
+                                      void *d_workspace, size_t workspace_bytes) {
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    if (nblocks == 0) return 0;
+    if (!d_workspace || workspace_bytes < zlz4_dest_size_workspace_bytes(nblocks, max_in_len) ||
+        ((uintptr_t)d_workspace & 7u))
+        return ZLZ4_ERR_INVALID_STATE;
+    return zlz4_launch_compress_dest_size((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
+                                          d_result, d_consumed, nblocks, max_in_len, d_workspace, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------- opt-in round-trip check (levels 10..12)

@@ -33,6 +33,8 @@ extern "c" fn zlz4_batch_load_dict(stream: ?*anyopaque, d_dict: [*]const u8, d_d
 extern "c" fn zlz4_batch_compress_fast_continue(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_table_in: [*]const u32, d_table_idx: ?[*]const u32, d_table_out: ?[*]u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) usize;
 extern "c" fn zlz4_batch_compress_hc(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4_batch_compress_dest_size_workspace(nblocks: u32, max_in_len: u32) usize;
+extern "c" fn zlz4_batch_compress_dest_size(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, d_consumed: [*]u32, nblocks: u32, max_in_len: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_verify(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_comp: [*]const u8, d_comp_off: [*]const u64, d_comp_result: [*]const i64, d_verify: [*]i64, nblocks: u32) i64;
 
 pub const CPrefs = extern struct {
@@ -322,6 +324,15 @@ pub const device = struct {
     /// batch form of compressHC (src/lz4hc.zig:1440-1453); `workspace` = device memory of compressHCWorkspace() bytes
     pub fn compressHCBatch(stream: ?*anyopaque, b: Blocks, max_in_len: u32, level: i32, workspace: ?*anyopaque, workspace_bytes: usize) Error!void {
         return mapLaunch(zlz4_batch_compress_hc(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks, max_in_len, level, workspace, workspace_bytes));
+    }
+    pub fn compressDestSizeWorkspace(nblocks: u32, max_in_len: u32) usize {
+        return zlz4_batch_compress_dest_size_workspace(nblocks, max_in_len);
+    }
+    /// batch form of compressDestSize (src/lz4.zig:551-616): in_len[i] = bytes available, out_cap[i] = dst.len;
+    /// result[i] = compressed size, consumed[i] = source bytes consumed; `workspace` = device memory of
+    /// compressDestSizeWorkspace() bytes; every in_len[i] <= max_in_len
+    pub fn compressDestSizeBatch(stream: ?*anyopaque, b: Blocks, consumed: [*]u32, max_in_len: u32, workspace: ?*anyopaque, workspace_bytes: usize) Error!void {
+        return mapLaunch(zlz4_batch_compress_dest_size(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, consumed, b.nblocks, max_in_len, workspace, workspace_bytes));
     }
     /// opt-in check for levels 10..12 (include/zlz4_amd.h): decodes the batch a compress call produced (`b` as passed to
     /// it) and compares with the input; verify[i] = b.result[i] or -9; returns the number of blocks that do not round-trip
