@@ -160,6 +160,39 @@ int64_t zlz4_stream_load_dict(uint32_t *table, const uint8_t *dict, size_t dict_
 int64_t zlz4_stream_compress_fast_continue(uint32_t *table, const uint8_t *src, size_t src_len, uint8_t *dst,
                                            size_t dst_cap, uint32_t acceleration);
 
+/* Streaming decompression, lz4.StreamDecode (src/lz4.zig:870-957).  The reference's fields as byte addresses (0 = null):
+ * dict / dict_len = externalDict / extDictSize, prefix / prefix_len = prefixEnd.ptr / prefixSize.  The state holds no
+ * data: a call never reads the previous output, only compares its address with the new dst (see the warning below).
+ *
+ * zlz4_stream_decode_init = StreamDecode.init (all zero).  zlz4_set_stream_decode = setStreamDecode (:904-909):
+ * (dict, dict_len, null, 0); dict == NULL is the null slice (dict_len is then taken as 0).
+ *
+ * zlz4_decompress_safe_continue = decompressSafeContinue (:912-939) on host buffers:
+ *   A  prefix_len == 0 && dict_len == 0: zlz4_decompress_safe; on success (prefix, prefix_len) = (dst, result).
+ *   B  otherwise, with a dictionary (dict_len > 0): zlz4_decompress_safe_using_dict (only its last 64 KiB is staged);
+ *      without one: decompressGeneric with lowPrefix = prefix (dst if prefix is 0), i.e. a match at output position op
+ *      with offset o is CorruptedData unless op - o >= max(0, prefix - dst), tested where decompressSafe tests
+ *      o > op.  On success the state becomes (0, 0, dst, result): the dictionary is used once (:936).
+ *   Any error leaves the state unchanged.  src_len == 0 or dst_cap == 0 return 0, a success (in B the pending
+ *   dictionary is consumed).  A state with dict_len > 0 and prefix != 0 (unreachable through these calls; the reference
+ *   would underflow at :213) returns InvalidState; sd == NULL -> InvalidState.  The previous output is never staged.
+ *
+ * WARNING (a defect of the reference, reproduced): lowPrefix is where the previous output STARTS, and without a
+ * dictionary nothing in front of it may be referenced.  When the previous output lies ABOVE dst in memory, every match
+ * that reaches further back than prefix - dst bytes before dst + op fails with CorruptedData.  Two layouts hit this: a
+ * ring buffer of zlz4_decoder_ring_buffer_size bytes once it wraps to its start, and a double buffer whose second half
+ * is lower in memory than the first.  Blocks whose matches stay inside their own output are not affected.
+ *
+ * zlz4_decoder_ring_buffer_size = decoderRingBufferSize (:954-957): 0 for 0, else 65536 + 14 + max_block_size. */
+typedef struct zlz4_stream_decode {
+    uint64_t dict, dict_len, prefix, prefix_len;
+} zlz4_stream_decode_t;
+void    zlz4_stream_decode_init(zlz4_stream_decode_t *sd);
+void    zlz4_set_stream_decode(zlz4_stream_decode_t *sd, const uint8_t *dict, size_t dict_len);
+int64_t zlz4_decompress_safe_continue(zlz4_stream_decode_t *sd, const uint8_t *src, size_t src_len, uint8_t *dst,
+                                      size_t dst_cap);
+size_t  zlz4_decoder_ring_buffer_size(size_t max_block_size);
+
 /* replaces lz4.sizeofState, src/lz4.zig:524-526 (= @sizeOf(HashTable) = 16384) */
 size_t  zlz4_sizeof_state(void);
 
@@ -232,6 +265,26 @@ int32_t zlz4_batch_compress_fast_continue(void *stream,
                                           const uint32_t *d_table_in, const uint32_t *d_table_idx, uint32_t *d_table_out,
                                           int64_t *d_result, uint32_t nblocks, uint32_t max_in_len,
                                           uint32_t acceleration);
+
+/* StreamDecode.decompressSafeContinue (src/lz4.zig:912-939) over whole streams in one call.  Stream s makes the calls
+ * [d_run_start[s], d_run_start[s + 1]) in that order (d_run_start: nstreams + 1 ascending entries, the first 0, the
+ * last nblocks), call i decoding block i as in zlz4_batch_decompress_safe, from the state d_state[s] (device memory;
+ * dict / prefix are DEVICE addresses).  d_result[i] = what the i-th call returns; every successful slot holds its bytes
+ * (failed slots are unspecified); d_state[s] ends as the reference's StreamDecode after the run.  One step of N streams
+ * is d_run_start[s] = s; one long stream is nstreams = 1.  A state with a dictionary and a prefix gives InvalidState
+ * for every call of its run (as the single call); a block outside every run gets InvalidState.  Output slots must not
+ * overlap each other, the inputs or the dictionaries.  The WARNING of zlz4_decompress_safe_continue applies: a slot
+ * placed below the previous call's slot of its stream sees only the bytes above the previous slot's start.
+ * Asynchronous, no allocation, nothing read back: the launch sequence does not depend on the data (graph-capturable).
+ * d_workspace: zlz4_batch_decompress_safe_continue_workspace(nblocks, nstreams) bytes, 16-byte aligned, else
+ * InvalidState (DESIGN.md section 4.2c describes the passes). */
+size_t  zlz4_batch_decompress_safe_continue_workspace(uint32_t nblocks, uint32_t nstreams);
+int32_t zlz4_batch_decompress_safe_continue(void *stream,
+                                            const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                            uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                            const uint32_t *d_run_start, zlz4_stream_decode_t *d_state,
+                                            int64_t *d_result, uint32_t nblocks, uint32_t nstreams,
+                                            void *d_workspace, size_t workspace_bytes);
 
 /* workspace for the HC path: bytes needed for `nblocks` blocks of at most `max_in_len` bytes (448 KiB per 64 KiB block
  * up to 8192 blocks = 3.5 GiB, about 6 GiB at most for large blocks; longer batches are processed in rounds) */

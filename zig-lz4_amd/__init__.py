@@ -79,6 +79,12 @@ SYMBOLS = {
     "zlz4_batch_compress_dest_size_workspace": (_SZ, [_U32, _U32]),
     "zlz4_batch_compress_dest_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
     "zlz4_batch_verify": (_I64, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_stream_decode_init": (None, [_VP]),
+    "zlz4_set_stream_decode": (None, [_VP, _VP, _SZ]),
+    "zlz4_decompress_safe_continue": (_I64, [_VP, _VP, _SZ, _VP, _SZ]),
+    "zlz4_decoder_ring_buffer_size": (_SZ, [_SZ]),
+    "zlz4_batch_decompress_safe_continue_workspace": (_SZ, [_U32, _U32]),
+    "zlz4_batch_decompress_safe_continue": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
     "zlz4f_compress_frame_bound": (_SZ, [_SZ, _PP]),
     "zlz4f_compress_frame": (_I64, [_VP, _SZ, _VP, _SZ, _PP]),
     "zlz4f_decompress_frame": (_I64, [_VP, _SZ, _VP, _SZ]),
@@ -297,6 +303,83 @@ def createStream():
 def freeStream(stream):
     """lz4.freeStream, src/lz4.zig:863-865."""
     stream.destroy()
+
+
+class _SdState(C.Structure):
+    """zlz4_stream_decode_t: StreamDecode's fields as byte addresses (0 = null)."""
+    _fields_ = [("dict", C.c_uint64), ("dict_len", C.c_uint64), ("prefix", C.c_uint64), ("prefix_len", C.c_uint64)]
+
+
+def _addr(buf):
+    """Address and length of a buffer the caller owns (numpy array, bytearray, memoryview, ctypes array): the stream
+    state compares these addresses, so the data is never copied."""
+    import numpy as np
+    a = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf.reshape(-1).view(np.uint8)
+    return (a.ctypes.data if a.size else 0), a.size
+
+
+class StreamDecode:
+    """lz4.StreamDecode (src/lz4.zig:870-951).  `dst` of decompressSafeContinue is a WRITABLE buffer of the caller
+    (numpy uint8 array, bytearray, writable memoryview): its address is what the state records, as in the reference.
+    The dictionary of setStreamDecode is borrowed the same way (keep it alive until it is consumed).  The fields
+    externalDict / extDictSize / prefixEnd / prefixSize mirror the reference's as addresses and lengths; see the WARNING
+    of zlz4_decompress_safe_continue in include/zlz4_amd.h for output placed below the previous output."""
+
+    def __init__(self):                               # init, :893-901
+        self._st = _SdState()
+        self._dict_ref = None
+
+    @classmethod
+    def create(cls):                                  # :877-882
+        return cls()
+
+    def destroy(self):                                # :885-889
+        pass
+
+    @classmethod
+    def init(cls):
+        return cls()
+
+    externalDict = property(lambda self: self._st.dict)
+    extDictSize = property(lambda self: self._st.dict_len)
+    prefixEnd = property(lambda self: self._st.prefix)
+    prefixSize = property(lambda self: self._st.prefix_len)
+
+    def setStreamDecode(self, dict):
+        """:904-909; dict None = the null slice.  A bytes object is pinned by this stream until the next call."""
+        if dict is None:
+            lib().zlz4_set_stream_decode(C.byref(self._st), None, 0)
+            self._dict_ref = None
+            return
+        if isinstance(dict, (bytes, str)):
+            dict = bytearray(dict)
+        p, n = _addr(dict)
+        if p == 0:                                    # an empty slice still has an address
+            dict = bytearray(1)
+            p, n = _addr(dict)[0], 0
+        self._dict_ref = dict
+        lib().zlz4_set_stream_decode(C.byref(self._st), C.c_void_p(p), n)
+
+    def decompressSafeContinue(self, src, dst):
+        """:912-939 -> bytes written to dst[0:r]; errors raise Lz4Error and leave the state unchanged."""
+        s, n = _in(src)
+        p, cap = _addr(dst)
+        return _check(lib().zlz4_decompress_safe_continue(C.byref(self._st), C.addressof(s), n, C.c_void_p(p), cap))
+
+
+def createStreamDecode():
+    """lz4.createStreamDecode, src/lz4.zig:943-945."""
+    return StreamDecode.create()
+
+
+def freeStreamDecode(stream):
+    """lz4.freeStreamDecode, src/lz4.zig:948-950."""
+    stream.destroy()
+
+
+def decoderRingBufferSize(maxBlockSize):
+    """lz4.decoderRingBufferSize, src/lz4.zig:954-957."""
+    return lib().zlz4_decoder_ring_buffer_size(maxBlockSize)
 
 
 def sizeofState():
@@ -588,3 +671,66 @@ def batch_verify(d_in, in_off, in_len, d_comp, comp_off, comp_result, verify):
     blocks that do not round-trip (verify[i] = the compress result, or ZLZ4_ERR_VERIFY = -9)."""
     return _check(lib().zlz4_batch_verify(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_comp), _ptr(comp_off),
                                           _ptr(comp_result), _ptr(verify), in_len.numel()))
+
+
+def batch_decompress_safe_continue_workspace(nblocks, nstreams):
+    return lib().zlz4_batch_decompress_safe_continue_workspace(nblocks, nstreams)
+
+
+def batch_decompress_safe_continue(d_in, in_off, in_len, d_out, out_off, out_cap, run_start, state, result, workspace):
+    """zlz4_batch_decompress_safe_continue: stream s makes the calls [run_start[s], run_start[s + 1]) (int32, nstreams + 1
+    entries) from state[s] (int64 tensor of shape (nstreams, 4): dict, dict_len, prefix, prefix_len as device addresses;
+    updated in place); result[i] (int64) = what call i returns.  `workspace`: uint8 tensor of at least
+    batch_decompress_safe_continue_workspace(nblocks, nstreams) bytes."""
+    _check(lib().zlz4_batch_decompress_safe_continue(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
+                                                     _ptr(out_off), _ptr(out_cap), _ptr(run_start), _ptr(state),
+                                                     _ptr(result), in_len.numel(), run_start.numel() - 1,
+                                                     _ptr(workspace), workspace.numel() if workspace is not None else 0))
+
+
+def decompressStreams(runs, caps, dicts=None, device="cuda"):
+    """Every run of `runs` (a list of lists of compressed blocks) decoded as one StreamDecode, in one batch call: call j
+    of run s into its own slot of caps[s][j] bytes, the slots of a run back to back in call order.  dicts[s] (bytes or
+    None) is set with setStreamDecode first.  -> (outputs, states): outputs[s][j] = bytes or an error code, states[s] =
+    the final (dict, dict_len, prefix, prefix_len) with addresses made relative: prefix as ("slot", j) or 0, dict as
+    ("dict", s) or 0."""
+    import numpy as np
+    import torch
+    blocks = [b for r in runs for b in r]
+    flat_caps = [int(c) for cs in caps for c in cs]
+    n, ns = len(blocks), len(runs)
+    d_src, src_off, src_len = _stage(blocks, device)
+    offs = _offsets(flat_caps)
+    d_dst = torch.empty(max(1, sum(flat_caps)), dtype=torch.uint8, device=device)
+    dst_off = torch.tensor(offs, dtype=torch.int64, device=device)
+    out_cap = torch.from_numpy(np.asarray(flat_caps, dtype=np.uint32).view(np.int32)).to(device)
+    rs = [0]
+    for r in runs:
+        rs.append(rs[-1] + len(r))
+    run_start = torch.tensor(rs, dtype=torch.int32, device=device)
+    dicts = list(dicts) if dicts is not None else [None] * ns
+    dbytes = [bytes(d) if d is not None else b"" for d in dicts]
+    d_dict, dict_off, _ = _stage(dbytes, device)
+    base = d_dict.data_ptr()
+    doffs = dict_off.cpu().tolist()
+    st = np.zeros((ns, 4), dtype=np.uint64)
+    for s, d in enumerate(dicts):
+        if d is not None:
+            st[s, 0] = base + doffs[s]
+            st[s, 1] = len(dbytes[s])
+    state = torch.from_numpy(st.view(np.int64)).to(device)
+    result = torch.empty(n, dtype=torch.int64, device=device)
+    ws = torch.empty(max(16, batch_decompress_safe_continue_workspace(n, ns)), dtype=torch.uint8, device=device)
+    batch_decompress_safe_continue(d_src, src_off, src_len.to(torch.int32), d_dst, dst_off, out_cap, run_start, state,
+                                   result, ws)
+    flat = _unstage(d_dst, offs, result)
+    final = state.cpu().numpy().view(np.uint64)
+    slot_of = {d_dst.data_ptr() + o: j for j, o in enumerate(offs)}
+    outs, states = [], []
+    for s in range(ns):
+        outs.append(flat[rs[s]:rs[s + 1]])
+        dct, dl, pre, pl = (int(x) for x in final[s])
+        dct = ("dict", s) if dct and dct == int(st[s, 0]) else (0 if dct == 0 else dct)
+        pre = ("slot", slot_of[pre] - rs[s]) if pre in slot_of else pre
+        states.append((dct, dl, pre, pl))
+    return outs, states

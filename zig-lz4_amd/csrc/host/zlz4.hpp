@@ -92,6 +92,18 @@ struct Stream {
     }
 };
 
+// lz4.StreamDecode, src/lz4.zig:870-957: the reference's fields as addresses (zlz4_stream_decode_t).  A call never reads
+// the previous output; see the WARNING in include/zlz4_amd.h for output placed below the previous output.
+struct StreamDecode {
+    zlz4_stream_decode_t st{0, 0, 0, 0};
+    StreamDecode() { zlz4_stream_decode_init(&st); }
+    void setStreamDecode(const std::uint8_t *dict, std::size_t dict_len) { zlz4_set_stream_decode(&st, dict, dict_len); }
+    Result decompressSafeContinue(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap) {
+        return wrap(zlz4_decompress_safe_continue(&st, src, n, dst, cap));
+    }
+};
+inline std::size_t decoderRingBufferSize(std::size_t max_block_size) { return zlz4_decoder_ring_buffer_size(max_block_size); }
+
 // lz4.sizeofState / compressFastExtState / compressDestSize, src/lz4.zig:524-616
 inline std::size_t sizeofState() { return zlz4_sizeof_state(); }
 inline Result compressFastExtState(void *state, std::size_t state_len, const std::uint8_t *src, std::size_t n,
@@ -134,6 +146,18 @@ struct DictBlocks {
 inline Result decompressSafeUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d) {
     return wrap(zlz4_batch_decompress_safe_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
                                                       d.dict_off, d.dict_len, b.result, b.nblocks));
+}
+// StreamDecode.decompressSafeContinue over whole streams: stream s makes the calls [run_start[s], run_start[s + 1]) of b
+// from d_state[s] (device addresses, updated in place)
+inline std::size_t decompressSafeContinueWorkspace(std::uint32_t nblocks, std::uint32_t nstreams) {
+    return zlz4_batch_decompress_safe_continue_workspace(nblocks, nstreams);
+}
+inline Result decompressSafeContinueBatch(void *stream, const Blocks &b, const std::uint32_t *d_run_start,
+                                          zlz4_stream_decode_t *d_state, std::uint32_t nstreams, void *d_workspace,
+                                          std::size_t workspace_bytes) {
+    return wrap(zlz4_batch_decompress_safe_continue(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap,
+                                                    d_run_start, d_state, b.result, b.nblocks, nstreams, d_workspace,
+                                                    workspace_bytes));
 }
 // Stream.loadDict per dictionary (table i of d_tables, ZLZ4_STREAM_TABLE_ENTRIES u32 each; result[i] = dictSize)
 inline Result loadDictBatch(void *stream, const DictBlocks &d, std::uint32_t *d_tables, std::int64_t *d_result, std::uint32_t ndicts) {

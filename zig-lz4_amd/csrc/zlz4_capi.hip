@@ -35,6 +35,13 @@ extern "C" int zlz4_launch_compress_dest_size(hipStream_t, const uint8_t *, cons
                                               const uint64_t *, const uint32_t *, int64_t *, uint32_t *, uint32_t, uint32_t,
                                               void *, const uint64_t *, const uint32_t *);
 extern "C" size_t zlz4_dest_size_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
+extern "C" int zlz4_launch_decompress_safe_bound(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
+                                                 uint8_t *, const uint64_t *, const uint32_t *, int64_t *, uint32_t,
+                                                 const uint8_t *, const uint64_t *, const uint32_t *, int);
+extern "C" size_t zlz4_sd_workspace_bytes(uint32_t nblocks, uint32_t nstreams);
+extern "C" int zlz4_launch_stream_decode(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
+                                         const uint64_t *, const uint32_t *, const uint32_t *, uint64_t *, int64_t *,
+                                         uint32_t, uint32_t, void *);
 extern "C" uint32_t zlz4_dest_size_slot_cap(uint32_t max_in_len);
 
 namespace {
@@ -62,12 +69,13 @@ bool device_ok() {
 using zlz4host::DevBuf;
 using zlz4host::DeviceCall;
 
-enum class Op { Fast, Hc, Decompress, DecompressDict };
+enum class Op { Fast, Hc, Decompress, DecompressDict, DecompressBound };
 
 // One block, host pointers: stage -> kernel -> copy back.  Op::DecompressDict stages the last min(dict_len, 65536)
 // bytes of `dict` (offsets are at most 65535: nothing in front of that tail can be reached, src/lz4.zig:189-192).
+// Op::DecompressBound decodes with the StreamDecode bound `bound` (k_decompress_safe, kBound).
 int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t accel,
-                   int32_t level, const uint8_t *dict = nullptr, size_t dict_len = 0) {
+                   int32_t level, const uint8_t *dict = nullptr, size_t dict_len = 0, uint32_t bound = 0) {
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     if (src_len > 0xFFFFFFFFull) return op == Op::Decompress ? ZLZ4_ERR_CORRUPTED_DATA : ZLZ4_ERR_INPUT_TOO_LARGE;
     // the kernels index with 32 bits; a destination larger than 4 GiB-1 is clamped (never reached:
@@ -85,8 +93,11 @@ int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size
     if (!d_in.p || !d_out.p || !d_meta.p || !d_ws.p || !d_dict.p) return ZLZ4_ERR_ALLOCATION_FAILED;
     struct Meta {
         uint64_t in_off; uint64_t out_off; int64_t result; uint32_t in_len; uint32_t out_cap; uint64_t dict_off; uint32_t dict_len;
+        uint32_t bound;                                             // (dict_len[1] of the kBound builds)
     } m;
     m.in_off = 0; m.out_off = 0; m.result = 0; m.in_len = len32; m.out_cap = cap32; m.dict_off = 0; m.dict_len = (uint32_t)dtail;
+    m.bound = bound;
+    static_assert(offsetof(Meta, bound) == offsetof(Meta, dict_len) + 4, "bound follows dict_len");
     dc.launched();
     if (src_len && hipMemcpyAsync(d_in.p, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
     if (dtail && hipMemcpyAsync(d_dict.p, dict + (dict_len - dtail), dtail, hipMemcpyHostToDevice, st) != hipSuccess)
@@ -108,6 +119,11 @@ int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size
     } else if (op == Op::Decompress) {
         rc = zlz4_launch_decompress_safe(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
                                          p_out_cap, p_res, 1);
+    } else if (op == Op::DecompressBound) {
+        rc = zlz4_launch_decompress_safe_bound(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
+                                               p_out_cap, p_res, 1, nullptr,
+                                               reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off)),
+                                               reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)), 0);
     } else {
         rc = zlz4_launch_decompress_safe_using_dict(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(),
                                                     p_out_off, p_out_cap, p_res, 1, d_dict.as<uint8_t>(),
@@ -360,6 +376,48 @@ int64_t zlz4_decompress_safe_partial_using_dict(const uint8_t *src, size_t n, ui
     return partial_target_zero(src, n);
 }
 
+void zlz4_stream_decode_init(zlz4_stream_decode_t *sd) {          // src/lz4.zig:893-901
+    if (sd) *sd = zlz4_stream_decode_t{0, 0, 0, 0};
+}
+
+void zlz4_set_stream_decode(zlz4_stream_decode_t *sd, const uint8_t *dict, size_t dict_len) {   // :904-909
+    if (!sd) return;
+    sd->dict = (uint64_t)(uintptr_t)dict;
+    sd->dict_len = dict ? (uint64_t)dict_len : 0;
+    sd->prefix = 0;
+    sd->prefix_len = 0;
+}
+
+int64_t zlz4_decompress_safe_continue(zlz4_stream_decode_t *sd, const uint8_t *src, size_t n, uint8_t *dst,
+                                      size_t cap) {                 // :912-939
+    if (!sd) return ZLZ4_ERR_INVALID_STATE;
+    const uint64_t d = (uint64_t)(uintptr_t)dst;
+    if (sd->prefix_len == 0 && sd->dict_len == 0) {                 // :914-921
+        const int64_t r = zlz4_decompress_safe(src, n, dst, cap);
+        if (r >= 0) { sd->prefix = d; sd->prefix_len = (uint64_t)r; }
+        return r;
+    }
+    if (sd->dict_len > 0 && sd->prefix != 0) return ZLZ4_ERR_INVALID_STATE;   // (restStart would underflow, :213)
+    int64_t r;
+    if (sd->dict_len > 0 && sd->dict != 0) {                        // prefix null: lowPrefix = dst (:924-930)
+        r = zlz4_decompress_safe_using_dict(src, n, dst, cap, (const uint8_t *)(uintptr_t)sd->dict, (size_t)sd->dict_len);
+    } else {
+        // lowPrefix = prefix (or dst), no dictionary: matches below it are CorruptedData (:181-185)
+        const uint64_t low = sd->prefix ? sd->prefix : d;
+        const uint64_t lo = low > d ? low - d : 0;
+        if (lo == 0) r = zlz4_decompress_safe(src, n, dst, cap);
+        else if (n == 0 || cap == 0) r = 0;                         // :97-98
+        else r = run_single(Op::DecompressBound, src, n, dst, cap, 0, 0, nullptr, 0,
+                            lo < 0xFFFF0000ull ? (uint32_t)lo : 0xFFFF0000u);
+    }
+    if (r >= 0) { sd->dict = 0; sd->dict_len = 0; sd->prefix = d; sd->prefix_len = (uint64_t)r; }   // :933-938
+    return r;
+}
+
+size_t zlz4_decoder_ring_buffer_size(size_t max_block_size) {        // :954-957
+    return max_block_size == 0 ? 0 : 65536 + 14 + max_block_size;
+}
+
 int64_t zlz4_stream_load_dict(uint32_t *table, const uint8_t *dict, size_t dict_len) {   // src/lz4.zig:798-820
     if (!table || (!dict && dict_len)) return ZLZ4_ERR_INVALID_STATE;
     return run_stream_single(table, dict, dict_len, nullptr, 0, nullptr, 0, 0);
@@ -525,6 +583,25 @@ int32_t zlz4_batch_compress_fast_continue(void *stream, const uint8_t *d_in, con
     return zlz4_launch_compress_fast_continue((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
                                               d_table_in, d_table_idx, d_table_out, d_result, nblocks, max_in_len,
                                               acceleration);
+}
+
+size_t zlz4_batch_decompress_safe_continue_workspace(uint32_t nblocks, uint32_t nstreams) {
+    return zlz4_sd_workspace_bytes(nblocks, nstreams);
+}
+
+int32_t zlz4_batch_decompress_safe_continue(void *stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                            const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                            const uint32_t *d_out_cap, const uint32_t *d_run_start,
+                                            zlz4_stream_decode_t *d_state, int64_t *d_result, uint32_t nblocks,
+                                            uint32_t nstreams, void *d_workspace, size_t workspace_bytes) {
+    if (nstreams == 0 && nblocks == 0) return 0;
+    if (!d_run_start || !d_state || (nblocks && !d_result) || !d_workspace || ((uintptr_t)d_workspace & 15u) ||
+        workspace_bytes < zlz4_sd_workspace_bytes(nblocks, nstreams))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_stream_decode((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
+                                     d_run_start, reinterpret_cast<uint64_t *>(d_state), d_result, nblocks, nstreams,
+                                     d_workspace);
 }
 
 size_t zlz4_batch_compress_hc_workspace(uint32_t nblocks, uint32_t max_in_len) {

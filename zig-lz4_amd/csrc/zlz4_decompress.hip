@@ -64,7 +64,14 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
 // wavefronts per SIMD (64 VGPRs; the lane-copy build would take 67 and spills two to scratch instead): measured on
 // MI355X, 7 -> 8 wavefronts beat the spill on every case of tools/time_dict_decompress.py (configs[1] with an empty
 // dictionary 10.96 -> 10.46 ms); the no-dict instantiations are compiled exactly as before.
-template <bool kWrite, bool kLaneCopy = false, bool kPhases = kLaneCopy, bool kDict = false>
+// kBound: StreamDecode.decompressSafeContinue (src/lz4.zig:912-939) with a previous output at prefix: a match at output
+// position op with offset o is CorruptedData unless op - o >= lo = max(0, prefix - dst) (:181-185 without a dictionary,
+// then :231), tested where the other builds test offset > op.  lo is d_dict_len[nblocks + blk] (the arguments stay
+// those of the other builds, so their code does not change); lo = kBoundSkip leaves block blk alone (its result too),
+// kBoundInvalid stores InvalidState and decodes nothing (zlz4_batch_decompress_safe_continue, DESIGN.md section 4.2c;
+// the constants are in zlz4_device.hpp).
+// With kDict too, a block decodes with its dictionary or with its bound, never both (d_dict_len[blk] == 0 or lo == 0).
+template <bool kWrite, bool kLaneCopy = false, bool kPhases = kLaneCopy, bool kDict = false, bool kBound = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 : 1))) void k_decompress_safe(
     const uint8_t *__restrict__ d_in, const uint64_t *__restrict__ d_in_off,
     const uint32_t *__restrict__ d_in_len, uint8_t *d_out, const uint64_t *__restrict__ d_out_off,
@@ -79,6 +86,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
     uint8_t *dst = d_out + d_out_off[blk];
     const uint32_t iend = rfl(d_in_len[blk]);   // src.len
     const uint32_t oend = rfl(d_out_cap[blk]);  // dst.len == targetOutputSize
+    // (kBound) lo <= kBoundMax: offset + lo cannot wrap
+    uint32_t lo = 0;
+    if constexpr (kBound) {
+        lo = rfl(d_dict_len[nblocks + blk]);
+        if (lo >= kBoundInvalid) {
+            if (lane == 0 && lo == kBoundInvalid) d_result[blk] = kErrInvalidState;
+            return;
+        }
+    }
     // dictionary end and reachable length (kDict only).  Hand-issued dictionary loads use the scalar base dend - 65536 and
     // the 32-bit offset 65536 - (bytes in front of dend), which is >= 65536 - dlen >= 0.
     const uint8_t *dend = nullptr, *dbase = nullptr;
@@ -292,7 +308,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                     // :181-186 / :231 offset > op, and (copy pass) a match source that reaches into this batch's
                     // matches: end the phase in front of the first such sequence
                     const uint32_t lit0 = rdlane(lit, 0);
-                    viol_err = off > op0 + relv + lit;
+                    viol_err = off + lo > op0 + relv + lit;       // (lo == 0 unless kBound)
                     if constexpr (kDict) {
                         // a match wholly inside the dictionary reads memory no batch writes: it is always taken, as long
                         // as it passes :190 and the 16-byte loads of the sequence-lane copy stay inside the dictionary
@@ -482,7 +498,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                     if (ml > oend - op) { res = kErrOutputTooSmall; break; }             // :174
                     if (offset > op) {                                                   // :181-186 / :231
                         if (!kDict || offset - op > dlen) { res = kErrCorrupted; break; }   // (dict: :189-192)
-                    }
+                    } else if (kBound && offset + lo > op) { res = kErrCorrupted; break; }   // (match below prefix)
                     if (kWrite) {
                         const uint8_t *m = dst + (op - offset);
                         // out[op+k] = out[op-offset + (k mod offset)]; ml <= 18 lanes, one load + one store
@@ -555,7 +571,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
             if (ml > oend - op) { res = kErrOutputTooSmall; break; }   // :174
             if (offset > op) {                                      // :181-186 (no dict) / :231
                 if (!kDict || offset - op > dlen) { res = kErrCorrupted; break; }   // (dict: :189-192)
-            }
+            } else if (kBound && offset + lo > op) { res = kErrCorrupted; break; }   // (match below prefix)
             if constexpr (kDict) {
                 if (offset > op) {
                     // :199-225: the dictionary part first; what is left of a match that spans the dictionary end is
@@ -812,6 +828,32 @@ extern "C" int zlz4_launch_decompress_safe_using_dict(hipStream_t stream, const 
         hipLaunchKernelGGL((zlz4::k_decompress_safe<true, false, false, true>), dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in,
                            d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
                            d_dict, d_dict_off, d_dict_len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+// StreamDecode builds (kBound): the grid and build choice of zlz4_launch_decompress_safe_using_dict.  d_dict_len holds
+// 2 * nblocks entries: the dictionary lengths (read only when with_dict), then one bound per block (k_decompress_safe).
+// with_dict = 0 runs the build without the dictionary path (d_dict / d_dict_off are then not read).
+extern "C" int zlz4_launch_decompress_safe_bound(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                 const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                                 const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks,
+                                                 const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                 const uint32_t *d_dict_len, int with_dict) {
+    if (nblocks == 0) return 0;
+    const uint32_t waves_per_wg = 4;
+    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
+    const uint32_t min_phase_tokens = 3;
+    const bool lane_copy = nblocks >= kLaneCopyMinBlocks;
+#define ZLZ4_BOUND_LAUNCH(LC, DICT)                                                                                      \
+    hipLaunchKernelGGL((zlz4::k_decompress_safe<true, LC, LC, DICT, true>), dim3(grid), dim3(64 * waves_per_wg), 0,      \
+                       stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks,                 \
+                       min_phase_tokens, d_dict, d_dict_off, d_dict_len)
+    if (with_dict) {
+        if (lane_copy) ZLZ4_BOUND_LAUNCH(true, true); else ZLZ4_BOUND_LAUNCH(false, true);
+    } else {
+        if (lane_copy) ZLZ4_BOUND_LAUNCH(true, false); else ZLZ4_BOUND_LAUNCH(false, false);
+    }
+#undef ZLZ4_BOUND_LAUNCH
     return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 

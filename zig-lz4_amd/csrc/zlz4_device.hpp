@@ -33,6 +33,10 @@ constexpr int64_t kErrInputTooLarge = -2;
 constexpr int64_t kErrCorrupted = -3;
 constexpr int64_t kErrInvalidState = -5;   // also: a batch block longer than the call's max_in_len (include/zlz4_amd.h)
 
+// the per-block bound of the StreamDecode decoder builds (k_decompress_safe, kBound): lo <= kBoundMax is a bound, the
+// other two values skip the block (kBoundSkip) or store InvalidState (kBoundInvalid)
+constexpr uint32_t kBoundSkip = 0xFFFFFFFFu, kBoundInvalid = 0xFFFFFFFEu, kBoundMax = 0xFFFF0000u;
+
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }

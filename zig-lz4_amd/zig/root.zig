@@ -29,6 +29,10 @@ extern "c" fn zlz4_compress_hc_ext_state(state: [*]u8, state_len: usize, src: [*
 extern "c" fn zlz4_batch_compress_fast(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_decompress_safe(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
 extern "c" fn zlz4_batch_decompress_safe_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: [*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
+extern "c" fn zlz4_decompress_safe_continue(sd: *CStreamDecode, src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize) i64;
+extern "c" fn zlz4_decoder_ring_buffer_size(max_block_size: usize) usize;
+extern "c" fn zlz4_batch_decompress_safe_continue_workspace(nblocks: u32, nstreams: u32) usize;
+extern "c" fn zlz4_batch_decompress_safe_continue(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_run_start: [*]const u32, d_state: [*]CStreamDecode, d_result: [*]i64, nblocks: u32, nstreams: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_load_dict(stream: ?*anyopaque, d_dict: [*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_tables: [*]u32, d_result: [*]i64, ndicts: u32) i32;
 extern "c" fn zlz4_batch_compress_fast_continue(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_table_in: [*]const u32, d_table_idx: ?[*]const u32, d_table_out: ?[*]u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) usize;
@@ -242,6 +246,75 @@ pub fn freeStream(stream: *Stream) void {
     stream.destroy();
 }
 
+/// zlz4_stream_decode_t: StreamDecode's fields as byte addresses (0 = null); also the device state of
+/// `device.decompressSafeContinueBatch`
+pub const CStreamDecode = extern struct {
+    dict: u64,
+    dict_len: u64,
+    prefix: u64,
+    prefix_len: u64,
+};
+
+/// The streaming decompressor, reference src/lz4.zig:870-951: same fields and methods.  A call never reads the previous
+/// output, only compares its address with dst (include/zlz4_amd.h): each call is one zlz4_decompress_safe_continue.
+/// WARNING (a defect of the reference, reproduced): when the previous output lies above dst in memory -- a ring buffer
+/// of decoderRingBufferSize bytes once it wraps, a double buffer whose second half is lower -- every match reaching
+/// further back than prefix - dst bytes before the match position fails with CorruptedData.
+pub const StreamDecode = struct {
+    externalDict: ?[]const u8,
+    prefixEnd: ?[]const u8,
+    extDictSize: usize,
+    prefixSize: usize,
+    allocator: ?std.mem.Allocator,
+
+    pub fn create(allocator: std.mem.Allocator) Error!*StreamDecode {
+        const stream = allocator.create(StreamDecode) catch return error.AllocationFailed;
+        stream.* = init();
+        stream.allocator = allocator;
+        return stream;
+    }
+    pub fn destroy(self: *StreamDecode) void {
+        if (self.allocator) |alloc| alloc.destroy(self);
+    }
+    pub fn init() StreamDecode {
+        return .{ .externalDict = null, .prefixEnd = null, .extDictSize = 0, .prefixSize = 0, .allocator = null };
+    }
+    /// reference src/lz4.zig:904-909
+    pub fn setStreamDecode(self: *StreamDecode, dict: ?[]const u8) void {
+        self.externalDict = dict;
+        self.prefixEnd = null;
+        self.extDictSize = if (dict) |d| d.len else 0;
+        self.prefixSize = 0;
+    }
+    /// reference src/lz4.zig:912-939; errors leave the state unchanged
+    pub fn decompressSafeContinue(self: *StreamDecode, src: []const u8, dst: []u8) Error!usize {
+        var c = CStreamDecode{
+            .dict = if (self.externalDict) |d| @intFromPtr(d.ptr) else 0,
+            .dict_len = self.extDictSize,
+            .prefix = if (self.prefixEnd) |p| @intFromPtr(p.ptr) else 0,
+            .prefix_len = self.prefixSize,
+        };
+        const result = try mapBlock(zlz4_decompress_safe_continue(&c, src.ptr, src.len, dst.ptr, dst.len));
+        self.prefixEnd = dst[0..result];
+        self.prefixSize = result;
+        if (c.dict == 0) self.externalDict = null; // :936 (mode A keeps it)
+        self.extDictSize = @intCast(c.dict_len);
+        return result;
+    }
+};
+/// reference src/lz4.zig:943-945
+pub fn createStreamDecode(allocator: std.mem.Allocator) Error!*StreamDecode {
+    return StreamDecode.create(allocator);
+}
+/// reference src/lz4.zig:948-950
+pub fn freeStreamDecode(stream: *StreamDecode) void {
+    stream.destroy();
+}
+/// reference src/lz4.zig:954-957
+pub fn decoderRingBufferSize(maxBlockSize: usize) usize {
+    return zlz4_decoder_ring_buffer_size(maxBlockSize);
+}
+
 /// `@import("lz4").lz4.compressDefault(...)` and `.lz4hc.compressHC(...)` keep working (reference src/root.zig:3-5)
 const root = @This();
 pub const lz4 = struct {
@@ -263,6 +336,10 @@ pub const lz4 = struct {
     pub const Stream = root.Stream;
     pub const createStream = root.createStream;
     pub const freeStream = root.freeStream;
+    pub const StreamDecode = root.StreamDecode;
+    pub const createStreamDecode = root.createStreamDecode;
+    pub const freeStreamDecode = root.freeStreamDecode;
+    pub const decoderRingBufferSize = root.decoderRingBufferSize;
 };
 pub const lz4hc = struct {
     pub const LZ4HC_CLEVEL_MIN = 2;
@@ -301,6 +378,15 @@ pub const device = struct {
     /// batch form of decompressSafe (src/lz4.zig:257-259)
     pub fn decompressSafeBatch(stream: ?*anyopaque, b: Blocks) Error!void {
         return mapLaunch(zlz4_batch_decompress_safe(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks));
+    }
+    pub fn decompressSafeContinueWorkspace(nblocks: u32, nstreams: u32) usize {
+        return zlz4_batch_decompress_safe_continue_workspace(nblocks, nstreams);
+    }
+    /// StreamDecode.decompressSafeContinue (src/lz4.zig:912-939) over whole streams: stream s makes the calls
+    /// [run_start[s], run_start[s + 1]) of `b` in order (nstreams + 1 entries) from state[s] (device addresses, updated in
+    /// place); b.result[i] = what call i returns.  Output slots must not overlap (zlz4_batch_decompress_safe_continue).
+    pub fn decompressSafeContinueBatch(stream: ?*anyopaque, b: Blocks, run_start: [*]const u32, state: [*]CStreamDecode, nstreams: u32, workspace: ?*anyopaque, workspace_bytes: usize) Error!void {
+        return mapLaunch(zlz4_batch_decompress_safe_continue(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, run_start, state, b.result, b.nblocks, nstreams, workspace, workspace_bytes));
     }
     /// batch form of Stream.loadDict (src/lz4.zig:798-820): table i of `tables` (LZ4_HASH_SIZE_U32 u32 each) receives
     /// the table of dict[dict_off[i] ..][0..dict_len[i]]; result[i] = dictSize
