@@ -38,6 +38,16 @@ def test_large_batch_decoder_malformed_and_capacity_statuses(zl, oracle, gpu):
     600..6000 bytes (text, repetitive text, mixed), fast / accelerated / HC streams; every 9th block is damaged (bit
     flip, byte replacement, offset 0, 255-chain, forced length extensions), truncated, or given a capacity around its
     exact size.  Status equals the oracle's for every block, bytes too where it decodes."""
+    names, comp, caps = large_batch_blocks(oracle)
+    want = [oracle.decompress_safe(c, cap) for c, cap in zip(comp, caps)]
+    nerr = sum(isinstance(w, int) for w in want)
+    assert nerr > 600 and len(want) - nerr > 5000, nerr
+    got = gh.decompress(zl, comp, caps, gpu)
+    _cmp(names, got, want)
+
+
+def large_batch_blocks(oracle):
+    """-> (names, streams, capacities) of the 7000-block batch above (also read by tools/decoder_census.py)"""
     rng = np.random.default_rng(20261005)
     nblocks = 7000
     names, comp, caps = [], [], []
@@ -65,11 +75,7 @@ def test_large_batch_decoder_malformed_and_capacity_statuses(zl, oracle, gpu):
             cap = n + int(rng.choice([-1, -4, -17, -31, -32, -33, -100, 1, 31, 32, -n // 2]))
             what = "cap%d" % cap
         names.append("blk%d/n%d/%s" % (i, n, what)); comp.append(c); caps.append(cap)
-    want = [oracle.decompress_safe(c, cap) for c, cap in zip(comp, caps)]
-    nerr = sum(isinstance(w, int) for w in want)
-    assert nerr > 600 and len(want) - nerr > 5000, nerr
-    got = gh.decompress(zl, comp, caps, gpu)
-    _cmp(names, got, want)
+    return names, comp, caps
 
 
 @pytest.mark.parametrize("level", [12, 10])

@@ -18,7 +18,10 @@
 
 #include "zlz4_device.hpp"
 
-// Diagnostic build only (-DZLZ4_STAMPS): per-phase shader-cycle sums of the wave decoder (tools/stamp_decode.py)
+// Diagnostic build only (-DZLZ4_STAMPS): per-phase shader-cycle sums of the wave decoder (tools/stamp_decode.py) in
+// slots 0-7, and event counts (tools/decoder_census.py, restated by tests/seqgen.py model()): 8 batches, 9 sequences
+// copied in batches, 11 single-path sequences, 12 later copy phases, 13 phases cut by cap_short(), 14 batches that end
+// their phase loop at its limit
 #ifdef ZLZ4_STAMPS
 __device__ unsigned long long g_zlz4_dstamps[16];
 #define DSTAMP_DECL unsigned long long st_acc[16] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0}; unsigned long long st_last = __builtin_amdgcn_s_memtime();
@@ -331,7 +334,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                 // the previous batch have had the whole parse / walk / scan to arrive.
                 asm volatile("s_waitcnt vmcnt(1)" : "+v"(X2), "+v"(pa), "+v"(pb), "+v"(pd0), "+v"(pd1), "+v"(tdummy));
                 if (R == 0) break;                                  // the single-sequence paths take this one
-                DSTAMP_ADD(8, 1); DSTAMP_ADD(9, __builtin_popcountll(R));
+                DSTAMP_ADD(8, 1);
                 // A batch is copied in PHASES.  The match loads of a phase are issued with it and stored when the next
                 // one begins, so a match whose source reaches into the output of an earlier match of the same phase ends
                 // the phase in front of it -- but not the batch: everything the parse side found out about the window
@@ -351,6 +354,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                             R &= (1ull << fb) - 1ull;
                             T = rdlane(relv, fb);
                             pos = fb;
+                            DSTAMP_ADD(13, 1);
                         }
                     }
                 };
@@ -429,6 +433,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                 }
                 };
                 cap_short();
+                DSTAMP_ADD(9, __builtin_popcountll(R));
                 copy_side(std::false_type{});
                 // ---- further phases: only the copy pass has them, only if the phase before was cut short, only while
                 //      enough tokens are left to pay for a phase (it costs about half a batch; a batch that lost its last
@@ -452,12 +457,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                         } else {
                             R = Rn; T = T_walk; pos = pos_walk;
                         }
-                        DSTAMP_ADD(12, 1); DSTAMP_ADD(9, __builtin_popcountll(R));
+                        DSTAMP_ADD(12, 1);
                         // the loads of the phase before must have landed before flush_pending() stores them (right in front
                         // of the copy side: every way into it passes this wait -- tools/check_decoder_asm.py)
                         cap_short();
+                        DSTAMP_ADD(9, __builtin_popcountll(R));
                         asm volatile("s_waitcnt vmcnt(0)" : "+v"(pa), "+v"(pb), "+v"(pd0), "+v"(pd1), "+v"(tdummy), "+v"(X2));
                         copy_side(std::true_type{});
+#ifdef ZLZ4_STAMPS
+                        if (phase == 5u && pos != pos_walk) DSTAMP_ADD(14, 1);   // the loop ends at its limit of six phases
+#endif
                     }
                 }
                 op += T;
