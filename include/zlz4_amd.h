@@ -193,6 +193,13 @@ int64_t zlz4_decompress_safe_continue(zlz4_stream_decode_t *sd, const uint8_t *s
                                       size_t dst_cap);
 size_t  zlz4_decoder_ring_buffer_size(size_t max_block_size);
 
+/* Decompressed size of one block, HOST pointer (no counterpart in the reference, whose callers must know it): what
+ * zlz4_decompress_safe returns for `src` into a destination of 0xFFFFFFFF bytes, or, with dict_len > 0, what
+ * zlz4_decompress_safe_using_dict returns there with a dictionary of dict_len bytes -- the size, CorruptedData, or
+ * OutputTooSmall for a block that decodes to more than 0xFFFFFFFF bytes.  Only the dictionary's length matters (:189-192);
+ * its bytes are not needed.  src_len == 0 gives 0.  Nothing is decoded: see zlz4_batch_decompressed_size. */
+int64_t zlz4_decompressed_size(const uint8_t *src, size_t src_len, size_t dict_len);
+
 /* replaces lz4.sizeofState, src/lz4.zig:524-526 (= @sizeOf(HashTable) = 16384) */
 size_t  zlz4_sizeof_state(void);
 
@@ -242,6 +249,36 @@ int32_t zlz4_batch_decompress_safe_using_dict(void *stream,
                                               uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                               const uint8_t *d_dict, const uint64_t *d_dict_off,
                                               const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks);
+
+/* Decompressed sizes, for compressed blocks whose decoded size the caller does not know (an LZ4 block does not carry it;
+ * no counterpart in the reference).  d_size[i] = what decompressSafe (src/lz4.zig:257-259) returns for block i into a
+ * destination of 0xFFFFFFFF bytes, the library's per-block limit; with d_dict_len given, what decompressSafeUsingDict
+ * (:960-962) returns there with a dictionary of d_dict_len[i] bytes (d_dict_len == NULL: no dictionary; only the length
+ * takes part, :189-192, no dictionary byte is read).  So d_size[i] is the size, CorruptedData, or OutputTooSmall for a
+ * block that decodes to more than 0xFFFFFFFF bytes; d_in_len[i] == 0 gives 0.  The walk is decompressGeneric's (:89-251)
+ * with the decoder's decision order; no output is touched.
+ * Consequence: for s = d_size[i] >= 1, zlz4_batch_decompress_safe(_using_dict) of block i with capacity s returns s, and
+ * with a capacity of s - 1 >= 1 it returns OutputTooSmall: s is the smallest capacity that decodes the block.  One
+ * limit: the decoders saturate a single literal or match length at 0xFFFF0000 while the query
+ * counts exactly, so the consequence holds for blocks in which no single literal run or match is longer than
+ * 0xFFFF0000 bytes; a block with a longer one gets its true size here and is not decoded to it.
+ * Device pointers, asynchronous, no allocation, no read-back (graph-capturable).  A null d_in / d_in_off / d_in_len /
+ * d_size or a misaligned array (8 bytes for the 64-bit arrays, 4 for the 32-bit ones) returns InvalidState and launches
+ * nothing.  StreamDecode runs have no size query: whether a match is valid there depends on where the caller puts the
+ * outputs; for outputs placed back to back, query every call's block on its own. */
+int32_t zlz4_batch_decompressed_size(void *stream,
+                                     const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                     const uint32_t *d_dict_len, int64_t *d_size, uint32_t nblocks);
+
+/* Output slots from sizes, on the device: slot i holds max(d_size[i], 0) bytes rounded up to a multiple of `align`,
+ * d_out_off[i] is the exclusive scan of the slot sizes (slots are packed in block order), d_out_cap[i] = d_size[i], or 0
+ * for a failed block (a decode call then returns 0 for it and writes nothing), *d_total = the bytes all slots take.  The
+ * three outputs are what zlz4_batch_decompress_safe takes as d_out_off / d_out_cap, so size -> plan -> decode needs one
+ * read-back (the total, to allocate) or none (an arena of known size).  align: 0 or 1 = packed, else a power of two up to
+ * 4096; anything else returns InvalidState.  Null or misaligned arrays return InvalidState and launch nothing (n == 0
+ * needs only d_total, which receives 0).  Asynchronous, no allocation, graph-capturable. */
+int32_t zlz4_batch_plan_outputs(void *stream, const int64_t *d_size, uint32_t n, uint32_t align,
+                                uint64_t *d_out_off, uint32_t *d_out_cap, uint64_t *d_total);
 
 /* Stream.loadDict (src/lz4.zig:798-820) per dictionary: table i (d_tables + i * ZLZ4_STREAM_TABLE_ENTRIES u32) receives
  * the table of dictionary i = d_dict + d_dict_off[i] (d_dict_len[i] bytes); d_result[i] = its return value, dictSize.
@@ -414,6 +451,26 @@ int32_t zlz4f_batch_decompress_frame(void *stream,
                                      uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
                                      int64_t *d_result, uint32_t nframes, uint32_t max_blocks, void *d_workspace,
                                      size_t workspace_bytes);
+
+/* Decompressed size of frames.  d_size[f] = what zlz4f_batch_decompress_frame stores in d_result[f] when d_dst_cap[f] is
+ * large enough: the decoded size, or the frame's error in the order of src/lz4f.zig:541-638 -- the header errors, then per
+ * block FrameSizeWrong (a missing block checksum, :591), BlockChecksumInvalid (:596), DecompressionFailed (:611), the
+ * first failing block deciding, then FrameSizeWrong of a broken chain (:565, :582) or of a missing content-checksum word
+ * (:626).  ONE EXCEPTION: the content checksum is not verified (it is a hash of the decoded bytes): a frame whose only
+ * defect is a wrong content checksum reports its size here and ContentChecksumInvalid when it is decoded.  Stored blocks
+ * count their data size.  The header's content_size field is not consulted (the reference's decoder ignores it).
+ * max_blocks and ZLZ4_ERR_INVALID_STATE per frame as in zlz4f_batch_decompress_frame.  The walk, scan and block-checksum
+ * passes are that call's; then the size kernel of zlz4_batch_decompressed_size runs over the block table and one
+ * wavefront per frame adds up.  Nothing is written besides d_size and the workspace
+ * (zlz4f_batch_frame_decompressed_size_workspace bytes, 16-byte aligned; too small, null or misaligned returns
+ * InvalidState and launches nothing).  Asynchronous, no allocation, no read-back (graph-capturable).
+ * zlz4f_frame_decompressed_size is the same for one frame in HOST memory. */
+int64_t zlz4f_frame_decompressed_size(const uint8_t *src, size_t src_len);
+size_t  zlz4f_batch_frame_decompressed_size_workspace(uint32_t nframes, uint32_t max_blocks);
+int32_t zlz4f_batch_frame_decompressed_size(void *stream,
+                                            const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                            int64_t *d_size, uint32_t nframes, uint32_t max_blocks, void *d_workspace,
+                                            size_t workspace_bytes);
 
 /* ======================================================================
  * 4. Introspection

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Build-time audit of the decoder's hand-issued loads (zig-lz4_amd/csrc/zlz4_decompress.hip).
+"""Build-time audit of the decoder's hand-issued loads (zig-lz4_amd/csrc/zlz4_decompress.hip) and of the same window
+loads in the size kernel (k_decompressed_size, zig-lz4_amd/csrc/zlz4_sizes.hip: window load and touch only).
 
 k_decompress_safe issues three kinds of loads from asm statements with plain register outputs and waits for them in
 separate asm `s_waitcnt` statements (the compiler's own vmcnt bookkeeping would drain the queue at the first use):
@@ -22,6 +23,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "zig-lz4_amd", "csrc", "zlz4_decompress.hip")
+SIZES_SRC = os.path.join(ROOT, "zig-lz4_amd", "csrc", "zlz4_sizes.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -34,13 +36,13 @@ def regs_in(line):
     return out
 
 
-def audit(asm_text):
+def audit(asm_text, kernel_prefix="_ZN4zlz417k_decompress_safe"):
     """Walk the control-flow graph from every hand-issued load to the asm waits that can follow it."""
     lines = asm_text.splitlines()
     # kernel extents
     kernels, start = [], None
     for i, ln in enumerate(lines):
-        if re.match(r"^_ZN4zlz417k_decompress_safe", ln):
+        if ln.startswith(kernel_prefix):
             start = i
         elif start is not None and "s_endpgm" in ln:
             kernels.append((start, i))
@@ -112,16 +114,25 @@ def audit(asm_text):
     return checked, problems
 
 
-def main():
+def compile_and_audit(src, kernel_prefix):
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "d.s")
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-S",
-                               "--cuda-device-only", SRC, "-o", out], stderr=subprocess.DEVNULL)
-        checked, problems = audit(open(out).read())
-    print("decoder asm audit: %d hand-issued loads checked, %d problems" % (checked, len(problems)))
-    for p in problems:
-        print("  " + p)
-    return 1 if problems or checked == 0 else 0
+                               "--cuda-device-only", src, "-o", out], stderr=subprocess.DEVNULL)
+        return audit(open(out).read(), kernel_prefix)
+
+
+def main():
+    rc = 0
+    for what, src, prefix in (("decoder", SRC, "_ZN4zlz417k_decompress_safe"),
+                              ("size kernel", SIZES_SRC, "_ZN4zlz419k_decompressed_size")):
+        checked, problems = compile_and_audit(src, prefix)
+        print("%s asm audit: %d hand-issued loads checked, %d problems" % (what, checked, len(problems)))
+        for p in problems:
+            print("  " + p)
+        if problems or checked == 0:
+            rc = 1
+    return rc
 
 
 if __name__ == "__main__":

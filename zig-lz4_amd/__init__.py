@@ -72,6 +72,12 @@ SYMBOLS = {
     "zlz4_batch_compress_fast": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_decompress_safe": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_decompress_safe_using_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_decompressed_size": (_I64, [_VP, _SZ, _SZ]),
+    "zlz4_batch_decompressed_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_batch_plan_outputs": (_I32, [_VP, _VP, _U32, _U32, _VP, _VP, _VP]),
+    "zlz4f_frame_decompressed_size": (_I64, [_VP, _SZ]),
+    "zlz4f_batch_frame_decompressed_size_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_frame_decompressed_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
     "zlz4_batch_load_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_compress_fast_continue": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_compress_hc_workspace": (_SZ, [_U32, _U32]),
@@ -216,6 +222,13 @@ def decompressSafePartialUsingDict(src, dst_cap, target_output_size, dict):
     """lz4.decompressSafePartialUsingDict(src, dst, targetOutputSize, dict), src/lz4.zig:967-969."""
     dk, dn = _in(dict)
     return _run(lib().zlz4_decompress_safe_partial_using_dict, src, dst_cap, target_output_size, C.addressof(dk), dn)
+
+
+def decompressedSize(src, dict_len=0):
+    """zlz4_decompressed_size: what decompressSafe (dict_len == 0) or decompressSafeUsingDict with a dictionary of
+    dict_len bytes returns for `src` into a destination of 0xFFFFFFFF bytes; errors raise Lz4Error.  Nothing is decoded."""
+    s, n = _in(src)
+    return _check(lib().zlz4_decompressed_size(C.addressof(s), n, dict_len))
 
 
 STREAM_TABLE_ENTRIES = 4096                           # Stream.hashTable, src/lz4.zig:752 (LZ4_HASH_SIZE_U32, :33)
@@ -515,19 +528,54 @@ class lz4f:
         return _unstage(d_dst, _offsets(caps), result)
 
     @staticmethod
-    def decompressFrames(frames, caps, device="cuda"):
-        """Every frame of `frames` decoded into a destination of caps[f] bytes, in one batch call -> list of contents
-        (bytes) or error codes."""
+    def frameDecompressedSize(src):
+        """zlz4f_frame_decompressed_size: what decompressFrame returns for `src` into a destination that is large enough
+        (the content checksum is not verified); errors raise Lz4Error.  Nothing is decoded."""
+        s, n = _in(src)
+        return _check(lib().zlz4f_frame_decompressed_size(C.addressof(s), n))
+
+    @staticmethod
+    def frameDecompressedSizeBatchWorkspace(nframes, max_blocks):
+        return lib().zlz4f_batch_frame_decompressed_size_workspace(nframes, max_blocks)
+
+    @staticmethod
+    def frameDecompressedSizeBatch(d_src, src_off, src_len, size, max_blocks=None, workspace=None):
+        """zlz4f_batch_frame_decompressed_size on torch CUDA tensors (layout as decompressFrameBatch; size int64 = decoded
+        size or the frame's error code).  max_blocks defaults as in decompressFrameBatch."""
         import torch
-        caps = list(caps)
+        if max_blocks is None:
+            max_blocks = int((src_len.cpu() // 256 + 1).sum()) if src_len.numel() else 0
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_frame_decompressed_size_workspace(src_len.numel(), max_blocks)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_frame_decompressed_size(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(size),
+                                                         src_len.numel(), max_blocks, _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def decompressFrames(frames, caps=None, device="cuda"):
+        """Every frame of `frames` decoded into a destination of caps[f] bytes, in one batch call -> list of contents
+        (bytes) or error codes.  caps None: the sizes are queried first (frameDecompressedSizeBatch) and every frame gets
+        exactly its size (a frame the query fails gets no room and reports the query's code)."""
+        import torch
         d_src, src_off, src_len = _stage(frames, device)
+        sizes = None
+        if caps is None:
+            size = torch.empty(len(frames), dtype=torch.int64, device=device)
+            lz4f.frameDecompressedSizeBatch(d_src, src_off, src_len, size,
+                                            max_blocks=sum(_chain_blocks(bytes(f)) for f in frames))
+            sizes = size.cpu().tolist()
+            caps = [max(s, 0) for s in sizes]
+        caps = list(caps)
         dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
         d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
         result = torch.empty(len(frames), dtype=torch.int64, device=device)
         lz4f.decompressFrameBatch(d_src, src_off, src_len, d_dst, dst_off,
                                   torch.tensor(caps, dtype=torch.int64, device=device), result,
                                   max_blocks=sum(_chain_blocks(bytes(f)) for f in frames))
-        return _unstage(d_dst, _offsets(caps), result)
+        out = _unstage(d_dst, _offsets(caps), result)
+        if sizes is not None:                         # (a frame the query failed got no room: the query's code stands)
+            out = [o if s >= 0 else s for o, s in zip(out, sizes)]
+        return out
 
 
 def _offsets(lens):
@@ -600,6 +648,53 @@ def batch_decompress_safe_using_dict(d_in, in_off, in_len, d_out, out_off, out_c
     _check(lib().zlz4_batch_decompress_safe_using_dict(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
                                                        _ptr(out_off), _ptr(out_cap), _ptr(d_dict), _ptr(dict_off),
                                                        _ptr(dict_len), _ptr(result), in_len.numel()))
+
+
+def batch_decompressed_size(d_in, in_off, in_len, size, dict_len=None):
+    """zlz4_batch_decompressed_size: size[i] (int64) = what batch_decompress_safe returns for block i into 0xFFFFFFFF
+    bytes, or batch_decompress_safe_using_dict with a dictionary of dict_len[i] bytes (int32; None = no dictionary)."""
+    _check(lib().zlz4_batch_decompressed_size(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(dict_len),
+                                              _ptr(size), in_len.numel()))
+
+
+def batch_plan_outputs(size, out_off, out_cap, total, align=0):
+    """zlz4_batch_plan_outputs: packed slots from sizes (int64): out_off[i] (int64) = exclusive scan of max(size, 0)
+    rounded up to `align`, out_cap[i] (int32) = size or 0 for a failed block, total[0] (int64) = bytes of all slots."""
+    _check(lib().zlz4_batch_plan_outputs(_stream(), _ptr(size), size.numel(), align, _ptr(out_off), _ptr(out_cap),
+                                         _ptr(total)))
+
+
+def decompressBlocks(blocks, dicts=None, device="cuda"):
+    """Every compressed block of `blocks` decoded without knowing its size: size query, output plan, one read-back of the
+    total, allocation, decode.  dicts[i] (bytes or None) is block i's dictionary.  -> list of contents (bytes) or error
+    codes."""
+    import torch
+    n = len(blocks)
+    if n == 0:
+        return []
+    d_src, src_off, src_len = _stage(blocks, device)
+    in_len = src_len.to(torch.int32)
+    size = torch.empty(n, dtype=torch.int64, device=device)
+    out_off = torch.empty(n, dtype=torch.int64, device=device)
+    out_cap = torch.empty(n, dtype=torch.int32, device=device)
+    total = torch.empty(1, dtype=torch.int64, device=device)
+    result = torch.empty(n, dtype=torch.int64, device=device)
+    if dicts is None:
+        batch_decompressed_size(d_src, src_off, in_len, size)
+    else:
+        dbytes = [bytes(d) if d is not None else b"" for d in dicts]
+        d_dict, dict_off, dl = _stage(dbytes, device)
+        dict_len = dl.to(torch.int32)
+        batch_decompressed_size(d_src, src_off, in_len, size, dict_len)
+    batch_plan_outputs(size, out_off, out_cap, total)
+    d_dst = torch.empty(max(1, int(total.item())), dtype=torch.uint8, device=device)
+    if dicts is None:
+        batch_decompress_safe(d_src, src_off, in_len, d_dst, out_off, out_cap, result)
+    else:
+        batch_decompress_safe_using_dict(d_src, src_off, in_len, d_dst, out_off, out_cap, d_dict, dict_off, dict_len, result)
+    sizes = size.cpu().tolist()
+    out = _unstage(d_dst, out_off.cpu().tolist(), result)
+    return [o if s >= 0 else s for o, s in zip(out, sizes)]      # (a failed block has capacity 0: the query's code stands)
 
 
 def batch_load_dict(d_dict, dict_off, dict_len, tables, result):

@@ -104,6 +104,12 @@ struct StreamDecode {
 };
 inline std::size_t decoderRingBufferSize(std::size_t max_block_size) { return zlz4_decoder_ring_buffer_size(max_block_size); }
 
+// no counterpart in the reference: what decompressSafe (dict_len 0) / decompressSafeUsingDict with a dictionary of dict_len
+// bytes returns for `src` into a destination of 0xFFFFFFFF bytes; nothing is decoded
+inline Result decompressedSize(const std::uint8_t *src, std::size_t n, std::size_t dict_len = 0) {
+    return wrap(zlz4_decompressed_size(src, n, dict_len));
+}
+
 // lz4.sizeofState / compressFastExtState / compressDestSize, src/lz4.zig:524-616
 inline std::size_t sizeofState() { return zlz4_sizeof_state(); }
 inline Result compressFastExtState(void *state, std::size_t state_len, const std::uint8_t *src, std::size_t n,
@@ -146,6 +152,18 @@ struct DictBlocks {
 inline Result decompressSafeUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d) {
     return wrap(zlz4_batch_decompress_safe_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
                                                       d.dict_off, d.dict_len, b.result, b.nblocks));
+}
+// decompressed sizes: size[i] = what decompressSafeBatch returns for block i into 0xFFFFFFFF bytes, or
+// decompressSafeUsingDictBatch with a dictionary of dict_len[i] bytes (nullptr = no dictionary); only b.in* and b.nblocks
+// are read
+inline Result decompressedSizeBatch(void *stream, const Blocks &b, const std::uint32_t *d_dict_len, std::int64_t *d_size) {
+    return wrap(zlz4_batch_decompressed_size(stream, b.in, b.in_off, b.in_len, d_dict_len, d_size, b.nblocks));
+}
+// packed output slots from sizes: out_off / out_cap as Blocks takes them, *total = bytes of all slots (align 0, 1 or a
+// power of two up to 4096)
+inline Result planOutputs(void *stream, const std::int64_t *d_size, std::uint32_t n, std::uint32_t align,
+                          std::uint64_t *d_out_off, std::uint32_t *d_out_cap, std::uint64_t *d_total) {
+    return wrap(zlz4_batch_plan_outputs(stream, d_size, n, align, d_out_off, d_out_cap, d_total));
 }
 // StreamDecode.decompressSafeContinue over whole streams: stream s makes the calls [run_start[s], run_start[s + 1]) of b
 // from d_state[s] (device addresses, updated in place)
@@ -236,6 +254,16 @@ inline std::size_t decompressFrameBatchWorkspace(std::uint32_t nframes, std::uin
 inline Result decompressFrameBatch(void *stream, const Frames &f, std::uint32_t max_blocks, void *ws, std::size_t ws_bytes) {
     return wrap(zlz4f_batch_decompress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes,
                                              max_blocks, ws, ws_bytes));
+}
+// decompressed size of frames: what decompressFrame(Batch) returns into a destination that is large enough (the content
+// checksum is not verified); nothing is decoded.  Only f.src*, f.nframes are read; d_size receives the sizes.
+inline Result frameDecompressedSize(const std::uint8_t *src, std::size_t n) { return wrap(zlz4f_frame_decompressed_size(src, n)); }
+inline std::size_t frameDecompressedSizeBatchWorkspace(std::uint32_t nframes, std::uint32_t max_blocks) {
+    return zlz4f_batch_frame_decompressed_size_workspace(nframes, max_blocks);
+}
+inline Result frameDecompressedSizeBatch(void *stream, const Frames &f, std::int64_t *d_size, std::uint32_t max_blocks, void *ws,
+                                         std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_frame_decompressed_size(stream, f.src, f.src_off, f.src_len, d_size, f.nframes, max_blocks, ws, ws_bytes));
 }
 }  // namespace lz4f
 

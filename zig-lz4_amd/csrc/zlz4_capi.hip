@@ -43,6 +43,9 @@ extern "C" int zlz4_launch_stream_decode(hipStream_t, const uint8_t *, const uin
                                          const uint64_t *, const uint32_t *, const uint32_t *, uint64_t *, int64_t *,
                                          uint32_t, uint32_t, void *);
 extern "C" uint32_t zlz4_dest_size_slot_cap(uint32_t max_in_len);
+extern "C" int zlz4_launch_decompressed_size(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
+                                             const uint32_t *, int64_t *, uint32_t);
+extern "C" int zlz4_launch_plan_outputs(hipStream_t, const int64_t *, uint32_t, uint32_t, uint64_t *, uint32_t *, uint64_t *);
 
 namespace {
 
@@ -414,6 +417,32 @@ int64_t zlz4_decompress_safe_continue(zlz4_stream_decode_t *sd, const uint8_t *s
     return r;
 }
 
+// what decompressSafe / decompressSafeUsingDict would return into 0xFFFFFFFF bytes: the size kernel on one staged block
+int64_t zlz4_decompressed_size(const uint8_t *src, size_t n, size_t dict_len) {
+    if (n == 0) return 0;                                           // src/lz4.zig:97
+    if (!src) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    if (n > 0xFFFFFFFFull) return ZLZ4_ERR_CORRUPTED_DATA;          // (as zlz4_decompress_safe)
+    hipStream_t st = nullptr;
+    DeviceCall dc(st);
+    DevBuf d_in(n, &dc), d_meta(64, &dc);
+    if (!d_in.p || !d_meta.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    struct Meta { uint64_t in_off; int64_t result; uint32_t in_len; uint32_t dict_len; } m;
+    m.in_off = 0; m.result = 0; m.in_len = (uint32_t)n; m.dict_len = dict_len < 65536u ? (uint32_t)dict_len : 65536u;
+    dc.launched();
+    if (hipMemcpyAsync(d_in.p, src, n, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    auto *dm = d_meta.as<uint8_t>();
+    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
+    const int rc = zlz4_launch_decompressed_size(st, d_in.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
+                                                 reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)),
+                                                 reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)), p_res, 1);
+    if (rc != 0) return rc;
+    int64_t result = 0;
+    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
+    return result;
+}
+
 size_t zlz4_decoder_ring_buffer_size(size_t max_block_size) {        // :954-957
     return max_block_size == 0 ? 0 : 65536 + 14 + max_block_size;
 }
@@ -583,6 +612,26 @@ int32_t zlz4_batch_compress_fast_continue(void *stream, const uint8_t *d_in, con
     return zlz4_launch_compress_fast_continue((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
                                               d_table_in, d_table_idx, d_table_out, d_result, nblocks, max_in_len,
                                               acceleration);
+}
+
+int32_t zlz4_batch_decompressed_size(void *stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                     const uint32_t *d_dict_len, int64_t *d_size, uint32_t nblocks) {
+    if (nblocks == 0) return 0;
+    if (!d_in || !d_in_off || !d_in_len || !d_size) return ZLZ4_ERR_INVALID_STATE;
+    if (((uintptr_t)d_in_off | (uintptr_t)d_size) & 7u || ((uintptr_t)d_in_len | (uintptr_t)d_dict_len) & 3u)
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_decompressed_size((hipStream_t)stream, d_in, d_in_off, d_in_len, d_dict_len, d_size, nblocks);
+}
+
+int32_t zlz4_batch_plan_outputs(void *stream, const int64_t *d_size, uint32_t n, uint32_t align, uint64_t *d_out_off,
+                                uint32_t *d_out_cap, uint64_t *d_total) {
+    if (align > 4096u || (align & (align - 1u))) return ZLZ4_ERR_INVALID_STATE;      // 0, 1 or a power of two up to 4096
+    if (!d_total || (n && (!d_size || !d_out_off || !d_out_cap))) return ZLZ4_ERR_INVALID_STATE;
+    if (((uintptr_t)d_size | (uintptr_t)d_out_off | (uintptr_t)d_total) & 7u || (uintptr_t)d_out_cap & 3u)
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_plan_outputs((hipStream_t)stream, d_size, n, align ? align : 1u, d_out_off, d_out_cap, d_total);
 }
 
 size_t zlz4_batch_decompress_safe_continue_workspace(uint32_t nblocks, uint32_t nstreams) {

@@ -32,6 +32,8 @@ extern "C" int zlz4_launch_decompress_safe(hipStream_t, const uint8_t *, const u
                                            const uint64_t *, const uint32_t *, int64_t *, uint32_t);
 extern "C" int zlz4_launch_decompress_sizes(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
                                             const uint64_t *, const uint32_t *, int64_t *, uint32_t);
+extern "C" int zlz4_launch_decompressed_size(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
+                                             const uint32_t *, int64_t *, uint32_t);
 extern "C" int zlz4_launch_compress_fast(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
                                          const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
 extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
@@ -1192,6 +1194,61 @@ __global__ void k_bfd_finish(const BFrame *__restrict__ fr, uint32_t nframes, ui
     result[f] = (int64_t)F.total;
 }
 
+// ------------------------------------------------------------------ decompressed-size query
+// per entry: the size kernel's input length (a stored block is not decoded: length 0)
+__global__ void k_bfq_len(const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags, uint32_t max_blocks,
+                          uint32_t *__restrict__ dec_len) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x)
+        dec_len[i] = (flags[i] & kBlkStored) ? 0u : data_len[i];
+}
+
+// one wavefront per frame: k_bfd_plan and k_bfd_finish for a destination that is never too small, without the content
+// checksum (it needs the decoded bytes).  The first failing block decides (:591, :596, :611), then the walk's error, then
+// the missing content-checksum word (:626); otherwise the sum of the block sizes (a stored block counts its data).
+__global__ __launch_bounds__(256) void k_bfq_total(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                                                   const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags,
+                                                   const int64_t *__restrict__ sizes, const uint32_t *__restrict__ cks_ok,
+                                                   const uint64_t *__restrict__ src_len, int64_t *__restrict__ result) {
+    const uint32_t f = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    int64_t out;
+    if (F.status < 0) out = F.status;                                                  // :547
+    else if (!bf_fits(F, max_blocks)) out = ZLZ4_ERR_INVALID_STATE;
+    else {
+        const bool bc = (F.flg & 0x10u) != 0;
+        unsigned long long sum = 0, bad = ~0ull;                      // bad = this lane's first failing block
+        int32_t code = 0;
+        for (uint64_t j = lane; j < F.nb && bad == ~0ull; j += 64u) {
+            const uint64_t i = F.base + j;
+            int32_t err = 0;
+            uint64_t sz = 0;
+            if (bc && cks_ok[i] == 2u) err = ZLZ4F_ERR_FRAME_SIZE_WRONG;               // :591
+            else if (bc && cks_ok[i] == 0u) err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID;    // :596
+            else if (flags[i] & kBlkStored) sz = data_len[i];                          // :603-608
+            else if (data_len[i] != 0) {                                               // :610 (src/lz4.zig:97)
+                const int64_t s = sizes[i];
+                if (s < 0) err = ZLZ4F_ERR_DECOMPRESSION_FAILED;                       // :611
+                else sz = (uint64_t)s;
+            }
+            if (err) { bad = j; code = err; } else sum += sz;
+        }
+        unsigned long long first = bad;
+        for (uint32_t d = 32u; d >= 1u; d >>= 1) {
+            const unsigned long long o = __shfl_xor(first, (int)d), t = __shfl_xor(sum, (int)d);
+            first = o < first ? o : first;
+            sum += t;
+        }
+        int64_t err = 0;
+        if (first != ~0ull) err = (int64_t)(int32_t)zlz4::rdlane((uint32_t)code, zlz4::first_lane(zlz4::ballot(bad == first)));
+        if (!err) err = F.err;
+        if (err) out = err;
+        else if ((F.flg & 0x04u) && F.end + 4 > src_len[f]) out = ZLZ4F_ERR_FRAME_SIZE_WRONG;   // :626
+        else out = (int64_t)sum;
+    }
+    if (lane == 0) result[f] = out;
+}
+
 // ------------------------------------------------------------------ workspace layout
 struct BatchLayout {
     size_t off[20];
@@ -1228,6 +1285,17 @@ BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks) {
     L.add((size_t)nframes * sizeof(BFrame));
     for (int k = 0; k < 4; k++) L.add(m * sizeof(uint64_t));
     for (int k = 0; k < 8; k++) L.add(m * sizeof(uint32_t));
+    L.add(m * sizeof(int64_t));
+    return L;
+}
+
+// size query: frames | data_off cks_off (u64) | data_len flags fidx cks_ok dec_len (u32) | sizes (i64)
+BatchLayout bfq_layout(uint32_t nframes, uint32_t max_blocks) {
+    const size_t m = max_blocks;
+    BatchLayout L;
+    L.add((size_t)nframes * sizeof(BFrame));
+    for (int k = 0; k < 2; k++) L.add(m * sizeof(uint64_t));
+    for (int k = 0; k < 5; k++) L.add(m * sizeof(uint32_t));
     L.add(m * sizeof(int64_t));
     return L;
 }
@@ -1358,6 +1426,85 @@ int32_t zlz4f_batch_decompress_frame(void *stream_, const uint8_t *d_src, const 
     hipLaunchKernelGGL(k_bfd_finish, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, d_src, d_src_off, d_src_len, d_dst,
                        d_dst_off, d_dst_cap, d_result);
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+size_t zlz4f_batch_frame_decompressed_size_workspace(uint32_t nframes, uint32_t max_blocks) {
+    return bfq_layout(nframes, max_blocks).bytes;
+}
+
+// the walk, scan and block-checksum passes of zlz4f_batch_decompress_frame, then the size kernel over the block table and
+// the per-frame total; nothing but d_size and the workspace is written
+int32_t zlz4f_batch_frame_decompressed_size(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
+                                            const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
+                                            uint32_t max_blocks, void *d_workspace, size_t workspace_bytes) {
+    if (nframes == 0) return 0;
+    const BatchLayout L = bfq_layout(nframes, max_blocks);
+    if (!d_src || !d_src_off || !d_src_len || !d_size || !d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < L.bytes)
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)stream_;
+    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
+    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
+    uint64_t *data_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *cks_off = reinterpret_cast<uint64_t *>(ws + L.off[2]);
+    uint32_t *data_len = reinterpret_cast<uint32_t *>(ws + L.off[3]), *flags = reinterpret_cast<uint32_t *>(ws + L.off[4]),
+             *fidx = reinterpret_cast<uint32_t *>(ws + L.off[5]), *cks_ok = reinterpret_cast<uint32_t *>(ws + L.off[6]),
+             *dec_len = reinterpret_cast<uint32_t *>(ws + L.off[7]);
+    int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[8]);
+    const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
+    if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
+    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
+                       data_off, data_len, flags, cks_off, fidx);
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
+    if (max_blocks) {
+        hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
+                           data_off, data_len, flags, cks_off, fidx);
+        hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, data_off, data_len, flags,
+                           cks_off, max_blocks, cks_ok);
+        hipLaunchKernelGGL(k_bfq_len, dim3(gb), dim3(256), 0, st, data_len, flags, max_blocks, dec_len);
+        if (zlz4_launch_decompressed_size(st, d_src, data_off, dec_len, nullptr, sizes, max_blocks) != 0) return ZLZ4_ERR_DEVICE;
+    }
+    hipLaunchKernelGGL(k_bfq_total, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags,
+                       sizes, cks_ok, d_src_len, d_size);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+// what zlz4f_decompress_frame returns into a destination that is large enough (the content checksum aside), host
+// pointers: the frame is staged and queried as a batch of one; the block count for the table comes from a host walk of
+// the chain (k_bfd_walk's)
+int64_t zlz4f_frame_decompressed_size(const uint8_t *src, size_t n) {
+    if (!src && n) return ZLZ4_ERR_INVALID_STATE;
+    const ParsedHeader ph = parse_header(src, n);      // header errors need no device
+    if (ph.size < 0) return ph.size;
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    const bool bc = (ph.flg & 0x10u) != 0;
+    uint64_t pos = (uint64_t)ph.size, nb = 0;
+    while (pos + 4 <= n) {
+        const uint32_t h = zx_rd32(src + pos);
+        const uint64_t sz = h & 0x7FFFFFFFu;
+        if (h == 0 || pos + 4 + sz > n) break;
+        pos += 4 + sz;
+        nb++;
+        if (bc) { if (pos + 4 > n) break; pos += 4; }
+    }
+    if (nb > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
+    const uint32_t max_blocks = (uint32_t)nb;
+    const size_t ws = zlz4f_batch_frame_decompressed_size_workspace(1, max_blocks);
+    hipStream_t st = nullptr;
+    zlz4host::DeviceCall dc(st);
+    DevBuf d_src(n, &dc), d_meta(64, &dc), d_ws(ws, &dc);
+    if (!d_src.p || !d_meta.p || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    struct Meta { uint64_t off, len; int64_t size; } m = {0, (uint64_t)n, 0};
+    dc.launched();
+    if (hipMemcpyAsync(d_src.p, src, n, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    auto *dm = d_meta.as<uint8_t>();
+    const int32_t rc = zlz4f_batch_frame_decompressed_size(st, d_src.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm),
+                                                           reinterpret_cast<const uint64_t *>(dm + 8),
+                                                           reinterpret_cast<int64_t *>(dm + 16), 1, max_blocks, d_ws.p, ws);
+    if (rc != 0) return rc;
+    int64_t r = 0;
+    if (hipMemcpyAsync(&r, dm + 16, sizeof r, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
+    return r;
 }
 
 }  // extern "C"

@@ -39,6 +39,9 @@ extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) us
 extern "c" fn zlz4_batch_compress_hc(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_compress_dest_size_workspace(nblocks: u32, max_in_len: u32) usize;
 extern "c" fn zlz4_batch_compress_dest_size(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, d_consumed: [*]u32, nblocks: u32, max_in_len: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4_decompressed_size(src: [*]const u8, src_len: usize, dict_len: usize) i64;
+extern "c" fn zlz4_batch_decompressed_size(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_dict_len: ?[*]const u32, d_size: [*]i64, nblocks: u32) i32;
+extern "c" fn zlz4_batch_plan_outputs(stream: ?*anyopaque, d_size: [*]const i64, n: u32, alignment: u32, d_out_off: [*]u64, d_out_cap: [*]u32, d_total: *u64) i32;
 extern "c" fn zlz4_batch_verify(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_comp: [*]const u8, d_comp_off: [*]const u64, d_comp_result: [*]const i64, d_verify: [*]i64, nblocks: u32) i64;
 
 pub const CPrefs = extern struct {
@@ -61,6 +64,9 @@ extern "c" fn zlz4f_decompress_frame_segment_device(stream: ?*anyopaque, d_src: 
 extern "c" fn zlz4f_batch_compress_frame_workspace(nframes: u32, max_blocks: u32, prefs: ?*const CPrefs) usize;
 extern "c" fn zlz4f_batch_compress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_batch_decompress_frame_workspace(nframes: u32, max_blocks: u32) usize;
+extern "c" fn zlz4f_frame_decompressed_size(src: [*]const u8, src_len: usize) i64;
+extern "c" fn zlz4f_batch_frame_decompressed_size_workspace(nframes: u32, max_blocks: u32) usize;
+extern "c" fn zlz4f_batch_frame_decompressed_size(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_size: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_batch_decompress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 
 // ---- constants (reference src/lz4.zig:12-25, src/lz4hc.zig:28-31) ----
@@ -123,6 +129,11 @@ pub fn decompressSafeUsingDict(src: []const u8, dst: []u8, dict: []const u8) Err
 /// reference src/lz4.zig:967-969
 pub fn decompressSafePartialUsingDict(src: []const u8, dst: []u8, targetOutputSize: usize, dict: []const u8) Error!usize {
     return mapBlock(zlz4_decompress_safe_partial_using_dict(src.ptr, src.len, dst.ptr, dst.len, targetOutputSize, dict.ptr, dict.len));
+}
+/// No counterpart in the reference: what decompressSafe (dict_len 0) or decompressSafeUsingDict with a dictionary of
+/// dict_len bytes returns for `src` into a destination of 0xFFFFFFFF bytes.  Nothing is decoded.
+pub fn decompressedSize(src: []const u8, dict_len: usize) Error!usize {
+    return mapBlock(zlz4_decompressed_size(src.ptr, src.len, dict_len));
 }
 /// reference src/lz4.zig:524-526
 pub fn sizeofState() usize {
@@ -330,6 +341,7 @@ pub const lz4 = struct {
     pub const decompressSafePartial = root.decompressSafePartial;
     pub const decompressSafeUsingDict = root.decompressSafeUsingDict;
     pub const decompressSafePartialUsingDict = root.decompressSafePartialUsingDict;
+    pub const decompressedSize = root.decompressedSize;
     pub const sizeofState = root.sizeofState;
     pub const compressFastExtState = root.compressFastExtState;
     pub const LZ4_HASH_SIZE_U32 = root.LZ4_HASH_SIZE_U32;
@@ -378,6 +390,16 @@ pub const device = struct {
     /// batch form of decompressSafe (src/lz4.zig:257-259)
     pub fn decompressSafeBatch(stream: ?*anyopaque, b: Blocks) Error!void {
         return mapLaunch(zlz4_batch_decompress_safe(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks));
+    }
+    /// decompressed sizes (zlz4_batch_decompressed_size): size[i] = what decompressSafeBatch returns for block i into
+    /// 0xFFFFFFFF bytes, or decompressSafeUsingDictBatch with a dictionary of dict_len[i] bytes (null = no dictionary)
+    pub fn decompressedSizeBatch(stream: ?*anyopaque, in: [*]const u8, in_off: [*]const u64, in_len: [*]const u32, dict_len: ?[*]const u32, size: [*]i64, nblocks: u32) Error!void {
+        return mapLaunch(zlz4_batch_decompressed_size(stream, in, in_off, in_len, dict_len, size, nblocks));
+    }
+    /// packed output slots from sizes (zlz4_batch_plan_outputs): out_off / out_cap as `Blocks` takes them, total = bytes
+    /// of all slots; alignment 0, 1 or a power of two up to 4096
+    pub fn planOutputs(stream: ?*anyopaque, size: [*]const i64, n: u32, alignment: u32, out_off: [*]u64, out_cap: [*]u32, total: *u64) Error!void {
+        return mapLaunch(zlz4_batch_plan_outputs(stream, size, n, alignment, out_off, out_cap, total));
     }
     pub fn decompressSafeContinueWorkspace(nblocks: u32, nstreams: u32) usize {
         return zlz4_batch_decompress_safe_continue_workspace(nblocks, nstreams);
@@ -532,6 +554,11 @@ pub const lz4f = struct {
     pub fn headerSize(src: []const u8) Error!usize {
         return mapFrame(zlz4f_header_size(src.ptr, src.len));
     }
+    /// No counterpart in the reference: what decompressFrame returns for `src` into a destination that is large enough
+    /// (the content checksum is not verified).  Nothing is decoded.
+    pub fn frameDecompressedSize(src: []const u8) Error!usize {
+        return mapFrame(zlz4f_frame_decompressed_size(src.ptr, src.len));
+    }
 
     /// Device-resident frames (BASELINE configs[4]): `d_src` / `d_dst` are device pointers.
     pub const SEG_FIRST: u32 = 1;
@@ -589,5 +616,12 @@ pub const lz4f = struct {
     }
     pub fn decompressFrameBatch(stream: ?*anyopaque, f: Frames, max_blocks: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
         return mapBatch(zlz4f_batch_decompress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, workspace, workspace_bytes));
+    }
+    pub fn frameDecompressedSizeBatchWorkspace(nframes: u32, max_blocks: u32) usize {
+        return zlz4f_batch_frame_decompressed_size_workspace(nframes, max_blocks);
+    }
+    /// size[f] = what decompressFrameBatch stores in result[f] when dst_cap[f] is large enough (content checksum aside)
+    pub fn frameDecompressedSizeBatch(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, size: [*]i64, nframes: u32, max_blocks: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_frame_decompressed_size(stream, src, src_off, src_len, size, nframes, max_blocks, workspace, workspace_bytes));
     }
 };
