@@ -160,6 +160,24 @@ int64_t zlz4_stream_load_dict(uint32_t *table, const uint8_t *dict, size_t dict_
 int64_t zlz4_stream_compress_fast_continue(uint32_t *table, const uint8_t *src, size_t src_len, uint8_t *dst,
                                            size_t dst_cap, uint32_t acceleration);
 
+/* Compression against an external dictionary (no counterpart in the reference: its Stream.compressFastContinue reads
+ * every loaded table entry as a position in the current block, src/lz4.zig:656-659, so its blocks never refer to the
+ * dictionary).  With tail = the last D = min(dict_len, 65536) bytes of `dict` and V = tail ++ src: the entry checks of
+ * compressFastContinue (:823-827: InputTooLarge above ZLZ4_MAX_INPUT_SIZE, 0 for 0 bytes, compressAsLiterals for 1..12
+ * bytes), then compressFastWithHashTable's loop (:624-740) statement for statement on V, with
+ *   - the table starting as Stream.loadDict(dict) leaves it (:798-820; what zlz4_batch_load_dict writes),
+ *   - anchor = D and ip = max(D, 1) at entry (:626-633): the record's first byte may match into the dictionary,
+ *   - mflimitPlusOne = D + src_len - 12, matchLimit = D + src_len - 5, every position a position in V,
+ *   - nothing else changed: validity test, unconditional put, skip schedule, no backward extension, forward extension
+ *     up to matchLimit (it may run from the dictionary into the record and over itself), one put after a match, every
+ *     OutputTooSmall test at the same point, offset = ip - match.  Position 0 of V is never matchable (0 = empty).
+ * The block decodes with zlz4_decompress_safe_using_dict(dst, .., dict, dict_len) (and with liblz4's decoder) to src;
+ * its size is at most zlz4_compress_bound(src_len).  With an empty dictionary the bytes and the status are
+ * zlz4_compress_fast's.  The record and the tail are staged and the table is computed on the device (correct, not
+ * fast: zlz4_batch_compress_fast_using_dict is the fast path).  dict == NULL with dict_len > 0 -> InvalidState. */
+int64_t zlz4_compress_fast_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                      const uint8_t *dict, size_t dict_len, uint32_t acceleration);
+
 /* Streaming decompression, lz4.StreamDecode (src/lz4.zig:870-957).  The reference's fields as byte addresses (0 = null):
  * dict / dict_len = externalDict / extDictSize, prefix / prefix_len = prefixEnd.ptr / prefixSize.  The state holds no
  * data: a call never reads the previous output, only compares its address with the new dst (see the warning below).
@@ -302,6 +320,29 @@ int32_t zlz4_batch_compress_fast_continue(void *stream,
                                           const uint32_t *d_table_in, const uint32_t *d_table_idx, uint32_t *d_table_out,
                                           int64_t *d_result, uint32_t nblocks, uint32_t max_in_len,
                                           uint32_t acceleration);
+
+/* zlz4_compress_fast_using_dict per block (no counterpart in the reference): block i is compressed against the
+ * dictionary d_dict + d_dict_off[i] (d_dict_len[i] bytes, any length; only the last 65536 take part) starting from
+ * table d_table_idx[i] of d_table (d_table_idx == NULL: table i), which must be what zlz4_batch_load_dict wrote for
+ * that dictionary: ZLZ4_STREAM_TABLE_ENTRIES u32 per table, d_table 16-byte aligned as for
+ * zlz4_batch_compress_fast_continue.  Any other table contents still give a block that decodes to the input
+ * (`match < ip` bounds every read, the 4-byte compare vouches for every match); only the dictionary's own table gives the
+ * specified bytes.  A shared dictionary = one dictionary, one table, the same offset and index for every block.  The
+ * previous record as dictionary = dictionaries inside d_in, their tables from one zlz4_batch_load_dict over the
+ * records.  Dictionaries and tables are read-only and must not overlap any output slot; no table is returned.
+ * max_in_len and max_dict_len are preconditions that select the table width (16-bit positions while
+ * max_in_len + min(max_dict_len, 65536) <= 65547): a block with d_in_len[i] > max_in_len or
+ * min(d_dict_len[i], 65536) > max_dict_len gets InvalidState and writes nothing.  d_result[i] = what the single call
+ * returns; no byte outside the block's output slot is written.  Null arrays (d_dict may be NULL when max_dict_len == 0),
+ * a d_table that is not 16-byte aligned or another misaligned array (8 bytes for the 64-bit arrays, 4 for the 32-bit
+ * ones) return InvalidState and launch nothing.  Asynchronous, no allocation, no read-back (graph-capturable). */
+int32_t zlz4_batch_compress_fast_using_dict(void *stream,
+                                            const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                            uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                            const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                            const uint32_t *d_table, const uint32_t *d_table_idx,
+                                            int64_t *d_result, uint32_t nblocks, uint32_t max_in_len,
+                                            uint32_t max_dict_len, uint32_t acceleration);
 
 /* StreamDecode.decompressSafeContinue (src/lz4.zig:912-939) over whole streams in one call.  Stream s makes the calls
  * [d_run_start[s], d_run_start[s + 1]) in that order (d_run_start: nstreams + 1 ascending entries, the first 0, the

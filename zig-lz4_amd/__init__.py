@@ -66,6 +66,7 @@ SYMBOLS = {
     "zlz4_decompress_safe_partial_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _SZ, _VP, _SZ]),
     "zlz4_stream_load_dict": (_I64, [_VP, _VP, _SZ]),
     "zlz4_stream_compress_fast_continue": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _U32]),
+    "zlz4_compress_fast_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _U32]),
     "zlz4_sizeof_state": (_SZ, []),
     "zlz4_compress_fast_ext_state": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _U32]),
     "zlz4_compress_dest_size": (_I64, [_VP, _VP, _SZ, C.POINTER(C.c_size_t)]),
@@ -80,6 +81,7 @@ SYMBOLS = {
     "zlz4f_batch_frame_decompressed_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
     "zlz4_batch_load_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_compress_fast_continue": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
+    "zlz4_batch_compress_fast_using_dict": (_I32, [_VP] * 13 + [_U32, _U32, _U32, _U32]),
     "zlz4_batch_compress_hc_workspace": (_SZ, [_U32, _U32]),
     "zlz4_batch_compress_hc": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _I32, _VP, _SZ]),
     "zlz4_batch_compress_dest_size_workspace": (_SZ, [_U32, _U32]),
@@ -222,6 +224,16 @@ def decompressSafePartialUsingDict(src, dst_cap, target_output_size, dict):
     """lz4.decompressSafePartialUsingDict(src, dst, targetOutputSize, dict), src/lz4.zig:967-969."""
     dk, dn = _in(dict)
     return _run(lib().zlz4_decompress_safe_partial_using_dict, src, dst_cap, target_output_size, C.addressof(dk), dn)
+
+
+def compressFastUsingDict(src, dict, acceleration=1, dst_cap=None):
+    """zlz4_compress_fast_using_dict (no counterpart in the reference): compressFast's loop on dict-tail ++ src from the
+    table Stream.loadDict(dict) leaves, so matches may reach into the dictionary; decodes with
+    decompressSafeUsingDict(out, len(src), dict).  dst_cap defaults to compressBound(len(src))."""
+    cap = compressBound(len(src)) if dst_cap is None else dst_cap
+    dk, dn = _in(dict)
+    return _run(lambda sp, n, dp, c: lib().zlz4_compress_fast_using_dict(sp, n, dp, c, C.addressof(dk), dn, acceleration),
+                src, cap)
 
 
 def decompressedSize(src, dict_len=0):
@@ -713,6 +725,51 @@ def batch_compress_fast_continue(d_in, in_off, in_len, d_out, out_off, out_cap, 
                                                    _ptr(out_off), _ptr(out_cap), _ptr(table_in), _ptr(table_idx),
                                                    _ptr(table_out), _ptr(result), in_len.numel(), max_in_len,
                                                    acceleration))
+
+
+def batch_compress_fast_using_dict(d_in, in_off, in_len, d_out, out_off, out_cap, d_dict, dict_off, dict_len, table,
+                                   table_idx, result, max_in_len, max_dict_len, acceleration=1):
+    """zlz4_batch_compress_fast_using_dict: as batch_compress_fast, block i against the dictionary
+    d_dict[dict_off[i] .. + dict_len[i]) (int64 offsets / int32 lengths) from table table_idx[i] of `table` (int32;
+    table_idx None = table i), the tables being batch_load_dict's of the dictionaries."""
+    _check(lib().zlz4_batch_compress_fast_using_dict(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
+                                                     _ptr(out_off), _ptr(out_cap), _ptr(d_dict), _ptr(dict_off),
+                                                     _ptr(dict_len), _ptr(table), _ptr(table_idx), _ptr(result),
+                                                     in_len.numel(), max_in_len, max_dict_len, acceleration))
+
+
+def compressBlocksUsingDict(blocks, dicts, dict_index=None, acceleration=1, device="cuda"):
+    """Every byte string of `blocks` compressed against its dictionary in one batch: block i uses
+    dicts[dict_index[i]] (dict_index None: dicts[i]; a shared dictionary is dicts = [d], dict_index = [0] * n).  Packs
+    the data, loads one table per dictionary (batch_load_dict), compresses into compressBound slots and reads the
+    streams back once.  -> list of streams (bytes) or error codes; decompressBlocks(streams, per-block dicts) gives
+    the blocks back."""
+    import numpy as np
+    import torch
+    n = len(blocks)
+    if n == 0:
+        return []
+    idx = list(range(n)) if dict_index is None else [int(k) for k in dict_index]
+    dbytes = [bytes(d) if d is not None else b"" for d in dicts]
+    d_src, src_off, src_len = _stage(blocks, device)
+    d_dict, dict_off, dict_len = _stage(dbytes, device)
+    nd = len(dbytes)
+    tables = torch.empty(max(1, nd) * STREAM_TABLE_ENTRIES, dtype=torch.int32, device=device)
+    lres = torch.empty(max(1, nd), dtype=torch.int64, device=device)
+    batch_load_dict(d_dict, dict_off, dict_len.to(torch.int32), tables, lres[:nd])
+    t_idx = torch.tensor(idx, dtype=torch.int32, device=device)
+    sel = t_idx.to(torch.int64)
+    caps = [compressBound(len(b)) for b in blocks]
+    dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+    d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+    result = torch.empty(n, dtype=torch.int64, device=device)
+    out_cap = torch.from_numpy(np.asarray(caps, dtype=np.uint32).view(np.int32)).to(device)
+    max_in = max(len(b) for b in blocks)
+    max_dict = min(65536, max((len(dbytes[k]) for k in idx), default=0))
+    batch_compress_fast_using_dict(d_src, src_off, src_len.to(torch.int32), d_dst, dst_off, out_cap, d_dict,
+                                   dict_off[sel].contiguous(), dict_len[sel].to(torch.int32).contiguous(), tables, t_idx,
+                                   result, max_in, max_dict, acceleration)
+    return _unstage(d_dst, _offsets(caps), result)
 
 
 def batch_compress_hc_workspace(nblocks, max_in_len):

@@ -53,6 +53,12 @@ inline Result decompressSafePartialUsingDict(const std::uint8_t *src, std::size_
                                              std::size_t target, const std::uint8_t *dict, std::size_t dict_len) {
     return wrap(zlz4_decompress_safe_partial_using_dict(src, n, dst, cap, target, dict, dict_len));
 }
+// no counterpart in the reference (its Stream never refers to a loaded dictionary): compressFast's loop on the last 64 KiB
+// of `dict` followed by `src`, from the table Stream.loadDict(dict) leaves; decodes with decompressSafeUsingDict
+inline Result compressFastUsingDict(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                                    const std::uint8_t *dict, std::size_t dict_len, std::uint32_t accel = 1) {
+    return wrap(zlz4_compress_fast_using_dict(src, n, dst, cap, dict, dict_len, accel));
+}
 // lz4.Stream, src/lz4.zig:751-866: the table lives on the host and is computed on the device by loadDict /
 // compressFastContinue; the rest is bookkeeping.  A loaded dictionary only changes which in-block matches are found (the
 // reference reads table entries as positions in the current block): no block refers to it, and saveDict copies the
@@ -190,6 +196,15 @@ inline Result compressFastContinueBatch(void *stream, const Blocks &b, const Str
                                         std::uint32_t accel = 1) {
     return wrap(zlz4_batch_compress_fast_continue(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, t.table_in,
                                                   t.table_idx, t.table_out, b.result, b.nblocks, max_in_len, accel));
+}
+// compressFastUsingDict per block: block i against dictionary d from table table_idx[i] of d_table (nullptr = table i),
+// the tables being loadDictBatch's of the dictionaries
+inline Result compressFastUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d, const std::uint32_t *d_table,
+                                         const std::uint32_t *d_table_idx, std::uint32_t max_in_len,
+                                         std::uint32_t max_dict_len, std::uint32_t accel = 1) {
+    return wrap(zlz4_batch_compress_fast_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
+                                                    d.dict_off, d.dict_len, d_table, d_table_idx, b.result, b.nblocks,
+                                                    max_in_len, max_dict_len, accel));
 }
 inline std::size_t compressHCWorkspace(std::uint32_t nblocks, std::uint32_t max_in_len) {
     return zlz4_batch_compress_hc_workspace(nblocks, max_in_len);

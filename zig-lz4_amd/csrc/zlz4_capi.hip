@@ -27,6 +27,10 @@ extern "C" int zlz4_launch_compress_fast_continue(hipStream_t, const uint8_t *, 
                                                   const uint32_t *, uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
 extern "C" int zlz4_launch_load_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint32_t *,
                                      int64_t *, uint32_t);
+extern "C" int zlz4_launch_compress_fast_using_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
+                                                    uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *,
+                                                    const uint64_t *, const uint32_t *, const uint32_t *, const uint32_t *,
+                                                    int64_t *, uint32_t, uint32_t, uint32_t, uint32_t);
 extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
                                        const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, int32_t,
                                        void *, size_t);
@@ -221,6 +225,55 @@ int64_t run_stream_single(uint32_t *table, const uint8_t *dict, size_t dict_len,
     }
     // the table is the reference's after the call on every exit (unchanged ones included)
     if (hipMemcpy(table, d_tab.p, tbytes, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return result;
+}
+
+// zlz4_compress_fast_using_dict for 1 <= src_len <= ZLZ4_MAX_INPUT_SIZE: the record and the last min(dict_len, 65536)
+// bytes of the dictionary are staged, k_load_dict builds the dictionary's table on the device and the batch kernel
+// (zlz4_compress_dict.hip) runs on one block.
+int64_t run_dict_compress_single(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, const uint8_t *dict,
+                                 size_t dict_len, uint32_t accel) {
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const uint32_t cap32 = dst_cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dst_cap;
+    const uint32_t len32 = (uint32_t)src_len;
+    const size_t dtail = dict_len < 65536u ? dict_len : 65536u;
+    const size_t tbytes = ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t);
+    hipStream_t st = nullptr;
+    DeviceCall dc(st);
+    DevBuf d_in(src_len, &dc), d_out(cap32, &dc), d_meta(64, &dc), d_dict(dtail, &dc), d_tab(tbytes, &dc);
+    if (!d_in.p || !d_out.p || !d_meta.p || !d_dict.p || !d_tab.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    struct Meta {
+        uint64_t in_off; uint64_t out_off; uint64_t dict_off; int64_t result; int64_t dict_size; uint32_t in_len;
+        uint32_t out_cap; uint32_t dict_len;
+    } m;
+    m.in_off = 0; m.out_off = 0; m.dict_off = 0; m.result = 0; m.dict_size = 0; m.in_len = len32; m.out_cap = cap32;
+    m.dict_len = (uint32_t)dtail;
+    dc.launched();
+    if (hipMemcpyAsync(d_in.p, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (dtail && hipMemcpyAsync(d_dict.p, dict + (dict_len - dtail), dtail, hipMemcpyHostToDevice, st) != hipSuccess)
+        return ZLZ4_ERR_DEVICE;
+    if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    auto *dm = d_meta.as<uint8_t>();
+    const uint64_t *p_dict_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off));
+    const uint32_t *p_dict_len = reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len));
+    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
+    int rc = zlz4_launch_load_dict(st, d_dict.as<uint8_t>(), p_dict_off, p_dict_len, d_tab.as<uint32_t>(),
+                                   reinterpret_cast<int64_t *>(dm + offsetof(Meta, dict_size)), 1);
+    if (rc != 0) return rc;
+    rc = zlz4_launch_compress_fast_using_dict(st, d_in.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
+                                              reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)),
+                                              d_out.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
+                                              reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)),
+                                              d_dict.as<uint8_t>(), p_dict_off, p_dict_len, d_tab.as<uint32_t>(), nullptr,
+                                              p_res, 1, len32, (uint32_t)dtail, accel);
+    if (rc != 0) return rc;
+    int64_t result = 0;
+    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
+    if (result > 0) {
+        if ((uint64_t)result > dst_cap) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
+        if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    }
     return result;
 }
 
@@ -460,6 +513,15 @@ int64_t zlz4_stream_compress_fast_continue(uint32_t *table, const uint8_t *src, 
     return run_stream_single(table, nullptr, 0, src, n, dst, cap, accel);
 }
 
+// DESIGN.md section 4.1c; the entry checks are compressFastContinue's (src/lz4.zig:823-824)
+int64_t zlz4_compress_fast_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const uint8_t *dict,
+                                      size_t dict_len, uint32_t accel) {
+    if (!dict && dict_len) return ZLZ4_ERR_INVALID_STATE;
+    if (n > ZLZ4_MAX_INPUT_SIZE) return ZLZ4_ERR_INPUT_TOO_LARGE;   // :823
+    if (n == 0) return 0;                                           // :824
+    return run_dict_compress_single(src, n, dst, cap, dict, dict_len, accel);
+}
+
 size_t zlz4_sizeof_state(void) { return 4096 * sizeof(uint32_t); }  // src/lz4.zig:524-526, :263-265
 
 // src/lz4hc.zig:1492-1494: @sizeOf(Context) -- hashTable 32768 x u32 + chainTable 65536 x u16 (:391-393) + the scalars
@@ -612,6 +674,26 @@ int32_t zlz4_batch_compress_fast_continue(void *stream, const uint8_t *d_in, con
     return zlz4_launch_compress_fast_continue((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
                                               d_table_in, d_table_idx, d_table_out, d_result, nblocks, max_in_len,
                                               acceleration);
+}
+
+int32_t zlz4_batch_compress_fast_using_dict(void *stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                            const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                            const uint32_t *d_out_cap, const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                            const uint32_t *d_dict_len, const uint32_t *d_table,
+                                            const uint32_t *d_table_idx, int64_t *d_result, uint32_t nblocks,
+                                            uint32_t max_in_len, uint32_t max_dict_len, uint32_t acceleration) {
+    if (nblocks == 0) return 0;
+    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_dict_off || !d_dict_len || !d_table ||
+        !d_result || (!d_dict && max_dict_len))
+        return ZLZ4_ERR_INVALID_STATE;
+    if ((uintptr_t)d_table & 15u) return ZLZ4_ERR_INVALID_STATE;    // the kernel loads tables in 16-byte vectors
+    if (((uintptr_t)d_in_off | (uintptr_t)d_out_off | (uintptr_t)d_dict_off | (uintptr_t)d_result) & 7u ||
+        ((uintptr_t)d_in_len | (uintptr_t)d_out_cap | (uintptr_t)d_dict_len | (uintptr_t)d_table_idx) & 3u)
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_compress_fast_using_dict((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
+                                                d_dict, d_dict_off, d_dict_len, d_table, d_table_idx, d_result, nblocks,
+                                                max_in_len, max_dict_len, acceleration);
 }
 
 int32_t zlz4_batch_decompressed_size(void *stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,

@@ -19,6 +19,7 @@ extern "c" fn zlz4_decompress_safe_using_dict(src: [*]const u8, src_len: usize, 
 extern "c" fn zlz4_decompress_safe_partial_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, target: usize, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4_stream_load_dict(table: *[LZ4_HASH_SIZE_U32]u32, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4_stream_compress_fast_continue(table: *[LZ4_HASH_SIZE_U32]u32, src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, acceleration: u32) i64;
+extern "c" fn zlz4_compress_fast_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize, acceleration: u32) i64;
 extern "c" fn zlz4_sizeof_state() usize;
 extern "c" fn zlz4_compress_fast_ext_state(state: [*]u8, state_len: usize, src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, acceleration: u32) i64;
 extern "c" fn zlz4_compress_dest_size(src: [*]const u8, dst: [*]u8, dst_cap: usize, src_size: *usize) i64;
@@ -35,6 +36,7 @@ extern "c" fn zlz4_batch_decompress_safe_continue_workspace(nblocks: u32, nstrea
 extern "c" fn zlz4_batch_decompress_safe_continue(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_run_start: [*]const u32, d_state: [*]CStreamDecode, d_result: [*]i64, nblocks: u32, nstreams: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_load_dict(stream: ?*anyopaque, d_dict: [*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_tables: [*]u32, d_result: [*]i64, ndicts: u32) i32;
 extern "c" fn zlz4_batch_compress_fast_continue(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_table_in: [*]const u32, d_table_idx: ?[*]const u32, d_table_out: ?[*]u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
+extern "c" fn zlz4_batch_compress_fast_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_table: [*]const u32, d_table_idx: ?[*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, max_dict_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) usize;
 extern "c" fn zlz4_batch_compress_hc(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_compress_dest_size_workspace(nblocks: u32, max_in_len: u32) usize;
@@ -129,6 +131,12 @@ pub fn decompressSafeUsingDict(src: []const u8, dst: []u8, dict: []const u8) Err
 /// reference src/lz4.zig:967-969
 pub fn decompressSafePartialUsingDict(src: []const u8, dst: []u8, targetOutputSize: usize, dict: []const u8) Error!usize {
     return mapBlock(zlz4_decompress_safe_partial_using_dict(src.ptr, src.len, dst.ptr, dst.len, targetOutputSize, dict.ptr, dict.len));
+}
+/// No counterpart in the reference (its Stream never refers to a loaded dictionary): compressFastWithHashTable's loop
+/// (src/lz4.zig:624-740) on the last 64 KiB of `dict` followed by `src`, from the table Stream.loadDict(dict) leaves
+/// (:798-820), so that matches may reach into the dictionary.  decompressSafeUsingDict(dst[0..r], out, dict) gives src back.
+pub fn compressFastUsingDict(src: []const u8, dst: []u8, dict: []const u8, acceleration: u32) Error!usize {
+    return mapBlock(zlz4_compress_fast_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len, acceleration));
 }
 /// No counterpart in the reference: what decompressSafe (dict_len 0) or decompressSafeUsingDict with a dictionary of
 /// dict_len bytes returns for `src` into a destination of 0xFFFFFFFF bytes.  Nothing is decoded.
@@ -341,6 +349,7 @@ pub const lz4 = struct {
     pub const decompressSafePartial = root.decompressSafePartial;
     pub const decompressSafeUsingDict = root.decompressSafeUsingDict;
     pub const decompressSafePartialUsingDict = root.decompressSafePartialUsingDict;
+    pub const compressFastUsingDict = root.compressFastUsingDict;
     pub const decompressedSize = root.decompressedSize;
     pub const sizeofState = root.sizeofState;
     pub const compressFastExtState = root.compressFastExtState;
@@ -425,6 +434,12 @@ pub const device = struct {
     /// batch form of Stream.compressFastContinue (src/lz4.zig:822-836); every in_len[i] <= max_in_len
     pub fn compressFastContinueBatch(stream: ?*anyopaque, b: Blocks, t: StreamTables, max_in_len: u32, acceleration: u32) Error!void {
         return mapLaunch(zlz4_batch_compress_fast_continue(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, t.table_in, t.table_idx, t.table_out, b.result, b.nblocks, max_in_len, acceleration));
+    }
+    /// batch form of compressFastUsingDict (no counterpart in the reference): block i against dictionary d (DictBlocks) from
+    /// table table_idx[i] of `table` (null = table i), the tables being loadDictBatch's of the dictionaries; every
+    /// in_len[i] <= max_in_len and min(dict_len[i], 65536) <= max_dict_len
+    pub fn compressFastUsingDictBatch(stream: ?*anyopaque, b: Blocks, d: DictBlocks, table: [*]const u32, table_idx: ?[*]const u32, max_in_len: u32, max_dict_len: u32, acceleration: u32) Error!void {
+        return mapLaunch(zlz4_batch_compress_fast_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict, d.dict_off, d.dict_len, table, table_idx, b.result, b.nblocks, max_in_len, max_dict_len, acceleration));
     }
     pub fn compressHCWorkspace(nblocks: u32, max_in_len: u32) usize {
         return zlz4_batch_compress_hc_workspace(nblocks, max_in_len);
