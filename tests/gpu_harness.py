@@ -76,7 +76,7 @@ def _out_slots(caps, layout=None):
     return np.array(offs, dtype=np.int64), ends, max(pos, 16)
 
 
-def _run(zl, kind, items, caps, dev, layout=None, **kw):
+def _run(zl, kind, items, caps, dev, layout=None, max_in=None, **kw):
     buf, offs, lens = _pack(items, layout=layout)
     caps = np.asarray(caps, dtype=np.int64)
     out_offs, guard_ends, total = _out_slots(caps, layout)
@@ -87,7 +87,8 @@ def _run(zl, kind, items, caps, dev, layout=None, **kw):
     t_out_off = torch.from_numpy(out_offs).to(dev)
     t_out_cap = torch.from_numpy(caps.astype(np.uint32).view(np.int32)).to(dev)
     res = torch.full((len(items),), -999, dtype=torch.int64, device=dev)
-    max_in = int(lens.max()) if len(lens) else 0
+    if max_in is None:                                # the declared bound defaults to the exact maximum
+        max_in = int(lens.max()) if len(lens) else 0
     if kind == "fast":
         zl.batch_compress_fast(d_in, t_in_off, t_in_len, d_out, t_out_off, t_out_cap, res, max_in, kw.get("accel", 1))
     elif kind == "hc":
@@ -118,14 +119,14 @@ def _collect(res, d_out, out_offs, guard_ends, caps):
     return outs
 
 
-def compress_fast(zl, items, dev, caps=None, accel=1, layout=None):
+def compress_fast(zl, items, dev, caps=None, accel=1, layout=None, max_in=None):
     caps = [zl.compressBound(len(b)) for b in items] if caps is None else caps
-    return _run(zl, "fast", items, caps, dev, layout=layout, accel=accel)
+    return _run(zl, "fast", items, caps, dev, layout=layout, max_in=max_in, accel=accel)
 
 
-def compress_hc(zl, items, dev, level, caps=None, layout=None):
+def compress_hc(zl, items, dev, level, caps=None, layout=None, max_in=None):
     caps = [zl.compressBound(len(b)) for b in items] if caps is None else caps
-    return _run(zl, "hc", items, caps, dev, layout=layout, level=level)
+    return _run(zl, "hc", items, caps, dev, layout=layout, max_in=max_in, level=level)
 
 
 def decompress(zl, items, caps, dev, layout=None):

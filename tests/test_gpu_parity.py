@@ -5,6 +5,7 @@ import pytest
 import cases
 import datagen as dg
 import gpu_harness as gh
+import hcrounds
 
 pytestmark = pytest.mark.gpu
 
@@ -360,20 +361,7 @@ def test_compress_hc_periodic_inputs(zl, oracle, gpu, level):
     between its walks (counted runs, k_hc_seg_search in zlz4_compress_hc.hip; at level 12 k_hc_search, which searches
     every position, shares it between the lanes of a wavefront and skips candidates that cannot be longer).  Bytes vs the oracle
     (insertAndFindBestMatch / lz4Count, src/lz4hc.zig:540-640, :234-264)."""
-    rng = np.random.default_rng(4242 + level)
-    items = []
-    for period in (1, 2, 3, 5, 16, 40, 63, 64, 100, 255, 256, 257, 1000, 1024, 4096, 5000, 40000):
-        for total in (65536, 30011, period * 2 + 70):
-            pat = rng.integers(0, 256, period, dtype=np.uint8).tobytes()
-            b = bytearray((pat * (total // period + 2))[:max(total, 13)])
-            items.append(bytes(b))
-            if total > 20000:
-                for _ in range(3):                                # a few damaged bytes: runs that end early
-                    b[int(rng.integers(0, len(b)))] ^= 0x55
-                items.append(bytes(b))
-                pat2 = rng.integers(0, 256, max(1, period // 2 + 1), dtype=np.uint8).tobytes()
-                half = len(b) // 2
-                items.append(bytes(b[:half]) + (pat2 * (half // len(pat2) + 2))[:len(b) - half])   # two periods in a row
+    items = hcrounds.periodic_items(level)
     got = gh.compress_hc(zl, items, gpu, level)
     want = [oracle.compress_hc(b, level) for b in items]
     _cmp(["periodic%d" % i for i in range(len(items))], got, want)
