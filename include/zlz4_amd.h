@@ -178,6 +178,29 @@ int64_t zlz4_stream_compress_fast_continue(uint32_t *table, const uint8_t *src, 
 int64_t zlz4_compress_fast_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                       const uint8_t *dict, size_t dict_len, uint32_t acceleration);
 
+/* Levels 3..9 with a dictionary (no counterpart in the reference: its HC stream type is not ported).
+ * With tail = the last D = min(dict_len, 65536) bytes of `dict`, V = tail ++ src and N = D + src_len:
+ *   - entry checks: dict == NULL with dict_len > 0 -> InvalidState; the level is normalised as compressHC does (< 2 -> 9,
+ *     > 12 -> 12, src/lz4hc.zig:1446-1452) and a level of 2, 10, 11 or 12 -> ZLZ4_ERR_UNSUPPORTED, nothing touched (level 2's
+ *     tables depend on the parse, so its state is not a function of the bytes; levels 10..12 reproduce a defect of the
+ *     reference whose streams do not always decode, see the HAZARD note at zlz4_compress_hc); then compressHC's and
+ *     compressHCExtState's checks on the record (:1442-1445, :1461): InputTooLarge above ZLZ4_MAX_INPUT_SIZE, 0 for 0
+ *     bytes, OutputTooSmall for dst_cap == 0;
+ *   - src_len < 13: encodeLiterals(src) (:995-998, :1394-1425), the dictionary plays no part;
+ *   - otherwise compressHashChain (:976-1064) statement for statement on V with a fresh context, nextToUpdate = 0,
+ *     prefixStart = V, dictLimit = lowLimit = 0 (the index of a byte is its position in V), ip = anchor = D, iend = N,
+ *     mflimit = N - 12, matchlimit = N - 5.  So insertHC puts every position of V below ip into the chain (all of the
+ *     tail before the first search), insertAndGetWiderMatch runs with iLowLimit = ip (no backward extension; position 0
+ *     of V reads as empty; nbAttempts counts dictionary and record candidates alike), level 9 runs the pattern analysis
+ *     (its reverse count may run down into the tail), a match may start in the tail, run into the record and over itself,
+ *     and the last literals are refused where the reference would overrun, as in zlz4_compress_hc.
+ * The block decodes with zlz4_decompress_safe_using_dict(dst, .., dict, dict_len) (and with liblz4's decoder) to src;
+ * its size is at most zlz4_compress_bound(src_len).  With an empty dictionary the bytes and the status are
+ * zlz4_compress_hc's.  The record and the tail are staged and the batch pipeline runs on one block (correct, not fast:
+ * zlz4_batch_compress_hc_using_dict is the fast path). */
+int64_t zlz4_compress_hc_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                    const uint8_t *dict, size_t dict_len, int32_t compression_level);
+
 /* Streaming decompression, lz4.StreamDecode (src/lz4.zig:870-957).  The reference's fields as byte addresses (0 = null):
  * dict / dict_len = externalDict / extDictSize, prefix / prefix_len = prefixEnd.ptr / prefixSize.  The state holds no
  * data: a call never reads the previous output, only compares its address with the new dst (see the warning below).
@@ -372,6 +395,27 @@ int32_t zlz4_batch_compress_hc(void *stream,
                                uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                int64_t *d_result, uint32_t nblocks, uint32_t max_in_len,
                                int32_t compression_level, void *d_workspace, size_t workspace_bytes);
+
+/* zlz4_compress_hc_using_dict per block: block i against the dictionary d_dict + d_dict_off[i] (d_dict_len[i] bytes, any
+ * length; only the last 65536 take part).  No table argument: the HC state is derived from the bytes.  A shared
+ * dictionary = one copy, the same offset for every block; dictionaries may lie inside d_in (the previous record); they
+ * are read-only and must not overlap any output slot.  Every block is staged as tail ++ record in the workspace
+ * (zlz4_batch_compress_hc_using_dict_workspace bytes, 16-byte aligned; longer batches run in rounds).  max_in_len and
+ * max_dict_len are preconditions that size the workspace and select the link width: chain links in LDS while
+ * min(max_dict_len, 65536) + max_in_len <= 65536, in device memory otherwise -- both give the specified bytes.  A block
+ * with d_in_len[i] > max_in_len or min(d_dict_len[i], 65536) > max_dict_len gets InvalidState and writes nothing; other
+ * blocks are unaffected.  d_result[i] = what the single call returns; no byte outside the block's output slot is
+ * written.  Null arrays (d_dict may be NULL when max_dict_len == 0), a misaligned array (8 bytes for the 64-bit arrays, 4
+ * for the 32-bit ones), a workspace that is too small, null or misaligned return InvalidState, a level the single call
+ * does not serve returns ZLZ4_ERR_UNSUPPORTED; all of them launch nothing.  Asynchronous, no allocation, no read-back
+ * (graph-capturable like zlz4_batch_compress_hc). */
+size_t  zlz4_batch_compress_hc_using_dict_workspace(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len);
+int32_t zlz4_batch_compress_hc_using_dict(void *stream,
+                                          const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                          uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                          const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                          int64_t *d_result, uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len,
+                                          int32_t compression_level, void *d_workspace, size_t workspace_bytes);
 
 /* lz4.compressDestSize (src/lz4.zig:551-616) per block: d_in_len[i] is *srcSizePtr on entry and d_out_cap[i] is dst.len.
  * d_result[i] and d_consumed[i] receive what zlz4_compress_dest_size returns and leaves in *src_size; bytes [0, result)

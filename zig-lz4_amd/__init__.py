@@ -83,6 +83,9 @@ SYMBOLS = {
     "zlz4_batch_compress_fast_continue": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_compress_fast_using_dict": (_I32, [_VP] * 13 + [_U32, _U32, _U32, _U32]),
     "zlz4_batch_compress_hc_workspace": (_SZ, [_U32, _U32]),
+    "zlz4_compress_hc_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _I32]),
+    "zlz4_batch_compress_hc_using_dict_workspace": (_SZ, [_U32, _U32, _U32]),
+    "zlz4_batch_compress_hc_using_dict": (_I32, [_VP] * 11 + [_U32, _U32, _U32, _I32, _VP, _SZ]),
     "zlz4_batch_compress_hc": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _I32, _VP, _SZ]),
     "zlz4_batch_compress_dest_size_workspace": (_SZ, [_U32, _U32]),
     "zlz4_batch_compress_dest_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
@@ -233,6 +236,16 @@ def compressFastUsingDict(src, dict, acceleration=1, dst_cap=None):
     cap = compressBound(len(src)) if dst_cap is None else dst_cap
     dk, dn = _in(dict)
     return _run(lambda sp, n, dp, c: lib().zlz4_compress_fast_using_dict(sp, n, dp, c, C.addressof(dk), dn, acceleration),
+                src, cap)
+
+
+def compressHCUsingDict(src, dict, compression_level, dst_cap=None):
+    """zlz4_compress_hc_using_dict (no counterpart in the reference): compressHashChain on dict-tail ++ src with the parse
+    starting at the record, levels 3..9 (1 and below become 9; 2 and 10..12 raise Unsupported); decodes with
+    decompressSafeUsingDict(out, len(src), dict).  dst_cap defaults to compressBound(len(src))."""
+    cap = compressBound(len(src)) if dst_cap is None else dst_cap
+    dk, dn = _in(dict)
+    return _run(lambda sp, n, dp, c: lib().zlz4_compress_hc_using_dict(sp, n, dp, c, C.addressof(dk), dn, compression_level),
                 src, cap)
 
 
@@ -780,6 +793,48 @@ def batch_compress_hc(d_in, in_off, in_len, d_out, out_off, out_cap, result, max
     _check(lib().zlz4_batch_compress_hc(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
                                         _ptr(out_off), _ptr(out_cap), _ptr(result), in_len.numel(), max_in_len,
                                         level, _ptr(workspace), workspace.numel()))
+
+
+def batch_compress_hc_using_dict_workspace(nblocks, max_in_len, max_dict_len):
+    return lib().zlz4_batch_compress_hc_using_dict_workspace(nblocks, max_in_len, max_dict_len)
+
+
+def batch_compress_hc_using_dict(d_in, in_off, in_len, d_out, out_off, out_cap, d_dict, dict_off, dict_len, result,
+                                 max_in_len, max_dict_len, level, workspace):
+    """zlz4_batch_compress_hc_using_dict: as batch_compress_hc, block i against the dictionary
+    d_dict[dict_off[i] .. + dict_len[i]) (int64 offsets / int32 lengths).  `workspace` is a uint8 tensor of at least
+    batch_compress_hc_using_dict_workspace(nblocks, max_in_len, max_dict_len) bytes."""
+    _check(lib().zlz4_batch_compress_hc_using_dict(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
+                                                   _ptr(out_off), _ptr(out_cap), _ptr(d_dict), _ptr(dict_off),
+                                                   _ptr(dict_len), _ptr(result), in_len.numel(), max_in_len, max_dict_len,
+                                                   level, _ptr(workspace), workspace.numel()))
+
+
+def compressBlocksHCUsingDict(blocks, dicts, dict_index=None, level=9, device="cuda"):
+    """compressBlocksUsingDict at an HC level (3..9): block i against dicts[dict_index[i]] (dict_index None: dicts[i]).
+    -> list of streams (bytes) or error codes; decompressBlocks(streams, per-block dicts) gives the blocks back."""
+    import numpy as np
+    import torch
+    n = len(blocks)
+    if n == 0:
+        return []
+    idx = list(range(n)) if dict_index is None else [int(k) for k in dict_index]
+    dbytes = [bytes(d) if d is not None else b"" for d in dicts]
+    d_src, src_off, src_len = _stage(blocks, device)
+    d_dict, dict_off, dict_len = _stage(dbytes, device)
+    sel = torch.tensor(idx, dtype=torch.int64, device=device)
+    caps = [compressBound(len(b)) for b in blocks]
+    dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+    d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+    result = torch.empty(n, dtype=torch.int64, device=device)
+    out_cap = torch.from_numpy(np.asarray(caps, dtype=np.uint32).view(np.int32)).to(device)
+    max_in = max(len(b) for b in blocks)
+    max_dict = min(65536, max((len(dbytes[k]) for k in idx), default=0))
+    ws = torch.empty(max(16, batch_compress_hc_using_dict_workspace(n, max_in, max_dict)), dtype=torch.uint8, device=device)
+    batch_compress_hc_using_dict(d_src, src_off, src_len.to(torch.int32), d_dst, dst_off, out_cap, d_dict,
+                                 dict_off[sel].contiguous(), dict_len[sel].to(torch.int32).contiguous(), result, max_in,
+                                 max_dict, level, ws)
+    return _unstage(d_dst, _offsets(caps), result)
 
 
 def batch_compress_dest_size_workspace(nblocks, max_in_len):

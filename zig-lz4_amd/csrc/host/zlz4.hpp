@@ -130,6 +130,13 @@ inline Result compressHC(const std::uint8_t *src, std::size_t n, std::uint8_t *d
     return wrap(zlz4_compress_hc(src, n, dst, cap, level));
 }
 
+// levels 3..9 against a dictionary (no counterpart in the reference): compressHashChain on dict-tail ++ src, the parse
+// starting at the record; levels 2 and 10..12 are Unsupported
+inline Result compressHCUsingDict(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                                  const std::uint8_t *dict, std::size_t dict_len, std::int32_t level) {
+    return wrap(zlz4_compress_hc_using_dict(src, n, dst, cap, dict, dict_len, level));
+}
+
 // lz4hc.sizeofStateHC / compressHCExtState, src/lz4hc.zig:1457-1494 (fresh context, passed as the bytes it occupies)
 inline std::size_t sizeofStateHC() { return zlz4_sizeof_state_hc(); }
 inline Result compressHCExtState(void *ctx, std::size_t ctx_len, const std::uint8_t *src, std::size_t n, std::uint8_t *dst,
@@ -211,6 +218,16 @@ inline std::size_t compressHCWorkspace(std::uint32_t nblocks, std::uint32_t max_
 }
 inline Result compressHCBatch(void *stream, const Blocks &b, std::uint32_t max_in_len, std::int32_t level, void *ws, std::size_t ws_bytes) {
     return wrap(zlz4_batch_compress_hc(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks, max_in_len, level, ws, ws_bytes));
+}
+inline std::size_t compressHCUsingDictWorkspace(std::uint32_t nblocks, std::uint32_t max_in_len, std::uint32_t max_dict_len) {
+    return zlz4_batch_compress_hc_using_dict_workspace(nblocks, max_in_len, max_dict_len);
+}
+// compressHCUsingDict per block: block i against dictionary d; ws = device memory of compressHCUsingDictWorkspace() bytes
+inline Result compressHCUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d, std::uint32_t max_in_len,
+                                       std::uint32_t max_dict_len, std::int32_t level, void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4_batch_compress_hc_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
+                                                  d.dict_off, d.dict_len, b.result, b.nblocks, max_in_len, max_dict_len, level,
+                                                  ws, ws_bytes));
 }
 inline std::size_t compressDestSizeWorkspace(std::uint32_t nblocks, std::uint32_t max_in_len) {
     return zlz4_batch_compress_dest_size_workspace(nblocks, max_in_len);

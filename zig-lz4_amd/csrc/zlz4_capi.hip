@@ -35,6 +35,10 @@ extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint6
                                        const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, int32_t,
                                        void *, size_t);
 extern "C" size_t zlz4_hc_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
+extern "C" int zlz4_launch_compress_hc_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
+                                            const uint64_t *, const uint32_t *, const uint8_t *, const uint64_t *,
+                                            const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t, int32_t, void *, size_t);
+extern "C" size_t zlz4_hc_dict_workspace_bytes(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len);
 extern "C" int zlz4_launch_compress_dest_size(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
                                               const uint64_t *, const uint32_t *, int64_t *, uint32_t *, uint32_t, uint32_t,
                                               void *, const uint64_t *, const uint32_t *);
@@ -275,6 +279,55 @@ int64_t run_dict_compress_single(const uint8_t *src, size_t src_len, uint8_t *ds
         if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
     }
     return result;
+}
+
+// zlz4_compress_hc_using_dict for 1 <= src_len <= ZLZ4_MAX_INPUT_SIZE and a level of 3..9: the record and the last
+// min(dict_len, 65536) bytes of the dictionary are staged and the batch pipeline runs on one block.
+int64_t run_hc_dict_single(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, const uint8_t *dict,
+                           size_t dict_len, int32_t level) {
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const uint32_t cap32 = dst_cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dst_cap;
+    const uint32_t len32 = (uint32_t)src_len;
+    const size_t dtail = dict_len < 65536u ? dict_len : 65536u;
+    const size_t ws = zlz4_hc_dict_workspace_bytes(1, len32, (uint32_t)dtail);
+    hipStream_t st = nullptr;
+    DeviceCall dc(st);
+    DevBuf d_in(src_len, &dc), d_out(cap32, &dc), d_meta(64, &dc), d_dict(dtail, &dc), d_ws(ws, &dc);
+    if (!d_in.p || !d_out.p || !d_meta.p || !d_dict.p || !d_ws.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    struct Meta {
+        uint64_t in_off; uint64_t out_off; uint64_t dict_off; int64_t result; uint32_t in_len; uint32_t out_cap; uint32_t dict_len;
+    } m;
+    m.in_off = 0; m.out_off = 0; m.dict_off = 0; m.result = 0; m.in_len = len32; m.out_cap = cap32; m.dict_len = (uint32_t)dtail;
+    dc.launched();
+    if (hipMemcpyAsync(d_in.p, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (dtail && hipMemcpyAsync(d_dict.p, dict + (dict_len - dtail), dtail, hipMemcpyHostToDevice, st) != hipSuccess)
+        return ZLZ4_ERR_DEVICE;
+    if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    auto *dm = d_meta.as<uint8_t>();
+    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
+    const int rc = zlz4_launch_compress_hc_dict(st, d_in.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
+                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)), d_out.as<uint8_t>(),
+                                                reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
+                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)), d_dict.as<uint8_t>(),
+                                                reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off)),
+                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)), p_res, 1, len32,
+                                                (uint32_t)dtail, level, d_ws.p, ws);
+    if (rc != 0) return rc;
+    int64_t result = 0;
+    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
+    if (result > 0) {
+        if ((uint64_t)result > dst_cap) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
+        if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    }
+    return result;
+}
+
+// the level compressHC runs (src/lz4hc.zig:1446-1452), or 0 where the dictionary call has none: 2 (lz4mid) and 10..12
+int32_t hc_dict_level(int32_t level) {
+    if (level < 2) level = ZLZ4HC_CLEVEL_DEFAULT;
+    if (level > ZLZ4HC_CLEVEL_MAX) level = ZLZ4HC_CLEVEL_MAX;
+    return level >= 3 && level <= 9 ? level : 0;
 }
 
 // compressDestSize's search branch (src/lz4.zig:567-615) for 1 <= *src_size <= ZLZ4_MAX_INPUT_SIZE and dst_cap below
@@ -522,6 +575,18 @@ int64_t zlz4_compress_fast_using_dict(const uint8_t *src, size_t n, uint8_t *dst
     return run_dict_compress_single(src, n, dst, cap, dict, dict_len, accel);
 }
 
+// DESIGN.md section 4.3c; the entry checks are compressHC's and compressHCExtState's (src/lz4hc.zig:1442-1445, :1461)
+int64_t zlz4_compress_hc_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const uint8_t *dict,
+                                    size_t dict_len, int32_t level) {
+    if (!dict && dict_len) return ZLZ4_ERR_INVALID_STATE;
+    level = hc_dict_level(level);
+    if (level == 0) return ZLZ4_ERR_UNSUPPORTED;                    // as the batch call: before any record is looked at
+    if (n > ZLZ4_MAX_INPUT_SIZE) return ZLZ4_ERR_INPUT_TOO_LARGE;   // :1442
+    if (n == 0) return 0;                                           // :1443
+    if (cap == 0) return ZLZ4_ERR_OUTPUT_TOO_SMALL;                 // :1461
+    return run_hc_dict_single(src, n, dst, cap, dict, dict_len, level);
+}
+
 size_t zlz4_sizeof_state(void) { return 4096 * sizeof(uint32_t); }  // src/lz4.zig:524-526, :263-265
 
 // src/lz4hc.zig:1492-1494: @sizeOf(Context) -- hashTable 32768 x u32 + chainTable 65536 x u16 (:391-393) + the scalars
@@ -694,6 +759,35 @@ int32_t zlz4_batch_compress_fast_using_dict(void *stream, const uint8_t *d_in, c
     return zlz4_launch_compress_fast_using_dict((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
                                                 d_dict, d_dict_off, d_dict_len, d_table, d_table_idx, d_result, nblocks,
                                                 max_in_len, max_dict_len, acceleration);
+}
+
+size_t zlz4_batch_compress_hc_using_dict_workspace(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len) {
+    return zlz4_hc_dict_workspace_bytes(nblocks, max_in_len, max_dict_len);
+}
+
+int32_t zlz4_batch_compress_hc_using_dict(void *stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                          const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                          const uint32_t *d_out_cap, const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                          const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks,
+                                          uint32_t max_in_len, uint32_t max_dict_len, int32_t compression_level,
+                                          void *d_workspace, size_t workspace_bytes) {
+    if (nblocks == 0) return 0;
+    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_dict_off || !d_dict_len || !d_result ||
+        (!d_dict && max_dict_len))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (((uintptr_t)d_in_off | (uintptr_t)d_out_off | (uintptr_t)d_dict_off | (uintptr_t)d_result) & 7u ||
+        ((uintptr_t)d_in_len | (uintptr_t)d_out_cap | (uintptr_t)d_dict_len) & 3u)
+        return ZLZ4_ERR_INVALID_STATE;
+    const int32_t level = hc_dict_level(compression_level);
+    if (level == 0) return ZLZ4_ERR_UNSUPPORTED;
+    // the staged blocks, the links and the results are moved in 16-byte vectors
+    if (!d_workspace || ((uintptr_t)d_workspace & 15u) ||
+        workspace_bytes < zlz4_hc_dict_workspace_bytes(nblocks, max_in_len, max_dict_len))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_compress_hc_dict((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_dict,
+                                        d_dict_off, d_dict_len, d_result, nblocks, max_in_len, max_dict_len, level,
+                                        d_workspace, workspace_bytes);
 }
 
 int32_t zlz4_batch_decompressed_size(void *stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,

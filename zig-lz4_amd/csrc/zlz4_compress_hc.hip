@@ -617,7 +617,14 @@ __device__ __forceinline__ uint32_t hc_coop_reverse_count_pattern(const uint8_t 
 //               in the workspace (zeroed by the launcher).  Here the walk also meets the two tests that cannot fire in
 //               a 64 KiB block: candidates further than 65535 bytes end the walk (:573), candidates below
 //               lowestMatchIndex are counted but not compared (:579).
-template <int kCands, bool kLds>   // kCands = candidates of a chain examined per loop trip (1, 2, 4 or 8; 4 ships)
+//
+// kDict = true (zlz4_batch_compress_hc_using_dict): the block is V = dictionary tail ++ record,
+//               staged by k_hc_dict_stage, and d_in_len holds PAIRS per block: { length of V, start = length of the tail }.
+//               The parse starts at `start` (compressHashChain with ip = anchor = start): start points are
+//               start + seg * seg_len, "the walk from 0" is the walk from `start`, nothing below `start` is searched or
+//               marked; candidates, counts and the pattern step reach below it as they reach below any other position.
+//               `start` waits in LDS (next_seg[3]) for the lanes that take a start point: it is no scalar state of the loop.
+template <int kCands, bool kLds, bool kDict = false>   // kCands = candidates of a chain examined per loop trip (1, 2, 4 or 8; 4 ships)
 __global__ __launch_bounds__(1024) void k_hc_seg_search(const uint8_t *__restrict__ d_in,
                                                          const uint64_t *__restrict__ d_in_off,
                                                          const uint32_t *__restrict__ d_in_len,
@@ -632,10 +639,15 @@ __global__ __launch_bounds__(1024) void k_hc_seg_search(const uint8_t *__restric
     typedef typename std::conditional<kLds, const lds_u16 *, const uint32_t *>::type LinkPtr;
     const uint32_t b = blockIdx.x;
     if (b >= nblocks) return;
-    const uint32_t n = d_in_len[blk0 + b];
+    const uint32_t n = kDict ? d_in_len[2u * (blk0 + b)] : d_in_len[blk0 + b];
     if (n > max_in_len) return;                                  // K3 reports it; the workspace is sized by max_in_len
     const uint32_t np = n_positions(n);
     if (np == 0) return;
+    [[maybe_unused]] uint32_t start = 0;
+    if constexpr (kDict) {
+        start = d_in_len[2u * (blk0 + b) + 1u];
+        if (n - start < kMfLimit + 1u) return;                   // a record below 13 bytes is all literals (:995-998)
+    }
     const uint8_t *src = d_in + d_in_off[blk0 + b];
     R *res = static_cast<R *>(d_res_v) + (uint64_t)b * link_stride;
     LinkPtr lk;
@@ -661,11 +673,13 @@ __global__ __launch_bounds__(1024) void k_hc_seg_search(const uint8_t *__restric
         for (uint32_t k = threadIdx.x; k < n16; k += blockDim.x) l4[k] = g4[k];
         for (uint32_t k = threadIdx.x; k <= bm_words + 2u; k += blockDim.x) bm_l[k] = 0;
         if (threadIdx.x < kRunSlots) runs[threadIdx.x] = 0;
+        if constexpr (kDict) { if (threadIdx.x == 0) next_seg[3] = start; }
     } else {
         lk = static_cast<const uint32_t *>(d_link_v) + (uint64_t)b * link_stride;
         bm_g = d_bitmap + (uint64_t)b * bitmap_stride;
         next_seg = (lds_u32 *)lds_raw;
         if (threadIdx.x < 3u) next_seg[threadIdx.x] = 0;
+        if constexpr (kDict) { if (threadIdx.x == 3u) next_seg[3] = start; }
         runs = (lds_u64 *)(lds_raw + 16u);
         if (threadIdx.x < kRunSlots) runs[threadIdx.x] = 0;
     }
@@ -689,7 +703,7 @@ __global__ __launch_bounds__(1024) void k_hc_seg_search(const uint8_t *__restric
     };
     const bool pattern_analysis = max_attempts > 128;            // :983
     const uint32_t limit = n - kLastLiterals;                    // iHighLimit = matchlimit :989, :1011
-    const uint32_t nseg = (np + seg_len - 1u) / seg_len;
+    const uint32_t nseg = ((kDict ? np - start : np) + seg_len - 1u) / seg_len;
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t lanes_below = (1ull << lane) - 1ull;
 
@@ -740,7 +754,7 @@ __global__ __launch_bounds__(1024) void k_hc_seg_search(const uint8_t *__restric
             base = rdlane(base, first_lane(want));
             if (!have && !exhausted) {
                 const uint32_t seg = base + (uint32_t)__popcll(want & lanes_below);
-                if (seg < nseg) { pos = seg * seg_len; have = true; in_chain = false; is_true = seg == 0u; mark0 = mark1 = mark2 = ~0u; }
+                if (seg < nseg) { pos = kDict ? next_seg[3] + seg * seg_len : seg * seg_len; have = true; in_chain = false; is_true = seg == 0u; mark0 = mark1 = mark2 = ~0u; }
                 else exhausted = true;
             }
         }
@@ -1115,7 +1129,11 @@ __global__ __launch_bounds__(1024) void k_hc_seg_search(const uint8_t *__restric
 }
 
 // ------------------------------------------------------------------ K3: greedy parse + emit
-template <typename R>
+// kDict = true: the block is V = dictionary tail ++ record and d_in_len holds the pairs { length of V, start } of
+// k_hc_seg_search; the entry checks run on the record (V's length - start), the parse and its literals on V from `start`.
+// k_hc_dict_stage has refused a block whose start is kHcDictTooLarge / kHcDictRefused (its V is empty).
+constexpr uint32_t kHcDictRefused = 0xFFFFFFFFu, kHcDictTooLarge = 0xFFFFFFFEu;
+template <typename R, bool kDict = false>
 __global__ __launch_bounds__(256) void k_hc_parse_emit(const uint8_t *__restrict__ d_in,
                                                         const uint64_t *__restrict__ d_in_off,
                                                         const uint32_t *__restrict__ d_in_len,
@@ -1131,37 +1149,41 @@ __global__ __launch_bounds__(256) void k_hc_parse_emit(const uint8_t *__restrict
     const uint32_t blk = blk0 + b;
     const uint8_t *src = d_in + d_in_off[blk];
     uint8_t *dst = d_out + d_out_off[blk];
-    const uint32_t n = rfl(d_in_len[blk]);
+    const uint32_t n = rfl(kDict ? d_in_len[2u * blk] : d_in_len[blk]);
+    const uint32_t start = kDict ? rfl(d_in_len[2u * blk + 1u]) : 0u;
     const uint32_t oend = rfl(d_out_cap[blk]);
     const R *res = d_res + (uint64_t)b * link_stride;
+    const uint32_t nr = kDict ? n - start : n;                   // the record: what the entry checks are about
 
     int64_t out;
-    if (n > kMaxInput) {                                         // :1442
+    if (kDict && (start == kHcDictTooLarge || start == kHcDictRefused)) {                     // :1442 / over max_in_len or max_dict_len: nothing was staged
+        out = start == kHcDictTooLarge ? kErrInputTooLarge : kErrInvalidState;
+    } else if (!kDict && n > kMaxInput) {                        // :1442
         out = kErrInputTooLarge;
     } else if (n > max_in_len) {                                 // K1/K2 skipped it: nothing of it is in the workspace
         out = kErrInvalidState;
-    } else if (n == 0) {                                         // :1443
+    } else if (nr == 0) {                                        // :1443
         out = 0;
     } else if (oend == 0) {                                      // :1461
         out = kErrOutputTooSmall;
-    } else if (n < kMfLimit + 1u) {                              // :995-998 encodeLiterals (:1394-1425)
-        if (oend < n + 1u + n / 255u) out = kErrOutputTooSmall;  // :1395
+    } else if (nr < kMfLimit + 1u) {                             // :995-998 encodeLiterals (:1394-1425)
+        if (oend < nr + 1u + nr / 255u) out = kErrOutputTooSmall;   // :1395
         else {
-            if (lane == 0) dst[0] = (uint8_t)(n << 4);           // n < 13 < 15
-            if (lane < n) dst[1u + lane] = src[lane];
-            out = (int64_t)n + 1;
+            if (lane == 0) dst[0] = (uint8_t)(nr << 4);          // n < 13 < 15
+            if (lane < nr) dst[1u + lane] = src[start + lane];
+            out = (int64_t)nr + 1;
         }
     } else {
         const uint32_t mflimit = n - kMfLimit;                   // :988
-        uint32_t ip = 0, anchor = 0, op = 0;
+        uint32_t ip = start, anchor = start, op = 0;
         bool failed = false;
         // 64-position window of search results held in registers -- and the window's input bytes with it: a sequence's
         // literals are stored straight from them (a byte per lane), so the loop has no load that a store waits for (round 3;
         // copy_bytes' load -> store per sequence made this kernel a chain of ~1 900-cycle steps).  The window starts at the
         // anchor whenever the pending literal run is shorter than 64 bytes, so its literals are inside.
-        uint32_t wbase = 0;
-        R w = (lane <= mflimit) ? res[lane] : (R)0;
-        uint32_t sb = lane < n ? src[lane] : 0u;
+        uint32_t wbase = start;
+        R w = (start + lane <= mflimit) ? res[start + lane] : (R)0;
+        uint32_t sb = start + lane < n ? src[start + lane] : 0u;
         // lanes of the window whose position holds a match; the loop steps over the others one by one (:1013-1016), i.e.
         // it goes to the first such lane at or after ip
         auto is_match = [](R r) {
@@ -1466,4 +1488,137 @@ extern "C" int zlz4_launch_compress_hc(hipStream_t stream, const uint8_t *d_in, 
     return zlz4::launch_hc_chunked<uint32_t, uint64_t>(stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
                                                        d_result, nblocks, max_in_len, max_attempts, ws, chunk, optimal,
                                                        sufficient);
+}
+
+// ------------------------------------------------------------------ levels 3..9 with a dictionary
+// zlz4_batch_compress_hc_using_dict: compressHashChain on V = dictionary tail ++ record with ip = anchor = D.  A staging
+// kernel (zlz4_compress_hc_dict.hip) writes V per block into the workspace; K1 runs on V as it is, K2s and K3 in their
+// kDict instantiations.  Rounds, side stream and result halves as in launch_hc_chunked; V alternates between two halves
+// with the results, because K3 of round r takes its literals from V while round r + 1 is staged.
+//
+// workspace: v_off u64[nblocks] | { v_len, start } u32[2 nblocks] | v_len u32[nblocks] | (16-byte boundary)
+//            links T[chunk * stride] | results R[chunk * stride] | visited bits (HBM links) | V [chunk * stride]
+extern "C" int zlz4_launch_hc_dict_stage(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *,
+                                         const uint64_t *, const uint32_t *, uint8_t *, uint64_t, uint64_t *, uint32_t *,
+                                         uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
+
+namespace {
+struct HcDictPlan {
+    uint32_t dmax, max_n;            // longest tail, longest V
+    bool lds;                        // LDS links (u16 / u32 results) or HBM links (u32 / u64)
+    uint64_t stride;                 // entries per block in links and results = bytes per block of V
+    uint64_t bm_stride;              // visited-bitmap words per block (HBM links)
+    uint64_t head, per_block;
+    uint32_t chunk;
+};
+HcDictPlan hc_dict_plan(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len) {
+    HcDictPlan p;
+    p.dmax = max_dict_len < 65536u ? max_dict_len : 65536u;
+    // (a record over ZLZ4_MAX_INPUT_SIZE is refused by the staging kernel: it never needs room)
+    p.max_n = p.dmax + (max_in_len < zlz4::kMaxInput ? max_in_len : zlz4::kMaxInput);
+    p.lds = p.max_n <= 65536u;
+    p.stride = ((uint64_t)p.max_n + 15u) & ~15ull;
+    if (p.stride == 0) p.stride = 16;                            // (a batch of empty records)
+    p.bm_stride = p.lds ? 0 : ((p.stride + 31u) / 32u + 1u + 3u) & ~3ull;   // (whole 16 bytes: V, which follows, stays aligned)
+    p.head = ((uint64_t)nblocks * 20u + 15u) & ~15ull;
+    p.per_block = p.stride * (p.lds ? 6u : 12u) + p.bm_stride * 4u + p.stride;
+    uint64_t c = (6ull << 30) / p.per_block;                     // as hc_chunk: around 6 GiB at most
+    if (c < 1) c = 1;
+    if (c > kHcChunkBlocks) c = kHcChunkBlocks;
+    if (c > nblocks) c = nblocks ? nblocks : 1;
+    p.chunk = (uint32_t)c;
+    return p;
+}
+}  // namespace
+
+namespace zlz4 {
+template <typename T, typename R>
+int launch_hc_dict_chunked(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                           uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_dict,
+                           const uint64_t *d_dict_off, const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks,
+                           uint32_t max_in_len, int32_t max_attempts, void *ws, const HcDictPlan &pl) {
+    constexpr bool kLds = sizeof(T) == 2;
+    const uint64_t stride = pl.stride;
+    const uint32_t chunk = pl.chunk;
+    uint64_t *v_off = static_cast<uint64_t *>(ws);
+    uint32_t *v_pair = reinterpret_cast<uint32_t *>(v_off + nblocks);
+    uint32_t *v_len = v_pair + 2u * (uint64_t)nblocks;
+    uint8_t *body = static_cast<uint8_t *>(ws) + pl.head;
+    T *d_link = reinterpret_cast<T *>(body);
+    R *d_res = reinterpret_cast<R *>(body + (uint64_t)chunk * stride * sizeof(T));
+    uint32_t *d_bitmap = reinterpret_cast<uint32_t *>(body + (uint64_t)chunk * stride * (sizeof(T) + sizeof(R)));
+    uint8_t *d_v = reinterpret_cast<uint8_t *>(d_bitmap) + (uint64_t)chunk * pl.bm_stride * 4u;
+    const uint32_t np_max = pl.max_n < 13u ? 1u : pl.max_n - 11u;
+    const uint32_t k1_lds = kHcTableSize * 4u + 4096u * sizeof(T) + 16u;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hc_build_links<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1_lds);
+    constexpr uint32_t seg_len = 32u;
+    // ~2 start points per lane, counted over the record (nothing below `start` is a start point); at least four
+    // wavefronts, which also copy the links of the whole of V into LDS
+    const uint32_t nseg_max = (max_in_len < zlz4::kMaxInput ? max_in_len : zlz4::kMaxInput) / seg_len + 1u;
+    uint32_t threads = (nseg_max / 2u + 63u) & ~63u;
+    if (threads > 1024u) threads = 1024u;
+    if (threads < 256u) threads = 256u;
+    const uint32_t lk_bytes = ((np_max * 2u + 15u) & ~15u) + 16u;            // + padding: the walk reads 3 links ahead
+    const uint32_t lds = kLds ? lk_bytes + 64u + ((np_max + 31u) / 32u + 4u) * 4u : 16u + 64u;   // as launch_hc_chunked, + the word for `start`
+    auto kern = &k_hc_seg_search<4, kLds, true>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    HcSideStream *side = (chunk >= 2u && nblocks > chunk / 2u) ? hc_side_stream() : nullptr;
+    const uint32_t sub = side ? chunk / 2u : chunk;
+    uint32_t round = 0;
+    auto fail = [&]() -> int { if (side) (void)hipStreamSynchronize(side->st); return -7; };
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += sub, round++) {
+        const uint32_t nb = nblocks - b0 < sub ? nblocks - b0 : sub;
+        const uint32_t half = side ? (round & 1u) : 0u;
+        R *res = d_res + (uint64_t)half * sub * stride;
+        if (side && round >= 2u && hipStreamWaitEvent(stream, side->emitted[half], 0) != hipSuccess) return fail();   // K3 of round - 2 read this half of V and of the results
+        if (zlz4_launch_hc_dict_stage(stream, d_in, d_in_off, d_in_len, d_dict, d_dict_off, d_dict_len, d_v, stride, v_off,
+                                      v_len, v_pair, b0, nb, half * sub, max_in_len, pl.dmax) != 0) return fail();
+        if (hipMemsetAsync(res, 0, (size_t)nb * stride * sizeof(R), stream) != hipSuccess) return fail();
+        if (!kLds && hipMemsetAsync(d_bitmap, 0, (size_t)nb * pl.bm_stride * 4u, stream) != hipSuccess) return fail();
+        hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), k1_lds, stream, d_v, v_off, v_len, d_link,
+                           stride, b0, nb, pl.max_n);
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(threads), lds, stream, d_v, v_off, v_pair, static_cast<const void *>(d_link),
+                           stride, static_cast<void *>(res), d_bitmap, pl.bm_stride, b0, nb, max_attempts, pl.max_n, lk_bytes,
+                           seg_len, 1);
+        hipStream_t emit_on = stream;
+        if (side) {
+            if (hipEventRecord(side->searched[half], stream) != hipSuccess ||
+                hipStreamWaitEvent(side->st, side->searched[half], 0) != hipSuccess) return fail();
+            emit_on = side->st;
+        }
+        hipLaunchKernelGGL((k_hc_parse_emit<R, true>), dim3((nb + 3u) / 4u), dim3(256), 0, emit_on, d_v, v_off, v_pair, d_out,
+                           d_out_off, d_out_cap, d_result, static_cast<const R *>(res), stride, b0, nb, pl.max_n);
+        if (side && hipEventRecord(side->emitted[half], side->st) != hipSuccess) return fail();
+    }
+    if (side)     // join
+        for (uint32_t k = 0; k < 2u && k < round; k++)
+            if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail();
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+}  // namespace zlz4
+
+extern "C" size_t zlz4_hc_dict_workspace_bytes(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len) {
+    const HcDictPlan p = hc_dict_plan(nblocks, max_in_len, max_dict_len);
+    return (size_t)(p.head + (uint64_t)p.chunk * p.per_block);
+}
+
+// `level` is normalised (3..9) by the caller
+extern "C" int zlz4_launch_compress_hc_dict(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                            const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                            const uint32_t *d_out_cap, const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                            const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks,
+                                            uint32_t max_in_len, uint32_t max_dict_len, int32_t level, void *ws,
+                                            size_t ws_bytes) {
+    if (nblocks == 0) return 0;
+    if (level < 3 || level > 9) return -8;
+    const HcDictPlan p = hc_dict_plan(nblocks, max_in_len, max_dict_len);
+    if (ws_bytes < p.head + (uint64_t)p.chunk * p.per_block) return -5;
+    const int32_t max_attempts = 1 << (level - 1);                              // 3 -> 4 ... 9 -> 256
+    if (p.lds)
+        return zlz4::launch_hc_dict_chunked<uint16_t, uint32_t>(stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_dict,
+                                                                d_dict_off, d_dict_len, d_result, nblocks, max_in_len,
+                                                                max_attempts, ws, p);
+    return zlz4::launch_hc_dict_chunked<uint32_t, uint64_t>(stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_dict,
+                                                            d_dict_off, d_dict_len, d_result, nblocks, max_in_len, max_attempts,
+                                                            ws, p);
 }

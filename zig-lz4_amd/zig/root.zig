@@ -38,6 +38,9 @@ extern "c" fn zlz4_batch_load_dict(stream: ?*anyopaque, d_dict: [*]const u8, d_d
 extern "c" fn zlz4_batch_compress_fast_continue(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_table_in: [*]const u32, d_table_idx: ?[*]const u32, d_table_out: ?[*]u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_compress_fast_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_table: [*]const u32, d_table_idx: ?[*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, max_dict_len: u32, acceleration: u32) i32;
 extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) usize;
+extern "c" fn zlz4_compress_hc_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize, level: i32) i64;
+extern "c" fn zlz4_batch_compress_hc_using_dict_workspace(nblocks: u32, max_in_len: u32, max_dict_len: u32) usize;
+extern "c" fn zlz4_batch_compress_hc_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, max_dict_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_compress_hc(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_compress_dest_size_workspace(nblocks: u32, max_in_len: u32) usize;
 extern "c" fn zlz4_batch_compress_dest_size(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, d_consumed: [*]u32, nblocks: u32, max_in_len: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
@@ -154,6 +157,12 @@ pub fn compressFastExtState(state: []u8, src: []const u8, dst: []u8, acceleratio
 /// reference src/lz4.zig:551-616 (srcSizePtr: in = available, out = consumed)
 pub fn compressDestSize(src: []const u8, dst: []u8, srcSizePtr: *usize) Error!usize {
     return mapBlock(zlz4_compress_dest_size(src.ptr, dst.ptr, dst.len, srcSizePtr));
+}
+/// No counterpart in the reference: compressHashChain (src/lz4hc.zig:976-1064) on dict-tail ++ src with the parse starting
+/// at the record, levels 3..9 (below 2 becomes 9 as in compressHC; 2 and 10..12 are error.Unsupported).  Decodes with
+/// decompressSafeUsingDict(dst[0..n], out, dict).
+pub fn compressHCUsingDict(src: []const u8, dst: []u8, dict: []const u8, compressionLevel: i32) Error!usize {
+    return mapBlock(zlz4_compress_hc_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len, compressionLevel));
 }
 pub fn compressHC(src: []const u8, dst: []u8, compressionLevel: i32) Error!usize {
     return mapBlock(zlz4_compress_hc(src.ptr, src.len, dst.ptr, dst.len, compressionLevel));
@@ -368,6 +377,7 @@ pub const lz4hc = struct {
     pub const LZ4HC_CLEVEL_MAX = 12;
     pub const compressHC = root.compressHC;
     pub const compressHCExtState = root.compressHCExtState;
+    pub const compressHCUsingDict = root.compressHCUsingDict;
     pub const sizeofStateHC = root.sizeofStateHC;
 };
 
@@ -447,6 +457,14 @@ pub const device = struct {
     /// batch form of compressHC (src/lz4hc.zig:1440-1453); `workspace` = device memory of compressHCWorkspace() bytes
     pub fn compressHCBatch(stream: ?*anyopaque, b: Blocks, max_in_len: u32, level: i32, workspace: ?*anyopaque, workspace_bytes: usize) Error!void {
         return mapLaunch(zlz4_batch_compress_hc(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks, max_in_len, level, workspace, workspace_bytes));
+    }
+    pub fn compressHCUsingDictWorkspace(nblocks: u32, max_in_len: u32, max_dict_len: u32) usize {
+        return zlz4_batch_compress_hc_using_dict_workspace(nblocks, max_in_len, max_dict_len);
+    }
+    /// batch form of compressHCUsingDict: block i against dictionary d (DictBlocks); `workspace` = device memory of
+    /// compressHCUsingDictWorkspace() bytes, 16-byte aligned
+    pub fn compressHCUsingDictBatch(stream: ?*anyopaque, b: Blocks, d: DictBlocks, max_in_len: u32, max_dict_len: u32, level: i32, workspace: ?*anyopaque, workspace_bytes: usize) Error!void {
+        return mapLaunch(zlz4_batch_compress_hc_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict, d.dict_off, d.dict_len, b.result, b.nblocks, max_in_len, max_dict_len, level, workspace, workspace_bytes));
     }
     pub fn compressDestSizeWorkspace(nblocks: u32, max_in_len: u32) usize {
         return zlz4_batch_compress_dest_size_workspace(nblocks, max_in_len);
