@@ -523,6 +523,20 @@ int64_t zlz4f_decompress_frame_segment_device(void *stream, const uint8_t *d_src
  * Decompress: every parameter comes from the frame's own header, so one batch may mix frames of any block size and
  * checksum flags (compressFrame, the lz4 CLI); error order of src/lz4f.zig:541-638 per frame. */
 #define ZLZ4F_BATCH_CONTENT_SIZE 1u   /* batch_flags: frame f's header carries src_len[f] as its content size */
+/* batch_flags: write LINKED frames (no counterpart in the reference, whose block_mode is a header bit only).  Block k of
+ * frame f is zlz4_compress_fast_using_dict(block, dict = frame input[max(0, k * bs - 65536) .. k * bs]) with that
+ * dictionary's own zlz4_batch_load_dict table and acceleration 1 -- the dictionary is the INPUT in front of the block,
+ * also when the previous block ends up stored.  Block 0, and so every one-block frame, is compressFast's bytes.
+ * Everything else is as without the flag: stored-block rule, checksums, content size, compressFrameBound check, header,
+ * end mark.  Every block of every frame is still independent work.  liblz4's LZ4F_decompress and
+ * zlz4f_batch_decompress_frame_ex(ZLZ4F_DECODE_LINKED) decode such a frame; the calls without that flag do not.
+ * The flag needs prefs->block_mode == 0, so that FLG declares what the blocks are (else ZLZ4F_ERR_PARAMETER_INVALID),
+ * compression_level <= 0 (else ZLZ4_ERR_UNSUPPORTED: HC linking is not built) and a workspace of
+ * zlz4f_batch_compress_frame_workspace_ex(.., batch_flags) bytes, which adds one loadDict table (16 KiB) and a dictionary
+ * descriptor per table entry (smaller: ZLZ4_ERR_INVALID_STATE); in each case nothing is launched. */
+#define ZLZ4F_BATCH_LINK_BLOCKS 4u   /* (2u is unassigned: ZLZ4F_ERR_PARAMETER_INVALID) */
+size_t  zlz4f_batch_compress_frame_workspace_ex(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
+                                                uint32_t batch_flags);
 size_t  zlz4f_batch_compress_frame_workspace(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs);
 int32_t zlz4f_batch_compress_frame(void *stream,
                                    const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
@@ -556,6 +570,42 @@ int32_t zlz4f_batch_frame_decompressed_size(void *stream,
                                             const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
                                             int64_t *d_size, uint32_t nframes, uint32_t max_blocks, void *d_workspace,
                                             size_t workspace_bytes);
+
+/* Linked-block frames (no counterpart in the reference: its decompressFrame gives every block only its own output, so a
+ * frame whose blocks refer to earlier output -- the default of liblz4's LZ4F_* API -- fails there, and in the calls
+ * above, with DecompressionFailed).  Each _ex call takes decode_flags; with 0 it is the call it is named after (an
+ * unknown bit: ZLZ4F_ERR_PARAMETER_INVALID, nothing launched).  With ZLZ4F_DECODE_LINKED, per frame:
+ *   - FLG has the block-independence bit (0x20) SET: today's path, bytes and status as without the flag.
+ *   - the bit is CLEAR: the blocks are walked in order, pos = the bytes of this frame decoded so far.  A stored block is
+ *     copied (and is history for later blocks); a compressed block is zlz4_decompress_safe_using_dict(block, dst[pos ..
+ *     cap], dict = dst[max(0, pos - 65536) .. pos]): a match may reach min(pos, 65536) bytes in front of the block, never
+ *     in front of the frame's first output byte (src/lz4.zig:189-192).  Error order of src/lz4f.zig:541-638 as above;
+ *     DecompressionFailed (:611) is decided by the history-aware decode.  Frames this library writes with default prefs
+ *     declare "linked" while their blocks are independent: they take this path and give the same bytes.
+ *   max_blocks, ZLZ4_ERR_INVALID_STATE per frame and the slot guarantee are unchanged.  One wavefront decodes one linked
+ *   frame (a frame is a serial chain), so the parallelism is across frames; the launch sequence is fixed (no read-back,
+ *   no allocation, graph-capturable).  The size query with the flag is the same walk without output: block k is what
+ *   zlz4_batch_decompressed_size gives with dict_len = min(pos, 65536); the content checksum is excepted as above.
+ * The workspaces grow by 8 bytes per frame (the _workspace_ex functions).  The single-frame calls run one frame through
+ * the batch call (their result is the batch call's for that frame) and synchronise; zlz4f_decompress_frame_device,
+ * zlz4f_decompress_frame and zlz4f_frame_decompressed_size are not rerouted.  The segment calls have no _ex form: a rank's
+ * first block would need the previous rank's output. */
+#define ZLZ4F_DECODE_LINKED 1u
+size_t  zlz4f_batch_decompress_frame_workspace_ex(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags);
+int32_t zlz4f_batch_decompress_frame_ex(void *stream,
+                                        const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                        uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                                        int64_t *d_result, uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags,
+                                        void *d_workspace, size_t workspace_bytes);
+size_t  zlz4f_batch_frame_decompressed_size_workspace_ex(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags);
+int32_t zlz4f_batch_frame_decompressed_size_ex(void *stream,
+                                               const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                               int64_t *d_size, uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags,
+                                               void *d_workspace, size_t workspace_bytes);
+int64_t zlz4f_decompress_frame_device_ex(void *stream, const uint8_t *d_src, size_t src_len,
+                                         uint8_t *d_dst, size_t dst_cap, uint32_t decode_flags);
+int64_t zlz4f_decompress_frame_ex(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t decode_flags);
+int64_t zlz4f_frame_decompressed_size_ex(const uint8_t *src, size_t src_len, uint32_t decode_flags);
 
 /* ======================================================================
  * 4. Introspection

@@ -79,6 +79,9 @@ SYMBOLS = {
     "zlz4f_frame_decompressed_size": (_I64, [_VP, _SZ]),
     "zlz4f_batch_frame_decompressed_size_workspace": (_SZ, [_U32, _U32]),
     "zlz4f_batch_frame_decompressed_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
+    "zlz4f_frame_decompressed_size_ex": (_I64, [_VP, _SZ, _U32]),
+    "zlz4f_batch_frame_decompressed_size_workspace_ex": (_SZ, [_U32, _U32, _U32]),
+    "zlz4f_batch_frame_decompressed_size_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _VP, _SZ]),
     "zlz4_batch_load_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_compress_fast_continue": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_compress_fast_using_dict": (_I32, [_VP] * 13 + [_U32, _U32, _U32, _U32]),
@@ -108,6 +111,11 @@ SYMBOLS = {
     "zlz4f_batch_compress_frame": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _PP, _U32, _VP, _SZ]),
     "zlz4f_batch_decompress_frame_workspace": (_SZ, [_U32, _U32]),
     "zlz4f_batch_decompress_frame": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
+    "zlz4f_batch_compress_frame_workspace_ex": (_SZ, [_U32, _U32, _PP, _U32]),
+    "zlz4f_batch_decompress_frame_workspace_ex": (_SZ, [_U32, _U32, _U32]),
+    "zlz4f_batch_decompress_frame_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _VP, _SZ]),
+    "zlz4f_decompress_frame_device_ex": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _U32]),
+    "zlz4f_decompress_frame_ex": (_I64, [_VP, _SZ, _VP, _SZ, _U32]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -459,8 +467,12 @@ class lz4f:
         return _run(lib().zlz4f_compress_frame, src, cap, C.byref(prefs) if prefs is not None else None)
 
     @staticmethod
-    def decompressFrame(src, dst_cap):
-        return _run(lib().zlz4f_decompress_frame, src, dst_cap)
+    def decompressFrame(src, dst_cap, flags=0):
+        """flags 0: zlz4f_decompress_frame.  lz4f.DECODE_LINKED: zlz4f_decompress_frame_ex, which also reads frames whose
+        blocks refer to earlier output (liblz4's default)."""
+        if flags == 0:
+            return _run(lib().zlz4f_decompress_frame, src, dst_cap)
+        return _run(lib().zlz4f_decompress_frame_ex, src, dst_cap, flags)
 
     @staticmethod
     def headerSize(src):
@@ -474,7 +486,10 @@ class lz4f:
                                                         C.byref(prefs) if prefs is not None else None))
 
     @staticmethod
-    def decompressFrameDevice(d_frame, frame_len, d_dst):
+    def decompressFrameDevice(d_frame, frame_len, d_dst, flags=0):
+        if flags:
+            return _check(lib().zlz4f_decompress_frame_device_ex(_stream(), _ptr(d_frame), frame_len, _ptr(d_dst),
+                                                                 d_dst.numel(), flags))
         return _check(lib().zlz4f_decompress_frame_device(_stream(), _ptr(d_frame), frame_len, _ptr(d_dst), d_dst.numel()))
 
     SEG_FIRST, SEG_LAST = 1, 2
@@ -493,15 +508,18 @@ class lz4f:
 
     # batch frames (include/zlz4_amd.h section 3): N independent frames per call, device descriptors, asynchronous
     BATCH_CONTENT_SIZE = 1
+    BATCH_LINK_BLOCKS = 4       # compress: block k against the 64 KiB of input in front of it (include/zlz4_amd.h)
+    DECODE_LINKED = 1           # decode `flags`: frames that declare linked blocks are decoded with their history
     BLOCK_SIZES = {0: 64 << 10, 4: 64 << 10, 5: 256 << 10, 6: 1 << 20, 7: 4 << 20}     # BlockSizeID.toBlockSize
 
     @staticmethod
-    def compressFrameBatchWorkspace(nframes, max_blocks, prefs=None):
-        return lib().zlz4f_batch_compress_frame_workspace(nframes, max_blocks, C.byref(prefs) if prefs is not None else None)
+    def compressFrameBatchWorkspace(nframes, max_blocks, prefs=None, batch_flags=0):
+        return lib().zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks,
+                                                             C.byref(prefs) if prefs is not None else None, batch_flags)
 
     @staticmethod
-    def decompressFrameBatchWorkspace(nframes, max_blocks):
-        return lib().zlz4f_batch_decompress_frame_workspace(nframes, max_blocks)
+    def decompressFrameBatchWorkspace(nframes, max_blocks, flags=0):
+        return lib().zlz4f_batch_decompress_frame_workspace_ex(nframes, max_blocks, flags)
 
     @staticmethod
     def compressFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, prefs=None, batch_flags=0,
@@ -516,27 +534,35 @@ class lz4f:
             max_blocks = int(((src_len.cpu() + bs - 1) // bs).sum()) if src_len.numel() else 0
         pp = C.byref(prefs) if prefs is not None else None
         if workspace is None:
-            workspace = torch.empty(max(1, lib().zlz4f_batch_compress_frame_workspace(src_len.numel(), max_blocks, pp)),
+            workspace = torch.empty(max(1, lib().zlz4f_batch_compress_frame_workspace_ex(src_len.numel(), max_blocks, pp,
+                                                                                         batch_flags)),
                                     dtype=torch.uint8, device=d_src.device)
         _check(lib().zlz4f_batch_compress_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
                                                 _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(), max_blocks,
                                                 pp, batch_flags, _ptr(workspace), workspace.numel()))
 
     @staticmethod
-    def decompressFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, max_blocks=None, workspace=None):
-        """zlz4f_batch_decompress_frame on torch CUDA tensors (layout as compressFrameBatch; result = decompressed size or
-        the frame's error code).  The block count of a frame is only known on the device, so the default max_blocks is
+    def decompressFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, max_blocks=None, workspace=None,
+                             flags=0):
+        """zlz4f_batch_decompress_frame(_ex with `flags`, e.g. lz4f.DECODE_LINKED) on torch CUDA tensors (layout as
+        compressFrameBatch; result = decompressed size or the frame's error code).  The block count of a frame is only known on the device, so the default max_blocks is
         one entry per started 256 frame bytes (reads the lengths back once): enough for frames whose blocks average 256
         bytes or more; pass the real count for anything denser, else such frames report InvalidState."""
         import torch
         if max_blocks is None:
             max_blocks = int((src_len.cpu() // 256 + 1).sum()) if src_len.numel() else 0
         if workspace is None:
-            workspace = torch.empty(max(1, lib().zlz4f_batch_decompress_frame_workspace(src_len.numel(), max_blocks)),
+            workspace = torch.empty(max(1, lib().zlz4f_batch_decompress_frame_workspace_ex(src_len.numel(), max_blocks,
+                                                                                           flags)),
                                     dtype=torch.uint8, device=d_src.device)
-        _check(lib().zlz4f_batch_decompress_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
-                                                  _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(), max_blocks,
-                                                  _ptr(workspace), workspace.numel()))
+        if flags == 0:
+            _check(lib().zlz4f_batch_decompress_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                      _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(),
+                                                      max_blocks, _ptr(workspace), workspace.numel()))
+        else:
+            _check(lib().zlz4f_batch_decompress_frame_ex(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                         _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(),
+                                                         max_blocks, flags, _ptr(workspace), workspace.numel()))
 
     @staticmethod
     def compressFrames(items, prefs=None, batch_flags=0, device="cuda"):
@@ -553,31 +579,40 @@ class lz4f:
         return _unstage(d_dst, _offsets(caps), result)
 
     @staticmethod
-    def frameDecompressedSize(src):
-        """zlz4f_frame_decompressed_size: what decompressFrame returns for `src` into a destination that is large enough
-        (the content checksum is not verified); errors raise Lz4Error.  Nothing is decoded."""
+    def frameDecompressedSize(src, flags=0):
+        """zlz4f_frame_decompressed_size(_ex with `flags`): what decompressFrame returns for `src` into a destination that
+        is large enough (the content checksum is not verified); errors raise Lz4Error.  Nothing is decoded."""
         s, n = _in(src)
+        if flags:
+            return _check(lib().zlz4f_frame_decompressed_size_ex(C.addressof(s), n, flags))
         return _check(lib().zlz4f_frame_decompressed_size(C.addressof(s), n))
 
     @staticmethod
-    def frameDecompressedSizeBatchWorkspace(nframes, max_blocks):
-        return lib().zlz4f_batch_frame_decompressed_size_workspace(nframes, max_blocks)
+    def frameDecompressedSizeBatchWorkspace(nframes, max_blocks, flags=0):
+        return lib().zlz4f_batch_frame_decompressed_size_workspace_ex(nframes, max_blocks, flags)
 
     @staticmethod
-    def frameDecompressedSizeBatch(d_src, src_off, src_len, size, max_blocks=None, workspace=None):
+    def frameDecompressedSizeBatch(d_src, src_off, src_len, size, max_blocks=None, workspace=None, flags=0):
         """zlz4f_batch_frame_decompressed_size on torch CUDA tensors (layout as decompressFrameBatch; size int64 = decoded
         size or the frame's error code).  max_blocks defaults as in decompressFrameBatch."""
         import torch
         if max_blocks is None:
             max_blocks = int((src_len.cpu() // 256 + 1).sum()) if src_len.numel() else 0
         if workspace is None:
-            workspace = torch.empty(max(16, lib().zlz4f_batch_frame_decompressed_size_workspace(src_len.numel(), max_blocks)),
+            workspace = torch.empty(max(16, lib().zlz4f_batch_frame_decompressed_size_workspace_ex(src_len.numel(),
+                                                                                                   max_blocks, flags)),
                                     dtype=torch.uint8, device=d_src.device)
-        _check(lib().zlz4f_batch_frame_decompressed_size(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(size),
-                                                         src_len.numel(), max_blocks, _ptr(workspace), workspace.numel()))
+        if flags == 0:
+            _check(lib().zlz4f_batch_frame_decompressed_size(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len),
+                                                             _ptr(size), src_len.numel(), max_blocks, _ptr(workspace),
+                                                             workspace.numel()))
+        else:
+            _check(lib().zlz4f_batch_frame_decompressed_size_ex(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len),
+                                                                _ptr(size), src_len.numel(), max_blocks, flags,
+                                                                _ptr(workspace), workspace.numel()))
 
     @staticmethod
-    def decompressFrames(frames, caps=None, device="cuda"):
+    def decompressFrames(frames, caps=None, device="cuda", flags=0):
         """Every frame of `frames` decoded into a destination of caps[f] bytes, in one batch call -> list of contents
         (bytes) or error codes.  caps None: the sizes are queried first (frameDecompressedSizeBatch) and every frame gets
         exactly its size (a frame the query fails gets no room and reports the query's code)."""
@@ -587,7 +622,7 @@ class lz4f:
         if caps is None:
             size = torch.empty(len(frames), dtype=torch.int64, device=device)
             lz4f.frameDecompressedSizeBatch(d_src, src_off, src_len, size,
-                                            max_blocks=sum(_chain_blocks(bytes(f)) for f in frames))
+                                            max_blocks=sum(_chain_blocks(bytes(f)) for f in frames), flags=flags)
             sizes = size.cpu().tolist()
             caps = [max(s, 0) for s in sizes]
         caps = list(caps)
@@ -596,7 +631,7 @@ class lz4f:
         result = torch.empty(len(frames), dtype=torch.int64, device=device)
         lz4f.decompressFrameBatch(d_src, src_off, src_len, d_dst, dst_off,
                                   torch.tensor(caps, dtype=torch.int64, device=device), result,
-                                  max_blocks=sum(_chain_blocks(bytes(f)) for f in frames))
+                                  max_blocks=sum(_chain_blocks(bytes(f)) for f in frames), flags=flags)
         out = _unstage(d_dst, _offsets(caps), result)
         if sizes is not None:                         # (a frame the query failed got no room: the query's code stands)
             out = [o if s >= 0 else s for o, s in zip(out, sizes)]

@@ -297,6 +297,42 @@ inline Result frameDecompressedSizeBatch(void *stream, const Frames &f, std::int
                                          std::size_t ws_bytes) {
     return wrap(zlz4f_batch_frame_decompressed_size(stream, f.src, f.src_off, f.src_len, d_size, f.nframes, max_blocks, ws, ws_bytes));
 }
+// linked-block frames (include/zlz4_amd.h; no counterpart in the reference).  DECODE_LINKED: a frame whose FLG declares
+// linked blocks is decoded in block order, block k against the 64 KiB of output in front of it (liblz4's default frames);
+// BATCH_LINK_BLOCKS: compressFrameBatch writes such frames (fast levels; workspace from compressFrameBatchWorkspaceEx).
+constexpr std::uint32_t DECODE_LINKED = ZLZ4F_DECODE_LINKED;
+constexpr std::uint32_t BATCH_LINK_BLOCKS = ZLZ4F_BATCH_LINK_BLOCKS;
+inline std::size_t compressFrameBatchWorkspaceEx(std::uint32_t nframes, std::uint32_t max_blocks, const Preferences *p, std::uint32_t batch_flags) {
+    return zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks, p, batch_flags);
+}
+inline std::size_t decompressFrameBatchWorkspaceEx(std::uint32_t nframes, std::uint32_t max_blocks, std::uint32_t decode_flags) {
+    return zlz4f_batch_decompress_frame_workspace_ex(nframes, max_blocks, decode_flags);
+}
+inline Result decompressFrameBatchEx(void *stream, const Frames &f, std::uint32_t max_blocks, std::uint32_t decode_flags, void *ws,
+                                     std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_decompress_frame_ex(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes,
+                                                max_blocks, decode_flags, ws, ws_bytes));
+}
+inline std::size_t frameDecompressedSizeBatchWorkspaceEx(std::uint32_t nframes, std::uint32_t max_blocks, std::uint32_t decode_flags) {
+    return zlz4f_batch_frame_decompressed_size_workspace_ex(nframes, max_blocks, decode_flags);
+}
+inline Result frameDecompressedSizeBatchEx(void *stream, const Frames &f, std::int64_t *d_size, std::uint32_t max_blocks,
+                                           std::uint32_t decode_flags, void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_frame_decompressed_size_ex(stream, f.src, f.src_off, f.src_len, d_size, f.nframes, max_blocks, decode_flags,
+                                                       ws, ws_bytes));
+}
+// one frame through the batch calls (the segment calls have no such form: a rank's first block would need the previous
+// rank's output)
+inline Result decompressFrameEx(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap, std::uint32_t decode_flags) {
+    return wrap(zlz4f_decompress_frame_ex(src, n, dst, cap, decode_flags));
+}
+inline Result decompressFrameDeviceEx(void *stream, const std::uint8_t *d_src, std::size_t n, std::uint8_t *d_dst, std::size_t cap,
+                                      std::uint32_t decode_flags) {
+    return wrap(zlz4f_decompress_frame_device_ex(stream, d_src, n, d_dst, cap, decode_flags));
+}
+inline Result frameDecompressedSizeEx(const std::uint8_t *src, std::size_t n, std::uint32_t decode_flags) {
+    return wrap(zlz4f_frame_decompressed_size_ex(src, n, decode_flags));
+}
 }  // namespace lz4f
 
 }  // namespace zlz4

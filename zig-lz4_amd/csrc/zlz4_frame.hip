@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "zlz4_device.hpp"
+#include "zlz4_frame_batch.hpp"
 #include "zlz4_host.hpp"
 
 extern "C" int zlz4_launch_decompress_safe(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
@@ -40,6 +41,20 @@ extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint6
                                        const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, int32_t,
                                        void *, size_t);
 extern "C" size_t zlz4_hc_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
+extern "C" int zlz4_launch_load_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint32_t *, int64_t *,
+                                     uint32_t);
+extern "C" int zlz4_launch_compress_fast_using_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
+                                                    uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *,
+                                                    const uint64_t *, const uint32_t *, const uint32_t *, const uint32_t *,
+                                                    int64_t *, uint32_t, uint32_t, uint32_t, uint32_t);
+// zlz4_frame_linked.hip; `frames` is the BFrame array
+extern "C" int zlz4_launch_bfl_save(hipStream_t, const void *frames, uint32_t, int64_t *);
+extern "C" int zlz4_launch_bfl_mask(hipStream_t, const void *frames, const uint32_t *, uint32_t, uint32_t *, uint32_t *);
+extern "C" int zlz4_launch_bfl_decode(hipStream_t, int write, void *frames, uint32_t, uint32_t, const uint8_t *, const uint64_t *,
+                                      const uint32_t *, const uint32_t *, const uint32_t *, const int64_t *, uint8_t *,
+                                      const uint64_t *, const uint64_t *, const uint64_t *, int64_t *);
+extern "C" int zlz4_launch_bfl_dict_desc(hipStream_t, const void *frames, uint32_t, uint32_t, const uint64_t *,
+                                         const uint64_t *, const uint32_t *, uint64_t *, uint32_t *);
 
 // ------------------------------------------------------------------ device buffers (zlz4_host.hpp)
 namespace {
@@ -790,23 +805,6 @@ int64_t zlz4f_decompress_frame(const uint8_t *src, size_t n, uint8_t *dst, size_
 // lane per frame; the block steps (compression, decoding, block checksums, copies) one entry per lane / wave / workgroup.
 namespace {
 
-constexpr uint32_t kNoFrame = 0xFFFFFFFFu;
-constexpr uint32_t kBlkStored = 1u, kBlkNoCks = 2u, kBlkCks = 4u;   // block flags (decompress table)
-
-struct BFrame {
-    uint64_t nb;        // block count: ceil(len / bs) (compress), what the block chain holds (decompress)
-    uint64_t base;      // first table entry (exclusive scan of nb)
-    int64_t status;     // compress: 0, DstMaxSizeTooSmall or SrcSizeTooLarge; decompress: header size or header error
-    uint64_t end;       // compress: frame bytes in front of the end mark; decompress: srcPos after the walk
-    int64_t err;        // compress: first failing block's code; decompress: the walk's error, then the plan's
-    uint64_t total;     // decompress: decoded bytes
-    uint64_t bs;        // decompress: block size from BD
-    uint32_t flg;       // decompress: FLG
-    uint32_t proven;    // decompress: 1 = the speculative layout is proven
-};
-
-__device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { return F.nb == 0 || F.base + F.nb <= max_blocks; }
-
 // exclusive scan of fr[].nb into fr[].base: one workgroup, thread t sums a contiguous run of frames, the 1024 run sums are
 // scanned in LDS, then every thread writes its run's bases
 __global__ __launch_bounds__(1024) void k_bf_scan(BFrame *__restrict__ fr, uint32_t nframes) {
@@ -1265,7 +1263,8 @@ int32_t bf_hc_level(const zlz4f_prefs &p) {   // compress_frame_impl's routing (
 uint64_t bf_slot(size_t bs) { return (zlz4_compress_bound(bs) + 15) & ~15ull; }
 
 // compress: frames | in_off out_off dst_off (u64) | in_len out_cap hdr cks (u32) | csize (i64) | slots | HC workspace
-BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p) {
+// with ZLZ4F_BATCH_LINK_BLOCKS also: | loadDict tables | dict_off (u64) | dict_len (u32) | dictSize (i64)
+BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t batch_flags = 0) {
     const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
     BatchLayout L;
     L.add((size_t)nframes * sizeof(BFrame));
@@ -1274,29 +1273,38 @@ BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs 
     L.add(m * sizeof(int64_t));
     L.add(m * bf_slot(bs));
     L.add(bf_hc_level(p) ? zlz4_hc_workspace_bytes(max_blocks, (uint32_t)bs) : 0);
+    if (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) {
+        L.add(m * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
+        L.add(m * sizeof(uint64_t));
+        L.add(m * sizeof(uint32_t));
+        L.add(m * sizeof(int64_t));
+    }
     return L;
 }
 
 // decompress: frames | data_off cks_off out_off x_off (u64) | data_len flags fidx cks_ok out_cap dec_len x_cap x_len (u32)
-// | sizes (i64)
-BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks) {
+// | sizes (i64); with ZLZ4F_DECODE_LINKED also: | walk_err (i64 per frame)
+BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0) {
     const size_t m = max_blocks;
     BatchLayout L;
     L.add((size_t)nframes * sizeof(BFrame));
     for (int k = 0; k < 4; k++) L.add(m * sizeof(uint64_t));
     for (int k = 0; k < 8; k++) L.add(m * sizeof(uint32_t));
     L.add(m * sizeof(int64_t));
+    if (decode_flags & ZLZ4F_DECODE_LINKED) L.add((size_t)nframes * sizeof(int64_t));
     return L;
 }
 
-// size query: frames | data_off cks_off (u64) | data_len flags fidx cks_ok dec_len (u32) | sizes (i64)
-BatchLayout bfq_layout(uint32_t nframes, uint32_t max_blocks) {
+// size query: frames | data_off cks_off (u64) | data_len flags fidx cks_ok dec_len (u32) | sizes (i64); with
+// ZLZ4F_DECODE_LINKED also: | walk_err (i64 per frame)
+BatchLayout bfq_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0) {
     const size_t m = max_blocks;
     BatchLayout L;
     L.add((size_t)nframes * sizeof(BFrame));
     for (int k = 0; k < 2; k++) L.add(m * sizeof(uint64_t));
     for (int k = 0; k < 5; k++) L.add(m * sizeof(uint32_t));
     L.add(m * sizeof(int64_t));
+    if (decode_flags & ZLZ4F_DECODE_LINKED) L.add((size_t)nframes * sizeof(int64_t));
     return L;
 }
 
@@ -1313,8 +1321,17 @@ size_t zlz4f_batch_compress_frame_workspace(uint32_t nframes, uint32_t max_block
     return bfc_layout(nframes, max_blocks, prefs ? *prefs : kDefaultPrefs).bytes;
 }
 
+size_t zlz4f_batch_compress_frame_workspace_ex(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
+                                               uint32_t batch_flags) {
+    return bfc_layout(nframes, max_blocks, prefs ? *prefs : kDefaultPrefs, batch_flags).bytes;
+}
+
 size_t zlz4f_batch_decompress_frame_workspace(uint32_t nframes, uint32_t max_blocks) {
     return bfd_layout(nframes, max_blocks).bytes;
+}
+
+size_t zlz4f_batch_decompress_frame_workspace_ex(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags) {
+    return bfd_layout(nframes, max_blocks, decode_flags).bytes;
 }
 
 int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
@@ -1322,11 +1339,14 @@ int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const ui
                                    uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
                                    void *d_workspace, size_t workspace_bytes) {
     const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
-    if (batch_flags & ~ZLZ4F_BATCH_CONTENT_SIZE) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (batch_flags & ~(ZLZ4F_BATCH_CONTENT_SIZE | ZLZ4F_BATCH_LINK_BLOCKS)) return ZLZ4F_ERR_PARAMETER_INVALID;
     const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
+    const bool link = (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) != 0;
     if (cs_from_len && p.content_size != 0) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (link && p.block_mode != 0) return ZLZ4F_ERR_PARAMETER_INVALID;     // FLG must declare what the blocks are
+    if (link && p.compression_level > 0) return ZLZ4_ERR_UNSUPPORTED;      // HC linking is not built
     if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    const BatchLayout L = bfc_layout(nframes, max_blocks, p);
+    const BatchLayout L = bfc_layout(nframes, max_blocks, p, batch_flags);
     if (nframes == 0) return 0;
     if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
     hipStream_t st = (hipStream_t)stream_;
@@ -1353,7 +1373,21 @@ int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const ui
         hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, fr, nframes, max_blocks,
                            d_src_off, d_src_len, (uint64_t)bs, slot, in_off, in_len, out_off, out_cap, hdr);
         int rc;
-        if (hc_level == 0)
+        if (link) {
+            // block k against the 64 KiB of input in front of it: descriptors, one loadDict table per entry, then the
+            // dictionary compressor over the table (block 0 of a frame has an empty dictionary: compressDefault's bytes)
+            uint32_t *tables = reinterpret_cast<uint32_t *>(ws + L.off[11]);
+            uint64_t *dict_off = reinterpret_cast<uint64_t *>(ws + L.off[12]);
+            uint32_t *dict_len = reinterpret_cast<uint32_t *>(ws + L.off[13]);
+            int64_t *dict_size = reinterpret_cast<int64_t *>(ws + L.off[14]);
+            rc = zlz4_launch_bfl_dict_desc(st, fr, nframes, max_blocks, d_src_off, in_off, in_len, dict_off, dict_len);
+            if (rc == 0) rc = zlz4_launch_load_dict(st, d_src, dict_off, dict_len, tables, dict_size, max_blocks);
+            if (rc == 0)
+                rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, in_len, slots, out_off, out_cap, d_src, dict_off,
+                                                          dict_len, tables, nullptr, csize, max_blocks, (uint32_t)bs, 65536u,
+                                                          1);
+            if (rc != 0) rc = ZLZ4_ERR_DEVICE;
+        } else if (hc_level == 0)
             rc = zlz4_launch_compress_fast(st, d_src, in_off, in_len, slots, out_off, out_cap, csize, max_blocks,
                                            (uint32_t)bs, 1);                                               // :400-404
         else
@@ -1373,12 +1407,21 @@ int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const ui
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
-int32_t zlz4f_batch_decompress_frame(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
-                                     const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
-                                     const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
-                                     void *d_workspace, size_t workspace_bytes) {
+}  // extern "C"
+
+namespace {
+
+// decode_flags 0: zlz4f_batch_decompress_frame.  ZLZ4F_DECODE_LINKED: the frames whose FLG declares linked blocks leave the
+// parallel decodes (k_bfl_mask after each kernel that fills a length / capacity array) and are decoded in block order by
+// k_bfl_decode, which leaves F.total / F.err for k_bfd_finish; the sequence of launches stays fixed.
+int32_t batch_decompress_frame_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
+                                    const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                    const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                    uint32_t decode_flags, void *d_workspace, size_t workspace_bytes) {
+    if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
+    const bool linked = (decode_flags & ZLZ4F_DECODE_LINKED) != 0;
     if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    const BatchLayout L = bfd_layout(nframes, max_blocks);
+    const BatchLayout L = bfd_layout(nframes, max_blocks, decode_flags);
     if (nframes == 0) return 0;
     if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
     hipStream_t st = (hipStream_t)stream_;
@@ -1391,11 +1434,13 @@ int32_t zlz4f_batch_decompress_frame(void *stream_, const uint8_t *d_src, const 
              *out_cap = reinterpret_cast<uint32_t *>(ws + L.off[9]), *dec_len = reinterpret_cast<uint32_t *>(ws + L.off[10]),
              *x_cap = reinterpret_cast<uint32_t *>(ws + L.off[11]), *x_len = reinterpret_cast<uint32_t *>(ws + L.off[12]);
     int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[13]);
+    int64_t *walk_err = linked ? reinterpret_cast<int64_t *>(ws + L.off[14]) : nullptr;
     const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
     if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
     hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                        data_off, data_len, flags, cks_off, fidx);
     hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
+    if (linked && zlz4_launch_bfl_save(st, fr, nframes, walk_err) != 0) return ZLZ4_ERR_DEVICE;
     if (max_blocks) {
         hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                            data_off, data_len, flags, cks_off, fidx);
@@ -1404,6 +1449,7 @@ int32_t zlz4f_batch_decompress_frame(void *stream_, const uint8_t *d_src, const 
                            cks_off, max_blocks, cks_ok);
         hipLaunchKernelGGL(k_bfd_spec, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, d_dst_off, d_dst_cap, max_blocks,
                            out_off, out_cap, dec_len);
+        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, out_cap, dec_len) != 0) return ZLZ4_ERR_DEVICE;
         int rc = zlz4_launch_decompress_safe(st, d_src, data_off, dec_len, d_dst, out_off, out_cap, sizes, max_blocks);
         if (rc != 0) return ZLZ4_ERR_DEVICE;
         hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, out_off,
@@ -1412,33 +1458,71 @@ int32_t zlz4f_batch_decompress_frame(void *stream_, const uint8_t *d_src, const 
                            sizes, cks_ok, out_cap);
         // exact path for the frames whose layout was not proven (always enqueued: the sequence does not depend on data)
         hipLaunchKernelGGL(k_bfd_mask, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, max_blocks, x_off, x_cap, x_len);
+        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
         rc = zlz4_launch_decompress_sizes(st, d_src, data_off, x_len, x_off, x_cap, sizes, max_blocks);
         if (rc != 0) return ZLZ4_ERR_DEVICE;
     }
     hipLaunchKernelGGL(k_bfd_plan, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags, sizes, cks_ok,
                        d_dst_off, d_dst_cap, x_off, x_cap, x_len);
     if (max_blocks) {
+        // (k_bfd_plan laid out the unproven frames, a linked one among them from sizes that mean nothing: masked again)
+        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
         const int rc = zlz4_launch_decompress_safe(st, d_src, data_off, x_len, d_dst, x_off, x_cap, sizes, max_blocks);
         if (rc != 0) return ZLZ4_ERR_DEVICE;
         hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, x_off,
                            x_cap, d_dst);
     }
+    if (linked && zlz4_launch_bfl_decode(st, 1, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err,
+                                         d_dst, d_dst_off, d_dst_cap, d_src_len, nullptr) != 0)
+        return ZLZ4_ERR_DEVICE;
     hipLaunchKernelGGL(k_bfd_finish, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, d_src, d_src_off, d_src_len, d_dst,
                        d_dst_off, d_dst_cap, d_result);
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t zlz4f_batch_decompress_frame(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                     const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                     const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                     void *d_workspace, size_t workspace_bytes) {
+    return batch_decompress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
+                                       max_blocks, 0, d_workspace, workspace_bytes);
+}
+
+int32_t zlz4f_batch_decompress_frame_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                        const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                        const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                        uint32_t decode_flags, void *d_workspace, size_t workspace_bytes) {
+    return batch_decompress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
+                                       max_blocks, decode_flags, d_workspace, workspace_bytes);
 }
 
 size_t zlz4f_batch_frame_decompressed_size_workspace(uint32_t nframes, uint32_t max_blocks) {
     return bfq_layout(nframes, max_blocks).bytes;
 }
 
+size_t zlz4f_batch_frame_decompressed_size_workspace_ex(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags) {
+    return bfq_layout(nframes, max_blocks, decode_flags).bytes;
+}
+
+}  // extern "C"
+
+namespace {
+
 // the walk, scan and block-checksum passes of zlz4f_batch_decompress_frame, then the size kernel over the block table and
-// the per-frame total; nothing but d_size and the workspace is written
-int32_t zlz4f_batch_frame_decompressed_size(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
-                                            const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
-                                            uint32_t max_blocks, void *d_workspace, size_t workspace_bytes) {
+// the per-frame total; nothing but d_size and the workspace is written.  ZLZ4F_DECODE_LINKED: the entries of the linked-
+// declared frames are masked out of the size kernel and k_bfl_decode<false> replaces their results.
+int32_t batch_frame_decompressed_size_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
+                                           const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
+                                           uint32_t max_blocks, uint32_t decode_flags, void *d_workspace,
+                                           size_t workspace_bytes) {
+    if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
+    const bool linked = (decode_flags & ZLZ4F_DECODE_LINKED) != 0;
     if (nframes == 0) return 0;
-    const BatchLayout L = bfq_layout(nframes, max_blocks);
+    const BatchLayout L = bfq_layout(nframes, max_blocks, decode_flags);
     if (!d_src || !d_src_off || !d_src_len || !d_size || !d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < L.bytes)
         return ZLZ4_ERR_INVALID_STATE;
     if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
@@ -1450,22 +1534,126 @@ int32_t zlz4f_batch_frame_decompressed_size(void *stream_, const uint8_t *d_src,
              *fidx = reinterpret_cast<uint32_t *>(ws + L.off[5]), *cks_ok = reinterpret_cast<uint32_t *>(ws + L.off[6]),
              *dec_len = reinterpret_cast<uint32_t *>(ws + L.off[7]);
     int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[8]);
+    int64_t *walk_err = linked ? reinterpret_cast<int64_t *>(ws + L.off[9]) : nullptr;
     const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
     if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
     hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                        data_off, data_len, flags, cks_off, fidx);
     hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
+    if (linked && zlz4_launch_bfl_save(st, fr, nframes, walk_err) != 0) return ZLZ4_ERR_DEVICE;
     if (max_blocks) {
         hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                            data_off, data_len, flags, cks_off, fidx);
         hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, data_off, data_len, flags,
                            cks_off, max_blocks, cks_ok);
         hipLaunchKernelGGL(k_bfq_len, dim3(gb), dim3(256), 0, st, data_len, flags, max_blocks, dec_len);
+        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, nullptr, dec_len) != 0) return ZLZ4_ERR_DEVICE;
         if (zlz4_launch_decompressed_size(st, d_src, data_off, dec_len, nullptr, sizes, max_blocks) != 0) return ZLZ4_ERR_DEVICE;
     }
     hipLaunchKernelGGL(k_bfq_total, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags,
                        sizes, cks_ok, d_src_len, d_size);
+    if (linked && zlz4_launch_bfl_decode(st, 0, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err,
+                                         nullptr, nullptr, nullptr, d_src_len, d_size) != 0)
+        return ZLZ4_ERR_DEVICE;
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+// One frame through the batch calls, device pointers: a counting walk finds the table size (read back), then the frame
+// is a batch of one.  d_dst == nullptr with want_size: the size query.
+int64_t single_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap, uint32_t decode_flags,
+                        bool want_size) {
+    if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    zlz4host::DeviceCall dc(st);
+    DevBuf d_meta(256, &dc);
+    if (!d_meta.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    struct Meta { uint64_t src_off, src_len, dst_off, dst_cap; int64_t result; uint64_t pad[3]; BFrame fr; } m = {};
+    m.src_len = n;
+    m.dst_cap = cap;
+    static_assert(sizeof(Meta) <= 256, "meta");
+    auto *dm = d_meta.as<uint8_t>();
+    dc.launched();
+    if (hipMemcpyAsync(dm, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    const uint64_t *p_src_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_off)),
+                   *p_src_len = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_len)),
+                   *p_dst_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_off)),
+                   *p_dst_cap = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_cap));
+    int64_t *p_result = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
+    BFrame *p_fr = reinterpret_cast<BFrame *>(dm + offsetof(Meta, fr));
+    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(1), dim3(256), 0, st, d_src, p_src_off, p_src_len, 1u, 0u, p_fr, nullptr,
+                       nullptr, nullptr, nullptr, nullptr);
+    BFrame F;
+    if (hipMemcpyAsync(&F, p_fr, sizeof F, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
+    if (F.status < 0) return F.status;
+    if (F.nb > 0x7FFFFFFFull) return ZLZ4F_ERR_FRAME_SIZE_WRONG;
+    const uint32_t max_blocks = (uint32_t)F.nb;
+    const size_t ws = want_size ? zlz4f_batch_frame_decompressed_size_workspace_ex(1, max_blocks, decode_flags)
+                                : zlz4f_batch_decompress_frame_workspace_ex(1, max_blocks, decode_flags);
+    DevBuf d_ws(ws, &dc);
+    if (!d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    dc.launched();
+    const int32_t rc = want_size
+        ? batch_frame_decompressed_size_impl(st, d_src, p_src_off, p_src_len, p_result, 1, max_blocks, decode_flags, d_ws.p, ws)
+        : batch_decompress_frame_impl(st, d_src, p_src_off, p_src_len, d_dst, p_dst_off, p_dst_cap, p_result, 1, max_blocks,
+                                      decode_flags, d_ws.p, ws);
+    if (rc != 0) return rc;
+    int64_t r = 0;
+    if (hipMemcpyAsync(&r, p_result, sizeof r, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t zlz4f_batch_frame_decompressed_size(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                            const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
+                                            uint32_t max_blocks, void *d_workspace, size_t workspace_bytes) {
+    return batch_frame_decompressed_size_impl(stream, d_src, d_src_off, d_src_len, d_size, nframes, max_blocks, 0,
+                                              d_workspace, workspace_bytes);
+}
+
+int32_t zlz4f_batch_frame_decompressed_size_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                               const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
+                                               uint32_t max_blocks, uint32_t decode_flags, void *d_workspace,
+                                               size_t workspace_bytes) {
+    return batch_frame_decompressed_size_impl(stream, d_src, d_src_off, d_src_len, d_size, nframes, max_blocks, decode_flags,
+                                              d_workspace, workspace_bytes);
+}
+
+// one frame through zlz4f_batch_decompress_frame_ex / zlz4f_batch_frame_decompressed_size_ex (the result is the batch
+// call's for that frame); synchronises `stream`
+int64_t zlz4f_decompress_frame_device_ex(void *stream, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
+                                         uint32_t decode_flags) {
+    return single_frame_ex((hipStream_t)stream, d_src, n, d_dst, cap, decode_flags, false);
+}
+
+int64_t zlz4f_decompress_frame_ex(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, uint32_t decode_flags) {
+    if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if ((!src && n) || (!dst && cap)) return ZLZ4_ERR_INVALID_STATE;
+    const ParsedHeader ph = parse_header(src, n);      // header errors need no device
+    if (ph.size < 0) return ph.size;
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    DevBuf d_src(n), d_dst(cap);
+    if (!d_src.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    const int64_t r = single_frame_ex(nullptr, d_src.as<uint8_t>(), n, d_dst.as<uint8_t>(), cap, decode_flags, false);
+    if (r <= 0) return r;
+    if ((uint64_t)r > cap) return ZLZ4_ERR_DEVICE;
+    if (hipMemcpy(dst, d_dst.p, (size_t)r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return r;
+}
+
+int64_t zlz4f_frame_decompressed_size_ex(const uint8_t *src, size_t n, uint32_t decode_flags) {
+    if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (!src && n) return ZLZ4_ERR_INVALID_STATE;
+    const ParsedHeader ph = parse_header(src, n);
+    if (ph.size < 0) return ph.size;
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    DevBuf d_src(n);
+    if (!d_src.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return single_frame_ex(nullptr, d_src.as<uint8_t>(), n, nullptr, 0, decode_flags, true);
 }
 
 // what zlz4f_decompress_frame returns into a destination that is large enough (the content checksum aside), host

@@ -72,6 +72,14 @@ extern "c" fn zlz4f_batch_decompress_frame_workspace(nframes: u32, max_blocks: u
 extern "c" fn zlz4f_frame_decompressed_size(src: [*]const u8, src_len: usize) i64;
 extern "c" fn zlz4f_batch_frame_decompressed_size_workspace(nframes: u32, max_blocks: u32) usize;
 extern "c" fn zlz4f_batch_frame_decompressed_size(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_size: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_compress_frame_workspace_ex(nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32) usize;
+extern "c" fn zlz4f_batch_decompress_frame_workspace_ex(nframes: u32, max_blocks: u32, decode_flags: u32) usize;
+extern "c" fn zlz4f_batch_decompress_frame_ex(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, decode_flags: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_frame_decompressed_size_workspace_ex(nframes: u32, max_blocks: u32, decode_flags: u32) usize;
+extern "c" fn zlz4f_batch_frame_decompressed_size_ex(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_size: [*]i64, nframes: u32, max_blocks: u32, decode_flags: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_decompress_frame_device_ex(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
+extern "c" fn zlz4f_decompress_frame_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
+extern "c" fn zlz4f_frame_decompressed_size_ex(src: [*]const u8, src_len: usize, decode_flags: u32) i64;
 extern "c" fn zlz4f_batch_decompress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 
 // ---- constants (reference src/lz4.zig:12-25, src/lz4hc.zig:28-31) ----
@@ -618,6 +626,13 @@ pub const lz4f = struct {
     /// (size, or a negative code).  Device pointers; asynchronous on `stream`; `workspace` = device memory of the size the
     /// workspace function gives.
     pub const BATCH_CONTENT_SIZE: u32 = 1;
+    /// compressFrameBatch: block k against the 64 KiB of input in front of it (fast levels, block_mode linked; the
+    /// workspace comes from compressFrameBatchWorkspaceEx).  No counterpart in the reference.
+    pub const BATCH_LINK_BLOCKS: u32 = 4;
+    /// decode flag of the ...Ex calls: a frame whose FLG declares linked blocks is decoded in block order, block k
+    /// against the 64 KiB of output in front of it (liblz4's default frames).  The segment calls have no such form: a
+    /// rank's first block would need the previous rank's output.
+    pub const DECODE_LINKED: u32 = 1;
     pub const Frames = struct {
         src: [*]const u8,
         src_off: [*]const u64,
@@ -649,6 +664,31 @@ pub const lz4f = struct {
     }
     pub fn decompressFrameBatch(stream: ?*anyopaque, f: Frames, max_blocks: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
         return mapBatch(zlz4f_batch_decompress_frame(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, workspace, workspace_bytes));
+    }
+    pub fn compressFrameBatchWorkspaceEx(nframes: u32, max_blocks: u32, prefs: ?Preferences, batch_flags: u32) usize {
+        if (prefs) |p| { const c = toC(p); return zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks, &c, batch_flags); }
+        return zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks, null, batch_flags);
+    }
+    pub fn decompressFrameBatchWorkspaceEx(nframes: u32, max_blocks: u32, decode_flags: u32) usize {
+        return zlz4f_batch_decompress_frame_workspace_ex(nframes, max_blocks, decode_flags);
+    }
+    pub fn decompressFrameBatchEx(stream: ?*anyopaque, f: Frames, max_blocks: u32, decode_flags: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_frame_ex(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, decode_flags, workspace, workspace_bytes));
+    }
+    pub fn frameDecompressedSizeBatchWorkspaceEx(nframes: u32, max_blocks: u32, decode_flags: u32) usize {
+        return zlz4f_batch_frame_decompressed_size_workspace_ex(nframes, max_blocks, decode_flags);
+    }
+    pub fn frameDecompressedSizeBatchEx(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, size: [*]i64, nframes: u32, max_blocks: u32, decode_flags: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_frame_decompressed_size_ex(stream, src, src_off, src_len, size, nframes, max_blocks, decode_flags, workspace, workspace_bytes));
+    }
+    pub fn decompressFrameEx(src: []const u8, dst: []u8, decode_flags: u32) Error!usize {
+        return mapFrame(zlz4f_decompress_frame_ex(src.ptr, src.len, dst.ptr, dst.len, decode_flags));
+    }
+    pub fn decompressFrameDeviceEx(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, decode_flags: u32) Error!usize {
+        return mapFrame(zlz4f_decompress_frame_device_ex(stream, d_src, src_len, d_dst, dst_cap, decode_flags));
+    }
+    pub fn frameDecompressedSizeEx(src: []const u8, decode_flags: u32) Error!usize {
+        return mapFrame(zlz4f_frame_decompressed_size_ex(src.ptr, src.len, decode_flags));
     }
     pub fn frameDecompressedSizeBatchWorkspace(nframes: u32, max_blocks: u32) usize {
         return zlz4f_batch_frame_decompressed_size_workspace(nframes, max_blocks);
