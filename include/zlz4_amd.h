@@ -531,9 +531,10 @@ int64_t zlz4f_decompress_frame_segment_device(void *stream, const uint8_t *d_src
  * end mark.  Every block of every frame is still independent work.  liblz4's LZ4F_decompress and
  * zlz4f_batch_decompress_frame_ex(ZLZ4F_DECODE_LINKED) decode such a frame; the calls without that flag do not.
  * The flag needs prefs->block_mode == 0, so that FLG declares what the blocks are (else ZLZ4F_ERR_PARAMETER_INVALID),
- * compression_level <= 0 (else ZLZ4_ERR_UNSUPPORTED: HC linking is not built) and a workspace of
- * zlz4f_batch_compress_frame_workspace_ex(.., batch_flags) bytes, which adds one loadDict table (16 KiB) and a dictionary
- * descriptor per table entry (smaller: ZLZ4_ERR_INVALID_STATE); in each case nothing is launched. */
+ * compression_level <= 0 in THIS call (else ZLZ4_ERR_UNSUPPORTED: the HC levels are linked by
+ * zlz4f_batch_compress_frame_ex below) and a workspace of zlz4f_batch_compress_frame_workspace_ex(.., batch_flags) bytes,
+ * which adds one loadDict table (16 KiB) and a dictionary descriptor per table entry (smaller: ZLZ4_ERR_INVALID_STATE); in
+ * each case nothing is launched. */
 #define ZLZ4F_BATCH_LINK_BLOCKS 4u   /* (2u is unassigned: ZLZ4F_ERR_PARAMETER_INVALID) */
 size_t  zlz4f_batch_compress_frame_workspace_ex(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
                                                 uint32_t batch_flags);
@@ -544,6 +545,48 @@ int32_t zlz4f_batch_compress_frame(void *stream,
                                    int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
                                    const zlz4f_prefs *prefs, uint32_t batch_flags, void *d_workspace,
                                    size_t workspace_bytes);
+/* zlz4f_batch_compress_frame with linked frames at the HC levels (what `lz4 -9 -BD` and liblz4's LZ4F_* API with a level
+ * write).  Same arguments.  L = prefs->compression_level as the frame calls read it: <= 0 is the fast level, 1 becomes 9,
+ * above 12 becomes 12.
+ *   - without ZLZ4F_BATCH_LINK_BLOCKS, or with it at the fast level: zlz4f_batch_compress_frame -- the same bytes,
+ *     statuses and launch sequence (one implementation).
+ *   - with ZLZ4F_BATCH_LINK_BLOCKS and L in 3..9: block k of frame f is zlz4_compress_hc_using_dict(block, dict = frame
+ *     input[max(0, k * bs - 65536) .. k * bs], L) -- the dictionary is the INPUT in front of the block, also when the
+ *     previous block ends up stored.  Block 0 has an empty dictionary and carries compressHC's bytes; a one-block frame
+ *     is the HC frame of the plain call with the FLG block-independence bit clear.  Everything else as above: stored-block
+ *     rule (csize >= len), block and content checksums, content size, the compressFrameBound check per frame, header, end
+ *     mark, max_blocks / ZLZ4_ERR_INVALID_STATE per frame, the slot guarantee.  tail ++ block is a contiguous stretch of
+ *     d_src, so the HC kernels read it where it lies (the staged copy of zlz4_batch_compress_hc_using_dict is not made);
+ *     they may read a few bytes past a block's end inside d_src's allocation, as the plain HC levels do.  Nothing is
+ *     allocated or read back, the launch sequence is fixed (graph-capturable).
+ *   - with the flag and L in {2, 10, 11, 12}: ZLZ4_ERR_UNSUPPORTED, nothing launched (the levels
+ *     zlz4_batch_compress_hc_using_dict refuses: lz4mid and the price-based parse have no dictionary form here).
+ *   - the other refusals are the plain call's, in its order: unknown flag bits, block_mode != 0 with the flag,
+ *     ZLZ4F_BATCH_CONTENT_SIZE with prefs->content_size != 0 (ZLZ4F_ERR_PARAMETER_INVALID); then the device; then a
+ *     workspace that is too small, null or not 16-byte aligned (ZLZ4_ERR_INVALID_STATE).
+ * zlz4f_batch_compress_frame itself keeps answering ZLZ4_ERR_UNSUPPORTED for the flag with L > 0.
+ * Workspace: zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks, prefs, ZLZ4F_BATCH_LINK_BLOCKS) with L in 3..9 is
+ *     the block table and slots of zlz4f_batch_compress_frame_workspace at the fast level
+ *   + chunk x (12 x stride + 4 x bm_stride) bytes of links (u32), results (u64) and visited bits, where
+ *     stride = 65536 + block size, bm_stride = (stride / 32 + 1) rounded up to 4 words, and
+ *     chunk = min(max_blocks, 8192, 6 GiB / per-entry bytes) (at least 1): longer tables run in rounds
+ *   + 20 bytes of descriptors per table entry,
+ * each area rounded up to 256 bytes.  It holds no loadDict tables, no plain-HC workspace and no staged copy.  For every
+ * other combination of arguments the function returns what it returned before.
+ * The single-frame calls run one frame through zlz4f_batch_compress_frame_ex (max_blocks = ceil(src_len / bs), workspace
+ * from the device cache; their result is the batch call's for that frame) and synchronise.  With batch_flags 0 the answer
+ * is that of the call they are named after.  Their refusals are host arithmetic and come before the device check.
+ * zlz4f_compress_frame_ex is the way to write one linked frame, at any supported level, from HOST memory. */
+int32_t zlz4f_batch_compress_frame_ex(void *stream,
+                                      const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                      uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                                      int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                      const zlz4f_prefs *prefs, uint32_t batch_flags, void *d_workspace,
+                                      size_t workspace_bytes);
+int64_t zlz4f_compress_frame_device_ex(void *stream, const uint8_t *d_src, size_t src_len,
+                                       uint8_t *d_dst, size_t dst_cap, const zlz4f_prefs *prefs, uint32_t batch_flags);
+int64_t zlz4f_compress_frame_ex(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                const zlz4f_prefs *prefs, uint32_t batch_flags);
 size_t  zlz4f_batch_decompress_frame_workspace(uint32_t nframes, uint32_t max_blocks);
 int32_t zlz4f_batch_decompress_frame(void *stream,
                                      const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,

@@ -112,6 +112,9 @@ SYMBOLS = {
     "zlz4f_batch_decompress_frame_workspace": (_SZ, [_U32, _U32]),
     "zlz4f_batch_decompress_frame": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
     "zlz4f_batch_compress_frame_workspace_ex": (_SZ, [_U32, _U32, _PP, _U32]),
+    "zlz4f_batch_compress_frame_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _PP, _U32, _VP, _SZ]),
+    "zlz4f_compress_frame_device_ex": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _PP, _U32]),
+    "zlz4f_compress_frame_ex": (_I64, [_VP, _SZ, _VP, _SZ, _PP, _U32]),
     "zlz4f_batch_decompress_frame_workspace_ex": (_SZ, [_U32, _U32, _U32]),
     "zlz4f_batch_decompress_frame_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _VP, _SZ]),
     "zlz4f_decompress_frame_device_ex": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _U32]),
@@ -462,9 +465,14 @@ class lz4f:
         return lib().zlz4f_compress_frame_bound(src_size, C.byref(prefs) if prefs is not None else None)
 
     @staticmethod
-    def compressFrame(src, prefs=None, dst_cap=None):
+    def compressFrame(src, prefs=None, dst_cap=None, flags=0):
+        """flags 0: zlz4f_compress_frame.  Batch flags (lz4f.BATCH_LINK_BLOCKS, lz4f.BATCH_CONTENT_SIZE):
+        zlz4f_compress_frame_ex, one frame through the batch pipeline -- linked blocks at the fast level and at the HC
+        levels 3..9."""
         cap = lz4f.compressFrameBound(len(src), prefs) if dst_cap is None else dst_cap
-        return _run(lib().zlz4f_compress_frame, src, cap, C.byref(prefs) if prefs is not None else None)
+        if flags == 0:
+            return _run(lib().zlz4f_compress_frame, src, cap, C.byref(prefs) if prefs is not None else None)
+        return _run(lib().zlz4f_compress_frame_ex, src, cap, C.byref(prefs) if prefs is not None else None, flags)
 
     @staticmethod
     def decompressFrame(src, dst_cap, flags=0):
@@ -481,7 +489,11 @@ class lz4f:
 
     # device-resident variants (torch CUDA uint8 tensors in, frame / content size out)
     @staticmethod
-    def compressFrameDevice(d_src, d_dst, prefs=None):
+    def compressFrameDevice(d_src, d_dst, prefs=None, flags=0):
+        if flags:
+            return _check(lib().zlz4f_compress_frame_device_ex(_stream(), _ptr(d_src), d_src.numel(), _ptr(d_dst),
+                                                               d_dst.numel(), C.byref(prefs) if prefs is not None else None,
+                                                               flags))
         return _check(lib().zlz4f_compress_frame_device(_stream(), _ptr(d_src), d_src.numel(), _ptr(d_dst), d_dst.numel(),
                                                         C.byref(prefs) if prefs is not None else None))
 
@@ -524,7 +536,7 @@ class lz4f:
     @staticmethod
     def compressFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, prefs=None, batch_flags=0,
                            max_blocks=None, workspace=None):
-        """zlz4f_batch_compress_frame on torch CUDA tensors: d_src / d_dst uint8, src_off / src_len / dst_off / dst_cap
+        """zlz4f_batch_compress_frame_ex (the plain call, and linked blocks at the HC levels 3..9) on torch CUDA tensors: d_src / d_dst uint8, src_off / src_len / dst_off / dst_cap
         int64 (one entry per frame), result int64 (frame size or the frame's error code).  max_blocks defaults to the
         total block count of the lengths (read back once), workspace to a fresh buffer of the size the library asks for.
         Enqueued on the current stream; nothing is synchronised."""
@@ -537,9 +549,9 @@ class lz4f:
             workspace = torch.empty(max(1, lib().zlz4f_batch_compress_frame_workspace_ex(src_len.numel(), max_blocks, pp,
                                                                                          batch_flags)),
                                     dtype=torch.uint8, device=d_src.device)
-        _check(lib().zlz4f_batch_compress_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
-                                                _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(), max_blocks,
-                                                pp, batch_flags, _ptr(workspace), workspace.numel()))
+        _check(lib().zlz4f_batch_compress_frame_ex(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                   _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(), max_blocks,
+                                                   pp, batch_flags, _ptr(workspace), workspace.numel()))
 
     @staticmethod
     def decompressFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, max_blocks=None, workspace=None,

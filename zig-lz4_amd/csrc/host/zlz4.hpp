@@ -299,11 +299,27 @@ inline Result frameDecompressedSizeBatch(void *stream, const Frames &f, std::int
 }
 // linked-block frames (include/zlz4_amd.h; no counterpart in the reference).  DECODE_LINKED: a frame whose FLG declares
 // linked blocks is decoded in block order, block k against the 64 KiB of output in front of it (liblz4's default frames);
-// BATCH_LINK_BLOCKS: compressFrameBatch writes such frames (fast levels; workspace from compressFrameBatchWorkspaceEx).
+// BATCH_LINK_BLOCKS: compressFrameBatch writes such frames at the fast level, compressFrameBatchEx also at the HC levels
+// 3..9 (block k = compressHCUsingDict against the 64 KiB of input in front of it); workspace from
+// compressFrameBatchWorkspaceEx.
 constexpr std::uint32_t DECODE_LINKED = ZLZ4F_DECODE_LINKED;
 constexpr std::uint32_t BATCH_LINK_BLOCKS = ZLZ4F_BATCH_LINK_BLOCKS;
 inline std::size_t compressFrameBatchWorkspaceEx(std::uint32_t nframes, std::uint32_t max_blocks, const Preferences *p, std::uint32_t batch_flags) {
     return zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks, p, batch_flags);
+}
+inline Result compressFrameBatchEx(void *stream, const Frames &f, std::uint32_t max_blocks, const Preferences *p, std::uint32_t batch_flags,
+                                   void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_compress_frame_ex(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes,
+                                              max_blocks, p, batch_flags, ws, ws_bytes));
+}
+// one frame through compressFrameBatchEx (batch_flags 0: the answer of compressFrame / compressFrameDevice)
+inline Result compressFrameEx(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap, const Preferences *p,
+                              std::uint32_t batch_flags) {
+    return wrap(zlz4f_compress_frame_ex(src, n, dst, cap, p, batch_flags));
+}
+inline Result compressFrameDeviceEx(void *stream, const std::uint8_t *d_src, std::size_t n, std::uint8_t *d_dst, std::size_t cap,
+                                    const Preferences *p, std::uint32_t batch_flags) {
+    return wrap(zlz4f_compress_frame_device_ex(stream, d_src, n, d_dst, cap, p, batch_flags));
 }
 inline std::size_t decompressFrameBatchWorkspaceEx(std::uint32_t nframes, std::uint32_t max_blocks, std::uint32_t decode_flags) {
     return zlz4f_batch_decompress_frame_workspace_ex(nframes, max_blocks, decode_flags);

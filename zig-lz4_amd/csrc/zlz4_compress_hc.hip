@@ -1622,3 +1622,102 @@ extern "C" int zlz4_launch_compress_hc_dict(hipStream_t stream, const uint8_t *d
                                                             d_dict_off, d_dict_len, d_result, nblocks, max_in_len, max_attempts,
                                                             ws, p);
 }
+
+// ------------------------------------------------------------------ levels 3..9 on linked frame blocks
+// Block k of a linked frame is compressHCUsingDict(block_k, dict = the 64 KiB of input in front of it): V_k = tail ++ block
+// already lies contiguous in the caller's input, so nothing is staged.  k_bfl_hc_desc (zlz4_frame_linked.hip) has written
+// v_off (absolute in d_in), v_len and the pairs { v_len, start }; K1, K2s and K3 run on d_in in the instantiations
+// launch_hc_dict_chunked uses.  Rounds, side stream and result halves as there; V has no halves: K3 takes its literals
+// from the caller's input, which does not move.  max_n = 65536 + max_block_len > 65536: HBM links (u32 / u64) always.
+//
+// workspace: links u32[chunk * stride] | results u64[chunk * stride] | visited bits u32[chunk * bm_stride]
+namespace {
+struct HcLinkedPlan {
+    uint32_t max_n;
+    uint64_t stride, bm_stride, per_block;
+    uint32_t chunk;
+};
+HcLinkedPlan hc_linked_plan(uint32_t nblocks, uint32_t max_block_len) {
+    HcLinkedPlan p;
+    p.max_n = 65536u + (max_block_len < zlz4::kMaxInput ? max_block_len : zlz4::kMaxInput);
+    p.stride = ((uint64_t)p.max_n + 15u) & ~15ull;
+    p.bm_stride = ((p.stride + 31u) / 32u + 1u + 3u) & ~3ull;
+    p.per_block = p.stride * 12u + p.bm_stride * 4u;
+    uint64_t c = (6ull << 30) / p.per_block;                     // as hc_chunk: around 6 GiB at most
+    if (c < 1) c = 1;
+    if (c > kHcChunkBlocks) c = kHcChunkBlocks;
+    if (c > nblocks) c = nblocks ? nblocks : 1;
+    p.chunk = (uint32_t)c;
+    return p;
+}
+}  // namespace
+
+extern "C" size_t zlz4_hc_linked_workspace_bytes(uint32_t nblocks, uint32_t max_block_len) {
+    const HcLinkedPlan p = hc_linked_plan(nblocks, max_block_len);
+    return (size_t)((uint64_t)p.chunk * p.per_block);
+}
+
+// `level` is normalised (3..9) by the caller; ws is 16-byte aligned
+extern "C" int zlz4_launch_compress_hc_linked(hipStream_t stream, const uint8_t *d_in, const uint64_t *v_off,
+                                              const uint32_t *v_len, const uint32_t *v_pair, uint8_t *d_out,
+                                              const uint64_t *d_out_off, const uint32_t *d_out_cap, int64_t *d_result,
+                                              uint32_t nblocks, uint32_t max_block_len, int32_t level, void *ws,
+                                              size_t ws_bytes) {
+    using namespace zlz4;
+    typedef uint32_t T;
+    typedef uint64_t R;
+    if (nblocks == 0) return 0;
+    if (level < 3 || level > 9) return -8;
+    const HcLinkedPlan pl = hc_linked_plan(nblocks, max_block_len);
+    if (ws_bytes < (uint64_t)pl.chunk * pl.per_block) return -5;
+    const int32_t max_attempts = 1 << (level - 1);                              // 3 -> 4 ... 9 -> 256
+    const uint64_t stride = pl.stride;
+    const uint32_t chunk = pl.chunk;
+    uint8_t *body = static_cast<uint8_t *>(ws);
+    T *d_link = reinterpret_cast<T *>(body);
+    R *d_res = reinterpret_cast<R *>(body + (uint64_t)chunk * stride * sizeof(T));
+    uint32_t *d_bitmap = reinterpret_cast<uint32_t *>(body + (uint64_t)chunk * stride * (sizeof(T) + sizeof(R)));
+    const uint32_t np_max = pl.max_n - 11u;
+    const uint32_t k1_lds = kHcTableSize * 4u + 4096u * sizeof(T) + 16u;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hc_build_links<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1_lds);
+    constexpr uint32_t seg_len = 32u;
+    // ~2 start points per lane, counted over the block (nothing below `start` is a start point), as launch_hc_dict_chunked
+    const uint32_t nseg_max = (max_block_len < kMaxInput ? max_block_len : kMaxInput) / seg_len + 1u;
+    uint32_t threads = (nseg_max / 2u + 63u) & ~63u;
+    if (threads > 1024u) threads = 1024u;
+    if (threads < 256u) threads = 256u;
+    const uint32_t lk_bytes = ((np_max * 2u + 15u) & ~15u) + 16u;            // (unused by the HBM-link instantiation)
+    const uint32_t lds = 16u + 64u;                                          // 4 words (the last one is `start`), counted runs
+    auto kern = &k_hc_seg_search<4, false, true>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    HcSideStream *side = (chunk >= 2u && nblocks > chunk / 2u) ? hc_side_stream() : nullptr;
+    const uint32_t sub = side ? chunk / 2u : chunk;
+    uint32_t round = 0;
+    auto fail = [&]() -> int { if (side) (void)hipStreamSynchronize(side->st); return -7; };
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += sub, round++) {
+        const uint32_t nb = nblocks - b0 < sub ? nblocks - b0 : sub;
+        const uint32_t half = side ? (round & 1u) : 0u;
+        R *res = d_res + (uint64_t)half * sub * stride;
+        if (side && round >= 2u && hipStreamWaitEvent(stream, side->emitted[half], 0) != hipSuccess) return fail();   // K3 of round - 2 read this half of the results
+        if (hipMemsetAsync(res, 0, (size_t)nb * stride * sizeof(R), stream) != hipSuccess) return fail();
+        if (hipMemsetAsync(d_bitmap, 0, (size_t)nb * pl.bm_stride * 4u, stream) != hipSuccess) return fail();
+        hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), k1_lds, stream, d_in, v_off, v_len, d_link,
+                           stride, b0, nb, pl.max_n);
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(threads), lds, stream, d_in, v_off, v_pair, static_cast<const void *>(d_link),
+                           stride, static_cast<void *>(res), d_bitmap, pl.bm_stride, b0, nb, max_attempts, pl.max_n, lk_bytes,
+                           seg_len, 1);
+        hipStream_t emit_on = stream;
+        if (side) {
+            if (hipEventRecord(side->searched[half], stream) != hipSuccess ||
+                hipStreamWaitEvent(side->st, side->searched[half], 0) != hipSuccess) return fail();
+            emit_on = side->st;
+        }
+        hipLaunchKernelGGL((k_hc_parse_emit<R, true>), dim3((nb + 3u) / 4u), dim3(256), 0, emit_on, d_in, v_off, v_pair, d_out,
+                           d_out_off, d_out_cap, d_result, static_cast<const R *>(res), stride, b0, nb, pl.max_n);
+        if (side && hipEventRecord(side->emitted[half], side->st) != hipSuccess) return fail();
+    }
+    if (side)     // join
+        for (uint32_t k = 0; k < 2u && k < round; k++)
+            if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail();
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}

@@ -53,6 +53,12 @@ extern "C" int zlz4_launch_bfl_mask(hipStream_t, const void *frames, const uint3
 extern "C" int zlz4_launch_bfl_decode(hipStream_t, int write, void *frames, uint32_t, uint32_t, const uint8_t *, const uint64_t *,
                                       const uint32_t *, const uint32_t *, const uint32_t *, const int64_t *, uint8_t *,
                                       const uint64_t *, const uint64_t *, const uint64_t *, int64_t *);
+extern "C" int zlz4_launch_bfl_hc_desc(hipStream_t, const void *frames, uint32_t, uint32_t, const uint64_t *, const uint64_t *,
+                                       const uint32_t *, uint64_t *, uint32_t *, uint32_t *);
+extern "C" size_t zlz4_hc_linked_workspace_bytes(uint32_t nblocks, uint32_t max_block_len);
+extern "C" int zlz4_launch_compress_hc_linked(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, const uint32_t *,
+                                              uint8_t *, const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t,
+                                              int32_t, void *, size_t);
 extern "C" int zlz4_launch_bfl_dict_desc(hipStream_t, const void *frames, uint32_t, uint32_t, const uint64_t *,
                                          const uint64_t *, const uint32_t *, uint64_t *, uint32_t *);
 
@@ -1264,6 +1270,13 @@ uint64_t bf_slot(size_t bs) { return (zlz4_compress_bound(bs) + 15) & ~15ull; }
 
 // compress: frames | in_off out_off dst_off (u64) | in_len out_cap hdr cks (u32) | csize (i64) | slots | HC workspace
 // with ZLZ4F_BATCH_LINK_BLOCKS also: | loadDict tables | dict_off (u64) | dict_len (u32) | dictSize (i64)
+// with ZLZ4F_BATCH_LINK_BLOCKS at levels 3..9 instead: frames ... slots | links, results, visited bits of
+// zlz4_launch_compress_hc_linked | v_off (u64) | { v_len, start } (2 x u32) | v_len (u32)
+bool bf_hc_linked(const zlz4f_prefs &p, uint32_t batch_flags) {
+    const int32_t lv = bf_hc_level(p);
+    return (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) && lv >= 3 && lv <= 9;
+}
+
 BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t batch_flags = 0) {
     const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
     BatchLayout L;
@@ -1272,6 +1285,13 @@ BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs 
     for (int k = 0; k < 4; k++) L.add(m * sizeof(uint32_t));
     L.add(m * sizeof(int64_t));
     L.add(m * bf_slot(bs));
+    if (bf_hc_linked(p, batch_flags)) {
+        L.add(zlz4_hc_linked_workspace_bytes(max_blocks, (uint32_t)bs));
+        L.add(m * sizeof(uint64_t));
+        L.add(m * 2 * sizeof(uint32_t));
+        L.add(m * sizeof(uint32_t));
+        return L;
+    }
     L.add(bf_hc_level(p) ? zlz4_hc_workspace_bytes(max_blocks, (uint32_t)bs) : 0);
     if (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) {
         L.add(m * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
@@ -1334,21 +1354,35 @@ size_t zlz4f_batch_decompress_frame_workspace_ex(uint32_t nframes, uint32_t max_
     return bfd_layout(nframes, max_blocks, decode_flags).bytes;
 }
 
-int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
-                                   uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
-                                   uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
-                                   void *d_workspace, size_t workspace_bytes) {
-    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+}  // extern "C"
+
+namespace {
+
+// the refusals of both compress calls that need no device, in their order.  ex: zlz4f_batch_compress_frame_ex, which links
+// blocks at the HC levels 3..9 (the levels zlz4_batch_compress_hc_using_dict takes); the plain call refuses every HC level.
+int32_t bfc_refusal(const zlz4f_prefs &p, uint32_t batch_flags, bool ex) {
     if (batch_flags & ~(ZLZ4F_BATCH_CONTENT_SIZE | ZLZ4F_BATCH_LINK_BLOCKS)) return ZLZ4F_ERR_PARAMETER_INVALID;
+    const bool link = (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) != 0;
+    if ((batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) && p.content_size != 0) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (link && p.block_mode != 0) return ZLZ4F_ERR_PARAMETER_INVALID;     // FLG must declare what the blocks are
+    if (link && bf_hc_level(p) > 0 && !(ex && bf_hc_linked(p, batch_flags))) return ZLZ4_ERR_UNSUPPORTED;
+    return 0;
+}
+
+int32_t batch_compress_frame_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                  uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
+                                  uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                  void *d_workspace, size_t workspace_bytes, bool ex) {
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    const int32_t refused = bfc_refusal(p, batch_flags, ex);
+    if (refused != 0) return refused;
     const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
     const bool link = (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) != 0;
-    if (cs_from_len && p.content_size != 0) return ZLZ4F_ERR_PARAMETER_INVALID;
-    if (link && p.block_mode != 0) return ZLZ4F_ERR_PARAMETER_INVALID;     // FLG must declare what the blocks are
-    if (link && p.compression_level > 0) return ZLZ4_ERR_UNSUPPORTED;      // HC linking is not built
     if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
     const BatchLayout L = bfc_layout(nframes, max_blocks, p, batch_flags);
     if (nframes == 0) return 0;
     if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
+    if (ex && (reinterpret_cast<uintptr_t>(d_workspace) & 15u)) return ZLZ4_ERR_INVALID_STATE;
     hipStream_t st = (hipStream_t)stream_;
     uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
@@ -1373,7 +1407,18 @@ int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const ui
         hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, fr, nframes, max_blocks,
                            d_src_off, d_src_len, (uint64_t)bs, slot, in_off, in_len, out_off, out_cap, hdr);
         int rc;
-        if (link) {
+        if (link && hc_level != 0) {
+            // levels 3..9: block k is compressHCUsingDict against the same 64 KiB; V_k = tail ++ block lies contiguous in
+            // d_src, so the descriptors point the HC kernels at the input itself (no staged copy, no loadDict table)
+            uint64_t *v_off = reinterpret_cast<uint64_t *>(ws + L.off[11]);
+            uint32_t *v_pair = reinterpret_cast<uint32_t *>(ws + L.off[12]);
+            uint32_t *v_len = reinterpret_cast<uint32_t *>(ws + L.off[13]);
+            rc = zlz4_launch_bfl_hc_desc(st, fr, nframes, max_blocks, d_src_off, in_off, in_len, v_off, v_len, v_pair);
+            if (rc == 0)
+                rc = zlz4_launch_compress_hc_linked(st, d_src, v_off, v_len, v_pair, slots, out_off, out_cap, csize, max_blocks,
+                                                    (uint32_t)bs, hc_level, hc_ws, L.off[11] - L.off[10]);
+            if (rc != 0) rc = ZLZ4_ERR_DEVICE;
+        } else if (link) {
             // block k against the 64 KiB of input in front of it: descriptors, one loadDict table per entry, then the
             // dictionary compressor over the table (block 0 of a frame has an empty dictionary: compressDefault's bytes)
             uint32_t *tables = reinterpret_cast<uint32_t *>(ws + L.off[11]);
@@ -1405,6 +1450,87 @@ int32_t zlz4f_batch_compress_frame(void *stream_, const uint8_t *d_src, const ui
     hipLaunchKernelGGL(k_bfc_head_tail, dim3(bf_grid(nframes, 64)), dim3(64), 0, st, fr, nframes, max_blocks, p,
                        cs_from_len, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_result);
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+// One frame through zlz4f_batch_compress_frame_ex, device pointers: a batch of one with max_blocks = ceil(n / bs) and a
+// workspace from the device cache; synchronises `st` (as single_frame_ex of the decode side)
+int64_t single_compress_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
+                                 const zlz4f_prefs &p, uint32_t batch_flags) {
+    const size_t bs = block_size_of(p.block_size_id);
+    const uint64_t nb = (uint64_t)n / bs + (n % bs != 0);
+    if (nb > 0x7FFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
+    const uint32_t max_blocks = (uint32_t)nb;
+    zlz4host::DeviceCall dc(st);
+    const size_t ws = bfc_layout(1, max_blocks, p, batch_flags).bytes;
+    DevBuf d_meta(64, &dc), d_ws(ws, &dc);
+    if (!d_meta.p || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    struct Meta { uint64_t src_off, src_len, dst_off, dst_cap; int64_t result; } m = {0, (uint64_t)n, 0, (uint64_t)cap, 0};
+    static_assert(sizeof(Meta) <= 64, "meta");
+    auto *dm = d_meta.as<uint8_t>();
+    dc.launched();
+    if (hipMemcpyAsync(dm, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    int64_t *p_result = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
+    const int32_t rc = batch_compress_frame_impl(st, d_src, reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_off)),
+                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_len)), d_dst,
+                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_off)),
+                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_cap)), p_result, 1,
+                                                 max_blocks, &p, batch_flags, d_ws.p, ws, true);
+    if (rc != 0) return rc;
+    int64_t r = 0;
+    if (hipMemcpyAsync(&r, p_result, sizeof r, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
+    return r;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t zlz4f_batch_compress_frame(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                   uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
+                                   uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                   void *d_workspace, size_t workspace_bytes) {
+    return batch_compress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
+                                     max_blocks, prefs, batch_flags, d_workspace, workspace_bytes, false);
+}
+
+// zlz4f_batch_compress_frame, and ZLZ4F_BATCH_LINK_BLOCKS at the HC levels 3..9
+int32_t zlz4f_batch_compress_frame_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                      uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
+                                      uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                      void *d_workspace, size_t workspace_bytes) {
+    return batch_compress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
+                                     max_blocks, prefs, batch_flags, d_workspace, workspace_bytes, true);
+}
+
+// one frame through zlz4f_batch_compress_frame_ex (the result is the batch call's for that frame); synchronises `stream`
+int64_t zlz4f_compress_frame_device_ex(void *stream, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
+                                       const zlz4f_prefs *prefs, uint32_t batch_flags) {
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    const int32_t refused = bfc_refusal(p, batch_flags, true);
+    if (refused != 0) return refused;
+    if ((!d_src && n) || (!d_dst && cap)) return ZLZ4_ERR_INVALID_STATE;
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    return single_compress_frame_ex((hipStream_t)stream, d_src, n, d_dst, cap, p, batch_flags);
+}
+
+// host pointers: stage -> the device call -> copy the frame back
+int64_t zlz4f_compress_frame_ex(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const zlz4f_prefs *prefs,
+                                uint32_t batch_flags) {
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    const int32_t refused = bfc_refusal(p, batch_flags, true);
+    if (refused != 0) return refused;
+    if ((!src && n) || (!dst && cap)) return ZLZ4_ERR_INVALID_STATE;
+    const size_t bound = zlz4f_compress_frame_bound(n, &p);
+    if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
+    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    DevBuf d_src(n), d_dst(bound);
+    if (!d_src.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (n && hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    const int64_t r = single_compress_frame_ex(nullptr, d_src.as<uint8_t>(), n, d_dst.as<uint8_t>(), bound, p, batch_flags);
+    if (r < 0) return r;
+    if ((uint64_t)r > cap) return ZLZ4_ERR_DEVICE;
+    if (hipMemcpy(dst, d_dst.p, (size_t)r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return r;
 }
 
 }  // extern "C"

@@ -11,7 +11,9 @@
 // parallel decodes (length and capacity 0), so that the frame is decoded once.
 //
 // Compress (ZLZ4F_BATCH_LINK_BLOCKS): block k of a frame is compressFastUsingDict(block_k, dict = the 64 KiB of INPUT in
-// front of it); k_bfl_dict_desc writes the dictionary descriptors, the dictionary compressor does the rest.
+// front of it); k_bfl_dict_desc writes the dictionary descriptors, the dictionary compressor does the rest.  At HC levels
+// 3..9 (zlz4f_batch_compress_frame_ex) block k is compressHCUsingDict of the same pair: V_k = tail ++ block is a contiguous
+// stretch of the input, so k_bfl_hc_desc describes it where it lies and the HC kernels run on the caller's bytes.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -196,6 +198,36 @@ __global__ void k_bfl_dict_desc(const BFrame *__restrict__ fr, uint32_t nframes,
     }
 }
 
+// compress at HC levels, one lane per table entry: V_k = input[k * bs - D_k .. k * bs + n_k) with D_k = min(k * bs, 65536),
+// as the three HC kernels consume it (zlz4_launch_compress_hc_linked): v_off absolute in the source arena, v_len = D_k + n_k
+// for K1, the pair { v_len, start = D_k } for K2s and K3.  Entries without a block (length 0) get an empty V: K1 and K2s
+// skip it, K3 writes the result 0.
+__global__ void k_bfl_hc_desc(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                              const uint64_t *__restrict__ src_off, const uint64_t *__restrict__ in_off,
+                              const uint32_t *__restrict__ in_len, uint64_t *__restrict__ v_off, uint32_t *__restrict__ v_len,
+                              uint32_t *__restrict__ v_pair) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        uint64_t o = 0;
+        uint32_t len = 0, start = 0;
+        const uint32_t n = in_len[i];
+        if (n != 0) {
+            uint32_t lo = 0, hi = nframes;                             // the last frame whose base is <= i (k_bfc_desc)
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2u;
+                if (fr[mid].base <= i) lo = mid + 1u; else hi = mid;
+            }
+            const uint64_t before = in_off[i] - src_off[lo - 1u];      // k * bs
+            start = before < 65536u ? (uint32_t)before : 65536u;
+            o = in_off[i] - start;
+            len = start + n;
+        }
+        v_off[i] = o;
+        v_len[i] = len;
+        v_pair[2u * i] = len;
+        v_pair[2u * i + 1u] = start;
+    }
+}
+
 inline uint32_t grid_of(uint64_t items, uint32_t threads, uint32_t cap = 0xFFFFFFFFu) {
     const uint64_t g = (items + threads - 1) / threads;
     return g == 0 ? 1u : (g > cap ? cap : (uint32_t)g);
@@ -241,5 +273,14 @@ extern "C" int zlz4_launch_bfl_dict_desc(hipStream_t st, const void *frames, uin
     if (max_blocks == 0) return 0;
     hipLaunchKernelGGL(k_bfl_dict_desc, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
                        static_cast<const BFrame *>(frames), nframes, max_blocks, src_off, in_off, in_len, dict_off, dict_len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_bfl_hc_desc(hipStream_t st, const void *frames, uint32_t nframes, uint32_t max_blocks,
+                                       const uint64_t *src_off, const uint64_t *in_off, const uint32_t *in_len,
+                                       uint64_t *v_off, uint32_t *v_len, uint32_t *v_pair) {
+    if (max_blocks == 0) return 0;
+    hipLaunchKernelGGL(k_bfl_hc_desc, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
+                       static_cast<const BFrame *>(frames), nframes, max_blocks, src_off, in_off, in_len, v_off, v_len, v_pair);
     return hipGetLastError() == hipSuccess ? 0 : -7;
 }

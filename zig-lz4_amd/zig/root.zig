@@ -73,6 +73,9 @@ extern "c" fn zlz4f_frame_decompressed_size(src: [*]const u8, src_len: usize) i6
 extern "c" fn zlz4f_batch_frame_decompressed_size_workspace(nframes: u32, max_blocks: u32) usize;
 extern "c" fn zlz4f_batch_frame_decompressed_size(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_size: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_batch_compress_frame_workspace_ex(nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32) usize;
+extern "c" fn zlz4f_batch_compress_frame_ex(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_compress_frame_device_ex(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, batch_flags: u32) i64;
+extern "c" fn zlz4f_compress_frame_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, batch_flags: u32) i64;
 extern "c" fn zlz4f_batch_decompress_frame_workspace_ex(nframes: u32, max_blocks: u32, decode_flags: u32) usize;
 extern "c" fn zlz4f_batch_decompress_frame_ex(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, decode_flags: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_batch_frame_decompressed_size_workspace_ex(nframes: u32, max_blocks: u32, decode_flags: u32) usize;
@@ -563,7 +566,7 @@ pub const lz4f = struct {
             -107 => error.BlockChecksumInvalid, -108 => error.ReservedFlagSet, -109 => error.AllocationFailed,
             -110 => error.SrcSizeTooLarge, -111 => error.DstMaxSizeTooSmall, -112 => error.FrameHeaderIncomplete,
             -113 => error.FrameTypeUnknown, -114 => error.FrameSizeWrong, -116 => error.DecompressionFailed,
-            -117 => error.HeaderChecksumInvalid, -118 => error.ContentChecksumInvalid, -8 => error.Unsupported,
+            -117 => error.HeaderChecksumInvalid, -118 => error.ContentChecksumInvalid, -8 => error.Unsupported, -104 => error.ParameterInvalid,
             else => error.DeviceError,
         };
     }
@@ -626,8 +629,9 @@ pub const lz4f = struct {
     /// (size, or a negative code).  Device pointers; asynchronous on `stream`; `workspace` = device memory of the size the
     /// workspace function gives.
     pub const BATCH_CONTENT_SIZE: u32 = 1;
-    /// compressFrameBatch: block k against the 64 KiB of input in front of it (fast levels, block_mode linked; the
-    /// workspace comes from compressFrameBatchWorkspaceEx).  No counterpart in the reference.
+    /// compressFrameBatch: block k against the 64 KiB of input in front of it (fast level, block_mode linked; the
+    /// workspace comes from compressFrameBatchWorkspaceEx).  compressFrameBatchEx also links at the HC levels 3..9
+    /// (block k = compressHCUsingDict against that input).  No counterpart in the reference.
     pub const BATCH_LINK_BLOCKS: u32 = 4;
     /// decode flag of the ...Ex calls: a frame whose FLG declares linked blocks is decoded in block order, block k
     /// against the 64 KiB of output in front of it (liblz4's default frames).  The segment calls have no such form: a
@@ -668,6 +672,23 @@ pub const lz4f = struct {
     pub fn compressFrameBatchWorkspaceEx(nframes: u32, max_blocks: u32, prefs: ?Preferences, batch_flags: u32) usize {
         if (prefs) |p| { const c = toC(p); return zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks, &c, batch_flags); }
         return zlz4f_batch_compress_frame_workspace_ex(nframes, max_blocks, null, batch_flags);
+    }
+    /// compressFrameBatch, and BATCH_LINK_BLOCKS at the HC levels 3..9 (levels 2 and 10..12 with the flag: Unsupported)
+    pub fn compressFrameBatchEx(stream: ?*anyopaque, f: Frames, max_blocks: u32, prefs: ?Preferences, batch_flags: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        if (prefs) |p| {
+            const c = toC(p);
+            return mapBatch(zlz4f_batch_compress_frame_ex(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, &c, batch_flags, workspace, workspace_bytes));
+        }
+        return mapBatch(zlz4f_batch_compress_frame_ex(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, null, batch_flags, workspace, workspace_bytes));
+    }
+    /// one frame through compressFrameBatchEx; batch_flags 0: the answer of compressFrame / compressFrameDevice
+    pub fn compressFrameEx(src: []const u8, dst: []u8, prefs: ?Preferences, batch_flags: u32) Error!usize {
+        if (prefs) |p| { const c = toC(p); return mapFrame(zlz4f_compress_frame_ex(src.ptr, src.len, dst.ptr, dst.len, &c, batch_flags)); }
+        return mapFrame(zlz4f_compress_frame_ex(src.ptr, src.len, dst.ptr, dst.len, null, batch_flags));
+    }
+    pub fn compressFrameDeviceEx(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, prefs: ?Preferences, batch_flags: u32) Error!usize {
+        if (prefs) |p| { const c = toC(p); return mapFrame(zlz4f_compress_frame_device_ex(stream, d_src, src_len, d_dst, dst_cap, &c, batch_flags)); }
+        return mapFrame(zlz4f_compress_frame_device_ex(stream, d_src, src_len, d_dst, dst_cap, null, batch_flags));
     }
     pub fn decompressFrameBatchWorkspaceEx(nframes: u32, max_blocks: u32, decode_flags: u32) usize {
         return zlz4f_batch_decompress_frame_workspace_ex(nframes, max_blocks, decode_flags);
