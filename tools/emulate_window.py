@@ -4,7 +4,12 @@ Mirrors the window logic of zig-lz4_amd/csrc/zlz4_compress_fast.hip as it was wh
 (12-byte in-register compare, hand-over at lane 49, one flush per sequence): the later refinements of the kernel
 (48-byte compare levels, extension bytes in the run flush, precomputed fast-run steps, hand-over at lane 64) change
 how many sequences a window resolves and how they are emitted, not the bytes, so the emulator still produces the
-oracle's output and remains the place to try a change of the lane logic on the CPU first."""
+oracle's output and remains the place to try a change of the lane logic on the CPU first.
+
+The window's epilogue is written the way the kernel has it: the lanes strictly inside a match are one mask (cov_acc)
+that every flush and every immediate emission ORs its own lanes into (run_cover / imm_cover), `ins` comes from that
+mask without another pass over the match lanes, and the table is settled by one write per lane (commit_one_write).
+tests/test_window_commit_model_cpu.py checks both against the definitions they replaced."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -25,6 +30,37 @@ def extend(src, m_pos, m_cand, mlen, match_limit):
     while ip < match_limit and src[ip] == src[mt]:
         ip += 1; mt += 1; mlen += 1
     return mlen
+
+def run_cover(mm_run, v_end):
+    """ballot(cov) of a flush: the lanes strictly inside a match of the run mm_run (lane i: the nearest match lane of the
+    run below it ends above it).  v_end[j] = anchor lane after a match at lane j (may be >= 64)."""
+    m, rest = 0, mm_run
+    while rest:
+        j = ctz(rest); rest &= rest - 1
+        top = min(v_end[j], ctz(rest) + 1 if rest else 64, 64)      # lanes j+1 .. top-1 (the next match lane looks at j too)
+        if top > j + 1: m |= ((1 << top) - 1) & ~((2 << j) - 1)
+    return m
+
+def imm_cover(j, e):
+    """lanes j+1 .. e-1 of a match at lane j that was emitted immediately (e = its anchor lane, may be >= 64)"""
+    return ((1 << min(e, 64)) - 1) & ~((2 << j) - 1)
+
+def ins_mask(wrmask, cov_acc, f_end):
+    """lanes the serial loop put(): written at all, below the frontier, not strictly inside a match"""
+    return wrmask & ~cov_acc & ((1 << min(f_end, 64)) - 1)
+
+def commit_one_write(table, h, mine, old, wr, grp, ins):
+    """Leave `table` as the serial loop would have, one write per lane: with gi = grp & ins, a written lane of a group
+    without an `ins` lane puts its old value back, the highest `ins` lane of a group stores its own entry, every other
+    lane writes nothing.  Returns [(lane, slot, value)], the writes in lane order (all lanes of a group read the same
+    old value before any put, so writes to one slot carry one value)."""
+    writes = []
+    for i in range(64):
+        gi = grp[i] & ins
+        if wr[i] and gi == 0: writes.append((i, h[i], old[i]))
+        elif (ins >> i) & 1 and (gi >> i) >> 1 == 0: writes.append((i, h[i], mine[i]))
+    for _, slot, v in writes: table[slot] = v
+    return writes
 
 def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
     n = len(src)
@@ -79,7 +115,7 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
             Sx = [first_ge(slow, i) for i in range(64)]
             v_end = [i + 4 + mlo[i] for i in range(64)]
             E = [v_end[J[i] & 63] for i in range(64)]
-            f, a, nseq, covered = 1, 0, 0, 0
+            f, a, nseq, cov_acc = 1, 0, 0, 0
             continue_generic = False
             tight = dst_len - op < 512
             while True:
@@ -93,7 +129,7 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                 if mm_run:
                     # ---- vector flush of the run ----
                     jlast = msb(mm_run)
-                    litmask = 0; cov_run = 0
+                    litmask = 0
                     info = []
                     for i in range(64):
                         mb = mm_run & ((1 << i) - 1)
@@ -103,7 +139,6 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                         is_m = (mm_run >> i) & 1
                         is_lit = i >= a0 and i < jlast and not cov and not is_m
                         if is_lit: litmask |= 1 << i
-                        if cov: cov_run |= 1 << i
                         info.append((pend, is_m, is_lit))
                     for i in range(64):
                         pend, is_m, is_lit = info[i]
@@ -117,7 +152,7 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                             out[o2:o2 + 2] = ((pos[i] - old[i]) & 0xFFFF).to_bytes(2, "little")
                             if trace: print("  fast seq A=%d j=%d cand=%d lit=%d mlen=%d" % (A, i, old[i], lit_k, mlo[i]))
                     op = op0 + 3 * bin(mm_run).count("1") + bin(litmask).count("1")
-                    covered |= cov_run
+                    cov_acc |= run_cover(mm_run, v_end)
                     nseq += bin(mm_run).count("1")
                 if f >= 64 or (f >= 49 and nseq > 0):
                     if nseq == 0: continue_generic = True
@@ -130,7 +165,7 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                     break
                 pm = 0
                 if (nsing >> x) & 1:
-                    pm = grp[x] & wrmask & ~covered & ((1 << x) - 1)
+                    pm = grp[x] & wrmask & ~cov_acc & ((1 << x) - 1)      # (no run is pending here)
                 if pm:
                     pr = msb(pm); ok = fwd[pr][0] == fwd[x][0]; m_cand = A + pr; c = fwd[pr]
                 else:
@@ -146,20 +181,15 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                 if trace: print("  slow seq A=%d j=%d cand=%d lit=%d mlen=%d" % (A, j, m_cand, lit, mlen))
                 emit_general(A + a, lit, m_pos - m_cand, mlen)
                 e = j + 4 + mlen
-                hi = min(e, 64)
-                covered |= ((1 << hi) - 1) & ~((2 << j) - 1)
+                cov_acc |= imm_cover(j, e)
                 nseq += 1
                 a = e
                 if e >= 64: break
                 f = e + 1
             anchor = A + a
-            inside = [bool((covered >> i) & 1) for i in range(64)]
             f_end = 64 if continue_generic else (64 if a >= 64 else a + 1)
-            ins = sum(1 << i for i in range(64) if wr[i] and i < f_end and not inside[i])
-            for i in range(64):
-                if wr[i] and not (ins >> i) & 1: table[h[i]] = old[i]
-            for i in range(64):
-                if (ins >> i) & 1 and (grp[i] & ins & ~((1 << i) - 1) & ~(1 << i)) == 0: table[h[i]] = pos[i]
+            ins = ins_mask(wrmask, cov_acc, f_end)
+            commit_one_write(table, h, pos, old, wr, grp, ins)
             if not continue_generic:
                 if anchor < L: has_ins, F0 = True, anchor + 1
                 else: has_ins, F0 = False, L

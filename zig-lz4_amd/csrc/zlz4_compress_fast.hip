@@ -431,19 +431,23 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 uint32_t f = 1;          // next lane to probe
                 uint32_t a = 0;          // lane of the current anchor
                 uint32_t nseq = 0;
-                uint64_t covered_x = 0;  // lanes strictly inside a match that was emitted immediately (Q6: never put())
-                uint64_t mm_win = 0;     // match lanes of the runs already flushed
+                // lanes strictly inside a match that has been emitted (Q6: never put()): every flush and every immediate
+                // emission ORs in the lanes of its own matches.  Runs and immediate sequences are consecutive lane ranges and
+                // a match's end lane is final once it is emitted, so no later event changes what an earlier one covered.
+                uint64_t cov_acc = 0;
                 bool continue_generic = false;
                 // with less than 512 bytes of room left every sequence takes the exact step, which checks the capacity
                 const bool tight = dst_len - op < 512u;
                 uint32_t a0 = a, op0 = op;   // anchor lane / output position at the start of the pending (unflushed) run
                 uint64_t mm_run = 0;         // match lanes of the pending run
-                // lanes strictly inside a match so far (never put(), Q6): from the match lanes and their end lanes
+                // lanes strictly inside a match so far, for an exact step: the emitted ones, and those of the pending run from
+                // its match lanes and their end lanes (mm_run is wave-uniform: shfl sees every lane, see zlz4_device.hpp)
                 auto covered_now = [&]() -> uint64_t {
-                    const uint64_t mb = (mm_win | mm_run) & lanes_below;
+                    if (mm_run == 0) return cov_acc;
+                    const uint64_t mb = mm_run & lanes_below;
                     const uint32_t pj = mb ? 63u - (uint32_t)__builtin_clzll(mb) : 0u;
-                    const uint32_t pe = shfl(v_end, pj);                // (unconditional: see zlz4_device.hpp)
-                    return covered_x | ballot(mb != 0 && lane < pe);
+                    const uint32_t pe = shfl(v_end, pj);
+                    return cov_acc | ballot(mb != 0 && lane < pe);
                 };
                 // flush of the pending run: every offset from popcounts, three stores for all its sequences
                 auto flush_run = [&]() {
@@ -481,7 +485,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     }
                     const uint32_t nm = (uint32_t)__popcll(mm_run);
                     op = op0 + 3u * nm + (uint32_t)__popcll(litmask) + (uint32_t)__popcll(extm) + (uint32_t)__popcll(lextm);
-                    mm_win |= mm_run;
+                    cov_acc |= ballot(cov);
                     mm_run = 0;
                     STAMP(10);
                 };
@@ -608,7 +612,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     op = (uint32_t)seq_end;
                     {
                         const uint64_t upto_e = e >= 64u ? ~0ull : (1ull << e) - 1ull;
-                        covered_x |= upto_e & ~((2ull << j) - 1ull);        // lanes j+1 .. e-1
+                        cov_acc |= upto_e & ~((2ull << j) - 1ull);          // lanes j+1 .. e-1
                     }
                     nseq++;
                     a = e;
@@ -629,17 +633,18 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 if (mm_run && !failed) flush_run();
                 anchor = A + a;
                 STAMP(4);
-                // lanes the serial loop put(): below the frontier and not strictly inside a match
+                // lanes the serial loop put(): below the frontier and not strictly inside a match (no run is pending here)
                 const uint32_t f_end = continue_generic ? 64u : (a >= 64u ? 64u : a + 1u);
-                const uint64_t ins = wrmask & ~covered_now() & (f_end >= 64u ? ~0ull : (1ull << f_end) - 1ull);
+                const uint64_t ins = wrmask & ~cov_acc & (f_end >= 64u ? ~0ull : (1ull << f_end) - 1ull);
                 if (failed) break;
                 // ---- leave the table as the serial loop would have ----
-                if (wr && !(ins & lane_bit)) table[h] = (T)old_e;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                if ((ins & lane_bit) && (grp & ins & ~lanes_below & ~lane_bit) == 0) {
-                    table[h] = (T)mine;
-                    if (kTag == 1) tags[h] = (uint8_t)tg;               // (the speculative put left the old tag in place)
-                }
+                // One write per lane: the slot's final value depends only on gi, the group's lanes in `ins`.  None: every
+                // written lane of the group puts the old value back (they all read it before any put, so equal addresses
+                // carry equal values).  Else the last `ins` lane of the group stores its entry and the others write nothing.
+                const uint64_t gi = grp & ins;
+                const bool put_mine = (ins & lane_bit) && (gi & ~lanes_below & ~lane_bit) == 0;
+                if (put_mine || (wr && gi == 0)) table[h] = (T)(put_mine ? mine : old_e);
+                if (kTag == 1 && put_mine) tags[h] = (uint8_t)tg;       // (the speculative put left the old tag in place)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 STAMP(5);
                 moved = anchor != A;
@@ -647,7 +652,8 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 if (next_win) {
                     has_ins = true;
                     F0 = anchor + 1u;
-                    if (++guard > src_size) { failed = true; break; }       // unreachable; never spin on the GPU
+                    // (no guard here: next_win implies a != 0, so this window moved the anchor forward, and
+                    //  A + a + 192 < L bounds the windows of one run; the outer loop's guard covers everything else)
                     continue;
                 }
                 break;
