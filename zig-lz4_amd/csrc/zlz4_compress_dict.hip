@@ -211,27 +211,34 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                 // pre-window candidates: the old table value passes `match > 0`, `match < ip` and the distance test
                 // (:656-658); its bytes (dictionary or record) are gathered once for the whole window, right away, so
                 // that the latency overlaps the speculative put / read-back below
-                const bool old_ok = wr && old > 0 && old < pos && (old + kMaxDist >= pos);
+                // (written mask by mask: see the note at `losers` below)
+                const uint64_t wrmask = has_ins ? ~0ull : ~1ull;        // wr is wave-uniform: all lanes or all but lane 0
+                const uint64_t okm = wrmask & ballot(old > 0) & ballot(old < pos) & ballot(old + kMaxDist >= pos);
+                const bool old_ok = in_mask(okm);
                 u32x4 cold = {0, 0, 0, 0};
                 if (old_ok) cold = V.ld128v(old);
                 u32x4 f2 = {0, 0, 0, 0}, c2 = f2, f3 = f2, c3 = f2;
                 if (wr) table[h] = (T)mine;                             // :661 (speculative)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 if (wr) rb = table[h];
-                uint64_t losers = ballot(wr && rb != mine);
+                // (a ballot is lowered to its compare only when its argument is one compare; a compound predicate goes
+                //  through v_cndmask and v_cmp_ne again.  So compound predicates are scalar combinations of one-compare
+                //  ballots, and a lane's own bit of such a mask is in_mask().)
+                uint64_t losers = wrmask & ballot(rb != mine);
                 uint64_t grp = lane_bit;
                 while (losers) {                                        // one round per duplicate-hash group
                     const uint32_t l = first_lane(losers);
                     const uint32_t hh = rdlane(h, l);
-                    const uint64_t same = ballot(wr && h == hh);
-                    if (wr && h == hh) grp = same;
+                    const uint64_t same = wrmask & ballot(h == hh);
+                    if (in_mask(same)) grp = same;
                     losers &= ~same;
                 }
 
                 // What a probe at lane i finds if its table slot still holds the pre-window value: validity
                 // (:656-659), the first 12 bytes of forward extension (:704-712) and the offset.  For a lane
                 // whose hash is unique in the window this does not depend on the parse at all.
-                const bool vo = old_ok && cold.x == fwd.x;
+                const uint64_t vom = okm & ballot(cold.x == fwd.x);
+                const bool vo = in_mask(vom);
                 uint32_t mlo;
                 {
                     // selects only (a nested ?: chain compiles to exec-mask branches, i.e. scalar instructions)
@@ -242,7 +249,7 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                 }
                 // second level: the few lanes whose 16 bytes all match compare 16 more (matches of 16..31 bytes are a
                 // fifth of all sequences on text; without this each of them costs an exact step and its own emission)
-                const bool need2 = vo && mlo == 12u;
+                const bool need2 = in_mask(vom & ballot(mlo == 12u));
                 if (need2) {                                  // (all loads in one round trip)
                     f2 = ld128(V.srcv + pos + 16u); f3 = ld128(V.srcv + pos + 32u);
                     c2 = V.ld128v(old + 16u); c3 = V.ld128v(old + 32u);
@@ -254,12 +261,12 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                 // a lane whose hash no EARLIER lane of the window shares reads the pre-window value whatever the parse does --
                 // the only lane of its hash, or the first of a duplicate group (the first of a group would otherwise take
                 // an exact step like the others, find no in-window candidate and fall back to the same registers)
-                const bool single = (grp & lanes_below) == 0;
-                const bool oldfast = vo && mlo < 44u;         // result against the pre-window value is complete in registers
-                const uint64_t wrmask = ballot(wr);
-                const uint64_t cfast = ballot(oldfast);                                       // usable if no in-window put precedes
-                const uint64_t slow = ballot(wr && ((!single && !oldfast) || (vo && mlo >= 44u)));   // exact step if reached
-                const uint64_t nsing = ballot(wr && !single);
+                const uint64_t singm = ballot(lane_rank(grp) == 0u);   // (grp & lanes_below) == 0
+                const uint64_t lt44 = ballot(mlo < 44u);
+                const uint64_t cfast = vom & lt44;            // oldfast: the result against the pre-window value is complete in
+                                                              // registers; usable if no in-window put precedes
+                const uint64_t nsing = wrmask & ~singm;
+                const uint64_t slow = (nsing & ~cfast) | (vom & ~lt44);   // wr && ((!single && !oldfast) || (vo && mlo >= 44)): exact step if reached
                 // per lane i: J = first cfast lane >= i, S = first slow lane >= i (64 = none),
                 // E = lane of the new anchor if the search that starts at i ends with the match at J
                 uint32_t J, S;
@@ -317,22 +324,24 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                     const uint32_t pj = has_prev ? 63u - (uint32_t)__builtin_clzll(mb) : 0u;   // previous match lane
                     const uint32_t pend_all = shfl(v_end, pj);          // (unconditional: see zlz4_device.hpp)
                     const uint32_t pend = has_prev ? pend_all : a0;     // first lane of my literal run
-                    const bool cov = has_prev && lane < pend_all;       // strictly inside a match of this run
-                    const bool is_m = (mm_run & lane_bit) != 0;
+                    const uint64_t covm = ballot(mb != 0) & ballot(lane < pend_all);   // strictly inside a match of this run
+                    const bool is_m = in_mask(mm_run);
                     const uint32_t jlast = 63u - (uint32_t)__builtin_clzll(mm_run);
-                    const bool is_lit = lane >= a0 && lane < jlast && !cov && !is_m;
-                    const uint64_t litmask = ballot(is_lit);
-                    const uint64_t extm = ballot(is_m && mlo_e >= 15u);                 // matches with one length-extension byte (:714-728)
+                    // literals: lanes from a0 on that are neither past the last match lane, nor covered, nor a match lane
+                    const uint64_t litmask = ballot(lane >= a0) & ~(ballot(lane >= jlast) | covm | mm_run);
+                    const bool is_lit = in_mask(litmask);
+                    const uint64_t extm = mm_run & ballot(mlo_e >= 15u);                // matches with one length-extension byte (:714-728)
                     // literal runs of 15..63 bytes carry one extension byte too (:673-687): a lane's sequence is the
                     // first match lane at or above it, its literal count that lane minus the start of the run
                     const uint64_t at_or_above = mm_run & ~lanes_below;
                     const uint32_t my_m = at_or_above ? (uint32_t)__builtin_ctzll(at_or_above) : lane;
-                    const uint32_t own_l = (my_m - pend >= 15u) ? 1u : 0u;
-                    const uint64_t lextm = ballot(is_m && own_l != 0u);
-                    const uint32_t k = (uint32_t)__popcll(mb);                          // sequences completed before me
-                    const uint32_t lb = (uint32_t)__popcll(litmask & lanes_below);      // literal bytes before me
-                    const uint32_t o1 = op0 + 3u * k + lb + 1u + (uint32_t)__popcll(extm & lanes_below) +
-                                        (uint32_t)__popcll(lextm & lanes_below) + own_l;
+                    const uint64_t ownm = ballot(my_m - pend >= 15u);
+                    const uint32_t own_l = in_mask(ownm) ? 1u : 0u;
+                    const uint64_t lextm = mm_run & ownm;
+                    // (prefix popcounts as lane_rank: v_mbcnt_lo / _hi)
+                    const uint32_t k = lane_rank(mm_run);                               // sequences completed before me
+                    const uint32_t lb = lane_rank(litmask);                             // literal bytes before me
+                    const uint32_t o1 = op0 + 3u * k + lb + 1u + lane_rank(extm) + lane_rank(lextm) + own_l;
                     if (is_lit) dst[o1] = (uint8_t)fwd.x;               // literals (:691)
                     if (is_m) {
                         const uint32_t lit_k = lane - pend;             // :668
@@ -345,7 +354,7 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                     }
                     const uint32_t nm = (uint32_t)__popcll(mm_run);
                     op = op0 + 3u * nm + (uint32_t)__popcll(litmask) + (uint32_t)__popcll(extm) + (uint32_t)__popcll(lextm);
-                    cov_acc |= ballot(cov);
+                    cov_acc |= covm;
                     mm_run = 0;
                 };
                 for (;;) {
@@ -490,7 +499,7 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                 // written lane of the group puts the old value back (they all read it before any put, so equal addresses
                 // carry equal values).  Else the last `ins` lane of the group stores its entry and the others write nothing.
                 const uint64_t gi = grp & ins;
-                const bool put_mine = (ins & lane_bit) && (gi & ~lanes_below & ~lane_bit) == 0;
+                const bool put_mine = in_mask(ins) && (gi & ~lanes_below & ~lane_bit) == 0;
                 if (put_mine || (wr && gi == 0)) table[h] = (T)(put_mine ? mine : old);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 moved = anchor != A;

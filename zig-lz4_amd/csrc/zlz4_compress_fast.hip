@@ -225,9 +225,14 @@ __global__ __launch_bounds__(256) void k_compress_fast(
         uint32_t ring_lim = 0;
         if constexpr (kRing) asm volatile("v_mov_b32 %0, %1" : "=v"(ring_lim) : "s"(src_size - 4u));
         auto ring_q = [&](uint32_t q) -> uint32_t { return q < ring_lim ? q : ring_lim; };
-        // W: lane l = the dword at src + (A & ~3) + 4l, i.e. the window's bytes from 4-byte-aligned A on (one select and
-        // one ds_bpermute over r0 / r1; moves or reloads the ring first)
-        auto ring_win = [&](uint32_t A) -> uint32_t {
+        // The window's dwords come out of the ring in one hop.  The window register W of A used to be a permute of its
+        // own: W[i] = lane (s0 + i) & 63 of sel, sel = lane >= s0 ? r0 : r1, s0 = (A - rbase) >> 2 -- the select depends on
+        // the source lane only (lanes below s0 hold the dwords that wrapped into r1).  So the dword a lane wants,
+        // W[jw + k], is sel[(s0 + jw + k) & 63]: the forward permutes read sel directly, and the window pays one
+        // ds_bpermute and one dependent LDS wait less.  ring_sel moves or reloads the ring first and yields the snapshot
+        // sel (a copy: it stays valid when the ring moves later) and ja, this lane's permute address of W[jw]:
+        // 4 * ((s0 + jw) & 63), jw = ((A & 3) + lane) >> 2.
+        auto ring_sel = [&](uint32_t A, uint32_t &ja) -> uint32_t {
             uint32_t rel = rfl(A - rpos);                               // A - rbase (lane 0)
             if (rel >= 256u) {
                 // The ring's loads are issued by hand, move and reload in one statement: the compiler carries the ring
@@ -258,28 +263,39 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 rpos = nb;
                 rel = reload ? A & 127u : rel - 256u;
             }
-            const uint32_t s0 = rel >> 2;
-            return shfl(lane >= s0 ? r0 : r1, (s0 + lane) & 63u);
+            // (rel & ~3) = 4 s0 < 256 and ((A & 3) + lane) & ~3 = 4 jw <= 64: the byte keeps the lane index modulo 64
+            ja = ((rel & ~3u) + (((A & 3u) + lane) & ~3u)) & 0xFFu;
+            return lane >= (rel >> 2) ? r0 : r1;
         };
-        // dwords k0 .. k0+n-1 of the bytes at A + lane (+ 4 k), from the window register W of A
-        auto win_bytes = [&](uint32_t W, uint32_t A, uint32_t k0, uint32_t *out, uint32_t n) {
-            const uint32_t o = (A & 3u) + lane, jw = (o >> 2) + k0;   // jw + n <= 16 + 4 + 8 < 64
-            uint32_t lo = shfl(W, jw);
-            for (uint32_t k = 0; k < n; k++) {
-                const uint32_t hi = shfl(W, jw + k + 1u);
-                out[k] = __builtin_amdgcn_alignbyte(hi, lo, o & 3u);
-                lo = hi;
-            }
+        // W[jw + K] of the snapshot (K <= 12).  The lane index is taken modulo 64 here, in the low byte of the address
+        // (add_wrap_byte); nothing is left to what the instruction's offset field does past lane 63.
+#define ZLZ4_SEL_DWORD(sel, ja, K) ((uint32_t)__builtin_amdgcn_ds_bpermute((int)add_wrap_byte<4u * (K)>(ja), (int)(sel)))
+        // the 16 bytes at A + lane; hi4 = W[jw + 4], the last dword fetched, which the second compare level starts from
+        auto ring_fwd = [&](uint32_t sel, uint32_t ja, uint32_t A, uint32_t &hi4) -> u32x4 {
+            const uint32_t sh = (A + lane) & 3u;
+            const uint32_t w0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)ja, (int)sel);
+            const uint32_t w1 = ZLZ4_SEL_DWORD(sel, ja, 1), w2 = ZLZ4_SEL_DWORD(sel, ja, 2), w3 = ZLZ4_SEL_DWORD(sel, ja, 3);
+            hi4 = ZLZ4_SEL_DWORD(sel, ja, 4);
+            return u32x4{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                         __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(hi4, w3, sh)};
         };
-        auto ring_fwd = [&](uint32_t W, uint32_t A) -> u32x4 {
-            uint32_t d[4];
-            win_bytes(W, A, 0u, d, 4u);
-            return u32x4{d[0], d[1], d[2], d[3]};
+        // bytes 16..47 at A + lane: dwords jw + 5 .. jw + 12 of the snapshot behind the kept hi4 (jw + 12 <= 28).  The
+        // second level used to fetch W[jw + 4] again.
+        auto ring_fwd2 = [&](uint32_t sel, uint32_t ja, uint32_t A, uint32_t hi4, u32x4 &f2, u32x4 &f3) {
+            const uint32_t sh = (A + lane) & 3u;
+            const uint32_t w5 = ZLZ4_SEL_DWORD(sel, ja, 5), w6 = ZLZ4_SEL_DWORD(sel, ja, 6), w7 = ZLZ4_SEL_DWORD(sel, ja, 7);
+            const uint32_t w8 = ZLZ4_SEL_DWORD(sel, ja, 8), w9 = ZLZ4_SEL_DWORD(sel, ja, 9), w10 = ZLZ4_SEL_DWORD(sel, ja, 10);
+            const uint32_t w11 = ZLZ4_SEL_DWORD(sel, ja, 11), w12 = ZLZ4_SEL_DWORD(sel, ja, 12);
+            f2 = u32x4{__builtin_amdgcn_alignbyte(w5, hi4, sh), __builtin_amdgcn_alignbyte(w6, w5, sh),
+                       __builtin_amdgcn_alignbyte(w7, w6, sh), __builtin_amdgcn_alignbyte(w8, w7, sh)};
+            f3 = u32x4{__builtin_amdgcn_alignbyte(w9, w8, sh), __builtin_amdgcn_alignbyte(w10, w9, sh),
+                       __builtin_amdgcn_alignbyte(w11, w10, sh), __builtin_amdgcn_alignbyte(w12, w11, sh)};
         };
+#undef ZLZ4_SEL_DWORD
         // forward bytes of the next window, taken from the ring (u32: loaded) as soon as its anchor is known (before the
         // emission and the table fix-up of the current window, which hide the permutes)
         u32x4 fwd_pf = {0, 0, 0, 0};
-        uint32_t w_pf = 0;
+        uint32_t sel_pf = 0, ja_pf = 0, hi4_pf = 0;                     // the snapshot the second level reads on
         uint32_t pf_anchor = 0xFFFFFFFFu;
         while (F0 < L) {                                                // :320
             if (++guard > src_size) { failed = true; break; }           // unreachable; never spin on the GPU
@@ -304,10 +320,10 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 const uint32_t pos = A + lane;
                 const bool wr = has_ins || lane > 0;                    // position 0 is never inserted (Q1)
                 if (kRing && pf_anchor != A) {
-                    w_pf = ring_win(A);
-                    fwd_pf = ring_fwd(w_pf, A);
+                    sel_pf = ring_sel(A, ja_pf);
+                    fwd_pf = ring_fwd(sel_pf, ja_pf, A, hi4_pf);
                 }
-                const uint32_t W = w_pf;
+                const uint32_t sel = sel_pf, ja = ja_pf, hi4 = hi4_pf;
                 const u32x4 fwd = (kRing || pf_anchor == A) ? fwd_pf : ld128(src + pos);
                 const uint32_t prod = fwd.x * kHashMul;
                 const uint32_t h = prod >> 20;                          // :341
@@ -325,7 +341,12 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 // pre-window candidates: the old table value passes `match > 0`, `match < ip` (always, unless seeded) and
                 // the distance test (:345-347); its bytes are gathered once for the whole window.  The gather is
                 // issued right away so that its latency overlaps the speculative put / read-back below.
-                const bool old_ok = wr && old > 0 && (!kSeed || old < pos) && (old + kMaxDist >= pos) && (kTag == 0 || told == tg);
+                // (written mask by mask: see the note at `losers` below)
+                const uint64_t wrmask = has_ins ? ~0ull : ~1ull;        // wr is wave-uniform: all lanes or all but lane 0
+                uint64_t okm = wrmask & ballot(old > 0) & ballot(old + kMaxDist >= pos);
+                if (kSeed) okm &= ballot(old < pos);
+                if (kTag != 0) okm &= ballot(told == tg);
+                const bool old_ok = in_mask(okm);
                 u32x4 cold = {0, 0, 0, 0};
                 if (old_ok) cold = ld128(src + old);
                 // the second compare level (bytes 16..47, below) is a round trip of its own behind the first -- unless it is
@@ -348,13 +369,16 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 if (wr) table[h] = (T)mine;                             // :350 (speculative)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 if (wr) rb = table[h];
-                uint64_t losers = ballot(wr && rb != mine);
+                // (a ballot is lowered to its compare only when its argument is one compare; a compound predicate goes
+                //  through v_cndmask and v_cmp_ne again.  So compound predicates are scalar combinations of one-compare
+                //  ballots, and a lane's own bit of such a mask is in_mask().)
+                uint64_t losers = wrmask & ballot(rb != mine);
                 uint64_t grp = lane_bit;
                 while (losers) {                                        // one round per duplicate-hash group
                     const uint32_t l = first_lane(losers);
                     const uint32_t hh = rdlane(h, l);
-                    const uint64_t same = ballot(wr && h == hh);
-                    if (wr && h == hh) grp = same;
+                    const uint64_t same = wrmask & ballot(h == hh);
+                    if (in_mask(same)) grp = same;
                     losers &= ~same;
                 }
                 STAMP(2);
@@ -362,7 +386,8 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 // What a probe at lane i finds if its table slot still holds the pre-window value: validity
                 // (:345-348), the first 12 bytes of forward extension (:401-413) and the offset.  For a lane
                 // whose hash is unique in the window this does not depend on the parse at all.
-                const bool vo = old_ok && cold.x == fwd.x;
+                const uint64_t vom = okm & ballot(cold.x == fwd.x);
+                const bool vo = in_mask(vom);
                 uint32_t mlo;
                 {
                     // selects only (a nested ?: chain compiles to exec-mask branches, i.e. scalar instructions)
@@ -373,17 +398,13 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 }
                 // second level: the few lanes whose 16 bytes all match compare 16 more (matches of 16..31 bytes are a
                 // fifth of all sequences on text; without this each of them costs an exact step and its own emission)
-                const bool need2 = vo && mlo == 12u;
+                const uint64_t need2m = vom & ballot(mlo == 12u);
+                const bool need2 = in_mask(need2m);
                 if (need2 && !pred2) {                        // (all loads in one round trip)
                     if (!kRing) { f2 = ld128(src + pos + 16u); f3 = ld128(src + pos + 32u); }
                     c2 = ld128(src + old + 16u); c3 = ld128(src + old + 32u);
                 }
-                if (kRing && ballot(need2)) {                 // (wave-uniform: the permutes read every lane of W)
-                    uint32_t d[8];
-                    win_bytes(W, A, 4u, d, 8u);
-                    f2 = u32x4{d[0], d[1], d[2], d[3]};
-                    f3 = u32x4{d[4], d[5], d[6], d[7]};
-                }
+                if (kRing && need2m) ring_fwd2(sel, ja, A, hi4, f2, f3);   // (wave-uniform: the permutes read every lane)
                 if (need2) {
                     const uint32_t d2 = first_diff16_sel(f2, c2);
                     mlo += d2 == 16u ? 16u + first_diff16_sel(f3, c3) : d2;
@@ -392,12 +413,12 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 // the only lane of its hash, or the first of a duplicate group (round 3: the first of a group used to take
                 // an exact step like the others, which found no in-window candidate and fell back to the same registers;
                 // 0.55 of the 0.72 exact steps per window on text were on duplicate-hash lanes, half of them first ones)
-                const bool single = (grp & lanes_below) == 0;
-                const bool oldfast = vo && mlo < 44u;         // result against the pre-window value is complete in registers
-                const uint64_t wrmask = ballot(wr);
-                const uint64_t cfast = ballot(oldfast);                                       // usable if no in-window put precedes
-                const uint64_t slow = ballot(wr && ((!single && !oldfast) || (vo && mlo >= 44u)));   // exact step if reached
-                const uint64_t nsing = ballot(wr && !single);
+                const uint64_t singm = ballot(lane_rank(grp) == 0u);   // (grp & lanes_below) == 0
+                const uint64_t lt44 = ballot(mlo < 44u);
+                const uint64_t cfast = vom & lt44;            // oldfast: the result against the pre-window value is complete in
+                                                              // registers; usable if no in-window put precedes
+                const uint64_t nsing = wrmask & ~singm;
+                const uint64_t slow = (nsing & ~cfast) | (vom & ~lt44);   // wr && ((!single && !oldfast) || (vo && mlo >= 44)): exact step if reached
                 // per lane i: J = first cfast lane >= i, S = first slow lane >= i (64 = none),
                 // E = lane of the new anchor if the search that starts at i ends with the match at J
                 uint32_t J, S;
@@ -457,22 +478,24 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     const uint32_t pj = has_prev ? 63u - (uint32_t)__builtin_clzll(mb) : 0u;   // previous match lane
                     const uint32_t pend_all = shfl(v_end, pj);          // (unconditional: see zlz4_device.hpp)
                     const uint32_t pend = has_prev ? pend_all : a0;     // first lane of my literal run
-                    const bool cov = has_prev && lane < pend_all;       // strictly inside a match of this run
-                    const bool is_m = (mm_run & lane_bit) != 0;
+                    const uint64_t covm = ballot(mb != 0) & ballot(lane < pend_all);   // strictly inside a match of this run
+                    const bool is_m = in_mask(mm_run);
                     const uint32_t jlast = 63u - (uint32_t)__builtin_clzll(mm_run);
-                    const bool is_lit = lane >= a0 && lane < jlast && !cov && !is_m;
-                    const uint64_t litmask = ballot(is_lit);
-                    const uint64_t extm = ballot(is_m && mlo_e >= 15u);                 // matches with one length-extension byte (:416-429)
+                    // literals: lanes from a0 on that are neither past the last match lane, nor covered, nor a match lane
+                    const uint64_t litmask = ballot(lane >= a0) & ~(ballot(lane >= jlast) | covm | mm_run);
+                    const bool is_lit = in_mask(litmask);
+                    const uint64_t extm = mm_run & ballot(mlo_e >= 15u);                // matches with one length-extension byte (:416-429)
                     // literal runs of 15..63 bytes carry one extension byte too (:368-382): a lane's sequence is the
                     // first match lane at or above it, its literal count that lane minus the start of the run
                     const uint64_t at_or_above = mm_run & ~lanes_below;
                     const uint32_t my_m = at_or_above ? (uint32_t)__builtin_ctzll(at_or_above) : lane;
-                    const uint32_t own_l = (my_m - pend >= 15u) ? 1u : 0u;
-                    const uint64_t lextm = ballot(is_m && own_l != 0u);
-                    const uint32_t k = (uint32_t)__popcll(mb);                          // sequences completed before me
-                    const uint32_t lb = (uint32_t)__popcll(litmask & lanes_below);      // literal bytes before me
-                    const uint32_t o1 = op0 + 3u * k + lb + 1u + (uint32_t)__popcll(extm & lanes_below) +
-                                        (uint32_t)__popcll(lextm & lanes_below) + own_l;
+                    const uint64_t ownm = ballot(my_m - pend >= 15u);
+                    const uint32_t own_l = in_mask(ownm) ? 1u : 0u;
+                    const uint64_t lextm = mm_run & ownm;
+                    // (prefix popcounts as lane_rank: v_mbcnt_lo / _hi)
+                    const uint32_t k = lane_rank(mm_run);                               // sequences completed before me
+                    const uint32_t lb = lane_rank(litmask);                             // literal bytes before me
+                    const uint32_t o1 = op0 + 3u * k + lb + 1u + lane_rank(extm) + lane_rank(lextm) + own_l;
                     if (is_lit) dst[o1] = (uint8_t)fwd.x;               // literals (:390)
                     if (is_m) {
                         const uint32_t lit_k = lane - pend;             // :360
@@ -485,7 +508,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     }
                     const uint32_t nm = (uint32_t)__popcll(mm_run);
                     op = op0 + 3u * nm + (uint32_t)__popcll(litmask) + (uint32_t)__popcll(extm) + (uint32_t)__popcll(lextm);
-                    cov_acc |= ballot(cov);
+                    cov_acc |= covm;
                     mm_run = 0;
                     STAMP(10);
                 };
@@ -624,8 +647,8 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 if (next_win) {
                     pf_anchor = A + a;
                     if constexpr (kRing) {
-                        w_pf = ring_win(pf_anchor);
-                        fwd_pf = ring_fwd(w_pf, pf_anchor);
+                        sel_pf = ring_sel(pf_anchor, ja_pf);
+                        fwd_pf = ring_fwd(sel_pf, ja_pf, pf_anchor, hi4_pf);
                     } else {
                         fwd_pf = ld128(src + pf_anchor + lane);
                     }
@@ -642,7 +665,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 // written lane of the group puts the old value back (they all read it before any put, so equal addresses
                 // carry equal values).  Else the last `ins` lane of the group stores its entry and the others write nothing.
                 const uint64_t gi = grp & ins;
-                const bool put_mine = (ins & lane_bit) && (gi & ~lanes_below & ~lane_bit) == 0;
+                const bool put_mine = in_mask(ins) && (gi & ~lanes_below & ~lane_bit) == 0;
                 if (put_mine || (wr && gi == 0)) table[h] = (T)(put_mine ? mine : old_e);
                 if (kTag == 1 && put_mine) tags[h] = (uint8_t)tg;       // (the speculative put left the old tag in place)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

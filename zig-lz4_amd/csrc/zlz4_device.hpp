@@ -46,6 +46,27 @@ __device__ __forceinline__ uint32_t shfl(uint32_t v, uint32_t src_lane) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane << 2), (int)v);
 }
 
+// number of set bits of `mask` below this lane, popcount(mask & lanes_below), as v_mbcnt_lo + v_mbcnt_hi: no lanes_below
+// operand, two instructions where the popcount form takes four
+__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+// this lane's bit of the wave-uniform `mask`, (mask >> lane) & 1: the mask is used as the lane's condition as it stands
+// (the inverse of a ballot), nothing is computed per lane
+__device__ __forceinline__ bool in_mask(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
+
+// (a + kOff) & 0xFF in one instruction: SDWA keeps the low byte of the sum and pads the rest with zeros.  For ds_bpermute
+// addresses (4 * lane index): in a byte they wrap modulo 64 lanes.  Only ds_bpermute may read the result (the compiler
+// does not see the partial write inside the statement, so no VALU instruction should consume it right behind).
+template <uint32_t kOff>
+__device__ __forceinline__ uint32_t add_wrap_byte(uint32_t a) {
+    static_assert(kOff <= 64u, "inline constant");
+    uint32_t r;
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD"
+        : "=v"(r) : "v"(a), "n"(kOff));
+    return r;
+}
+
 // write the wave-uniform `val` into lane `l` (uniform) of `old` (v_cmp + v_cndmask; VALU has headroom here)
 __device__ __forceinline__ uint32_t wrlane(uint32_t val, uint32_t l, uint32_t old) {
     return (__lane_id() == l) ? val : old;
