@@ -8,22 +8,26 @@ TUNELIB := $(PKG)/libzlz4_amd_tuning.so
 HIPSRC  := $(CSRC)/zlz4_capi.hip $(CSRC)/zlz4_frame.hip $(CSRC)/zlz4_decompress.hip \
            $(CSRC)/zlz4_compress_fast.hip $(CSRC)/zlz4_compress_hc.hip $(CSRC)/zlz4_compress_hc_serial.hip \
            $(CSRC)/zlz4_dest_size.hip $(CSRC)/zlz4_stream_decode.hip $(CSRC)/zlz4_sizes.hip \
-           $(CSRC)/zlz4_compress_dict.hip $(CSRC)/zlz4_compress_hc_dict.hip $(CSRC)/zlz4_frame_linked.hip
+           $(CSRC)/zlz4_compress_dict.hip $(CSRC)/zlz4_compress_hc_dict.hip $(CSRC)/zlz4_frame_linked.hip \
+           $(CSRC)/zlz4_host.hip
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude
 
 all: $(LIB) $(TUNELIB) oracle
 
-$(LIB): $(HIPSRC) $(CSRC)/zlz4_device.hpp $(CSRC)/zlz4_frame_batch.hpp $(CSRC)/zlz4_host.hpp include/zlz4_amd.h
+$(LIB): $(HIPSRC) $(CSRC)/zlz4_device.hpp $(CSRC)/zlz4_frame_batch.hpp $(CSRC)/zlz4_host.hpp $(CSRC)/zlz4_launch.hpp \
+        include/zlz4_amd.h
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIPSRC)
 
 # the same library with the experiment / A-B knobs of DESIGN.md section 7 compiled in (environment variables); used by
 # tests/test_gpu_lane_decoder.py and the tools/ scripts, never by bench.py or the parity tests
 tuning: $(TUNELIB)
-$(TUNELIB): $(HIPSRC) $(CSRC)/zlz4_device.hpp $(CSRC)/zlz4_frame_batch.hpp $(CSRC)/zlz4_host.hpp include/zlz4_amd.h
+$(TUNELIB): $(HIPSRC) $(CSRC)/zlz4_device.hpp $(CSRC)/zlz4_frame_batch.hpp $(CSRC)/zlz4_host.hpp $(CSRC)/zlz4_launch.hpp \
+        include/zlz4_amd.h
 	$(HIPCC) $(HIPFLAGS) -DZLZ4_TUNING -shared -o $@ $(HIPSRC)
 
 # diagnostic build: per-phase cycle stamps inside the compress kernel (never shipped / never benchmarked)
-stamps: $(HIPSRC) $(CSRC)/zlz4_device.hpp $(CSRC)/zlz4_frame_batch.hpp $(CSRC)/zlz4_host.hpp include/zlz4_amd.h
+stamps: $(HIPSRC) $(CSRC)/zlz4_device.hpp $(CSRC)/zlz4_frame_batch.hpp $(CSRC)/zlz4_host.hpp $(CSRC)/zlz4_launch.hpp \
+        include/zlz4_amd.h
 	$(HIPCC) $(HIPFLAGS) -DZLZ4_STAMPS -DZLZ4_TUNING -shared -o $(PKG)/libzlz4_amd_stamps.so $(HIPSRC)
 
 oracle:

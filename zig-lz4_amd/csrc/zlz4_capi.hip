@@ -8,147 +8,62 @@
 
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/zlz4_amd.h"
 #include "zlz4_host.hpp"
+#include "zlz4_launch.hpp"
 
-// kernel launchers (one per .hip file)
-extern "C" int zlz4_launch_decompress_safe(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                           const uint64_t *, const uint32_t *, int64_t *, uint32_t);
-extern "C" int zlz4_launch_decompress_safe_using_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                                      uint8_t *, const uint64_t *, const uint32_t *, int64_t *, uint32_t,
-                                                      const uint8_t *, const uint64_t *, const uint32_t *);
-extern "C" int zlz4_launch_compress_fast(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                         const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
-extern "C" int zlz4_launch_compress_fast_continue(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                                  uint8_t *, const uint64_t *, const uint32_t *, const uint32_t *,
-                                                  const uint32_t *, uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
-extern "C" int zlz4_launch_load_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint32_t *,
-                                     int64_t *, uint32_t);
-extern "C" int zlz4_launch_compress_fast_using_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                                    uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *,
-                                                    const uint64_t *, const uint32_t *, const uint32_t *, const uint32_t *,
-                                                    int64_t *, uint32_t, uint32_t, uint32_t, uint32_t);
-extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                       const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, int32_t,
-                                       void *, size_t);
-extern "C" size_t zlz4_hc_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
-extern "C" int zlz4_launch_compress_hc_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                            const uint64_t *, const uint32_t *, const uint8_t *, const uint64_t *,
-                                            const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t, int32_t, void *, size_t);
-extern "C" size_t zlz4_hc_dict_workspace_bytes(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len);
-extern "C" int zlz4_launch_compress_dest_size(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                              const uint64_t *, const uint32_t *, int64_t *, uint32_t *, uint32_t, uint32_t,
-                                              void *, const uint64_t *, const uint32_t *);
-extern "C" size_t zlz4_dest_size_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
-extern "C" int zlz4_launch_decompress_safe_bound(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                                 uint8_t *, const uint64_t *, const uint32_t *, int64_t *, uint32_t,
-                                                 const uint8_t *, const uint64_t *, const uint32_t *, int);
-extern "C" size_t zlz4_sd_workspace_bytes(uint32_t nblocks, uint32_t nstreams);
-extern "C" int zlz4_launch_stream_decode(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                         const uint64_t *, const uint32_t *, const uint32_t *, uint64_t *, int64_t *,
-                                         uint32_t, uint32_t, void *);
-extern "C" uint32_t zlz4_dest_size_slot_cap(uint32_t max_in_len);
-extern "C" int zlz4_launch_decompressed_size(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                             const uint32_t *, int64_t *, uint32_t);
-extern "C" int zlz4_launch_plan_outputs(hipStream_t, const int64_t *, uint32_t, uint32_t, uint64_t *, uint32_t *, uint64_t *);
+using namespace zlz4host;
 
 namespace {
 
-// ---------------------------------------------------------------- device context
-std::once_flag g_once;
-int g_device_ok = ZLZ4_ERR_DEVICE;
-
-void probe_device() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, dev) != hipSuccess) return;
-    if (std::strncmp(p.gcnArchName, "gfx950", 6) != 0) return;   // kernels are built for gfx950 only
-    g_device_ok = 0;
-}
-
-bool device_ok() {
-    std::call_once(g_once, probe_device);
-    return g_device_ok == 0;
-}
-
-using zlz4host::DevBuf;
-using zlz4host::DeviceCall;
-
 enum class Op { Fast, Hc, Decompress, DecompressDict, DecompressBound };
 
-// One block, host pointers: stage -> kernel -> copy back.  Op::DecompressDict stages the last min(dict_len, 65536)
-// bytes of `dict` (offsets are at most 65535: nothing in front of that tail can be reached, src/lz4.zig:189-192).
-// Op::DecompressBound decodes with the StreamDecode bound `bound` (k_decompress_safe, kBound).
+// One block, host pointers: stage -> kernel -> copy back.  Op::DecompressDict stages the tail of `dict` (dict_tail,
+// zlz4_host.hpp).  Op::DecompressBound decodes with the StreamDecode bound `bound` (k_decompress_safe, kBound).
 int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t accel,
                    int32_t level, const uint8_t *dict = nullptr, size_t dict_len = 0, uint32_t bound = 0) {
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     if (src_len > 0xFFFFFFFFull) return op == Op::Decompress ? ZLZ4_ERR_CORRUPTED_DATA : ZLZ4_ERR_INPUT_TOO_LARGE;
-    // the kernels index with 32 bits; a destination larger than 4 GiB-1 is clamped (never reached:
-    // compressBound(0x7E000000) and the largest decodable block both fit)
-    const uint32_t cap32 = dst_cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dst_cap;
-    const uint32_t len32 = (uint32_t)src_len;
+    const uint32_t cap32 = clamp_cap32(dst_cap), len32 = (uint32_t)src_len;
 
     // scratch from the parked-buffer cache (zlz4_host.hpp): a caller that loops over single blocks does not pay a
     // hipMalloc / hipFree pair per call
     hipStream_t st = nullptr;
     DeviceCall dc(st);
     const size_t ws = op == Op::Hc ? zlz4_hc_workspace_bytes(1, len32) : 0;
-    const size_t dtail = op == Op::DecompressDict ? (dict_len < 65536u ? dict_len : 65536u) : 0;
-    DevBuf d_in(src_len, &dc), d_out(cap32, &dc), d_meta(64, &dc), d_ws(ws, &dc), d_dict(dtail, &dc);
-    if (!d_in.p || !d_out.p || !d_meta.p || !d_ws.p || !d_dict.p) return ZLZ4_ERR_ALLOCATION_FAILED;
-    struct Meta {
-        uint64_t in_off; uint64_t out_off; int64_t result; uint32_t in_len; uint32_t out_cap; uint64_t dict_off; uint32_t dict_len;
-        uint32_t bound;                                             // (dict_len[1] of the kBound builds)
-    } m;
-    m.in_off = 0; m.out_off = 0; m.result = 0; m.in_len = len32; m.out_cap = cap32; m.dict_off = 0; m.dict_len = (uint32_t)dtail;
-    m.bound = bound;
-    static_assert(offsetof(Meta, bound) == offsetof(Meta, dict_len) + 4, "bound follows dict_len");
+    const size_t dtail = op == Op::DecompressDict ? dict_tail(dict_len) : 0;
+    DevBuf d_in(src_len, &dc), d_out(cap32, &dc);
+    Staged<BlockRec> rec(&dc);
+    DevBuf d_ws(ws, &dc), d_dict(dtail, &dc);
+    if (!d_in.p || !d_out.p || !rec.d || !d_ws.p || !d_dict.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    rec.h.in_len = len32; rec.h.out_cap = cap32; rec.h.dict_len = (uint32_t)dtail; rec.h.bound = bound;
     dc.launched();
-    if (src_len && hipMemcpyAsync(d_in.p, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (dtail && hipMemcpyAsync(d_dict.p, dict + (dict_len - dtail), dtail, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (!upload(d_in, src, src_len, st) || !upload(d_dict, dict + (dict_len - dtail), dtail, st) || !rec.upload(st))
         return ZLZ4_ERR_DEVICE;
-    if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    auto *dm = d_meta.as<uint8_t>();
-    const uint64_t *p_in_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off));
-    const uint64_t *p_out_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off));
-    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
-    const uint32_t *p_in_len = reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len));
-    const uint32_t *p_out_cap = reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap));
+    BlockRec *r = rec.d;
+    const uint8_t *in = d_in.as<uint8_t>();
+    uint8_t *out = d_out.as<uint8_t>();
     int rc;
     if (op == Op::Fast) {
-        rc = zlz4_launch_compress_fast(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
-                                       p_out_cap, p_res, 1, len32, accel);
+        rc = zlz4_launch_compress_fast(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap, &r->result, 1, len32,
+                                       accel);
     } else if (op == Op::Hc) {
-        rc = zlz4_launch_compress_hc(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
-                                     p_out_cap, p_res, 1, len32, level, d_ws.p, ws);
+        rc = zlz4_launch_compress_hc(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap, &r->result, 1, len32,
+                                     level, d_ws.p, ws);
     } else if (op == Op::Decompress) {
-        rc = zlz4_launch_decompress_safe(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
-                                         p_out_cap, p_res, 1);
+        rc = zlz4_launch_decompress_safe(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap, &r->result, 1);
     } else if (op == Op::DecompressBound) {
-        rc = zlz4_launch_decompress_safe_bound(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(), p_out_off,
-                                               p_out_cap, p_res, 1, nullptr,
-                                               reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off)),
-                                               reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)), 0);
+        rc = zlz4_launch_decompress_safe_bound(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap, &r->result, 1,
+                                               nullptr, &r->dict_off, &r->dict_len, 0);
     } else {
-        rc = zlz4_launch_decompress_safe_using_dict(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(),
-                                                    p_out_off, p_out_cap, p_res, 1, d_dict.as<uint8_t>(),
-                                                    reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off)),
-                                                    reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)));
+        rc = zlz4_launch_decompress_safe_using_dict(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap,
+                                                    &r->result, 1, d_dict.as<uint8_t>(), &r->dict_off, &r->dict_len);
     }
     if (rc != 0) return rc;
     int64_t result = 0;
-    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
-    if (result > 0) {
-        if ((uint64_t)result > dst_cap) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
-        if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    }
+    if (!read_result(dc, &r->result, result) || !copy_back(dst, dst_cap, d_out, result)) return ZLZ4_ERR_DEVICE;
     return result;
 }
 
@@ -185,141 +100,100 @@ int64_t partial_target_zero(const uint8_t *src, size_t n) {
 }
 
 // Stream.loadDict / compressFastContinue on a HOST table of 4096 u32: the table is staged with the data, the kernel
-// updates it in place on the device, and it is copied back.  src == nullptr: loadDict of `dict` (its last
-// min(dict_len, 65536) bytes are staged); else compressFastContinue of src[0..src_len).
+// updates it in place on the device, and it is copied back.  src == nullptr: loadDict of `dict` (its tail is staged);
+// else compressFastContinue of src[0..src_len).
 int64_t run_stream_single(uint32_t *table, const uint8_t *dict, size_t dict_len, const uint8_t *src, size_t src_len,
                           uint8_t *dst, size_t dst_cap, uint32_t accel) {
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     const bool load = src == nullptr;
-    const size_t in_len = load ? (dict_len < 65536u ? dict_len : 65536u) : src_len;
+    const size_t in_len = load ? dict_tail(dict_len) : src_len;
     const uint8_t *in = load ? dict + (dict_len - in_len) : src;
-    const uint32_t cap32 = dst_cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dst_cap;
+    const uint32_t cap32 = clamp_cap32(dst_cap);
     const size_t tbytes = ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t);
     hipStream_t st = nullptr;
     DeviceCall dc(st);
-    DevBuf d_in(in_len, &dc), d_out(load ? 0 : cap32, &dc), d_meta(64, &dc), d_tab(tbytes, &dc);
-    if (!d_in.p || !d_out.p || !d_meta.p || !d_tab.p) return ZLZ4_ERR_ALLOCATION_FAILED;
-    struct Meta { uint64_t in_off; uint64_t out_off; int64_t result; uint32_t in_len; uint32_t out_cap; } m;
-    m.in_off = 0; m.out_off = 0; m.result = 0; m.in_len = (uint32_t)in_len; m.out_cap = cap32;
+    DevBuf d_in(in_len, &dc), d_out(load ? 0 : cap32, &dc);
+    Staged<BlockRec> rec(&dc);
+    DevBuf d_tab(tbytes, &dc);
+    if (!d_in.p || !d_out.p || !rec.d || !d_tab.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    rec.h.in_len = (uint32_t)in_len; rec.h.out_cap = cap32;
     dc.launched();
-    if (in_len && hipMemcpyAsync(d_in.p, in, in_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (!load && hipMemcpyAsync(d_tab.p, table, tbytes, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    auto *dm = d_meta.as<uint8_t>();
-    const uint64_t *p_in_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off));
-    const uint32_t *p_in_len = reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len));
-    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
+    if (!upload(d_in, in, in_len, st) || !(load || upload(d_tab, table, tbytes, st)) || !rec.upload(st))
+        return ZLZ4_ERR_DEVICE;
+    BlockRec *r = rec.d;
     int rc;
     if (load) {
-        rc = zlz4_launch_load_dict(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_tab.as<uint32_t>(), p_res, 1);
+        rc = zlz4_launch_load_dict(st, d_in.as<uint8_t>(), &r->in_off, &r->in_len, d_tab.as<uint32_t>(), &r->result, 1);
     } else {
-        rc = zlz4_launch_compress_fast_continue(st, d_in.as<uint8_t>(), p_in_off, p_in_len, d_out.as<uint8_t>(),
-                                                reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
-                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)),
-                                                d_tab.as<uint32_t>(), nullptr, d_tab.as<uint32_t>(), p_res, 1,
-                                                (uint32_t)in_len, accel);
+        rc = zlz4_launch_compress_fast_continue(st, d_in.as<uint8_t>(), &r->in_off, &r->in_len, d_out.as<uint8_t>(),
+                                                &r->out_off, &r->out_cap, d_tab.as<uint32_t>(), nullptr,
+                                                d_tab.as<uint32_t>(), &r->result, 1, (uint32_t)in_len, accel);
     }
     if (rc != 0) return rc;
     int64_t result = 0;
-    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
-    if (!load && result > 0) {
-        if ((uint64_t)result > dst_cap) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
-        if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    }
+    if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
+    if (!load && !copy_back(dst, dst_cap, d_out, result)) return ZLZ4_ERR_DEVICE;
     // the table is the reference's after the call on every exit (unchanged ones included)
     if (hipMemcpy(table, d_tab.p, tbytes, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
     return result;
 }
 
-// zlz4_compress_fast_using_dict for 1 <= src_len <= ZLZ4_MAX_INPUT_SIZE: the record and the last min(dict_len, 65536)
-// bytes of the dictionary are staged, k_load_dict builds the dictionary's table on the device and the batch kernel
-// (zlz4_compress_dict.hip) runs on one block.
+// zlz4_compress_fast_using_dict for 1 <= src_len <= ZLZ4_MAX_INPUT_SIZE: the record and the tail of the dictionary are
+// staged, k_load_dict builds the dictionary's table on the device and the batch kernel (zlz4_compress_dict.hip) runs on
+// one block.
 int64_t run_dict_compress_single(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, const uint8_t *dict,
                                  size_t dict_len, uint32_t accel) {
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const uint32_t cap32 = dst_cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dst_cap;
-    const uint32_t len32 = (uint32_t)src_len;
-    const size_t dtail = dict_len < 65536u ? dict_len : 65536u;
+    const uint32_t cap32 = clamp_cap32(dst_cap), len32 = (uint32_t)src_len;
+    const size_t dtail = dict_tail(dict_len);
     const size_t tbytes = ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t);
     hipStream_t st = nullptr;
     DeviceCall dc(st);
-    DevBuf d_in(src_len, &dc), d_out(cap32, &dc), d_meta(64, &dc), d_dict(dtail, &dc), d_tab(tbytes, &dc);
-    if (!d_in.p || !d_out.p || !d_meta.p || !d_dict.p || !d_tab.p) return ZLZ4_ERR_ALLOCATION_FAILED;
-    struct Meta {
-        uint64_t in_off; uint64_t out_off; uint64_t dict_off; int64_t result; int64_t dict_size; uint32_t in_len;
-        uint32_t out_cap; uint32_t dict_len;
-    } m;
-    m.in_off = 0; m.out_off = 0; m.dict_off = 0; m.result = 0; m.dict_size = 0; m.in_len = len32; m.out_cap = cap32;
-    m.dict_len = (uint32_t)dtail;
+    DevBuf d_in(src_len, &dc), d_out(cap32, &dc);
+    Staged<BlockRec> rec(&dc);
+    DevBuf d_dict(dtail, &dc), d_tab(tbytes, &dc);
+    if (!d_in.p || !d_out.p || !rec.d || !d_dict.p || !d_tab.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    rec.h.in_len = len32; rec.h.out_cap = cap32; rec.h.dict_len = (uint32_t)dtail;
     dc.launched();
-    if (hipMemcpyAsync(d_in.p, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (dtail && hipMemcpyAsync(d_dict.p, dict + (dict_len - dtail), dtail, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (!upload(d_in, src, src_len, st) || !upload(d_dict, dict + (dict_len - dtail), dtail, st) || !rec.upload(st))
         return ZLZ4_ERR_DEVICE;
-    if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    auto *dm = d_meta.as<uint8_t>();
-    const uint64_t *p_dict_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off));
-    const uint32_t *p_dict_len = reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len));
-    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
-    int rc = zlz4_launch_load_dict(st, d_dict.as<uint8_t>(), p_dict_off, p_dict_len, d_tab.as<uint32_t>(),
-                                   reinterpret_cast<int64_t *>(dm + offsetof(Meta, dict_size)), 1);
+    BlockRec *r = rec.d;
+    int rc = zlz4_launch_load_dict(st, d_dict.as<uint8_t>(), &r->dict_off, &r->dict_len, d_tab.as<uint32_t>(), &r->dict_size, 1);
     if (rc != 0) return rc;
-    rc = zlz4_launch_compress_fast_using_dict(st, d_in.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
-                                              reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)),
-                                              d_out.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
-                                              reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)),
-                                              d_dict.as<uint8_t>(), p_dict_off, p_dict_len, d_tab.as<uint32_t>(), nullptr,
-                                              p_res, 1, len32, (uint32_t)dtail, accel);
+    rc = zlz4_launch_compress_fast_using_dict(st, d_in.as<uint8_t>(), &r->in_off, &r->in_len, d_out.as<uint8_t>(), &r->out_off,
+                                              &r->out_cap, d_dict.as<uint8_t>(), &r->dict_off, &r->dict_len,
+                                              d_tab.as<uint32_t>(), nullptr, &r->result, 1, len32, (uint32_t)dtail, accel);
     if (rc != 0) return rc;
     int64_t result = 0;
-    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
-    if (result > 0) {
-        if ((uint64_t)result > dst_cap) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
-        if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    }
+    if (!read_result(dc, &r->result, result) || !copy_back(dst, dst_cap, d_out, result)) return ZLZ4_ERR_DEVICE;
     return result;
 }
 
-// zlz4_compress_hc_using_dict for 1 <= src_len <= ZLZ4_MAX_INPUT_SIZE and a level of 3..9: the record and the last
-// min(dict_len, 65536) bytes of the dictionary are staged and the batch pipeline runs on one block.
+// zlz4_compress_hc_using_dict for 1 <= src_len <= ZLZ4_MAX_INPUT_SIZE and a level of 3..9: the record and the tail of the
+// dictionary are staged and the batch pipeline runs on one block.
 int64_t run_hc_dict_single(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, const uint8_t *dict,
                            size_t dict_len, int32_t level) {
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const uint32_t cap32 = dst_cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dst_cap;
-    const uint32_t len32 = (uint32_t)src_len;
-    const size_t dtail = dict_len < 65536u ? dict_len : 65536u;
+    const uint32_t cap32 = clamp_cap32(dst_cap), len32 = (uint32_t)src_len;
+    const size_t dtail = dict_tail(dict_len);
     const size_t ws = zlz4_hc_dict_workspace_bytes(1, len32, (uint32_t)dtail);
     hipStream_t st = nullptr;
     DeviceCall dc(st);
-    DevBuf d_in(src_len, &dc), d_out(cap32, &dc), d_meta(64, &dc), d_dict(dtail, &dc), d_ws(ws, &dc);
-    if (!d_in.p || !d_out.p || !d_meta.p || !d_dict.p || !d_ws.p) return ZLZ4_ERR_ALLOCATION_FAILED;
-    struct Meta {
-        uint64_t in_off; uint64_t out_off; uint64_t dict_off; int64_t result; uint32_t in_len; uint32_t out_cap; uint32_t dict_len;
-    } m;
-    m.in_off = 0; m.out_off = 0; m.dict_off = 0; m.result = 0; m.in_len = len32; m.out_cap = cap32; m.dict_len = (uint32_t)dtail;
+    DevBuf d_in(src_len, &dc), d_out(cap32, &dc);
+    Staged<BlockRec> rec(&dc);
+    DevBuf d_dict(dtail, &dc), d_ws(ws, &dc);
+    if (!d_in.p || !d_out.p || !rec.d || !d_dict.p || !d_ws.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    rec.h.in_len = len32; rec.h.out_cap = cap32; rec.h.dict_len = (uint32_t)dtail;
     dc.launched();
-    if (hipMemcpyAsync(d_in.p, src, src_len, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (dtail && hipMemcpyAsync(d_dict.p, dict + (dict_len - dtail), dtail, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (!upload(d_in, src, src_len, st) || !upload(d_dict, dict + (dict_len - dtail), dtail, st) || !rec.upload(st))
         return ZLZ4_ERR_DEVICE;
-    if (hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    auto *dm = d_meta.as<uint8_t>();
-    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
-    const int rc = zlz4_launch_compress_hc_dict(st, d_in.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
-                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)), d_out.as<uint8_t>(),
-                                                reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
-                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)), d_dict.as<uint8_t>(),
-                                                reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dict_off)),
-                                                reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)), p_res, 1, len32,
-                                                (uint32_t)dtail, level, d_ws.p, ws);
+    BlockRec *r = rec.d;
+    const int rc = zlz4_launch_compress_hc_dict(st, d_in.as<uint8_t>(), &r->in_off, &r->in_len, d_out.as<uint8_t>(), &r->out_off,
+                                                &r->out_cap, d_dict.as<uint8_t>(), &r->dict_off, &r->dict_len, &r->result, 1,
+                                                len32, (uint32_t)dtail, level, d_ws.p, ws);
     if (rc != 0) return rc;
     int64_t result = 0;
-    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    if (!dc.sync()) return ZLZ4_ERR_DEVICE;
-    if (result > 0) {
-        if ((uint64_t)result > dst_cap) return ZLZ4_ERR_DEVICE;   // cannot happen; never overrun the caller
-        if (hipMemcpy(dst, d_out.p, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    }
+    if (!read_result(dc, &r->result, result) || !copy_back(dst, dst_cap, d_out, result)) return ZLZ4_ERR_DEVICE;
     return result;
 }
 
@@ -336,40 +210,35 @@ int32_t hc_dict_level(int32_t level) {
 int64_t dest_size_batch_of_one(const uint8_t *src, uint8_t *dst, size_t cap, size_t *src_size) {
     const uint32_t n = (uint32_t)*src_size;
     const uint32_t cap32 = (uint32_t)cap;                     // < compressBound(n) <= 2^31
-    struct Meta {
+    struct Rec {
         uint64_t in_off, out_off, slot_off; int64_t result; uint32_t in_len, out_cap, slot_cap, consumed;
     };
-    const size_t out_bytes = ((size_t)cap32 + 15u) & ~(size_t)15u;   // [out | meta | input]
-    const size_t meta_bytes = (sizeof(Meta) + 15u) & ~(size_t)15u;
+    const size_t out_bytes = ((size_t)cap32 + 15u) & ~(size_t)15u;   // [out | record | input]
+    const size_t rec_bytes = (sizeof(Rec) + 15u) & ~(size_t)15u;
     const size_t ws_bytes = zlz4_dest_size_workspace_bytes(1, n);
     hipStream_t st = nullptr;
     DeviceCall dc(st);
-    DevBuf d_buf(out_bytes + meta_bytes + n, &dc), d_ws(ws_bytes, &dc);
+    DevBuf d_buf(out_bytes + rec_bytes + n, &dc), d_ws(ws_bytes, &dc);
     if (!d_buf.p || !d_ws.p) return ZLZ4_ERR_ALLOCATION_FAILED;
-    std::vector<uint8_t> h(meta_bytes + n);
-    Meta m;
+    std::vector<uint8_t> h(rec_bytes + n);
+    Rec m;
     std::memset(&m, 0, sizeof m);
-    m.in_off = meta_bytes;                                    // relative to the meta block
+    m.in_off = rec_bytes;                                     // relative to the record
     m.in_len = n;
     m.out_off = 0;
     m.out_cap = cap32;
     m.slot_off = 0;
     m.slot_cap = zlz4_dest_size_slot_cap(n);
     std::memcpy(h.data(), &m, sizeof m);
-    std::memcpy(h.data() + meta_bytes, src, n);
+    std::memcpy(h.data() + rec_bytes, src, n);
     uint8_t *dm = d_buf.as<uint8_t>() + out_bytes;
+    Rec *r = reinterpret_cast<Rec *>(dm);
     dc.launched();
     if (hipMemcpyAsync(dm, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    const int rc = zlz4_launch_compress_dest_size(
-        st, dm, reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
-        reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)), d_buf.as<uint8_t>(),
-        reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
-        reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)), reinterpret_cast<int64_t *>(dm + offsetof(Meta, result)),
-        reinterpret_cast<uint32_t *>(dm + offsetof(Meta, consumed)), 1, n, d_ws.p,
-        reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, slot_off)),
-        reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, slot_cap)));
+    const int rc = zlz4_launch_compress_dest_size(st, dm, &r->in_off, &r->in_len, d_buf.as<uint8_t>(), &r->out_off, &r->out_cap,
+                                                  &r->result, &r->consumed, 1, n, d_ws.p, &r->slot_off, &r->slot_cap);
     if (rc != 0) return rc;
-    std::vector<uint8_t> back(out_bytes + sizeof(Meta));
+    std::vector<uint8_t> back(out_bytes + sizeof(Rec));
     if (hipMemcpyAsync(back.data(), d_buf.p, back.size(), hipMemcpyDeviceToHost, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
     if (!dc.sync()) return ZLZ4_ERR_DEVICE;
     std::memcpy(&m, back.data() + out_bytes, sizeof m);
@@ -531,21 +400,17 @@ int64_t zlz4_decompressed_size(const uint8_t *src, size_t n, size_t dict_len) {
     if (n > 0xFFFFFFFFull) return ZLZ4_ERR_CORRUPTED_DATA;          // (as zlz4_decompress_safe)
     hipStream_t st = nullptr;
     DeviceCall dc(st);
-    DevBuf d_in(n, &dc), d_meta(64, &dc);
-    if (!d_in.p || !d_meta.p) return ZLZ4_ERR_ALLOCATION_FAILED;
-    struct Meta { uint64_t in_off; int64_t result; uint32_t in_len; uint32_t dict_len; } m;
-    m.in_off = 0; m.result = 0; m.in_len = (uint32_t)n; m.dict_len = dict_len < 65536u ? (uint32_t)dict_len : 65536u;
+    DevBuf d_in(n, &dc);
+    Staged<BlockRec> rec(&dc);
+    if (!d_in.p || !rec.d) return ZLZ4_ERR_ALLOCATION_FAILED;
+    rec.h.in_len = (uint32_t)n; rec.h.dict_len = (uint32_t)dict_tail(dict_len);
     dc.launched();
-    if (hipMemcpyAsync(d_in.p, src, n, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    auto *dm = d_meta.as<uint8_t>();
-    int64_t *p_res = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
-    const int rc = zlz4_launch_decompressed_size(st, d_in.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
-                                                 reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)),
-                                                 reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, dict_len)), p_res, 1);
+    if (!upload(d_in, src, n, st) || !rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    BlockRec *r = rec.d;
+    const int rc = zlz4_launch_decompressed_size(st, d_in.as<uint8_t>(), &r->in_off, &r->in_len, &r->dict_len, &r->result, 1);
     if (rc != 0) return rc;
     int64_t result = 0;
-    if (hipMemcpyAsync(&result, p_res, sizeof result, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
+    if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
     return result;
 }
 
@@ -628,29 +493,25 @@ int64_t zlz4_compress_dest_size(const uint8_t *src, uint8_t *dst, size_t cap, si
     // limit fail with InputTooLarge in the reference (:594-607 -> `high = mid - 1`), so the device never needs more
     // than ZLZ4_MAX_INPUT_SIZE source bytes.
     const size_t stage = (size_t)ZLZ4_MAX_INPUT_SIZE;
-    const uint32_t cap32 = cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap;
-    DevBuf d_in(stage), d_out(cap32), d_meta(64);
-    if (!d_in.p || !d_out.p || !d_meta.p) return ZLZ4_ERR_ALLOCATION_FAILED;
+    const uint32_t cap32 = clamp_cap32(cap);
+    DevBuf d_in(stage), d_out(cap32);
+    Staged<BlockRec> rec(nullptr);
+    if (!d_in.p || !d_out.p || !rec.d) return ZLZ4_ERR_ALLOCATION_FAILED;
     if (hipMemcpy(d_in.p, src, stage, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    struct Meta { uint64_t in_off; uint64_t out_off; int64_t result; uint32_t in_len; uint32_t out_cap; };
-    auto *dm = d_meta.as<uint8_t>();
+    rec.h.out_cap = cap32;
+    BlockRec *r = rec.d;
     // one probe = compressDefault(src[0..len], dst) on the device; the input stays resident
     auto probe = [&](size_t len) -> int64_t {
         if (len > ZLZ4_MAX_INPUT_SIZE) return ZLZ4_ERR_INPUT_TOO_LARGE;        // src/lz4.zig:296
         if (len == 0) return 0;                                                // :299
-        Meta m; m.in_off = 0; m.out_off = 0; m.result = 0; m.in_len = (uint32_t)len; m.out_cap = cap32;
-        if (hipMemcpy(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-        const int rc = zlz4_launch_compress_fast(nullptr, d_in.as<uint8_t>(),
-                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, in_off)),
-                                                 reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, in_len)),
-                                                 d_out.as<uint8_t>(),
-                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, out_off)),
-                                                 reinterpret_cast<const uint32_t *>(dm + offsetof(Meta, out_cap)),
-                                                 reinterpret_cast<int64_t *>(dm + offsetof(Meta, result)), 1, (uint32_t)len, 1);
+        rec.h.in_len = (uint32_t)len;
+        if (hipMemcpy(r, &rec.h, sizeof rec.h, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+        const int rc = zlz4_launch_compress_fast(nullptr, d_in.as<uint8_t>(), &r->in_off, &r->in_len, d_out.as<uint8_t>(),
+                                                 &r->out_off, &r->out_cap, &r->result, 1, (uint32_t)len, 1);
         if (rc != 0) return rc;
-        int64_t r = 0;
-        if (hipMemcpy(&r, dm + offsetof(Meta, result), sizeof r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-        return r;
+        int64_t res = 0;
+        if (hipMemcpy(&res, &r->result, sizeof res, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+        return res;
     };
     size_t low = 1, high = max_src, best = 0, best_c = 0, last_ok_len = (size_t)-1;     // :567-570
     auto attempt = [&](size_t len, bool &fits) -> int64_t {

@@ -28,6 +28,7 @@
 // src - D + p); the lane whose read would straddle the dictionary's end (possible only in the extension, or with a
 // foreign table) assembles it from bytes.
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 namespace zlz4 {
 

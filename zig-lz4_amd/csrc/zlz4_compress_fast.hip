@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 // Diagnostic build only (-DZLZ4_STAMPS): per-phase shader-cycle sums, see profiles/ notes.
 #ifdef ZLZ4_STAMPS

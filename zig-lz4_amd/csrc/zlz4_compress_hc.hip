@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 #ifdef ZLZ4_STAMPS
 __device__ unsigned long long g_zlz4_hstamps[16];
@@ -539,7 +540,6 @@ __global__ __launch_bounds__(256) void k_hc_search(const uint8_t *__restrict__ d
     else r = (R)((uint64_t)(uint32_t)best_len | ((uint64_t)best_off << 32));
     d_res[(uint64_t)b * link_stride + p] = r;
 }
-
 
 // ------------------------------------------------------------------ K2s: parse-aware search (levels 3..9, blocks <= 64 KiB)
 // The greedy parse (:1009-1032) is a walk in a functional graph: next(p) = p + len(p) when the search at p finds a match,
@@ -1253,18 +1253,6 @@ __global__ __launch_bounds__(256) void k_hc_parse_emit(const uint8_t *__restrict
     if (lane == 0) d_result[blk] = out;
 }
 
-}  // namespace zlz4
-
-extern "C" int zlz4_launch_hc_mid(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *, const uint64_t *,
-                                  const uint32_t *, int64_t *, uint32_t, void *, uint32_t, uint32_t);
-extern "C" int zlz4_launch_hc_opt_parse(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                        const uint64_t *, const uint32_t *, int64_t *, const void *, uint64_t, int, void *,
-                                        uint32_t, uint32_t, uint32_t, uint32_t);
-extern "C" size_t zlz4_hc_mid_workspace_bytes(uint32_t chunk_blocks);
-extern "C" size_t zlz4_hc_opt_workspace_bytes(uint32_t chunk_blocks);
-
-namespace zlz4 {
-
 // A second stream per host thread and device for the emit pass: K3 of one round needs no LDS and is bound by the scalar
 // unit, the search of the next round owns the LDS and leaves half the wave slots empty, so the two share the CUs well.
 struct HcSideStream {
@@ -1498,9 +1486,6 @@ extern "C" int zlz4_launch_compress_hc(hipStream_t stream, const uint8_t *d_in, 
 //
 // workspace: v_off u64[nblocks] | { v_len, start } u32[2 nblocks] | v_len u32[nblocks] | (16-byte boundary)
 //            links T[chunk * stride] | results R[chunk * stride] | visited bits (HBM links) | V [chunk * stride]
-extern "C" int zlz4_launch_hc_dict_stage(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *,
-                                         const uint64_t *, const uint32_t *, uint8_t *, uint64_t, uint64_t *, uint32_t *,
-                                         uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
 
 namespace {
 struct HcDictPlan {

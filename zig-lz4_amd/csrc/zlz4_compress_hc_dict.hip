@@ -3,6 +3,7 @@
 // dictionary call is that pipeline on V = last min(dict_len, 65536) bytes of the dictionary ++ record: this kernel makes
 // V contiguous in the workspace, so that the three kernels need nothing but where the record starts in it.
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 namespace zlz4 {
 

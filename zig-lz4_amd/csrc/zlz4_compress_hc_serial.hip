@@ -21,6 +21,7 @@
 // this is reached often and the emitted sequences are not always real matches: the reference's level-10
 // stream does not always decode.  Parity here means the same bytes as the reference, decodable or not.
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 namespace zlz4 {
 

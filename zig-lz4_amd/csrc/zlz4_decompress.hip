@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 // Diagnostic build only (-DZLZ4_STAMPS): per-phase shader-cycle sums of the wave decoder (tools/stamp_decode.py) in
 // slots 0-7, and event counts (tools/decoder_census.py, restated by tests/seqgen.py model()): 8 batches, 9 sequences

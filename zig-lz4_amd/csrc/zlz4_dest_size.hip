@@ -22,6 +22,7 @@
 // checkpoints always suffice (a sequence consumes at least 5 input bytes): 3 KiB of LDS per wavefront whatever
 // max_in_len.  The walk is lazy: it only goes as far as the largest probe so far needs.
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 namespace zlz4 {
 
@@ -279,9 +280,6 @@ extern "C" size_t zlz4_dest_size_workspace_bytes(uint32_t nblocks, uint32_t max_
     if (nblocks == 0) return 0;
     return (size_t)(dsz_meta(nblocks) + (uint64_t)nblocks * dsz_slot(max_in_len));
 }
-
-extern "C" int zlz4_launch_compress_fast(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                         const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
 
 extern "C" uint32_t zlz4_dest_size_slot_cap(uint32_t max_in_len) { return (uint32_t)(dsz_slot(max_in_len) - zlz4::kSlotPad); }
 

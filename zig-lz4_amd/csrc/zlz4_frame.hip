@@ -19,84 +19,14 @@
 
 #include <cstdint>
 #include <cstring>
-#include <vector>
 
 #include "../../include/zlz4_amd.h"
-#include <mutex>
-#include <vector>
-
 #include "zlz4_device.hpp"
 #include "zlz4_frame_batch.hpp"
 #include "zlz4_host.hpp"
+#include "zlz4_launch.hpp"
 
-extern "C" int zlz4_launch_decompress_safe(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                           const uint64_t *, const uint32_t *, int64_t *, uint32_t);
-extern "C" int zlz4_launch_decompress_sizes(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                            const uint64_t *, const uint32_t *, int64_t *, uint32_t);
-extern "C" int zlz4_launch_decompressed_size(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                             const uint32_t *, int64_t *, uint32_t);
-extern "C" int zlz4_launch_compress_fast(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                         const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, uint32_t);
-extern "C" int zlz4_launch_compress_hc(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint8_t *,
-                                       const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t, int32_t,
-                                       void *, size_t);
-extern "C" size_t zlz4_hc_workspace_bytes(uint32_t nblocks, uint32_t max_in_len);
-extern "C" int zlz4_launch_load_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, uint32_t *, int64_t *,
-                                     uint32_t);
-extern "C" int zlz4_launch_compress_fast_using_dict(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                                    uint8_t *, const uint64_t *, const uint32_t *, const uint8_t *,
-                                                    const uint64_t *, const uint32_t *, const uint32_t *, const uint32_t *,
-                                                    int64_t *, uint32_t, uint32_t, uint32_t, uint32_t);
-// zlz4_frame_linked.hip; `frames` is the BFrame array
-extern "C" int zlz4_launch_bfl_save(hipStream_t, const void *frames, uint32_t, int64_t *);
-extern "C" int zlz4_launch_bfl_mask(hipStream_t, const void *frames, const uint32_t *, uint32_t, uint32_t *, uint32_t *);
-extern "C" int zlz4_launch_bfl_decode(hipStream_t, int write, void *frames, uint32_t, uint32_t, const uint8_t *, const uint64_t *,
-                                      const uint32_t *, const uint32_t *, const uint32_t *, const int64_t *, uint8_t *,
-                                      const uint64_t *, const uint64_t *, const uint64_t *, int64_t *);
-extern "C" int zlz4_launch_bfl_hc_desc(hipStream_t, const void *frames, uint32_t, uint32_t, const uint64_t *, const uint64_t *,
-                                       const uint32_t *, uint64_t *, uint32_t *, uint32_t *);
-extern "C" size_t zlz4_hc_linked_workspace_bytes(uint32_t nblocks, uint32_t max_block_len);
-extern "C" int zlz4_launch_compress_hc_linked(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *, const uint32_t *,
-                                              uint8_t *, const uint64_t *, const uint32_t *, int64_t *, uint32_t, uint32_t,
-                                              int32_t, void *, size_t);
-extern "C" int zlz4_launch_bfl_dict_desc(hipStream_t, const void *frames, uint32_t, uint32_t, const uint64_t *,
-                                         const uint64_t *, const uint32_t *, uint64_t *, uint32_t *);
-
-// ------------------------------------------------------------------ device buffers (zlz4_host.hpp)
-namespace {
-struct ParkedBuf { void *p; size_t n; int dev; };
-std::mutex g_park_mutex;
-std::vector<ParkedBuf> g_parked;
-size_t g_parked_bytes = 0;
-constexpr size_t kMaxParked = 12;
-constexpr size_t kMaxParkedBytes = 8ull << 30;   // ~3 % of the HBM: one configs[4] slot arena (4 GiB) and its tables
-}  // namespace
-
-namespace zlz4host {
-void *cache_take(size_t &n, int dev) {
-    std::lock_guard<std::mutex> lock(g_park_mutex);
-    size_t best = g_parked.size();
-    for (size_t i = 0; i < g_parked.size(); i++)     // smallest parked buffer that fits and is not wastefully large
-        if (g_parked[i].dev == dev && g_parked[i].n >= n && g_parked[i].n / 2 <= n + (1u << 20) &&
-            (best == g_parked.size() || g_parked[i].n < g_parked[best].n))
-            best = i;
-    if (best == g_parked.size()) return nullptr;
-    void *p = g_parked[best].p;
-    n = g_parked[best].n;
-    g_parked_bytes -= n;
-    g_parked.erase(g_parked.begin() + (long)best);
-    return p;
-}
-bool cache_give(void *p, size_t n, int dev) {
-    std::lock_guard<std::mutex> lock(g_park_mutex);
-    if (g_parked.size() >= kMaxParked || g_parked_bytes + n > kMaxParkedBytes) return false;
-    g_parked.push_back({p, n, dev});
-    g_parked_bytes += n;
-    return true;
-}
-}  // namespace zlz4host
-using zlz4host::DevBuf;
-typedef zlz4host::DeviceCall FrameCall;
+using namespace zlz4host;
 
 namespace {
 
@@ -209,16 +139,6 @@ __host__ __device__ inline ParsedHeader parse_header(const uint8_t *src, size_t 
     r.size = (int64_t)pos;
     r.flg = flg;
     return r;
-}
-
-extern "C" void zlz4_release_device_cache(void) {
-    std::vector<ParkedBuf> take;
-    {
-        std::lock_guard<std::mutex> lock(g_park_mutex);
-        take.swap(g_parked);
-        g_parked_bytes = 0;
-    }
-    for (const ParkedBuf &b : take) (void)hipFree(b.p);
 }
 
 // ------------------------------------------------------------------ compress-side kernels
@@ -521,8 +441,6 @@ __host__ __device__ inline int64_t map_block_error(int64_t e) {     // mapCompre
     return ZLZ4F_ERR_GENERIC;
 }
 
-bool gfx950_ok() { return zlz4_device_check() == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -564,7 +482,7 @@ constexpr uint32_t kSegFirst = 1u, kSegLast = 2u;
 int64_t compress_frame_impl(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap, const zlz4f_prefs &p,
                             uint32_t seg) {
     if (cap < zlz4f_compress_frame_bound(n, &p)) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;   // :363-366
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
     HeaderBytes hb = encode_header(p);                                                     // :369
     if (!(seg & kSegFirst)) hb.n = 0;
     const size_t bs = block_size_of(p.block_size_id);                                      // :372
@@ -579,7 +497,7 @@ int64_t compress_frame_impl(hipStream_t st, const uint8_t *d_src, size_t n, uint
     const uint32_t tail = (seg & kSegLast) ? 1u : 0u;
     const uint32_t content_checksum = (tail && p.content_checksum == 1) ? 1u : 0u;
     const uint64_t slot = (zlz4_compress_bound(bs) + 15) & ~15ull;
-    FrameCall fc(st);
+    DeviceCall fc(st);
     DevBuf d_plan(4 * sizeof(int64_t), &fc);
     if (!d_plan.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     int64_t total = 0;
@@ -635,8 +553,8 @@ int64_t compress_frame_impl(hipStream_t st, const uint8_t *d_src, size_t n, uint
 // the bytes are expected to end after a block (no end mark, no content checksum).
 int64_t decompress_frame_impl(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap, const zlz4f_prefs &p,
                               uint32_t seg) {
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    FrameCall fc(st);
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    DeviceCall fc(st);
     DevBuf d_walk(12 * sizeof(int64_t), &fc);
     if (!d_walk.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     int64_t *walk = d_walk.as<int64_t>(), *dplan = walk + 8;
@@ -734,6 +652,18 @@ int64_t decompress_frame_impl(hipStream_t st, const uint8_t *d_src, size_t n, ui
     }
 }
 
+// The host-pointer frame calls: stage src, run device_call(d_src, d_dst) into a device destination of d_cap bytes, copy
+// the first `result` bytes back.  A result <= 0 leaves dst unwritten.
+template <typename Call>
+int64_t host_frame_call(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t d_cap, Call device_call) {
+    DevBuf d_src(n), d_dst(d_cap);
+    if (!d_src.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (n && hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    const int64_t r = device_call(d_src.as<uint8_t>(), d_dst.as<uint8_t>());
+    if (!copy_back(dst, cap, d_dst, r)) return ZLZ4_ERR_DEVICE;
+    return r;
+}
+
 }  // namespace
 
 extern "C" {
@@ -772,30 +702,20 @@ int64_t zlz4f_compress_frame(const uint8_t *src, size_t n, uint8_t *dst, size_t 
     const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
     const size_t bound = zlz4f_compress_frame_bound(n, &p);
     if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    DevBuf d_src(n), d_dst(bound);
-    if (!d_src.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    if (n && hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    const int64_t r = zlz4f_compress_frame_device(nullptr, d_src.as<uint8_t>(), n, d_dst.as<uint8_t>(), bound, &p);
-    if (r < 0) return r;
-    if ((uint64_t)r > cap) return ZLZ4_ERR_DEVICE;
-    if (hipMemcpy(dst, d_dst.p, (size_t)r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    return r;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
+        return zlz4f_compress_frame_device(nullptr, d_src, n, d_dst, bound, &p);
+    });
 }
 
 // src/lz4f.zig:541-638, host pointers
 int64_t zlz4f_decompress_frame(const uint8_t *src, size_t n, uint8_t *dst, size_t cap) {
     const ParsedHeader ph = parse_header(src, n);      // header errors need no device
     if (ph.size < 0) return ph.size;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    DevBuf d_src(n), d_dst(cap);
-    if (!d_src.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    if (hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    const int64_t r = zlz4f_decompress_frame_device(nullptr, d_src.as<uint8_t>(), n, d_dst.as<uint8_t>(), cap);
-    if (r <= 0) return r;
-    if ((uint64_t)r > cap) return ZLZ4_ERR_DEVICE;
-    if (hipMemcpy(dst, d_dst.p, (size_t)r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    return r;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return host_frame_call(src, n, dst, cap, cap, [&](const uint8_t *d_src, uint8_t *d_dst) {
+        return zlz4f_decompress_frame_device(nullptr, d_src, n, d_dst, cap);
+    });
 }
 
 }  // extern "C"
@@ -1378,7 +1298,7 @@ int32_t batch_compress_frame_impl(void *stream_, const uint8_t *d_src, const uin
     if (refused != 0) return refused;
     const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
     const bool link = (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) != 0;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
     const BatchLayout L = bfc_layout(nframes, max_blocks, p, batch_flags);
     if (nframes == 0) return 0;
     if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
@@ -1460,25 +1380,21 @@ int64_t single_compress_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n,
     const uint64_t nb = (uint64_t)n / bs + (n % bs != 0);
     if (nb > 0x7FFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const uint32_t max_blocks = (uint32_t)nb;
-    zlz4host::DeviceCall dc(st);
+    DeviceCall dc(st);
     const size_t ws = bfc_layout(1, max_blocks, p, batch_flags).bytes;
-    DevBuf d_meta(64, &dc), d_ws(ws, &dc);
-    if (!d_meta.p || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    struct Meta { uint64_t src_off, src_len, dst_off, dst_cap; int64_t result; } m = {0, (uint64_t)n, 0, (uint64_t)cap, 0};
-    static_assert(sizeof(Meta) <= 64, "meta");
-    auto *dm = d_meta.as<uint8_t>();
+    Staged<FrameRec> rec(&dc);
+    DevBuf d_ws(ws, &dc);
+    if (!rec.d || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    rec.h.src_len = n; rec.h.dst_cap = cap;
     dc.launched();
-    if (hipMemcpyAsync(dm, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    int64_t *p_result = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
-    const int32_t rc = batch_compress_frame_impl(st, d_src, reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_off)),
-                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_len)), d_dst,
-                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_off)),
-                                                 reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_cap)), p_result, 1,
-                                                 max_blocks, &p, batch_flags, d_ws.p, ws, true);
+    if (!rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    FrameRec *r = rec.d;
+    const int32_t rc = batch_compress_frame_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap, &r->result,
+                                                 1, max_blocks, &p, batch_flags, d_ws.p, ws, true);
     if (rc != 0) return rc;
-    int64_t r = 0;
-    if (hipMemcpyAsync(&r, p_result, sizeof r, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
-    return r;
+    int64_t result = 0;
+    if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
+    return result;
 }
 
 }  // namespace
@@ -1509,7 +1425,7 @@ int64_t zlz4f_compress_frame_device_ex(void *stream, const uint8_t *d_src, size_
     const int32_t refused = bfc_refusal(p, batch_flags, true);
     if (refused != 0) return refused;
     if ((!d_src && n) || (!d_dst && cap)) return ZLZ4_ERR_INVALID_STATE;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
     return single_compress_frame_ex((hipStream_t)stream, d_src, n, d_dst, cap, p, batch_flags);
 }
 
@@ -1522,15 +1438,10 @@ int64_t zlz4f_compress_frame_ex(const uint8_t *src, size_t n, uint8_t *dst, size
     if ((!src && n) || (!dst && cap)) return ZLZ4_ERR_INVALID_STATE;
     const size_t bound = zlz4f_compress_frame_bound(n, &p);
     if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    DevBuf d_src(n), d_dst(bound);
-    if (!d_src.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    if (n && hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    const int64_t r = single_compress_frame_ex(nullptr, d_src.as<uint8_t>(), n, d_dst.as<uint8_t>(), bound, p, batch_flags);
-    if (r < 0) return r;
-    if ((uint64_t)r > cap) return ZLZ4_ERR_DEVICE;
-    if (hipMemcpy(dst, d_dst.p, (size_t)r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    return r;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
+        return single_compress_frame_ex(nullptr, d_src, n, d_dst, bound, p, batch_flags);
+    });
 }
 
 }  // extern "C"
@@ -1546,7 +1457,7 @@ int32_t batch_decompress_frame_impl(void *stream_, const uint8_t *d_src, const u
                                     uint32_t decode_flags, void *d_workspace, size_t workspace_bytes) {
     if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
     const bool linked = (decode_flags & ZLZ4F_DECODE_LINKED) != 0;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
     const BatchLayout L = bfd_layout(nframes, max_blocks, decode_flags);
     if (nframes == 0) return 0;
     if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
@@ -1651,7 +1562,7 @@ int32_t batch_frame_decompressed_size_impl(void *stream_, const uint8_t *d_src, 
     const BatchLayout L = bfq_layout(nframes, max_blocks, decode_flags);
     if (!d_src || !d_src_off || !d_src_len || !d_size || !d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < L.bytes)
         return ZLZ4_ERR_INVALID_STATE;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
     hipStream_t st = (hipStream_t)stream_;
     uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
@@ -1689,24 +1600,17 @@ int32_t batch_frame_decompressed_size_impl(void *stream_, const uint8_t *d_src, 
 int64_t single_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap, uint32_t decode_flags,
                         bool want_size) {
     if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    zlz4host::DeviceCall dc(st);
-    DevBuf d_meta(256, &dc);
-    if (!d_meta.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    struct Meta { uint64_t src_off, src_len, dst_off, dst_cap; int64_t result; uint64_t pad[3]; BFrame fr; } m = {};
-    m.src_len = n;
-    m.dst_cap = cap;
-    static_assert(sizeof(Meta) <= 256, "meta");
-    auto *dm = d_meta.as<uint8_t>();
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    DeviceCall dc(st);
+    struct Rec { FrameRec f; uint64_t pad[3]; BFrame fr; };
+    Staged<Rec> rec(&dc, 256);
+    if (!rec.d) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    rec.h.f.src_len = n; rec.h.f.dst_cap = cap;
     dc.launched();
-    if (hipMemcpyAsync(dm, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    const uint64_t *p_src_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_off)),
-                   *p_src_len = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, src_len)),
-                   *p_dst_off = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_off)),
-                   *p_dst_cap = reinterpret_cast<const uint64_t *>(dm + offsetof(Meta, dst_cap));
-    int64_t *p_result = reinterpret_cast<int64_t *>(dm + offsetof(Meta, result));
-    BFrame *p_fr = reinterpret_cast<BFrame *>(dm + offsetof(Meta, fr));
-    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(1), dim3(256), 0, st, d_src, p_src_off, p_src_len, 1u, 0u, p_fr, nullptr,
+    if (!rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    FrameRec *r = &rec.d->f;
+    BFrame *p_fr = &rec.d->fr;
+    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(1), dim3(256), 0, st, d_src, &r->src_off, &r->src_len, 1u, 0u, p_fr, nullptr,
                        nullptr, nullptr, nullptr, nullptr);
     BFrame F;
     if (hipMemcpyAsync(&F, p_fr, sizeof F, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
@@ -1719,13 +1623,13 @@ int64_t single_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t 
     if (!d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     dc.launched();
     const int32_t rc = want_size
-        ? batch_frame_decompressed_size_impl(st, d_src, p_src_off, p_src_len, p_result, 1, max_blocks, decode_flags, d_ws.p, ws)
-        : batch_decompress_frame_impl(st, d_src, p_src_off, p_src_len, d_dst, p_dst_off, p_dst_cap, p_result, 1, max_blocks,
-                                      decode_flags, d_ws.p, ws);
+        ? batch_frame_decompressed_size_impl(st, d_src, &r->src_off, &r->src_len, &r->result, 1, max_blocks, decode_flags, d_ws.p, ws)
+        : batch_decompress_frame_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap, &r->result, 1,
+                                      max_blocks, decode_flags, d_ws.p, ws);
     if (rc != 0) return rc;
-    int64_t r = 0;
-    if (hipMemcpyAsync(&r, p_result, sizeof r, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
-    return r;
+    int64_t result = 0;
+    if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
+    return result;
 }
 
 }  // namespace
@@ -1759,15 +1663,10 @@ int64_t zlz4f_decompress_frame_ex(const uint8_t *src, size_t n, uint8_t *dst, si
     if ((!src && n) || (!dst && cap)) return ZLZ4_ERR_INVALID_STATE;
     const ParsedHeader ph = parse_header(src, n);      // header errors need no device
     if (ph.size < 0) return ph.size;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
-    DevBuf d_src(n), d_dst(cap);
-    if (!d_src.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    if (hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    const int64_t r = single_frame_ex(nullptr, d_src.as<uint8_t>(), n, d_dst.as<uint8_t>(), cap, decode_flags, false);
-    if (r <= 0) return r;
-    if ((uint64_t)r > cap) return ZLZ4_ERR_DEVICE;
-    if (hipMemcpy(dst, d_dst.p, (size_t)r, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    return r;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return host_frame_call(src, n, dst, cap, cap, [&](const uint8_t *d_src, uint8_t *d_dst) {
+        return single_frame_ex(nullptr, d_src, n, d_dst, cap, decode_flags, false);
+    });
 }
 
 int64_t zlz4f_frame_decompressed_size_ex(const uint8_t *src, size_t n, uint32_t decode_flags) {
@@ -1775,7 +1674,7 @@ int64_t zlz4f_frame_decompressed_size_ex(const uint8_t *src, size_t n, uint32_t 
     if (!src && n) return ZLZ4_ERR_INVALID_STATE;
     const ParsedHeader ph = parse_header(src, n);
     if (ph.size < 0) return ph.size;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
     DevBuf d_src(n);
     if (!d_src.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     if (hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
@@ -1789,7 +1688,7 @@ int64_t zlz4f_frame_decompressed_size(const uint8_t *src, size_t n) {
     if (!src && n) return ZLZ4_ERR_INVALID_STATE;
     const ParsedHeader ph = parse_header(src, n);      // header errors need no device
     if (ph.size < 0) return ph.size;
-    if (!gfx950_ok()) return ZLZ4_ERR_DEVICE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
     const bool bc = (ph.flg & 0x10u) != 0;
     uint64_t pos = (uint64_t)ph.size, nb = 0;
     while (pos + 4 <= n) {
@@ -1804,21 +1703,21 @@ int64_t zlz4f_frame_decompressed_size(const uint8_t *src, size_t n) {
     const uint32_t max_blocks = (uint32_t)nb;
     const size_t ws = zlz4f_batch_frame_decompressed_size_workspace(1, max_blocks);
     hipStream_t st = nullptr;
-    zlz4host::DeviceCall dc(st);
-    DevBuf d_src(n, &dc), d_meta(64, &dc), d_ws(ws, &dc);
-    if (!d_src.p || !d_meta.p || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    struct Meta { uint64_t off, len; int64_t size; } m = {0, (uint64_t)n, 0};
+    DeviceCall dc(st);
+    DevBuf d_src(n, &dc);
+    Staged<FrameRec> rec(&dc);
+    DevBuf d_ws(ws, &dc);
+    if (!d_src.p || !rec.d || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    rec.h.src_len = n;
     dc.launched();
-    if (hipMemcpyAsync(d_src.p, src, n, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_meta.p, &m, sizeof m, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    auto *dm = d_meta.as<uint8_t>();
-    const int32_t rc = zlz4f_batch_frame_decompressed_size(st, d_src.as<uint8_t>(), reinterpret_cast<const uint64_t *>(dm),
-                                                           reinterpret_cast<const uint64_t *>(dm + 8),
-                                                           reinterpret_cast<int64_t *>(dm + 16), 1, max_blocks, d_ws.p, ws);
+    if (!upload(d_src, src, n, st) || !rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    FrameRec *r = rec.d;
+    const int32_t rc = zlz4f_batch_frame_decompressed_size(st, d_src.as<uint8_t>(), &r->src_off, &r->src_len, &r->result, 1,
+                                                           max_blocks, d_ws.p, ws);
     if (rc != 0) return rc;
-    int64_t r = 0;
-    if (hipMemcpyAsync(&r, dm + 16, sizeof r, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
-    return r;
+    int64_t result = 0;
+    if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
+    return result;
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 #include "../../include/zlz4_amd.h"
 #include "zlz4_device.hpp"
 #include "zlz4_frame_batch.hpp"
+#include "zlz4_launch.hpp"
 
 namespace {
 

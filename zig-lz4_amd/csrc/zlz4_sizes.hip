@@ -19,6 +19,7 @@
 //
 // k_plan_outputs turns sizes into packed output slots (offset, capacity, total) on the device.
 #include "zlz4_device.hpp"
+#include "zlz4_launch.hpp"
 
 namespace zlz4 {
 

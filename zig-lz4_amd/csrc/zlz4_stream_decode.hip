@@ -23,10 +23,7 @@
 
 #include "../../include/zlz4_amd.h"
 #include "zlz4_device.hpp"
-
-extern "C" int zlz4_launch_decompress_safe_bound(hipStream_t, const uint8_t *, const uint64_t *, const uint32_t *,
-                                                 uint8_t *, const uint64_t *, const uint32_t *, int64_t *, uint32_t,
-                                                 const uint8_t *, const uint64_t *, const uint32_t *, int);
+#include "zlz4_launch.hpp"
 
 namespace zlz4 {
 
