@@ -650,6 +650,97 @@ int64_t zlz4f_decompress_frame_device_ex(void *stream, const uint8_t *d_src, siz
 int64_t zlz4f_decompress_frame_ex(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t decode_flags);
 int64_t zlz4f_frame_decompressed_size_ex(const uint8_t *src, size_t src_len, uint32_t decode_flags);
 
+/* Dictionary frames (the lz4 frame format's dictID frames: `lz4 -D dict`, liblz4's LZ4F_compressFrame_usingCDict /
+ * LZ4F_decompress_usingDict; no counterpart in the reference).  T is the last D = min(dict_len, 65536) bytes of a frame's
+ * dictionary, pos the bytes of the frame decoded (or consumed) so far.  Header (prefs->dict_id as given), block headers,
+ * the stored-block rule, checksums, content size and the end mark are those of the calls above.
+ *
+ * Dictionary arguments, the same in every batch call: dictionary d is d_dict + d_dict_off[d], d_dict_len[d] bytes (any
+ * length), d < ndicts; frame f uses dictionary d_dict_idx[f] (d_dict_idx == NULL: dictionary 0 for every frame; one shared
+ * dictionary is ndicts = 1 with a NULL index).  d_dict_idx[f] >= ndicts gives that frame ZLZ4_ERR_INVALID_STATE (in front
+ * of every other status of the frame), nothing is written for it and the other frames are unaffected.  Dictionaries are
+ * read-only and must not overlap any destination slot.  The header's dictID stays informational: the caller picks the
+ * dictionary, as with liblz4 (zlz4f_batch_frame_dict_id reads the field: d_dict_id[f] = the dictID, 0 when the frame has
+ * none, or the header's error code; one lane per frame, so that a d_dict_idx can be built on the device).
+ *
+ * Decode (always history-aware, no decode_flags).  A compressed block of a frame whose FLG has the block-independence bit
+ *   - SET is zlz4_decompress_safe_using_dict(block, dst[pos .. cap], dict = T): every block sees the dictionary.  These
+ *     frames stay on the parallel pipeline of zlz4f_batch_decompress_frame with a dictionary descriptor per table entry.
+ *   - CLEAR has the last 65536 bytes of T ++ dst[0 .. pos) as its history: a match at block output position op with offset
+ *     o copies from index D + pos + op - o of W = T ++ dst[0 .. pos + op), byte by byte -- it may start in T, run across
+ *     T's end into the frame's first output bytes and run over itself -- and is CorruptedData iff o > op + pos + D
+ *     (tested after the match's OutputTooSmall test, src/lz4.zig:174, :189-192).  Stored blocks are copied and are
+ *     history.  One wavefront per frame, as with ZLZ4F_DECODE_LINKED -- except a frame of one block, whose history is T
+ *     alone: it is decoded with the independent frames (the same bytes and status; what the default preferences write for
+ *     a small record).
+ *   With D == 0: bytes and status of zlz4f_batch_decompress_frame_ex(.., ZLZ4F_DECODE_LINKED, ..).  Error order of
+ *   src/lz4f.zig:541-638 as there; DecompressionFailed (:611) is decided by the dictionary-aware decode.
+ *   Workspace: the layout of zlz4f_batch_decompress_frame_workspace_ex(.., ZLZ4F_DECODE_LINKED) + 12 bytes per frame (where
+ *   T ends, D) + 12 bytes per table entry (dictionary descriptors), each area rounded up to 256 bytes.
+ * Size query: the same two paths with nothing written; only the dictionary lengths are needed (zlz4_batch_decompressed_size);
+ *   the content checksum is excepted as in zlz4f_batch_frame_decompressed_size.  Workspace: that of
+ *   zlz4f_batch_frame_decompressed_size_workspace_ex(.., ZLZ4F_DECODE_LINKED) + 4 bytes per frame + 4 bytes per table entry.
+ *
+ * Compress: the fast level only (compression_level <= 0, acceleration 1); prefs->block_mode decides, so that FLG declares
+ * what the blocks are:
+ *   - block_mode == 1: block k = zlz4_compress_fast_using_dict(X_k, dict = T) with T's own zlz4_batch_load_dict table, every k.
+ *   - block_mode == 0: block 0 is the same call; block k >= 1 is the ZLZ4F_BATCH_LINK_BLOCKS block (dict = the input
+ *     [k * bs - 65536, k * bs): block sizes are >= 64 KiB, so T is out of reach from block 1 on).
+ *   With an empty dictionary, byte for byte and status for status: zlz4f_batch_compress_frame (block_mode 1) and
+ *   zlz4f_batch_compress_frame(.., ZLZ4F_BATCH_LINK_BLOCKS) (block_mode 0).  A using-dict block is at most
+ *   zlz4_compress_bound(len), so the compressFrameBound check per frame and zlz4f_compress_frame_bound stay as they are.
+ *   batch_flags: ZLZ4F_BATCH_CONTENT_SIZE only (with its rule about prefs->content_size).  Refusals, each launching nothing,
+ *   in this order: another flag bit, ZLZ4F_BATCH_LINK_BLOCKS included, or the content-size rule (ZLZ4F_ERR_PARAMETER_INVALID);
+ *   compression_level > 0 (ZLZ4_ERR_UNSUPPORTED); the device; null or misaligned arrays (8 bytes for the 64-bit arrays, 4
+ *   for the 32-bit ones; d_dict may be NULL when max_dict_len == 0), a workspace that is too small, null or not 16-byte
+ *   aligned (ZLZ4_ERR_INVALID_STATE).
+ *   max_src_len and max_dict_len are preconditions as in the block calls: a frame with d_src_len[f] > max_src_len
+ *   (max_src_len == 0: no bound) or whose dictionary has min(len, 65536) > max_dict_len gets ZLZ4_ERR_INVALID_STATE and
+ *   writes nothing.  The dictionary compressor is given min(bs, max_src_len) as its max_in_len, so small records against a
+ *   small dictionary keep the 16-bit table; output bytes do not depend on it.  The ndicts dictionaries are hashed once per
+ *   call, not once per frame.
+ *   Workspace: frames | 3 x u64, 4 x u32, i64 per table entry | a compressBound-sized slot per entry | one loadDict table
+ *   (16 KiB) and an i64 per dictionary | 20 bytes of descriptors per entry; when block_mode == 0 and a frame may have a
+ *   second block (max_src_len == 0 or > block size) also one loadDict table and 36 bytes per entry; each area rounded up to
+ *   256 bytes.  batch_flags and max_dict_len do not change it.
+ * max_blocks, ZLZ4_ERR_INVALID_STATE per frame, the slot guarantee and "nothing allocated, nothing read back, fixed launch
+ * sequence, graph-capturable" are those of the batch frame calls above.  The single-frame calls take HOST pointers, stage
+ * the frame and the dictionary's tail and run a batch of one; dict == NULL with dict_len > 0 gives InvalidState.
+ * HC levels with a frame dictionary and the segment calls have no dictionary form. */
+size_t  zlz4f_batch_compress_frame_using_dict_workspace(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
+                                                        uint32_t batch_flags, uint32_t ndicts, uint64_t max_src_len,
+                                                        uint32_t max_dict_len);
+int32_t zlz4f_batch_compress_frame_using_dict(void *stream,
+                                              const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                              uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                                              int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                              const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                              const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                              uint32_t ndicts, const uint32_t *d_dict_idx,
+                                              uint64_t max_src_len, uint32_t max_dict_len,
+                                              void *d_workspace, size_t workspace_bytes);
+size_t  zlz4f_batch_decompress_frame_using_dict_workspace(uint32_t nframes, uint32_t max_blocks);
+int32_t zlz4f_batch_decompress_frame_using_dict(void *stream,
+                                                const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                                uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                                                int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                                const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                                uint32_t ndicts, const uint32_t *d_dict_idx,
+                                                void *d_workspace, size_t workspace_bytes);
+size_t  zlz4f_batch_frame_decompressed_size_using_dict_workspace(uint32_t nframes, uint32_t max_blocks);
+int32_t zlz4f_batch_frame_decompressed_size_using_dict(void *stream,
+                                                       const uint8_t *d_src, const uint64_t *d_src_off,
+                                                       const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
+                                                       uint32_t max_blocks, const uint32_t *d_dict_len, uint32_t ndicts,
+                                                       const uint32_t *d_dict_idx, void *d_workspace, size_t workspace_bytes);
+int32_t zlz4f_batch_frame_dict_id(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                  int64_t *d_dict_id, uint32_t nframes);
+int64_t zlz4f_compress_frame_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                        const zlz4f_prefs *prefs, const uint8_t *dict, size_t dict_len);
+int64_t zlz4f_decompress_frame_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                          const uint8_t *dict, size_t dict_len);
+int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t src_len, size_t dict_len);
+
 /* ======================================================================
  * 4. Introspection
  * ====================================================================== */

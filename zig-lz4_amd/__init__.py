@@ -119,6 +119,17 @@ SYMBOLS = {
     "zlz4f_batch_decompress_frame_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32, _VP, _SZ]),
     "zlz4f_decompress_frame_device_ex": (_I64, [_VP, _VP, _SZ, _VP, _SZ, _U32]),
     "zlz4f_decompress_frame_ex": (_I64, [_VP, _SZ, _VP, _SZ, _U32]),
+    "zlz4f_batch_compress_frame_using_dict_workspace": (_SZ, [_U32, _U32, _PP, _U32, _U32, C.c_uint64, _U32]),
+    "zlz4f_batch_compress_frame_using_dict": (_I32, [_VP] * 8 + [_U32, _U32, _PP, _U32, _VP, _VP, _VP, _U32, _VP, C.c_uint64,
+                                                     _U32, _VP, _SZ]),
+    "zlz4f_batch_decompress_frame_using_dict_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_decompress_frame_using_dict": (_I32, [_VP] * 8 + [_U32, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _SZ]),
+    "zlz4f_batch_frame_decompressed_size_using_dict_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_frame_decompressed_size_using_dict": (_I32, [_VP] * 5 + [_U32, _U32, _VP, _U32, _VP, _VP, _SZ]),
+    "zlz4f_batch_frame_dict_id": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4f_compress_frame_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _PP, _VP, _SZ]),
+    "zlz4f_decompress_frame_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ]),
+    "zlz4f_frame_decompressed_size_using_dict": (_I64, [_VP, _SZ, _SZ]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -646,6 +657,170 @@ class lz4f:
                                   max_blocks=sum(_chain_blocks(bytes(f)) for f in frames), flags=flags)
         out = _unstage(d_dst, _offsets(caps), result)
         if sizes is not None:                         # (a frame the query failed got no room: the query's code stands)
+            out = [o if s >= 0 else s for o, s in zip(out, sizes)]
+        return out
+
+    # dictionary frames (include/zlz4_amd.h: the _using_dict frame calls)
+    @staticmethod
+    def compressFrameUsingDict(src, dict, prefs=None, dst_cap=None):
+        """zlz4f_compress_frame_using_dict: one frame whose blocks are compressed against `dict` (fast level;
+        prefs.block_mode 1: every block, 0: block 0, the later blocks against the input in front of them)."""
+        cap = lz4f.compressFrameBound(len(src), prefs) if dst_cap is None else dst_cap
+        d, dn = _in(dict if dict is not None else b"")
+        return _run(lib().zlz4f_compress_frame_using_dict, src, cap, C.byref(prefs) if prefs is not None else None,
+                    C.addressof(d) if dn else None, dn)
+
+    @staticmethod
+    def decompressFrameUsingDict(src, dst_cap, dict):
+        """zlz4f_decompress_frame_using_dict: what liblz4's LZ4F_decompress_usingDict gives for `src` and `dict`."""
+        d, dn = _in(dict if dict is not None else b"")
+        return _run(lib().zlz4f_decompress_frame_using_dict, src, dst_cap, C.addressof(d) if dn else None, dn)
+
+    @staticmethod
+    def frameDecompressedSizeUsingDict(src, dict_len):
+        s, n = _in(src)
+        return _check(lib().zlz4f_frame_decompressed_size_using_dict(C.addressof(s), n, dict_len))
+
+    @staticmethod
+    def compressFrameUsingDictBatchWorkspace(nframes, max_blocks, prefs=None, batch_flags=0, ndicts=1, max_src_len=0,
+                                             max_dict_len=65536):
+        return lib().zlz4f_batch_compress_frame_using_dict_workspace(nframes, max_blocks,
+                                                                     C.byref(prefs) if prefs is not None else None,
+                                                                     batch_flags, ndicts, max_src_len, max_dict_len)
+
+    @staticmethod
+    def decompressFrameUsingDictBatchWorkspace(nframes, max_blocks):
+        return lib().zlz4f_batch_decompress_frame_using_dict_workspace(nframes, max_blocks)
+
+    @staticmethod
+    def frameDecompressedSizeUsingDictBatchWorkspace(nframes, max_blocks):
+        return lib().zlz4f_batch_frame_decompressed_size_using_dict_workspace(nframes, max_blocks)
+
+    @staticmethod
+    def compressFrameUsingDictBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, d_dict, dict_off, dict_len,
+                                    dict_idx=None, prefs=None, batch_flags=0, max_blocks=None, max_src_len=0,
+                                    max_dict_len=65536, workspace=None):
+        """zlz4f_batch_compress_frame_using_dict on torch CUDA tensors (layout as compressFrameBatch): dictionary d is
+        d_dict[dict_off[d] .. + dict_len[d]) (int64 offsets, int32 lengths), frame f uses dictionary dict_idx[f] (int32;
+        None: dictionary 0).  Enqueued on the current stream; nothing is synchronised."""
+        import torch
+        if max_blocks is None:
+            bs = lz4f.BLOCK_SIZES.get(prefs.block_size_id if prefs is not None else 0, 64 << 10)
+            max_blocks = int(((src_len.cpu() + bs - 1) // bs).sum()) if src_len.numel() else 0
+        pp = C.byref(prefs) if prefs is not None else None
+        nd = dict_len.numel()
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_compress_frame_using_dict_workspace(
+                src_len.numel(), max_blocks, pp, batch_flags, nd, max_src_len, max_dict_len)), dtype=torch.uint8,
+                device=d_src.device)
+        _check(lib().zlz4f_batch_compress_frame_using_dict(
+            _stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst), _ptr(dst_off), _ptr(dst_cap), _ptr(result),
+            src_len.numel(), max_blocks, pp, batch_flags, _ptr(d_dict), _ptr(dict_off), _ptr(dict_len), nd, _ptr(dict_idx),
+            max_src_len, max_dict_len, _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def decompressFrameUsingDictBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, d_dict, dict_off, dict_len,
+                                      dict_idx=None, max_blocks=None, workspace=None):
+        """zlz4f_batch_decompress_frame_using_dict on torch CUDA tensors (layout as decompressFrameBatch, dictionaries as
+        compressFrameUsingDictBatch); max_blocks defaults as in decompressFrameBatch."""
+        import torch
+        if max_blocks is None:
+            max_blocks = int((src_len.cpu() // 256 + 1).sum()) if src_len.numel() else 0
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_decompress_frame_using_dict_workspace(src_len.numel(),
+                                                                                                    max_blocks)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_decompress_frame_using_dict(
+            _stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst), _ptr(dst_off), _ptr(dst_cap), _ptr(result),
+            src_len.numel(), max_blocks, _ptr(d_dict), _ptr(dict_off), _ptr(dict_len), dict_len.numel(), _ptr(dict_idx),
+            _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def frameDecompressedSizeUsingDictBatch(d_src, src_off, src_len, size, dict_len, dict_idx=None, max_blocks=None,
+                                            workspace=None):
+        """zlz4f_batch_frame_decompressed_size_using_dict on torch CUDA tensors: only the dictionary lengths (int32) are
+        needed."""
+        import torch
+        if max_blocks is None:
+            max_blocks = int((src_len.cpu() // 256 + 1).sum()) if src_len.numel() else 0
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_frame_decompressed_size_using_dict_workspace(
+                src_len.numel(), max_blocks)), dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_frame_decompressed_size_using_dict(
+            _stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(size), src_len.numel(), max_blocks, _ptr(dict_len),
+            dict_len.numel(), _ptr(dict_idx), _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def frameDictIDBatch(d_src, src_off, src_len, dict_id):
+        """zlz4f_batch_frame_dict_id: dict_id[f] (int64) = the header's dictID, 0 without one, or the header's error."""
+        _check(lib().zlz4f_batch_frame_dict_id(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(dict_id),
+                                               src_len.numel()))
+
+    @staticmethod
+    def frameDictIDs(frames, device="cuda"):
+        """The dictID of every frame of `frames` (0: none; a negative code: the header's error) -> list of ints."""
+        import torch
+        if len(frames) == 0:
+            return []
+        d_src, src_off, src_len = _stage(frames, device)
+        ids = torch.empty(len(frames), dtype=torch.int64, device=device)
+        lz4f.frameDictIDBatch(d_src, src_off, src_len, ids)
+        return ids.cpu().tolist()
+
+    @staticmethod
+    def _stage_dicts(dicts, dict_index, n, device):
+        import torch
+        dbytes = [bytes(d) if d is not None else b"" for d in dicts]
+        d_dict, dict_off, dict_len = _stage(dbytes, device)
+        idx = None if dict_index is None else torch.tensor([int(k) for k in dict_index], dtype=torch.int32, device=device)
+        return d_dict, dict_off, dict_len.to(torch.int32), idx, dbytes
+
+    @staticmethod
+    def compressFramesUsingDict(items, dicts, dict_index=None, prefs=None, device="cuda"):
+        """Every byte string of `items` as its own frame against dicts[dict_index[f]] (dict_index None: dicts[0] for every
+        frame), in one batch call -> list of frames (bytes) or error codes."""
+        import torch
+        if len(items) == 0:
+            return []
+        lens = [len(b) for b in items]
+        caps = [lz4f.compressFrameBound(n, prefs) for n in lens]
+        d_src, src_off, src_len = _stage(items, device)
+        d_dict, dict_off, dict_len, idx, dbytes = lz4f._stage_dicts(dicts, dict_index, len(items), device)
+        dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+        d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+        result = torch.empty(len(items), dtype=torch.int64, device=device)
+        lz4f.compressFrameUsingDictBatch(d_src, src_off, src_len, d_dst, dst_off,
+                                         torch.tensor(caps, dtype=torch.int64, device=device), result, d_dict, dict_off,
+                                         dict_len, idx, prefs, 0, max_src_len=max(lens),
+                                         max_dict_len=min(65536, max((len(d) for d in dbytes), default=0)))
+        return _unstage(d_dst, _offsets(caps), result)
+
+    @staticmethod
+    def decompressFramesUsingDict(frames, dicts, dict_index=None, caps=None, device="cuda"):
+        """Every frame of `frames` decoded with dicts[dict_index[f]] (dict_index None: dicts[0]) into caps[f] bytes, in one
+        batch call -> list of contents (bytes) or error codes.  caps None: the sizes are queried first, as in
+        decompressFrames."""
+        import torch
+        if len(frames) == 0:
+            return []
+        d_src, src_off, src_len = _stage(frames, device)
+        d_dict, dict_off, dict_len, idx, _ = lz4f._stage_dicts(dicts, dict_index, len(frames), device)
+        mb = sum(_chain_blocks(bytes(f)) for f in frames)
+        sizes = None
+        if caps is None:
+            size = torch.empty(len(frames), dtype=torch.int64, device=device)
+            lz4f.frameDecompressedSizeUsingDictBatch(d_src, src_off, src_len, size, dict_len, idx, max_blocks=mb)
+            sizes = size.cpu().tolist()
+            caps = [max(s, 0) for s in sizes]
+        caps = list(caps)
+        dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+        d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+        result = torch.empty(len(frames), dtype=torch.int64, device=device)
+        lz4f.decompressFrameUsingDictBatch(d_src, src_off, src_len, d_dst, dst_off,
+                                           torch.tensor(caps, dtype=torch.int64, device=device), result, d_dict, dict_off,
+                                           dict_len, idx, max_blocks=mb)
+        out = _unstage(d_dst, _offsets(caps), result)
+        if sizes is not None:
             out = [o if s >= 0 else s for o, s in zip(out, sizes)]
         return out
 

@@ -879,6 +879,21 @@ extern "C" int zlz4_launch_decompress_sizes(hipStream_t stream, const uint8_t *d
     return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 
+// the size pass of decompressSafeUsingDict: the kDict build without a byte written or a dictionary byte read (every
+// dictionary load sits under kWrite); dend is address arithmetic only
+extern "C" int zlz4_launch_decompress_sizes_using_dict(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                       const uint32_t *d_in_len, const uint64_t *d_out_off,
+                                                       const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks,
+                                                       const uint64_t *d_dict_off, const uint32_t *d_dict_len) {
+    if (nblocks == 0) return 0;
+    const uint32_t waves_per_wg = 4;
+    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
+    hipLaunchKernelGGL((zlz4::k_decompress_safe<false, false, false, true>), dim3(grid), dim3(64 * waves_per_wg), 0, stream,
+                       d_in, d_in_off, d_in_len, (uint8_t *)nullptr, d_out_off, d_out_cap, d_result, nblocks, 0u,
+                       (const uint8_t *)nullptr, d_dict_off, d_dict_len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
 #ifdef ZLZ4_STAMPS
 extern "C" int zlz4_debug_read_dstamps(unsigned long long *out16, int reset) {
     if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_zlz4_dstamps), 16 * sizeof(unsigned long long)) != hipSuccess) return -7;

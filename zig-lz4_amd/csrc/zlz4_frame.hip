@@ -1175,7 +1175,7 @@ __global__ __launch_bounds__(256) void k_bfq_total(const BFrame *__restrict__ fr
 
 // ------------------------------------------------------------------ workspace layout
 struct BatchLayout {
-    size_t off[20];
+    size_t off[24];
     size_t bytes = 0;
     int n = 0;
     size_t add(size_t b) { const size_t o = bytes; off[n++] = o; bytes = (o + b + 255) & ~(size_t)255; return o; }
@@ -1224,7 +1224,9 @@ BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs 
 
 // decompress: frames | data_off cks_off out_off x_off (u64) | data_len flags fidx cks_ok out_cap dec_len x_cap x_len (u32)
 // | sizes (i64); with ZLZ4F_DECODE_LINKED also: | walk_err (i64 per frame)
-BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0) {
+// with a dictionary (the _using_dict calls, always history-aware) also: | fd_end (u64 per frame) | fd_len (u32 per frame)
+// | e_off (u64 per entry) | e_len (u32 per entry)
+BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0, bool dict = false) {
     const size_t m = max_blocks;
     BatchLayout L;
     L.add((size_t)nframes * sizeof(BFrame));
@@ -1232,12 +1234,19 @@ BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_fl
     for (int k = 0; k < 8; k++) L.add(m * sizeof(uint32_t));
     L.add(m * sizeof(int64_t));
     if (decode_flags & ZLZ4F_DECODE_LINKED) L.add((size_t)nframes * sizeof(int64_t));
+    if (dict) {
+        L.add((size_t)nframes * sizeof(uint64_t));
+        L.add((size_t)nframes * sizeof(uint32_t));
+        L.add(m * sizeof(uint64_t));
+        L.add(m * sizeof(uint32_t));
+    }
     return L;
 }
 
 // size query: frames | data_off cks_off (u64) | data_len flags fidx cks_ok dec_len (u32) | sizes (i64); with
 // ZLZ4F_DECODE_LINKED also: | walk_err (i64 per frame)
-BatchLayout bfq_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0) {
+// with a dictionary also: | fd_len (u32 per frame) | e_len (u32 per entry)
+BatchLayout bfq_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0, bool dict = false) {
     const size_t m = max_blocks;
     BatchLayout L;
     L.add((size_t)nframes * sizeof(BFrame));
@@ -1245,8 +1254,23 @@ BatchLayout bfq_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_fl
     for (int k = 0; k < 5; k++) L.add(m * sizeof(uint32_t));
     L.add(m * sizeof(int64_t));
     if (decode_flags & ZLZ4F_DECODE_LINKED) L.add((size_t)nframes * sizeof(int64_t));
+    if (dict) {
+        L.add((size_t)nframes * sizeof(uint32_t));
+        L.add(m * sizeof(uint32_t));
+    }
     return L;
 }
+
+// the dictionary arguments of the _using_dict calls (include/zlz4_amd.h); a null BfDict * is a call without them
+struct BfDict {
+    const uint8_t *dict;
+    const uint64_t *off;
+    const uint32_t *len;
+    uint32_t n;
+    const uint32_t *idx;
+};
+
+inline bool bf_misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 inline uint32_t bf_grid(uint64_t items, uint32_t threads, uint32_t cap = 0xFFFFFFFFu) {
     const uint64_t g = (items + threads - 1) / threads;
@@ -1372,6 +1396,134 @@ int32_t batch_compress_frame_impl(void *stream_, const uint8_t *d_src, const uin
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
+// ------------------------------------------------------------------ dictionary frames, compress
+// Launch B (the linked path of section 4.4c for the blocks k >= 1) is needed when FLG declares linked blocks and a frame
+// can have a second block.
+bool bfcd_link_b(const zlz4f_prefs &p, uint64_t max_src_len) {
+    return p.block_mode != 1 && !(max_src_len != 0 && max_src_len <= block_size_of(p.block_size_id));
+}
+
+// frames | in_off out_off dst_off (u64) | in_len out_cap hdr cks (u32) | csize (i64) | slots | loadDict tables of the
+// dictionaries | their dictSize (i64) | len_a (u32) | a_off (u64) | a_len a_tix (u32); with launch B also: | len_b (u32) |
+// loadDict tables per entry | b_off (u64) | b_len (u32) | dictSize (i64) | csize_b (i64)
+BatchLayout bfcd_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t ndicts, uint64_t max_src_len) {
+    const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
+    BatchLayout L;
+    L.add((size_t)nframes * sizeof(BFrame));
+    for (int k = 0; k < 3; k++) L.add(m * sizeof(uint64_t));
+    for (int k = 0; k < 4; k++) L.add(m * sizeof(uint32_t));
+    L.add(m * sizeof(int64_t));
+    L.add(m * bf_slot(bs));
+    L.add((size_t)ndicts * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
+    L.add((size_t)ndicts * sizeof(int64_t));
+    L.add(m * sizeof(uint32_t));
+    L.add(m * sizeof(uint64_t));
+    for (int k = 0; k < 2; k++) L.add(m * sizeof(uint32_t));
+    if (bfcd_link_b(p, max_src_len)) {
+        L.add(m * sizeof(uint32_t));
+        L.add(m * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
+        L.add(m * sizeof(uint64_t));
+        L.add(m * sizeof(uint32_t));
+        for (int k = 0; k < 2; k++) L.add(m * sizeof(int64_t));
+    }
+    return L;
+}
+
+// the refusals that need no device, in their order: parameter errors, then the levels this call does not serve
+int32_t bfcd_refusal(const zlz4f_prefs &p, uint32_t batch_flags) {
+    if (batch_flags & ~ZLZ4F_BATCH_CONTENT_SIZE) return ZLZ4F_ERR_PARAMETER_INVALID;   // block_mode says "linked"
+    if ((batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) && p.content_size != 0) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (bf_hc_level(p) > 0) return ZLZ4_ERR_UNSUPPORTED;
+    return 0;
+}
+
+// batch_compress_frame_impl at the fast level with a dictionary per frame.  The ndicts dictionaries are hashed once
+// (zlz4_launch_load_dict over them, never per frame); launch A compresses every block of an independent frame and block 0
+// of a linked one against the frame's dictionary where it lies in d_dict, launch B the blocks k >= 1 of a linked frame
+// against the input in front of them where it lies in d_src (section 4.4c).  The two launches run over complementary
+// length arrays into the same slots; k_bfcd_merge takes B's results for B's entries only.
+int32_t batch_compress_frame_dict_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
+                                       const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                       const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                       const zlz4f_prefs *prefs, uint32_t batch_flags, const BfDict &dd, uint64_t max_src_len,
+                                       uint32_t max_dict_len, void *d_workspace, size_t workspace_bytes) {
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    const int32_t refused = bfcd_refusal(p, batch_flags);
+    if (refused != 0) return refused;
+    const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const BatchLayout L = bfcd_layout(nframes, max_blocks, p, dd.n, max_src_len);
+    if (nframes == 0) return 0;
+    if (!d_src || !d_src_off || !d_src_len || !d_dst || !d_dst_off || !d_dst_cap || !d_result ||
+        (dd.n && (!dd.off || !dd.len)) || (dd.n && max_dict_len && !dd.dict) || bf_misaligned(d_src_off, 8) ||
+        bf_misaligned(d_src_len, 8) || bf_misaligned(d_dst_off, 8) || bf_misaligned(d_dst_cap, 8) || bf_misaligned(d_result, 8) ||
+        bf_misaligned(dd.off, 8) || bf_misaligned(dd.len, 4) || bf_misaligned(dd.idx, 4))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (workspace_bytes < L.bytes || !d_workspace || bf_misaligned(d_workspace, 16)) return ZLZ4_ERR_INVALID_STATE;
+    hipStream_t st = (hipStream_t)stream_;
+    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
+    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
+    uint64_t *in_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *out_off = reinterpret_cast<uint64_t *>(ws + L.off[2]),
+             *dst_off = reinterpret_cast<uint64_t *>(ws + L.off[3]);
+    uint32_t *in_len = reinterpret_cast<uint32_t *>(ws + L.off[4]), *out_cap = reinterpret_cast<uint32_t *>(ws + L.off[5]),
+             *hdr = reinterpret_cast<uint32_t *>(ws + L.off[6]), *cks = reinterpret_cast<uint32_t *>(ws + L.off[7]);
+    int64_t *csize = reinterpret_cast<int64_t *>(ws + L.off[8]);
+    uint8_t *slots = ws + L.off[9];
+    uint32_t *d_tables = reinterpret_cast<uint32_t *>(ws + L.off[10]);
+    int64_t *d_sizes = reinterpret_cast<int64_t *>(ws + L.off[11]);
+    uint32_t *len_a = reinterpret_cast<uint32_t *>(ws + L.off[12]);
+    uint64_t *a_off = reinterpret_cast<uint64_t *>(ws + L.off[13]);
+    uint32_t *a_len = reinterpret_cast<uint32_t *>(ws + L.off[14]), *a_tix = reinterpret_cast<uint32_t *>(ws + L.off[15]);
+    const bool link_b = bfcd_link_b(p, max_src_len);
+    const size_t bs = block_size_of(p.block_size_id);
+    const uint32_t bc = p.block_checksum == 1 ? 1u : 0u;
+    const uint64_t slot = bf_slot(bs);
+    const uint64_t per_block = 4 + zlz4_compress_bound(bs) + (bc ? 4 : 0);       // zlz4f_compress_frame_bound
+    const uint64_t fixed = 19 + 4 + (p.content_checksum == 1 ? 4 : 0);
+    hipLaunchKernelGGL(k_bfc_count, dim3(bf_grid(nframes, 256)), dim3(256), 0, st, d_src_len, d_dst_cap, nframes,
+                       (uint64_t)bs, per_block, fixed, fr);
+    if (zlz4_launch_bfcd_pre(st, fr, nframes, d_src_len, dd.len, dd.n, dd.idx, max_src_len, max_dict_len) != 0)
+        return ZLZ4_ERR_DEVICE;
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
+    if (max_blocks) {
+        hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, fr, nframes, max_blocks,
+                           d_src_off, d_src_len, (uint64_t)bs, slot, in_off, in_len, out_off, out_cap, hdr);
+        uint32_t *len_b = link_b ? reinterpret_cast<uint32_t *>(ws + L.off[16]) : nullptr;
+        // (without launch B every frame has one block at most: all entries are launch A's, len_b does not exist)
+        int rc = zlz4_launch_bfcd_desc(st, fr, nframes, max_blocks, link_b, dd.off, dd.len, dd.idx, in_len, len_a, len_b, a_off,
+                                       a_len, a_tix);
+        if (rc == 0 && dd.n) rc = zlz4_launch_load_dict(st, dd.dict, dd.off, dd.len, d_tables, d_sizes, dd.n);
+        const uint32_t in_max = max_src_len != 0 && max_src_len < bs ? (uint32_t)max_src_len : (uint32_t)bs;
+        if (rc == 0)
+            rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_a, slots, out_off, out_cap, dd.dict, a_off, a_len,
+                                                      d_tables, a_tix, csize, max_blocks, in_max, max_dict_len, 1);
+        if (rc == 0 && link_b) {
+            uint32_t *tables = reinterpret_cast<uint32_t *>(ws + L.off[17]);
+            uint64_t *b_off = reinterpret_cast<uint64_t *>(ws + L.off[18]);
+            uint32_t *b_len = reinterpret_cast<uint32_t *>(ws + L.off[19]);
+            int64_t *b_size = reinterpret_cast<int64_t *>(ws + L.off[20]);
+            int64_t *csize_b = reinterpret_cast<int64_t *>(ws + L.off[21]);
+            rc = zlz4_launch_bfl_dict_desc(st, fr, nframes, max_blocks, d_src_off, in_off, len_b, b_off, b_len);
+            if (rc == 0) rc = zlz4_launch_load_dict(st, d_src, b_off, b_len, tables, b_size, max_blocks);
+            if (rc == 0)
+                rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_b, slots, out_off, out_cap, d_src, b_off, b_len,
+                                                          tables, nullptr, csize_b, max_blocks, (uint32_t)bs, 65536u, 1);
+            if (rc == 0) rc = zlz4_launch_bfcd_merge(st, len_b, csize_b, csize, max_blocks);
+        }
+        if (rc != 0) return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bfc_plan, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, csize, in_len,
+                           bc, p, cs_from_len, d_src_len, d_dst_off, dst_off, hdr);
+        if (bc)
+            hipLaunchKernelGGL(k_block_xxh32, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, in_off, slots, out_off,
+                               hdr, max_blocks, cks);
+        hipLaunchKernelGGL(k_bf_scatter, dim3(max_blocks), dim3(256), 0, st, d_src, in_off, slots, out_off, hdr, dst_off,
+                           cks, bc, d_dst);
+    }
+    hipLaunchKernelGGL(k_bfc_head_tail, dim3(bf_grid(nframes, 64)), dim3(64), 0, st, fr, nframes, max_blocks, p,
+                       cs_from_len, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
 // One frame through zlz4f_batch_compress_frame_ex, device pointers: a batch of one with max_blocks = ceil(n / bs) and a
 // workspace from the device cache; synchronises `st` (as single_frame_ex of the decode side)
 int64_t single_compress_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
@@ -1454,13 +1606,27 @@ namespace {
 int32_t batch_decompress_frame_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
                                     const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
                                     const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
-                                    uint32_t decode_flags, void *d_workspace, size_t workspace_bytes) {
+                                    uint32_t decode_flags, void *d_workspace, size_t workspace_bytes,
+                                    const BfDict *dd = nullptr) {
     if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
     const bool linked = (decode_flags & ZLZ4F_DECODE_LINKED) != 0;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const BatchLayout L = bfd_layout(nframes, max_blocks, decode_flags);
+    const BatchLayout L = bfd_layout(nframes, max_blocks, decode_flags, dd != nullptr);
     if (nframes == 0) return 0;
     if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
+    if (dd) {
+        if (!d_src || !d_src_off || !d_src_len || !d_dst || !d_dst_off || !d_dst_cap || !d_result ||
+            (dd->n && (!dd->off || !dd->len)) || bf_misaligned(d_workspace, 16) || bf_misaligned(d_src_off, 8) ||
+            bf_misaligned(d_src_len, 8) || bf_misaligned(d_dst_off, 8) || bf_misaligned(d_dst_cap, 8) ||
+            bf_misaligned(d_result, 8) || bf_misaligned(dd->off, 8) || bf_misaligned(dd->len, 4) || bf_misaligned(dd->idx, 4))
+            return ZLZ4_ERR_INVALID_STATE;
+    }
+    // dictionary frames: the linked-declared frames of several blocks go through k_bfl_decode with
+    // the external tail, the others stay on the parallel decodes, which get a dictionary descriptor per entry
+    uint64_t *fd_end = dd ? reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_workspace) + L.off[15]) : nullptr;
+    uint32_t *fd_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[16]) : nullptr;
+    uint64_t *e_off = dd ? reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_workspace) + L.off[17]) : nullptr;
+    uint32_t *e_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[18]) : nullptr;
     hipStream_t st = (hipStream_t)stream_;
     uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
@@ -1473,21 +1639,27 @@ int32_t batch_decompress_frame_impl(void *stream_, const uint8_t *d_src, const u
     int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[13]);
     int64_t *walk_err = linked ? reinterpret_cast<int64_t *>(ws + L.off[14]) : nullptr;
     const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
+    const auto mask_serial = dd ? zlz4_launch_bfdd_mask : zlz4_launch_bfl_mask;   // (the frames k_bfl_decode takes)
     if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
     hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                        data_off, data_len, flags, cks_off, fidx);
+    if (dd && zlz4_launch_bfdd_frame(st, fr, nframes, dd->off, dd->len, dd->n, dd->idx, fd_end, fd_len) != 0)
+        return ZLZ4_ERR_DEVICE;
     hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
     if (linked && zlz4_launch_bfl_save(st, fr, nframes, walk_err) != 0) return ZLZ4_ERR_DEVICE;
     if (max_blocks) {
         hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                            data_off, data_len, flags, cks_off, fidx);
+        if (dd && zlz4_launch_bfdd_entry(st, fr, fidx, max_blocks, fd_end, fd_len, e_off, e_len) != 0) return ZLZ4_ERR_DEVICE;
         // speculative layout, proven per frame
         hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, data_off, data_len, flags,
                            cks_off, max_blocks, cks_ok);
         hipLaunchKernelGGL(k_bfd_spec, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, d_dst_off, d_dst_cap, max_blocks,
                            out_off, out_cap, dec_len);
-        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, out_cap, dec_len) != 0) return ZLZ4_ERR_DEVICE;
-        int rc = zlz4_launch_decompress_safe(st, d_src, data_off, dec_len, d_dst, out_off, out_cap, sizes, max_blocks);
+        if (linked && mask_serial(st, fr, fidx, max_blocks, out_cap, dec_len) != 0) return ZLZ4_ERR_DEVICE;
+        int rc = dd ? zlz4_launch_decompress_safe_using_dict(st, d_src, data_off, dec_len, d_dst, out_off, out_cap, sizes,
+                                                             max_blocks, dd->dict, e_off, e_len)
+                    : zlz4_launch_decompress_safe(st, d_src, data_off, dec_len, d_dst, out_off, out_cap, sizes, max_blocks);
         if (rc != 0) return ZLZ4_ERR_DEVICE;
         hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, out_off,
                            out_cap, d_dst);
@@ -1495,22 +1667,30 @@ int32_t batch_decompress_frame_impl(void *stream_, const uint8_t *d_src, const u
                            sizes, cks_ok, out_cap);
         // exact path for the frames whose layout was not proven (always enqueued: the sequence does not depend on data)
         hipLaunchKernelGGL(k_bfd_mask, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, max_blocks, x_off, x_cap, x_len);
-        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
-        rc = zlz4_launch_decompress_sizes(st, d_src, data_off, x_len, x_off, x_cap, sizes, max_blocks);
+        if (linked && mask_serial(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
+        rc = dd ? zlz4_launch_decompress_sizes_using_dict(st, d_src, data_off, x_len, x_off, x_cap, sizes, max_blocks, e_off,
+                                                          e_len)
+                : zlz4_launch_decompress_sizes(st, d_src, data_off, x_len, x_off, x_cap, sizes, max_blocks);
         if (rc != 0) return ZLZ4_ERR_DEVICE;
     }
     hipLaunchKernelGGL(k_bfd_plan, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags, sizes, cks_ok,
                        d_dst_off, d_dst_cap, x_off, x_cap, x_len);
     if (max_blocks) {
         // (k_bfd_plan laid out the unproven frames, a linked one among them from sizes that mean nothing: masked again)
-        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
-        const int rc = zlz4_launch_decompress_safe(st, d_src, data_off, x_len, d_dst, x_off, x_cap, sizes, max_blocks);
+        if (linked && mask_serial(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
+        const int rc = dd ? zlz4_launch_decompress_safe_using_dict(st, d_src, data_off, x_len, d_dst, x_off, x_cap, sizes,
+                                                                   max_blocks, dd->dict, e_off, e_len)
+                          : zlz4_launch_decompress_safe(st, d_src, data_off, x_len, d_dst, x_off, x_cap, sizes, max_blocks);
         if (rc != 0) return ZLZ4_ERR_DEVICE;
         hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, x_off,
                            x_cap, d_dst);
     }
-    if (linked && zlz4_launch_bfl_decode(st, 1, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err,
-                                         d_dst, d_dst_off, d_dst_cap, d_src_len, nullptr) != 0)
+    if (dd) {
+        if (zlz4_launch_bfl_decode_dict(st, 1, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err, d_dst,
+                                        d_dst_off, d_dst_cap, d_src_len, nullptr, dd->dict, fd_end, fd_len) != 0)
+            return ZLZ4_ERR_DEVICE;
+    } else if (linked && zlz4_launch_bfl_decode(st, 1, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok,
+                                                walk_err, d_dst, d_dst_off, d_dst_cap, d_src_len, nullptr) != 0)
         return ZLZ4_ERR_DEVICE;
     hipLaunchKernelGGL(k_bfd_finish, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, d_src, d_src_off, d_src_len, d_dst,
                        d_dst_off, d_dst_cap, d_result);
@@ -1555,14 +1735,19 @@ namespace {
 int32_t batch_frame_decompressed_size_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
                                            const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
                                            uint32_t max_blocks, uint32_t decode_flags, void *d_workspace,
-                                           size_t workspace_bytes) {
+                                           size_t workspace_bytes, const BfDict *dd = nullptr) {
     if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
     const bool linked = (decode_flags & ZLZ4F_DECODE_LINKED) != 0;
     if (nframes == 0) return 0;
-    const BatchLayout L = bfq_layout(nframes, max_blocks, decode_flags);
+    const BatchLayout L = bfq_layout(nframes, max_blocks, decode_flags, dd != nullptr);
     if (!d_src || !d_src_off || !d_src_len || !d_size || !d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < L.bytes)
         return ZLZ4_ERR_INVALID_STATE;
+    if (dd && ((dd->n && !dd->len) || bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) || bf_misaligned(d_size, 8) ||
+               bf_misaligned(dd->len, 4) || bf_misaligned(dd->idx, 4)))
+        return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    uint32_t *fd_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[10]) : nullptr;
+    uint32_t *e_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[11]) : nullptr;
     hipStream_t st = (hipStream_t)stream_;
     uint8_t *ws = static_cast<uint8_t *>(d_workspace);
     BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
@@ -1573,39 +1758,48 @@ int32_t batch_frame_decompressed_size_impl(void *stream_, const uint8_t *d_src, 
     int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[8]);
     int64_t *walk_err = linked ? reinterpret_cast<int64_t *>(ws + L.off[9]) : nullptr;
     const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
+    const auto mask_serial = dd ? zlz4_launch_bfdd_mask : zlz4_launch_bfl_mask;   // (the frames k_bfl_decode takes)
     if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
     hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                        data_off, data_len, flags, cks_off, fidx);
+    if (dd && zlz4_launch_bfdd_frame(st, fr, nframes, nullptr, dd->len, dd->n, dd->idx, nullptr, fd_len) != 0)
+        return ZLZ4_ERR_DEVICE;
     hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
     if (linked && zlz4_launch_bfl_save(st, fr, nframes, walk_err) != 0) return ZLZ4_ERR_DEVICE;
     if (max_blocks) {
         hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
                            data_off, data_len, flags, cks_off, fidx);
+        if (dd && zlz4_launch_bfdd_entry(st, fr, fidx, max_blocks, nullptr, fd_len, nullptr, e_len) != 0) return ZLZ4_ERR_DEVICE;
         hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, data_off, data_len, flags,
                            cks_off, max_blocks, cks_ok);
         hipLaunchKernelGGL(k_bfq_len, dim3(gb), dim3(256), 0, st, data_len, flags, max_blocks, dec_len);
-        if (linked && zlz4_launch_bfl_mask(st, fr, fidx, max_blocks, nullptr, dec_len) != 0) return ZLZ4_ERR_DEVICE;
-        if (zlz4_launch_decompressed_size(st, d_src, data_off, dec_len, nullptr, sizes, max_blocks) != 0) return ZLZ4_ERR_DEVICE;
+        if (linked && mask_serial(st, fr, fidx, max_blocks, nullptr, dec_len) != 0) return ZLZ4_ERR_DEVICE;
+        if (zlz4_launch_decompressed_size(st, d_src, data_off, dec_len, e_len, sizes, max_blocks) != 0) return ZLZ4_ERR_DEVICE;
     }
     hipLaunchKernelGGL(k_bfq_total, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags,
                        sizes, cks_ok, d_src_len, d_size);
-    if (linked && zlz4_launch_bfl_decode(st, 0, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err,
-                                         nullptr, nullptr, nullptr, d_src_len, d_size) != 0)
+    if (dd) {
+        if (zlz4_launch_bfl_decode_dict(st, 0, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err,
+                                        nullptr, nullptr, nullptr, d_src_len, d_size, nullptr, nullptr, fd_len) != 0)
+            return ZLZ4_ERR_DEVICE;
+    } else if (linked && zlz4_launch_bfl_decode(st, 0, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok,
+                                                walk_err, nullptr, nullptr, nullptr, d_src_len, d_size) != 0)
         return ZLZ4_ERR_DEVICE;
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
 // One frame through the batch calls, device pointers: a counting walk finds the table size (read back), then the frame
 // is a batch of one.  d_dst == nullptr with want_size: the size query.
+// with_dict: the _using_dict calls with one dictionary of dict_len bytes at d_dict (the size query needs no bytes).
 int64_t single_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap, uint32_t decode_flags,
-                        bool want_size) {
+                        bool want_size, bool with_dict = false, const uint8_t *d_dict = nullptr, uint32_t dict_len = 0) {
     if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     DeviceCall dc(st);
-    struct Rec { FrameRec f; uint64_t pad[3]; BFrame fr; };
+    struct Rec { FrameRec f; uint64_t dict_off; uint32_t dict_len; uint32_t pad[3]; BFrame fr; };
     Staged<Rec> rec(&dc, 256);
     if (!rec.d) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    rec.h.f.src_len = n; rec.h.f.dst_cap = cap;
+    rec.h.f.src_len = n; rec.h.f.dst_cap = cap; rec.h.dict_len = dict_len;
     dc.launched();
     if (!rec.upload(st)) return ZLZ4_ERR_DEVICE;
     FrameRec *r = &rec.d->f;
@@ -1617,15 +1811,17 @@ int64_t single_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t 
     if (F.status < 0) return F.status;
     if (F.nb > 0x7FFFFFFFull) return ZLZ4F_ERR_FRAME_SIZE_WRONG;
     const uint32_t max_blocks = (uint32_t)F.nb;
-    const size_t ws = want_size ? zlz4f_batch_frame_decompressed_size_workspace_ex(1, max_blocks, decode_flags)
-                                : zlz4f_batch_decompress_frame_workspace_ex(1, max_blocks, decode_flags);
+    const size_t ws = want_size ? bfq_layout(1, max_blocks, decode_flags, with_dict).bytes
+                                : bfd_layout(1, max_blocks, decode_flags, with_dict).bytes;
     DevBuf d_ws(ws, &dc);
     if (!d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     dc.launched();
+    const BfDict one = {d_dict, &rec.d->dict_off, &rec.d->dict_len, 1u, nullptr};
+    const BfDict *dd = with_dict ? &one : nullptr;
     const int32_t rc = want_size
-        ? batch_frame_decompressed_size_impl(st, d_src, &r->src_off, &r->src_len, &r->result, 1, max_blocks, decode_flags, d_ws.p, ws)
+        ? batch_frame_decompressed_size_impl(st, d_src, &r->src_off, &r->src_len, &r->result, 1, max_blocks, decode_flags, d_ws.p, ws, dd)
         : batch_decompress_frame_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap, &r->result, 1,
-                                      max_blocks, decode_flags, d_ws.p, ws);
+                                      max_blocks, decode_flags, d_ws.p, ws, dd);
     if (rc != 0) return rc;
     int64_t result = 0;
     if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
@@ -1718,6 +1914,163 @@ int64_t zlz4f_frame_decompressed_size(const uint8_t *src, size_t n) {
     int64_t result = 0;
     if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
     return result;
+}
+
+}  // extern "C"
+
+// ====================================================================== dictionary frames
+namespace {
+
+// one lane per frame: the header's dictID (0 when the frame carries none), or the header's error
+__global__ void k_bf_dict_id(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                             const uint64_t *__restrict__ src_len, uint32_t nframes, int64_t *__restrict__ dict_id) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const uint8_t *s = src + src_off[f];
+    const uint64_t n = src_len[f];
+    uint8_t head[19];
+    const uint32_t have = n < sizeof head ? (uint32_t)n : (uint32_t)sizeof head;
+    for (uint32_t k = 0; k < have; k++) head[k] = s[k];
+    const ParsedHeader ph = parse_header(head, have);
+    if (ph.size < 0) { dict_id[f] = ph.size; return; }
+    dict_id[f] = (ph.flg & 0x01u) ? (int64_t)zx_rd32(head + 6 + ((ph.flg & 0x08u) ? 8 : 0)) : 0;
+}
+
+// One frame with one dictionary through zlz4f_batch_compress_frame_using_dict, device pointers (single_compress_frame_ex)
+int64_t single_compress_frame_dict(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
+                                   const zlz4f_prefs &p, const uint8_t *d_dict, uint32_t dict_len) {
+    const size_t bs = block_size_of(p.block_size_id);
+    const uint64_t nb = (uint64_t)n / bs + (n % bs != 0);
+    if (nb > 0x7FFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
+    const uint32_t max_blocks = (uint32_t)nb;
+    DeviceCall dc(st);
+    const size_t ws = bfcd_layout(1, max_blocks, p, 1, n).bytes;
+    struct Rec { FrameRec f; uint64_t dict_off; uint32_t dict_len; };
+    Staged<Rec> rec(&dc);
+    DevBuf d_ws(ws, &dc);
+    if (!rec.d || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    rec.h.f.src_len = n; rec.h.f.dst_cap = cap; rec.h.dict_len = dict_len;
+    dc.launched();
+    if (!rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    FrameRec *r = &rec.d->f;
+    const BfDict dd = {d_dict, &rec.d->dict_off, &rec.d->dict_len, 1u, nullptr};
+    const int32_t rc = batch_compress_frame_dict_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap,
+                                                      &r->result, 1, max_blocks, &p, 0, dd, n, dict_len, d_ws.p, ws);
+    if (rc != 0) return rc;
+    int64_t result = 0;
+    if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
+    return result;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t zlz4f_batch_compress_frame_using_dict_workspace(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
+                                                       uint32_t batch_flags, uint32_t ndicts, uint64_t max_src_len,
+                                                       uint32_t max_dict_len) {
+    (void)batch_flags; (void)max_dict_len;
+    return bfcd_layout(nframes, max_blocks, prefs ? *prefs : kDefaultPrefs, ndicts, max_src_len).bytes;
+}
+
+int32_t zlz4f_batch_compress_frame_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                              const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                              const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes,
+                                              uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                              const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                              uint32_t ndicts, const uint32_t *d_dict_idx, uint64_t max_src_len,
+                                              uint32_t max_dict_len, void *d_workspace, size_t workspace_bytes) {
+    const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
+    return batch_compress_frame_dict_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
+                                          max_blocks, prefs, batch_flags, dd, max_src_len, max_dict_len, d_workspace,
+                                          workspace_bytes);
+}
+
+size_t zlz4f_batch_decompress_frame_using_dict_workspace(uint32_t nframes, uint32_t max_blocks) {
+    return bfd_layout(nframes, max_blocks, ZLZ4F_DECODE_LINKED, true).bytes;
+}
+
+int32_t zlz4f_batch_decompress_frame_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                                const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes,
+                                                uint32_t max_blocks, const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                const uint32_t *d_dict_len, uint32_t ndicts, const uint32_t *d_dict_idx,
+                                                void *d_workspace, size_t workspace_bytes) {
+    const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
+    return batch_decompress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
+                                       max_blocks, ZLZ4F_DECODE_LINKED, d_workspace, workspace_bytes, &dd);
+}
+
+size_t zlz4f_batch_frame_decompressed_size_using_dict_workspace(uint32_t nframes, uint32_t max_blocks) {
+    return bfq_layout(nframes, max_blocks, ZLZ4F_DECODE_LINKED, true).bytes;
+}
+
+int32_t zlz4f_batch_frame_decompressed_size_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                       const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
+                                                       uint32_t max_blocks, const uint32_t *d_dict_len, uint32_t ndicts,
+                                                       const uint32_t *d_dict_idx, void *d_workspace,
+                                                       size_t workspace_bytes) {
+    const BfDict dd = {nullptr, nullptr, d_dict_len, ndicts, d_dict_idx};
+    return batch_frame_decompressed_size_impl(stream, d_src, d_src_off, d_src_len, d_size, nframes, max_blocks,
+                                              ZLZ4F_DECODE_LINKED, d_workspace, workspace_bytes, &dd);
+}
+
+int32_t zlz4f_batch_frame_dict_id(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                  int64_t *d_dict_id, uint32_t nframes) {
+    if (nframes == 0) return 0;
+    if (!d_src || !d_src_off || !d_src_len || !d_dict_id || bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) ||
+        bf_misaligned(d_dict_id, 8))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipLaunchKernelGGL(k_bf_dict_id, dim3(bf_grid(nframes, 256)), dim3(256), 0, (hipStream_t)stream, d_src, d_src_off,
+                       d_src_len, nframes, d_dict_id);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+// host pointers: the frame, the dictionary's tail and a batch of one (zlz4f_compress_frame_ex)
+int64_t zlz4f_compress_frame_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const zlz4f_prefs *prefs,
+                                        const uint8_t *dict, size_t dict_len) {
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    const int32_t refused = bfcd_refusal(p, 0);
+    if (refused != 0) return refused;
+    if ((!src && n) || (!dst && cap) || (!dict && dict_len)) return ZLZ4_ERR_INVALID_STATE;
+    const size_t bound = zlz4f_compress_frame_bound(n, &p);
+    if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const size_t D = dict_tail(dict_len);
+    DevBuf d_dict(D);
+    if (!d_dict.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (D && hipMemcpy(d_dict.p, dict + (dict_len - D), D, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
+        return single_compress_frame_dict(nullptr, d_src, n, d_dst, bound, p, d_dict.as<uint8_t>(), (uint32_t)D);
+    });
+}
+
+int64_t zlz4f_decompress_frame_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const uint8_t *dict,
+                                          size_t dict_len) {
+    if ((!src && n) || (!dst && cap) || (!dict && dict_len)) return ZLZ4_ERR_INVALID_STATE;
+    const ParsedHeader ph = parse_header(src, n);      // header errors need no device
+    if (ph.size < 0) return ph.size;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const size_t D = dict_tail(dict_len);
+    DevBuf d_dict(D);
+    if (!d_dict.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (D && hipMemcpy(d_dict.p, dict + (dict_len - D), D, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return host_frame_call(src, n, dst, cap, cap, [&](const uint8_t *d_src, uint8_t *d_dst) {
+        return single_frame_ex(nullptr, d_src, n, d_dst, cap, ZLZ4F_DECODE_LINKED, false, true, d_dict.as<uint8_t>(), (uint32_t)D);
+    });
+}
+
+int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t n, size_t dict_len) {
+    if (!src && n) return ZLZ4_ERR_INVALID_STATE;
+    const ParsedHeader ph = parse_header(src, n);
+    if (ph.size < 0) return ph.size;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    DevBuf d_src(n);
+    if (!d_src.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return single_frame_ex(nullptr, d_src.as<uint8_t>(), n, nullptr, 0, ZLZ4F_DECODE_LINKED, true, true, nullptr,
+                           (uint32_t)dict_tail(dict_len));
 }
 
 }  // extern "C"

@@ -23,4 +23,9 @@ struct BFrame {
 
 __device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { return F.nb == 0 || F.base + F.nb <= max_blocks; }
 
+// Dictionary frames: which frames the one-wavefront decoder takes.  A linked-declared frame of one
+// block has T alone as its history -- what the block of an independent frame sees -- so it stays on the parallel decodes
+// (the default preferences write such frames for small records).
+__device__ __forceinline__ bool bfd_dict_serial(const BFrame &F) { return !(F.flg & 0x20u) && F.nb > 1; }
+
 }  // namespace

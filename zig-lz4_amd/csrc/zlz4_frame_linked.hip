@@ -14,6 +14,11 @@
 // front of it); k_bfl_dict_desc writes the dictionary descriptors, the dictionary compressor does the rest.  At HC levels
 // 3..9 (zlz4f_batch_compress_frame_ex) block k is compressHCUsingDict of the same pair: V_k = tail ++ block is a contiguous
 // stretch of the input, so k_bfl_hc_desc describes it where it lies and the HC kernels run on the caller's bytes.
+//
+// Dictionary frames (the zlz4f_*_using_dict calls): the history of a linked-declared frame starts
+// inside an external buffer, the tail T of the frame's dictionary (k_bfl_decode<.., kDict = true>); the k_bfdd_* kernels
+// describe each frame's and each table entry's dictionary for the decode, the k_bfcd_* kernels the two compressor launches
+// (against the dictionary, against the input in front of the block) and the merge of their results.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -35,9 +40,14 @@ __device__ __forceinline__ uint32_t byte_at(const uint8_t *p) { return rfl((uint
 // be referenced (<= 65536).  :181-192 with dict.len = hist: CorruptedData iff offset > op + hist; every other match is a
 // plain copy from out + op - offset, whether it starts in the history, spans its end or lies in the block.
 // kWrite false: the same walk without a byte written or read from the output (the size query).
-template <bool kWrite>
+// kDict (dictionary frames): the history is the tail of T ++ dst[0..pos), T the frame's dictionary
+// tail of D bytes that ends at `tend`.  `hist` then counts min(pos + D, 65536) and `inframe` = min(pos, 65536) of it lie
+// directly in front of `out`; the rest is T.  A match that starts more than `inframe` bytes in front of the block starts
+// in T: its first bytes come from tend - a (a = offset - op - inframe), it may end there or run across T's end into the
+// frame's first output byte, from where it is the in-output match at distance `offset` (overlap rule included).
+template <bool kWrite, bool kDict = false>
 __device__ int64_t decode_linked_block(const uint8_t *src, uint32_t iend, uint8_t *out, uint32_t oend, uint32_t hist,
-                                       uint32_t lane) {
+                                       uint32_t lane, const uint8_t *tend = nullptr, uint32_t inframe = 0) {
     if (iend == 0 || oend == 0) return 0;                              // :97-98
     uint32_t ip = 0, op = 0;
     for (;;) {
@@ -79,15 +89,26 @@ __device__ int64_t decode_linked_block(const uint8_t *src, uint32_t iend, uint8_
         if (offset > op && offset - op > hist) return kErrCorrupted;   // :181-192: in front of the history
         if (kWrite) {                                                  // :195-248: out[op + k] = out[op - offset + k]
             uint8_t *o = out + op;
+            uint32_t n = ml;
+            if constexpr (kDict) {
+                if (offset > op + inframe) {                           // :199-225: the part that lies in T comes first
+                    const uint32_t a = offset - op - inframe, n1 = a < n ? a : n;
+                    copy_bytes(o, tend - a, n1, lane);
+                    o += n1;
+                    n -= n1;
+                }
+            }
             const uint8_t *m = o - offset;
-            if (offset >= ml || offset >= 1024u) {
-                copy_bytes(o, m, ml, lane);
+            if (n == 0) {
+                // (the match ended inside T)
+            } else if (offset >= n || offset >= 1024u) {
+                copy_bytes(o, m, n, lane);
             } else {
                 // overlap (:235-241): what is made so far is copied again as a whole -- offset bytes, then 2 x, 4 x ... --
                 // each copy disjoint from its source
                 uint32_t made = 0;
-                while (made < ml) {
-                    const uint32_t have = made + offset, left = ml - made;
+                while (made < n) {
+                    const uint32_t have = made + offset, left = n - made;
                     const uint32_t n1 = have < left ? have : left;
                     copy_bytes(o + made, m, n1, lane);
                     made += n1;
@@ -103,18 +124,22 @@ __device__ int64_t decode_linked_block(const uint8_t *src, uint32_t iend, uint8_
 // decode; the error order is k_bfd_plan's (:591, :596, a stored block's DstMaxSizeTooSmall, :611), then the walk's error.
 // kWrite: decodes into the frame's slot and leaves F.total / F.err for k_bfd_finish.  !kWrite: a destination that is
 // never too small, nothing written but size[f] (k_bfq_total's result for the frame, the content checksum excepted).
-template <bool kWrite>
+// kDict: frame f's dictionary tail is dict[fd_end[f] - fd_len[f] .. fd_end[f]) (k_bfdd_frame); the size query reads fd_len
+// only.  The dictionary arguments come last and the kDict == false instantiations never read them.
+template <bool kWrite, bool kDict = false>
 __global__ __launch_bounds__(256) void k_bfl_decode(BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
                                                     const uint8_t *__restrict__ src, const uint64_t *__restrict__ data_off,
                                                     const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags,
                                                     const uint32_t *__restrict__ cks_ok, const int64_t *__restrict__ walk_err,
                                                     uint8_t *dst, const uint64_t *__restrict__ dst_off,
                                                     const uint64_t *__restrict__ dst_cap, const uint64_t *__restrict__ src_len,
-                                                    int64_t *__restrict__ size) {
+                                                    int64_t *__restrict__ size, const uint8_t *__restrict__ dict,
+                                                    const uint64_t *__restrict__ fd_end, const uint32_t *__restrict__ fd_len) {
     const uint32_t f = rfl(blockIdx.x * 4u + threadIdx.x / 64u), lane = threadIdx.x & 63u;
     if (f >= nframes) return;
     const BFrame F = fr[f];
     if (F.status < 0 || (F.flg & 0x20u)) return;                       // header error, or declared independent: not ours
+    if (kDict && !bfd_dict_serial(F)) return;                          // one block: T is its whole history (parallel path)
     if (!bf_fits(F, max_blocks)) {
         if (!kWrite && lane == 0) size[f] = ZLZ4_ERR_INVALID_STATE;
         return;
@@ -123,6 +148,8 @@ __global__ __launch_bounds__(256) void k_bfl_decode(BFrame *__restrict__ fr, uin
     const uint64_t nb = rfl64(F.nb), base = rfl64(F.base);
     const uint64_t cap = kWrite ? rfl64(dst_cap[f]) : ~0ull;
     uint8_t *out = kWrite ? dst + rfl64(dst_off[f]) : nullptr;
+    const uint32_t D = kDict ? rfl(fd_len[f]) : 0u;                    // <= 65536
+    const uint8_t *tend = kDict && kWrite ? dict + rfl64(fd_end[f]) : nullptr;
     uint64_t pos = 0;
     int64_t err = 0;
     for (uint64_t j = 0; j < nb; j++) {
@@ -141,8 +168,10 @@ __global__ __launch_bounds__(256) void k_bfl_decode(BFrame *__restrict__ fr, uin
             pos += len;
         } else {                                                       // :610
             const uint32_t oend = rem < 0xFFFFFFFFull ? (uint32_t)rem : 0xFFFFFFFFu;
-            const uint32_t hist = pos < 65536u ? (uint32_t)pos : 65536u;
-            const int64_t r = decode_linked_block<kWrite>(p, len, kWrite ? out + pos : nullptr, oend, hist, lane);
+            const uint32_t inframe = pos < 65536u ? (uint32_t)pos : 65536u;
+            const uint32_t hist = inframe + D < 65536u ? inframe + D : 65536u;
+            const int64_t r = decode_linked_block<kWrite, kDict>(p, len, kWrite ? out + pos : nullptr, oend, hist, lane, tend,
+                                                                 inframe);
             if (r < 0) { err = ZLZ4F_ERR_DECOMPRESSION_FAILED; break; }             // :611
             pos += (uint64_t)r;
         }
@@ -229,6 +258,117 @@ __global__ void k_bfl_hc_desc(const BFrame *__restrict__ fr, uint32_t nframes, u
     }
 }
 
+// ------------------------------------------------------------------ dictionary frames
+// decode, one lane per frame, between the counting walk and the scan: frame f's dictionary is number idx[f] (idx == nullptr:
+// 0) of `ndicts`; T = its last D = min(len, 65536) bytes, described by where it ends (absolute in the dictionary arena)
+// and D.  A frame whose index names no dictionary gets InvalidState and owns no table entries.  dict_off == nullptr (the
+// size query knows lengths only): fd_end is not written.
+__global__ void k_bfdd_frame(BFrame *__restrict__ fr, uint32_t nframes, const uint64_t *__restrict__ dict_off,
+                             const uint32_t *__restrict__ dict_len, uint32_t ndicts, const uint32_t *__restrict__ dict_idx,
+                             uint64_t *__restrict__ fd_end, uint32_t *__restrict__ fd_len) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const uint32_t d = dict_idx ? dict_idx[f] : 0u;
+    if (d >= ndicts) {
+        fr[f].status = ZLZ4_ERR_INVALID_STATE;
+        fr[f].nb = 0;
+        if (fd_end) fd_end[f] = 0;
+        fd_len[f] = 0;
+        return;
+    }
+    const uint32_t len = dict_len[d];
+    if (fd_end) fd_end[f] = dict_off[d] + len;
+    fd_len[f] = len < 65536u ? len : 65536u;
+}
+
+// decode, one lane per table entry: the dictionary descriptor of an entry whose frame declares independent blocks or has
+// one block (every block sees T, decompressSafeUsingDict); the other entries are decoded by k_bfl_decode and get none
+__global__ void k_bfdd_entry(const BFrame *__restrict__ fr, const uint32_t *__restrict__ fidx, uint32_t max_blocks,
+                             const uint64_t *__restrict__ fd_end, const uint32_t *__restrict__ fd_len,
+                             uint64_t *__restrict__ e_off, uint32_t *__restrict__ e_len) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        const uint32_t f = fidx[i];
+        const bool mine = f != kNoFrame && !bfd_dict_serial(fr[f]);
+        const uint32_t D = mine ? fd_len[f] : 0u;
+        if (e_off) e_off[i] = mine && fd_end ? fd_end[f] - D : 0u;
+        e_len[i] = D;
+    }
+}
+
+// k_bfl_mask for a call with dictionaries: the entries of the frames k_bfl_decode<.., true> takes
+__global__ void k_bfdd_mask(const BFrame *__restrict__ fr, const uint32_t *__restrict__ fidx, uint32_t max_blocks,
+                            uint32_t *__restrict__ cap, uint32_t *__restrict__ len) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        const uint32_t f = fidx[i];
+        if (f == kNoFrame || !bfd_dict_serial(fr[f])) continue;
+        if (cap) cap[i] = 0;
+        len[i] = 0;
+    }
+}
+
+// compress, one lane per frame, after k_bfc_count: the preconditions of the call.  A frame that names no dictionary, is
+// longer than max_src_len (0: no bound) or whose T is longer than max_dict_len gets InvalidState in front of every other
+// status; k_bfc_desc then gives its entries length 0.
+__global__ void k_bfcd_pre(BFrame *__restrict__ fr, uint32_t nframes, const uint64_t *__restrict__ src_len,
+                           const uint32_t *__restrict__ dict_len, uint32_t ndicts, const uint32_t *__restrict__ dict_idx,
+                           uint64_t max_src_len, uint32_t max_dict_len) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nframes) return;
+    const uint32_t d = dict_idx ? dict_idx[f] : 0u;
+    bool bad = d >= ndicts || (max_src_len != 0 && src_len[f] > max_src_len);
+    if (!bad) {
+        const uint32_t len = dict_len[d];
+        bad = (len < 65536u ? len : 65536u) > max_dict_len;
+    }
+    if (bad) fr[f].status = ZLZ4_ERR_INVALID_STATE;
+}
+
+// compress, one lane per table entry (next to k_bfl_dict_desc).  Launch A compresses against the frame's dictionary, read
+// from the dictionary arena with the dictionary's own loadDict table: every block of an independent frame, block 0 of a
+// linked one.  Launch B is the linked path of section 4.4c for the blocks k >= 1 of a linked frame (dictionary = the input
+// in front of the block, read from the source arena).  len_a / len_b are the complementary length arrays of the two
+// launches (an entry that takes no part has length 0 there: result 0, nothing written); a_off / a_len / a_tix describe
+// launch A's dictionary and table.  !with_b (independent frames, or linked ones that cannot have a second block): every
+// entry is launch A's and len_b, which the caller then does not have, is not written.
+__global__ void k_bfcd_desc(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks, bool with_b,
+                            const uint64_t *__restrict__ dict_off, const uint32_t *__restrict__ dict_len,
+                            const uint32_t *__restrict__ dict_idx, const uint32_t *__restrict__ in_len,
+                            uint32_t *__restrict__ len_a, uint32_t *__restrict__ len_b, uint64_t *__restrict__ a_off,
+                            uint32_t *__restrict__ a_len, uint32_t *__restrict__ a_tix) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        const uint32_t n = in_len[i];
+        uint32_t la = 0, lb = 0, tix = 0, dl = 0;
+        uint64_t off = 0;
+        if (n != 0) {                                                  // (a frame with a block passed k_bfcd_pre)
+            uint32_t lo = 0, hi = nframes;                             // the last frame whose base is <= i (k_bfc_desc)
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2u;
+                if (fr[mid].base <= i) lo = mid + 1u; else hi = mid;
+            }
+            const uint32_t f = lo - 1u;
+            if (with_b && i != fr[f].base) lb = n;
+            else {
+                la = n;
+                tix = dict_idx ? dict_idx[f] : 0u;
+                off = dict_off[tix];
+                dl = dict_len[tix];
+            }
+        }
+        len_a[i] = la;
+        if (with_b) len_b[i] = lb;
+        a_off[i] = off;
+        a_len[i] = dl;
+        a_tix[i] = tix;
+    }
+}
+
+// compress, one lane per table entry: launch B's result for the entries that took part in it; launch A's stands elsewhere
+__global__ void k_bfcd_merge(const uint32_t *__restrict__ len_b, const int64_t *__restrict__ csize_b,
+                             int64_t *__restrict__ csize, uint32_t max_blocks) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x)
+        if (len_b[i] != 0) csize[i] = csize_b[i];
+}
+
 inline uint32_t grid_of(uint64_t items, uint32_t threads, uint32_t cap = 0xFFFFFFFFu) {
     const uint64_t g = (items + threads - 1) / threads;
     return g == 0 ? 1u : (g > cap ? cap : (uint32_t)g);
@@ -261,10 +401,80 @@ extern "C" int zlz4_launch_bfl_decode(hipStream_t st, int write, void *frames, u
     const dim3 grid(grid_of(nframes, 4)), block(256);
     if (write)
         hipLaunchKernelGGL(k_bfl_decode<true>, grid, block, 0, st, fr, nframes, max_blocks, src, data_off, data_len, flags,
-                           cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size);
+                           cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size, nullptr, nullptr, nullptr);
     else
         hipLaunchKernelGGL(k_bfl_decode<false>, grid, block, 0, st, fr, nframes, max_blocks, src, data_off, data_len, flags,
-                           cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size);
+                           cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size, nullptr, nullptr, nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+// the same with a dictionary per frame: fd_end / fd_len are k_bfdd_frame's
+extern "C" int zlz4_launch_bfl_decode_dict(hipStream_t st, int write, void *frames, uint32_t nframes, uint32_t max_blocks,
+                                           const uint8_t *src, const uint64_t *data_off, const uint32_t *data_len,
+                                           const uint32_t *flags, const uint32_t *cks_ok, const int64_t *walk_err,
+                                           uint8_t *dst, const uint64_t *dst_off, const uint64_t *dst_cap,
+                                           const uint64_t *src_len, int64_t *d_size, const uint8_t *dict,
+                                           const uint64_t *fd_end, const uint32_t *fd_len) {
+    BFrame *fr = static_cast<BFrame *>(frames);
+    const dim3 grid(grid_of(nframes, 4)), block(256);
+    if (write)
+        hipLaunchKernelGGL((k_bfl_decode<true, true>), grid, block, 0, st, fr, nframes, max_blocks, src, data_off, data_len,
+                           flags, cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size, dict, fd_end, fd_len);
+    else
+        hipLaunchKernelGGL((k_bfl_decode<false, true>), grid, block, 0, st, fr, nframes, max_blocks, src, data_off, data_len,
+                           flags, cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size, dict, fd_end, fd_len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_bfdd_frame(hipStream_t st, void *frames, uint32_t nframes, const uint64_t *dict_off,
+                                      const uint32_t *dict_len, uint32_t ndicts, const uint32_t *dict_idx, uint64_t *fd_end,
+                                      uint32_t *fd_len) {
+    hipLaunchKernelGGL(k_bfdd_frame, dim3(grid_of(nframes, 256)), dim3(256), 0, st, static_cast<BFrame *>(frames), nframes,
+                       dict_off, dict_len, ndicts, dict_idx, fd_end, fd_len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_bfdd_entry(hipStream_t st, const void *frames, const uint32_t *fidx, uint32_t max_blocks,
+                                      const uint64_t *fd_end, const uint32_t *fd_len, uint64_t *e_off, uint32_t *e_len) {
+    if (max_blocks == 0) return 0;
+    hipLaunchKernelGGL(k_bfdd_entry, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
+                       static_cast<const BFrame *>(frames), fidx, max_blocks, fd_end, fd_len, e_off, e_len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_bfdd_mask(hipStream_t st, const void *frames, const uint32_t *fidx, uint32_t max_blocks,
+                                     uint32_t *cap, uint32_t *len) {
+    if (max_blocks == 0) return 0;
+    hipLaunchKernelGGL(k_bfdd_mask, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
+                       static_cast<const BFrame *>(frames), fidx, max_blocks, cap, len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_bfcd_pre(hipStream_t st, void *frames, uint32_t nframes, const uint64_t *src_len,
+                                    const uint32_t *dict_len, uint32_t ndicts, const uint32_t *dict_idx, uint64_t max_src_len,
+                                    uint32_t max_dict_len) {
+    hipLaunchKernelGGL(k_bfcd_pre, dim3(grid_of(nframes, 256)), dim3(256), 0, st, static_cast<BFrame *>(frames), nframes,
+                       src_len, dict_len, ndicts, dict_idx, max_src_len, max_dict_len);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_bfcd_desc(hipStream_t st, const void *frames, uint32_t nframes, uint32_t max_blocks, int with_b,
+                                     const uint64_t *dict_off, const uint32_t *dict_len, const uint32_t *dict_idx,
+                                     const uint32_t *in_len, uint32_t *len_a, uint32_t *len_b, uint64_t *a_off,
+                                     uint32_t *a_len, uint32_t *a_tix) {
+    if (max_blocks == 0) return 0;
+    if (with_b && !len_b) return -5;
+    hipLaunchKernelGGL(k_bfcd_desc, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
+                       static_cast<const BFrame *>(frames), nframes, max_blocks, with_b != 0, dict_off, dict_len, dict_idx,
+                       in_len, len_a, len_b, a_off, a_len, a_tix);
+    return hipGetLastError() == hipSuccess ? 0 : -7;
+}
+
+extern "C" int zlz4_launch_bfcd_merge(hipStream_t st, const uint32_t *len_b, const int64_t *csize_b, int64_t *csize,
+                                      uint32_t max_blocks) {
+    if (max_blocks == 0) return 0;
+    hipLaunchKernelGGL(k_bfcd_merge, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st, len_b, csize_b, csize,
+                       max_blocks);
     return hipGetLastError() == hipSuccess ? 0 : -7;
 }
 

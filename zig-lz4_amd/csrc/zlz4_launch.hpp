@@ -88,6 +88,13 @@ int zlz4_launch_decompress_safe_bound(hipStream_t stream, const uint8_t *d_in, c
 int zlz4_launch_decompress_sizes(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
                                  const uint64_t *d_out_off, const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks);
 
+// the size pass with a dictionary per block: only d_dict_len decides (a match may reach min(d_dict_len[i], 65536) bytes in
+// front of the block); no dictionary byte is read.  d_dict_off must be a readable array of nblocks entries.
+int zlz4_launch_decompress_sizes_using_dict(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                            const uint32_t *d_in_len, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                            int64_t *d_result, uint32_t nblocks, const uint64_t *d_dict_off,
+                                            const uint32_t *d_dict_len);
+
 // zlz4_stream_decode.hip
 size_t zlz4_sd_workspace_bytes(uint32_t nblocks, uint32_t nstreams);
 int zlz4_launch_stream_decode(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
@@ -109,6 +116,26 @@ int zlz4_launch_bfl_decode(hipStream_t st, int write, void *frames, uint32_t nfr
                            const uint64_t *data_off, const uint32_t *data_len, const uint32_t *flags, const uint32_t *cks_ok,
                            const int64_t *walk_err, uint8_t *dst, const uint64_t *dst_off, const uint64_t *dst_cap,
                            const uint64_t *src_len, int64_t *d_size);
+int zlz4_launch_bfl_decode_dict(hipStream_t st, int write, void *frames, uint32_t nframes, uint32_t max_blocks,
+                                const uint8_t *src, const uint64_t *data_off, const uint32_t *data_len, const uint32_t *flags,
+                                const uint32_t *cks_ok, const int64_t *walk_err, uint8_t *dst, const uint64_t *dst_off,
+                                const uint64_t *dst_cap, const uint64_t *src_len, int64_t *d_size, const uint8_t *dict,
+                                const uint64_t *fd_end, const uint32_t *fd_len);
+// dictionary frames: per-frame and per-entry dictionary descriptors of the decode, the
+// preconditions, descriptors and result merge of the compress call
+int zlz4_launch_bfdd_frame(hipStream_t st, void *frames, uint32_t nframes, const uint64_t *dict_off, const uint32_t *dict_len,
+                           uint32_t ndicts, const uint32_t *dict_idx, uint64_t *fd_end, uint32_t *fd_len);
+int zlz4_launch_bfdd_entry(hipStream_t st, const void *frames, const uint32_t *fidx, uint32_t max_blocks,
+                           const uint64_t *fd_end, const uint32_t *fd_len, uint64_t *e_off, uint32_t *e_len);
+int zlz4_launch_bfdd_mask(hipStream_t st, const void *frames, const uint32_t *fidx, uint32_t max_blocks, uint32_t *cap,
+                          uint32_t *len);
+int zlz4_launch_bfcd_pre(hipStream_t st, void *frames, uint32_t nframes, const uint64_t *src_len, const uint32_t *dict_len,
+                         uint32_t ndicts, const uint32_t *dict_idx, uint64_t max_src_len, uint32_t max_dict_len);
+int zlz4_launch_bfcd_desc(hipStream_t st, const void *frames, uint32_t nframes, uint32_t max_blocks, int with_b,
+                          const uint64_t *dict_off, const uint32_t *dict_len, const uint32_t *dict_idx, const uint32_t *in_len,
+                          uint32_t *len_a, uint32_t *len_b, uint64_t *a_off, uint32_t *a_len, uint32_t *a_tix);
+int zlz4_launch_bfcd_merge(hipStream_t st, const uint32_t *len_b, const int64_t *csize_b, int64_t *csize,
+                           uint32_t max_blocks);
 int zlz4_launch_bfl_dict_desc(hipStream_t st, const void *frames, uint32_t nframes, uint32_t max_blocks,
                               const uint64_t *src_off, const uint64_t *in_off, const uint32_t *in_len, uint64_t *dict_off,
                               uint32_t *dict_len);

@@ -83,6 +83,16 @@ extern "c" fn zlz4f_batch_frame_decompressed_size_ex(stream: ?*anyopaque, d_src:
 extern "c" fn zlz4f_decompress_frame_device_ex(stream: ?*anyopaque, d_src: [*]const u8, src_len: usize, d_dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
 extern "c" fn zlz4f_decompress_frame_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
 extern "c" fn zlz4f_frame_decompressed_size_ex(src: [*]const u8, src_len: usize, decode_flags: u32) i64;
+extern "c" fn zlz4f_batch_compress_frame_using_dict_workspace(nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, ndicts: u32, max_src_len: u64, max_dict_len: u32) usize;
+extern "c" fn zlz4f_batch_compress_frame_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, max_src_len: u64, max_dict_len: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_decompress_frame_using_dict_workspace(nframes: u32, max_blocks: u32) usize;
+extern "c" fn zlz4f_batch_decompress_frame_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_frame_decompressed_size_using_dict_workspace(nframes: u32, max_blocks: u32) usize;
+extern "c" fn zlz4f_batch_frame_decompressed_size_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_size: [*]i64, nframes: u32, max_blocks: u32, d_dict_len: [*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_frame_dict_id(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dict_id: [*]i64, nframes: u32) i32;
+extern "c" fn zlz4f_compress_frame_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4f_decompress_frame_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4f_frame_decompressed_size_using_dict(src: [*]const u8, src_len: usize, dict_len: usize) i64;
 extern "c" fn zlz4f_batch_decompress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 
 // ---- constants (reference src/lz4.zig:12-25, src/lz4hc.zig:28-31) ----
@@ -710,6 +720,52 @@ pub const lz4f = struct {
     }
     pub fn frameDecompressedSizeEx(src: []const u8, decode_flags: u32) Error!usize {
         return mapFrame(zlz4f_frame_decompressed_size_ex(src.ptr, src.len, decode_flags));
+    }
+    // dictionary frames (include/zlz4_amd.h): dictionary d = dict[off[d] .. off[d] + len[d]), frame f uses dictionary
+    // idx[f] (idx null: dictionary 0 for every frame).  Fast level only; prefs.block_mode says linked or independent.
+    pub const Dicts = struct {
+        dict: ?[*]const u8,
+        off: [*]const u64,
+        len: [*]const u32,
+        ndicts: u32,
+        idx: ?[*]const u32,
+    };
+    pub fn compressFrameBatchUsingDictWorkspace(nframes: u32, max_blocks: u32, prefs: ?Preferences, batch_flags: u32, ndicts: u32, max_src_len: u64, max_dict_len: u32) usize {
+        if (prefs) |p| { const c = toC(p); return zlz4f_batch_compress_frame_using_dict_workspace(nframes, max_blocks, &c, batch_flags, ndicts, max_src_len, max_dict_len); }
+        return zlz4f_batch_compress_frame_using_dict_workspace(nframes, max_blocks, null, batch_flags, ndicts, max_src_len, max_dict_len);
+    }
+    pub fn compressFrameBatchUsingDict(stream: ?*anyopaque, f: Frames, max_blocks: u32, prefs: ?Preferences, batch_flags: u32, d: Dicts, max_src_len: u64, max_dict_len: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        if (prefs) |p| {
+            const c = toC(p);
+            return mapBatch(zlz4f_batch_compress_frame_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, &c, batch_flags, d.dict, d.off, d.len, d.ndicts, d.idx, max_src_len, max_dict_len, workspace, workspace_bytes));
+        }
+        return mapBatch(zlz4f_batch_compress_frame_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, null, batch_flags, d.dict, d.off, d.len, d.ndicts, d.idx, max_src_len, max_dict_len, workspace, workspace_bytes));
+    }
+    pub fn decompressFrameBatchUsingDictWorkspace(nframes: u32, max_blocks: u32) usize {
+        return zlz4f_batch_decompress_frame_using_dict_workspace(nframes, max_blocks);
+    }
+    pub fn decompressFrameBatchUsingDict(stream: ?*anyopaque, f: Frames, max_blocks: u32, d: Dicts, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_frame_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, d.dict, d.off, d.len, d.ndicts, d.idx, workspace, workspace_bytes));
+    }
+    pub fn frameDecompressedSizeBatchUsingDictWorkspace(nframes: u32, max_blocks: u32) usize {
+        return zlz4f_batch_frame_decompressed_size_using_dict_workspace(nframes, max_blocks);
+    }
+    pub fn frameDecompressedSizeBatchUsingDict(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, size: [*]i64, nframes: u32, max_blocks: u32, dict_len: [*]const u32, ndicts: u32, dict_idx: ?[*]const u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_frame_decompressed_size_using_dict(stream, src, src_off, src_len, size, nframes, max_blocks, dict_len, ndicts, dict_idx, workspace, workspace_bytes));
+    }
+    /// dict_id[f] = the header's dictID, 0 when the frame has none, or the header's error code
+    pub fn frameDictIDBatch(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, dict_id: [*]i64, nframes: u32) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_frame_dict_id(stream, src, src_off, src_len, dict_id, nframes));
+    }
+    pub fn compressFrameUsingDict(src: []const u8, dst: []u8, prefs: ?Preferences, dict: []const u8) Error!usize {
+        if (prefs) |p| { const c = toC(p); return mapFrame(zlz4f_compress_frame_using_dict(src.ptr, src.len, dst.ptr, dst.len, &c, dict.ptr, dict.len)); }
+        return mapFrame(zlz4f_compress_frame_using_dict(src.ptr, src.len, dst.ptr, dst.len, null, dict.ptr, dict.len));
+    }
+    pub fn decompressFrameUsingDict(src: []const u8, dst: []u8, dict: []const u8) Error!usize {
+        return mapFrame(zlz4f_decompress_frame_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len));
+    }
+    pub fn frameDecompressedSizeUsingDict(src: []const u8, dict_len: usize) Error!usize {
+        return mapFrame(zlz4f_frame_decompressed_size_using_dict(src.ptr, src.len, dict_len));
     }
     pub fn frameDecompressedSizeBatchWorkspace(nframes: u32, max_blocks: u32) usize {
         return zlz4f_batch_frame_decompressed_size_workspace(nframes, max_blocks);
