@@ -706,7 +706,7 @@ int64_t zlz4f_frame_decompressed_size_ex(const uint8_t *src, size_t src_len, uin
  * max_blocks, ZLZ4_ERR_INVALID_STATE per frame, the slot guarantee and "nothing allocated, nothing read back, fixed launch
  * sequence, graph-capturable" are those of the batch frame calls above.  The single-frame calls take HOST pointers, stage
  * the frame and the dictionary's tail and run a batch of one; dict == NULL with dict_len > 0 gives InvalidState.
- * HC levels with a frame dictionary and the segment calls have no dictionary form. */
+ * HC levels with a frame dictionary are served by the _ex calls below; the segment calls have no dictionary form. */
 size_t  zlz4f_batch_compress_frame_using_dict_workspace(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
                                                         uint32_t batch_flags, uint32_t ndicts, uint64_t max_src_len,
                                                         uint32_t max_dict_len);
@@ -740,6 +740,61 @@ int64_t zlz4f_compress_frame_using_dict(const uint8_t *src, size_t src_len, uint
 int64_t zlz4f_decompress_frame_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                           const uint8_t *dict, size_t dict_len);
 int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t src_len, size_t dict_len);
+
+/* ---- dictionary frames at the HC levels 3..9 (what `lz4 -9 -D dict` and LZ4F_compressFrame_usingCDict with a level
+ * produce; no counterpart in the reference).  The _ex calls are the calls they are named after, with the same argument
+ * lists; the plain calls keep refusing every level > 0.  L = prefs->compression_level as the frame calls read it (<= 0:
+ * fast, 1 -> 9, > 12 -> 12); T, X_k, bs as above.
+ *   - L <= 0: the plain call -- the same bytes, statuses, workspace size and launch sequence.
+ *   - L in 3..9, block_mode == 1: block k = zlz4_compress_hc_using_dict(X_k, dict = T, L), every k.
+ *   - L in 3..9, block_mode == 0: block 0 is the same call; block k >= 1 is the ZLZ4F_BATCH_LINK_BLOCKS block of
+ *     zlz4f_batch_compress_frame_ex at level L (dict = the input [k * bs - 65536, k * bs), read where it lies in d_src; bs
+ *     >= 65536, so T is out of reach from block 1 on).
+ *   - L in { 2, 10, 11, 12 }: ZLZ4_ERR_UNSUPPORTED, nothing launched (the levels zlz4_batch_compress_hc_using_dict refuses).
+ *   Header, stored-block rule (csize >= len), checksums, ZLZ4F_BATCH_CONTENT_SIZE, the compressFrameBound check per frame,
+ *   the end mark, max_blocks and the three per-frame preconditions (d_dict_idx[f] >= ndicts, d_src_len[f] > max_src_len, D >
+ *   max_dict_len: ZLZ4_ERR_INVALID_STATE, nothing written) are the plain call's.  An HC dictionary block is at most
+ *   zlz4_compress_bound(len), so zlz4f_compress_frame_bound stands.
+ *   With an empty dictionary, byte for byte and status for status: zlz4f_batch_compress_frame at level L (block_mode 1) and
+ *   zlz4f_batch_compress_frame_ex(.., ZLZ4F_BATCH_LINK_BLOCKS) at level L (block_mode 0).  Every frame decodes with
+ *   zlz4f_batch_decompress_frame_using_dict and the same dictionary, and with liblz4's LZ4F_decompress_usingDict.
+ *   Refusals, each launching nothing, in this order: a flag bit other than ZLZ4F_BATCH_CONTENT_SIZE or that flag's
+ *   content_size rule (ZLZ4F_ERR_PARAMETER_INVALID); an unsupported level (ZLZ4_ERR_UNSUPPORTED); the device; null or
+ *   misaligned arrays, a workspace that is too small, null or not 16-byte aligned (ZLZ4_ERR_INVALID_STATE).
+ *   Two compressor launches, one after the other on `stream`: A = the HC dictionary compressor over every block of an
+ *   independent frame and block 0 of a linked one, with the dictionaries read from d_dict (no loadDict table is built),
+ *   max_in_len = min(bs, max_src_len) and max_dict_len as given -- records and dictionary tail that together fit 65536
+ *   bytes (4 KiB records against a dictionary of 60 KiB or less) keep the chain links in LDS; B, only when block_mode == 0
+ *   and a frame may have a second block (max_src_len == 0 or > bs) = the linked HC compressor over the blocks k >= 1.  An
+ *   entry that takes no part in a launch has record and dictionary length 0 there: nothing is staged for it, its result is
+ *   0 and nothing is written.  Output bytes do not depend on max_src_len, max_dict_len or the link width they select.
+ *   Workspace for L in 3..9: frames | 3 x u64, 4 x u32, i64 per table entry | a compressBound-sized slot per entry | 20
+ *   bytes of launch A's descriptors per entry | ONE HC scratch region of max(zlz4_batch_compress_hc_using_dict_workspace(
+ *   max_blocks, min(bs, max_src_len), max_dict_len), the linked HC scratch of zlz4f_batch_compress_frame_workspace_ex) --
+ *   launch B is ordered behind all of launch A's work, the side stream of the HC launchers included, so the two share it
+ *   -- | with launch B also 32 bytes per entry (len_b, v_off, { v_len, start }, v_len, csize_b); each area rounded up to
+ *   256 bytes.  max_dict_len CHANGES this size (it sizes the staged V = T ++ record); batch_flags does not.  For every
+ *   other level the function returns what zlz4f_batch_compress_frame_using_dict_workspace returns.  The chunking of the HC
+ *   launchers (8192 blocks, about 6 GiB of scratch) applies as it is: longer batches run in rounds.
+ *   The host call stages the frame and the dictionary's tail and runs a batch of one; its refusals are host arithmetic and
+ *   come before the device check; dict == NULL with dict_len > 0 gives ZLZ4_ERR_INVALID_STATE.
+ *   Nothing is allocated, nothing is read back and the launch sequence is fixed.  Under stream capture the call behaves as
+ *   its HC launchers do (they fork K3 to a side stream and join it before they return, as zlz4_batch_compress_hc does):
+ *   that property is inherited from them, not new. */
+size_t  zlz4f_batch_compress_frame_using_dict_workspace_ex(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
+                                                           uint32_t batch_flags, uint32_t ndicts, uint64_t max_src_len,
+                                                           uint32_t max_dict_len);
+int32_t zlz4f_batch_compress_frame_using_dict_ex(void *stream,
+                                                 const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                                 uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                                                 int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                                 const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                                 const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                                 uint32_t ndicts, const uint32_t *d_dict_idx,
+                                                 uint64_t max_src_len, uint32_t max_dict_len,
+                                                 void *d_workspace, size_t workspace_bytes);
+int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                           const zlz4f_prefs *prefs, const uint8_t *dict, size_t dict_len);
 
 /* ======================================================================
  * 4. Introspection

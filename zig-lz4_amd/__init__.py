@@ -130,6 +130,10 @@ SYMBOLS = {
     "zlz4f_compress_frame_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _PP, _VP, _SZ]),
     "zlz4f_decompress_frame_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ]),
     "zlz4f_frame_decompressed_size_using_dict": (_I64, [_VP, _SZ, _SZ]),
+    "zlz4f_batch_compress_frame_using_dict_workspace_ex": (_SZ, [_U32, _U32, _PP, _U32, _U32, C.c_uint64, _U32]),
+    "zlz4f_batch_compress_frame_using_dict_ex": (_I32, [_VP] * 8 + [_U32, _U32, _PP, _U32, _VP, _VP, _VP, _U32, _VP,
+                                                        C.c_uint64, _U32, _VP, _SZ]),
+    "zlz4f_compress_frame_using_dict_ex": (_I64, [_VP, _SZ, _VP, _SZ, _PP, _VP, _SZ]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -671,6 +675,15 @@ class lz4f:
                     C.addressof(d) if dn else None, dn)
 
     @staticmethod
+    def compressFrameUsingDictEx(src, dict, prefs=None, dst_cap=None):
+        """zlz4f_compress_frame_using_dict_ex: compressFrameUsingDict, and the HC levels 3..9 (prefs.compression_level;
+        block 0 / every block is compressHCUsingDict against `dict`)."""
+        cap = lz4f.compressFrameBound(len(src), prefs) if dst_cap is None else dst_cap
+        d, dn = _in(dict if dict is not None else b"")
+        return _run(lib().zlz4f_compress_frame_using_dict_ex, src, cap, C.byref(prefs) if prefs is not None else None,
+                    C.addressof(d) if dn else None, dn)
+
+    @staticmethod
     def decompressFrameUsingDict(src, dst_cap, dict):
         """zlz4f_decompress_frame_using_dict: what liblz4's LZ4F_decompress_usingDict gives for `src` and `dict`."""
         d, dn = _in(dict if dict is not None else b"")
@@ -687,6 +700,14 @@ class lz4f:
         return lib().zlz4f_batch_compress_frame_using_dict_workspace(nframes, max_blocks,
                                                                      C.byref(prefs) if prefs is not None else None,
                                                                      batch_flags, ndicts, max_src_len, max_dict_len)
+
+    @staticmethod
+    def compressFrameUsingDictBatchWorkspaceEx(nframes, max_blocks, prefs=None, batch_flags=0, ndicts=1, max_src_len=0,
+                                               max_dict_len=65536):
+        """zlz4f_batch_compress_frame_using_dict_workspace_ex (at levels 3..9 max_dict_len changes the size)."""
+        return lib().zlz4f_batch_compress_frame_using_dict_workspace_ex(nframes, max_blocks,
+                                                                        C.byref(prefs) if prefs is not None else None,
+                                                                        batch_flags, ndicts, max_src_len, max_dict_len)
 
     @staticmethod
     def decompressFrameUsingDictBatchWorkspace(nframes, max_blocks):
@@ -714,6 +735,28 @@ class lz4f:
                 src_len.numel(), max_blocks, pp, batch_flags, nd, max_src_len, max_dict_len)), dtype=torch.uint8,
                 device=d_src.device)
         _check(lib().zlz4f_batch_compress_frame_using_dict(
+            _stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst), _ptr(dst_off), _ptr(dst_cap), _ptr(result),
+            src_len.numel(), max_blocks, pp, batch_flags, _ptr(d_dict), _ptr(dict_off), _ptr(dict_len), nd, _ptr(dict_idx),
+            max_src_len, max_dict_len, _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def compressFrameUsingDictBatchEx(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, d_dict, dict_off, dict_len,
+                                      dict_idx=None, prefs=None, batch_flags=0, max_blocks=None, max_src_len=0,
+                                      max_dict_len=65536, workspace=None):
+        """zlz4f_batch_compress_frame_using_dict_ex on torch CUDA tensors: compressFrameUsingDictBatch, and the HC levels
+        3..9 (prefs.compression_level).  The same parameters; the workspace is that of
+        compressFrameUsingDictBatchWorkspaceEx."""
+        import torch
+        if max_blocks is None:
+            bs = lz4f.BLOCK_SIZES.get(prefs.block_size_id if prefs is not None else 0, 64 << 10)
+            max_blocks = int(((src_len.cpu() + bs - 1) // bs).sum()) if src_len.numel() else 0
+        pp = C.byref(prefs) if prefs is not None else None
+        nd = dict_len.numel()
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_compress_frame_using_dict_workspace_ex(
+                src_len.numel(), max_blocks, pp, batch_flags, nd, max_src_len, max_dict_len)), dtype=torch.uint8,
+                device=d_src.device)
+        _check(lib().zlz4f_batch_compress_frame_using_dict_ex(
             _stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst), _ptr(dst_off), _ptr(dst_cap), _ptr(result),
             src_len.numel(), max_blocks, pp, batch_flags, _ptr(d_dict), _ptr(dict_off), _ptr(dict_len), nd, _ptr(dict_idx),
             max_src_len, max_dict_len, _ptr(workspace), workspace.numel()))
@@ -778,7 +821,8 @@ class lz4f:
     @staticmethod
     def compressFramesUsingDict(items, dicts, dict_index=None, prefs=None, device="cuda"):
         """Every byte string of `items` as its own frame against dicts[dict_index[f]] (dict_index None: dicts[0] for every
-        frame), in one batch call -> list of frames (bytes) or error codes."""
+        frame), in one batch call -> list of frames (bytes) or error codes.  Goes through the _ex call, so
+        prefs.compression_level may be 3..9 (at the fast level the frames are compressFrameUsingDictBatch's)."""
         import torch
         if len(items) == 0:
             return []
@@ -789,10 +833,10 @@ class lz4f:
         dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
         d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
         result = torch.empty(len(items), dtype=torch.int64, device=device)
-        lz4f.compressFrameUsingDictBatch(d_src, src_off, src_len, d_dst, dst_off,
-                                         torch.tensor(caps, dtype=torch.int64, device=device), result, d_dict, dict_off,
-                                         dict_len, idx, prefs, 0, max_src_len=max(lens),
-                                         max_dict_len=min(65536, max((len(d) for d in dbytes), default=0)))
+        lz4f.compressFrameUsingDictBatchEx(d_src, src_off, src_len, d_dst, dst_off,
+                                           torch.tensor(caps, dtype=torch.int64, device=device), result, d_dict, dict_off,
+                                           dict_len, idx, prefs, 0, max_src_len=max(lens),
+                                           max_dict_len=min(65536, max((len(d) for d in dbytes), default=0)))
         return _unstage(d_dst, _offsets(caps), result)
 
     @staticmethod

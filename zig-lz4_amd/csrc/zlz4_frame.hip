@@ -1403,10 +1403,27 @@ bool bfcd_link_b(const zlz4f_prefs &p, uint64_t max_src_len) {
     return p.block_mode != 1 && !(max_src_len != 0 && max_src_len <= block_size_of(p.block_size_id));
 }
 
+// the _ex calls at the HC levels zlz4_batch_compress_hc_using_dict takes; every other level is
+// the plain call's business
+bool bfcd_hc(const zlz4f_prefs &p, bool ex) {
+    const int32_t lv = bf_hc_level(p);
+    return ex && lv >= 3 && lv <= 9;
+}
+
+// what the dictionary compressor of launch A is given as its max_in_len
+uint32_t bfcd_in_max(size_t bs, uint64_t max_src_len) {
+    return max_src_len != 0 && max_src_len < bs ? (uint32_t)max_src_len : (uint32_t)bs;
+}
+
 // frames | in_off out_off dst_off (u64) | in_len out_cap hdr cks (u32) | csize (i64) | slots | loadDict tables of the
 // dictionaries | their dictSize (i64) | len_a (u32) | a_off (u64) | a_len a_tix (u32); with launch B also: | len_b (u32) |
 // loadDict tables per entry | b_off (u64) | b_len (u32) | dictSize (i64) | csize_b (i64)
-BatchLayout bfcd_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t ndicts, uint64_t max_src_len) {
+// hc (bfcd_hc): frames ... slots | len_a (u32) | a_off (u64) | a_len a_tix (u32) | HC scratch; with launch B also: | len_b
+// (u32) | v_off (u64) | { v_len, start } (2 x u32) | v_len (u32) | csize_b (i64).  The HC scratch is ONE region, the larger
+// of zlz4_hc_dict_workspace_bytes (launch A) and zlz4_hc_linked_workspace_bytes (launch B): both launchers join their side
+// stream into the caller's before they return, so launch B's first memset is ordered behind all of launch A's work.
+BatchLayout bfcd_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t ndicts, uint64_t max_src_len,
+                        uint32_t max_dict_len = 0, bool hc = false) {
     const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
     BatchLayout L;
     L.add((size_t)nframes * sizeof(BFrame));
@@ -1414,6 +1431,23 @@ BatchLayout bfcd_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs
     for (int k = 0; k < 4; k++) L.add(m * sizeof(uint32_t));
     L.add(m * sizeof(int64_t));
     L.add(m * bf_slot(bs));
+    if (hc) {
+        const bool link_b = bfcd_link_b(p, max_src_len);
+        L.add(m * sizeof(uint32_t));
+        L.add(m * sizeof(uint64_t));
+        for (int k = 0; k < 2; k++) L.add(m * sizeof(uint32_t));
+        const size_t scratch_a = zlz4_hc_dict_workspace_bytes(max_blocks, bfcd_in_max(bs, max_src_len), max_dict_len);
+        const size_t scratch_b = link_b ? zlz4_hc_linked_workspace_bytes(max_blocks, (uint32_t)bs) : 0;
+        L.add(scratch_a > scratch_b ? scratch_a : scratch_b);
+        if (link_b) {
+            L.add(m * sizeof(uint32_t));
+            L.add(m * sizeof(uint64_t));
+            L.add(m * 2 * sizeof(uint32_t));
+            L.add(m * sizeof(uint32_t));
+            L.add(m * sizeof(int64_t));
+        }
+        return L;
+    }
     L.add((size_t)ndicts * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
     L.add((size_t)ndicts * sizeof(int64_t));
     L.add(m * sizeof(uint32_t));
@@ -1429,11 +1463,12 @@ BatchLayout bfcd_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs
     return L;
 }
 
-// the refusals that need no device, in their order: parameter errors, then the levels this call does not serve
-int32_t bfcd_refusal(const zlz4f_prefs &p, uint32_t batch_flags) {
+// the refusals that need no device, in their order: parameter errors, then the levels the call does not serve (the plain
+// call: every HC level; ex, the _ex calls: 2 and 10..12, which zlz4_batch_compress_hc_using_dict refuses)
+int32_t bfcd_refusal(const zlz4f_prefs &p, uint32_t batch_flags, bool ex = false) {
     if (batch_flags & ~ZLZ4F_BATCH_CONTENT_SIZE) return ZLZ4F_ERR_PARAMETER_INVALID;   // block_mode says "linked"
     if ((batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) && p.content_size != 0) return ZLZ4F_ERR_PARAMETER_INVALID;
-    if (bf_hc_level(p) > 0) return ZLZ4_ERR_UNSUPPORTED;
+    if (bf_hc_level(p) > 0 && !bfcd_hc(p, ex)) return ZLZ4_ERR_UNSUPPORTED;
     return 0;
 }
 
@@ -1442,17 +1477,22 @@ int32_t bfcd_refusal(const zlz4f_prefs &p, uint32_t batch_flags) {
 // of a linked one against the frame's dictionary where it lies in d_dict, launch B the blocks k >= 1 of a linked frame
 // against the input in front of them where it lies in d_src (section 4.4c).  The two launches run over complementary
 // length arrays into the same slots; k_bfcd_merge takes B's results for B's entries only.
+// ex at levels 3..9 (the _ex calls, section 4.4e): the same two launches with the HC compressors.  Launch A is
+// zlz4_launch_compress_hc_dict over len_a / a_off / a_len (an entry that takes no part has record and dictionary length 0:
+// nothing staged, result 0), launch B zlz4_launch_compress_hc_linked over the V descriptors k_bfl_hc_desc derives from
+// len_b (block 0 and the empty entries get an empty V).  No loadDict table is built.
 int32_t batch_compress_frame_dict_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
                                        const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
                                        const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
                                        const zlz4f_prefs *prefs, uint32_t batch_flags, const BfDict &dd, uint64_t max_src_len,
-                                       uint32_t max_dict_len, void *d_workspace, size_t workspace_bytes) {
+                                       uint32_t max_dict_len, void *d_workspace, size_t workspace_bytes, bool ex) {
     const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
-    const int32_t refused = bfcd_refusal(p, batch_flags);
+    const int32_t refused = bfcd_refusal(p, batch_flags, ex);
     if (refused != 0) return refused;
     const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const BatchLayout L = bfcd_layout(nframes, max_blocks, p, dd.n, max_src_len);
+    const bool hc = bfcd_hc(p, ex);
+    const BatchLayout L = bfcd_layout(nframes, max_blocks, p, dd.n, max_src_len, max_dict_len, hc);
     if (nframes == 0) return 0;
     if (!d_src || !d_src_off || !d_src_len || !d_dst || !d_dst_off || !d_dst_cap || !d_result ||
         (dd.n && (!dd.off || !dd.len)) || (dd.n && max_dict_len && !dd.dict) || bf_misaligned(d_src_off, 8) ||
@@ -1469,11 +1509,10 @@ int32_t batch_compress_frame_dict_impl(void *stream_, const uint8_t *d_src, cons
              *hdr = reinterpret_cast<uint32_t *>(ws + L.off[6]), *cks = reinterpret_cast<uint32_t *>(ws + L.off[7]);
     int64_t *csize = reinterpret_cast<int64_t *>(ws + L.off[8]);
     uint8_t *slots = ws + L.off[9];
-    uint32_t *d_tables = reinterpret_cast<uint32_t *>(ws + L.off[10]);
-    int64_t *d_sizes = reinterpret_cast<int64_t *>(ws + L.off[11]);
-    uint32_t *len_a = reinterpret_cast<uint32_t *>(ws + L.off[12]);
-    uint64_t *a_off = reinterpret_cast<uint64_t *>(ws + L.off[13]);
-    uint32_t *a_len = reinterpret_cast<uint32_t *>(ws + L.off[14]), *a_tix = reinterpret_cast<uint32_t *>(ws + L.off[15]);
+    const int a0 = hc ? 10 : 12;                                   // launch A's descriptors (bfcd_layout)
+    uint32_t *len_a = reinterpret_cast<uint32_t *>(ws + L.off[a0]);
+    uint64_t *a_off = reinterpret_cast<uint64_t *>(ws + L.off[a0 + 1]);
+    uint32_t *a_len = reinterpret_cast<uint32_t *>(ws + L.off[a0 + 2]), *a_tix = reinterpret_cast<uint32_t *>(ws + L.off[a0 + 3]);
     const bool link_b = bfcd_link_b(p, max_src_len);
     const size_t bs = block_size_of(p.block_size_id);
     const uint32_t bc = p.block_checksum == 1 ? 1u : 0u;
@@ -1488,27 +1527,50 @@ int32_t batch_compress_frame_dict_impl(void *stream_, const uint8_t *d_src, cons
     if (max_blocks) {
         hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, fr, nframes, max_blocks,
                            d_src_off, d_src_len, (uint64_t)bs, slot, in_off, in_len, out_off, out_cap, hdr);
-        uint32_t *len_b = link_b ? reinterpret_cast<uint32_t *>(ws + L.off[16]) : nullptr;
+        uint32_t *len_b = link_b ? reinterpret_cast<uint32_t *>(ws + L.off[hc ? 15 : 16]) : nullptr;
         // (without launch B every frame has one block at most: all entries are launch A's, len_b does not exist)
         int rc = zlz4_launch_bfcd_desc(st, fr, nframes, max_blocks, link_b, dd.off, dd.len, dd.idx, in_len, len_a, len_b, a_off,
                                        a_len, a_tix);
-        if (rc == 0 && dd.n) rc = zlz4_launch_load_dict(st, dd.dict, dd.off, dd.len, d_tables, d_sizes, dd.n);
-        const uint32_t in_max = max_src_len != 0 && max_src_len < bs ? (uint32_t)max_src_len : (uint32_t)bs;
-        if (rc == 0)
-            rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_a, slots, out_off, out_cap, dd.dict, a_off, a_len,
-                                                      d_tables, a_tix, csize, max_blocks, in_max, max_dict_len, 1);
-        if (rc == 0 && link_b) {
-            uint32_t *tables = reinterpret_cast<uint32_t *>(ws + L.off[17]);
-            uint64_t *b_off = reinterpret_cast<uint64_t *>(ws + L.off[18]);
-            uint32_t *b_len = reinterpret_cast<uint32_t *>(ws + L.off[19]);
-            int64_t *b_size = reinterpret_cast<int64_t *>(ws + L.off[20]);
-            int64_t *csize_b = reinterpret_cast<int64_t *>(ws + L.off[21]);
-            rc = zlz4_launch_bfl_dict_desc(st, fr, nframes, max_blocks, d_src_off, in_off, len_b, b_off, b_len);
-            if (rc == 0) rc = zlz4_launch_load_dict(st, d_src, b_off, b_len, tables, b_size, max_blocks);
+        const uint32_t in_max = bfcd_in_max(bs, max_src_len);
+        if (hc) {
+            const int32_t level = bf_hc_level(p);
+            void *hc_ws = ws + L.off[14];
+            const size_t hc_bytes = (link_b ? L.off[15] : L.bytes) - L.off[14];
             if (rc == 0)
-                rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_b, slots, out_off, out_cap, d_src, b_off, b_len,
-                                                          tables, nullptr, csize_b, max_blocks, (uint32_t)bs, 65536u, 1);
-            if (rc == 0) rc = zlz4_launch_bfcd_merge(st, len_b, csize_b, csize, max_blocks);
+                rc = zlz4_launch_compress_hc_dict(st, d_src, in_off, len_a, slots, out_off, out_cap, dd.dict, a_off, a_len, csize,
+                                                  max_blocks, in_max, max_dict_len, level, hc_ws, hc_bytes);
+            if (rc == 0 && link_b) {
+                uint64_t *v_off = reinterpret_cast<uint64_t *>(ws + L.off[16]);
+                uint32_t *v_pair = reinterpret_cast<uint32_t *>(ws + L.off[17]);
+                uint32_t *v_len = reinterpret_cast<uint32_t *>(ws + L.off[18]);
+                int64_t *csize_b = reinterpret_cast<int64_t *>(ws + L.off[19]);
+                rc = zlz4_launch_bfl_hc_desc(st, fr, nframes, max_blocks, d_src_off, in_off, len_b, v_off, v_len, v_pair);
+                if (rc == 0)
+                    rc = zlz4_launch_compress_hc_linked(st, d_src, v_off, v_len, v_pair, slots, out_off, out_cap, csize_b,
+                                                        max_blocks, (uint32_t)bs, level, hc_ws, hc_bytes);
+                if (rc == 0) rc = zlz4_launch_bfcd_merge(st, len_b, csize_b, csize, max_blocks);
+            }
+        } else {
+            uint32_t *d_tables = reinterpret_cast<uint32_t *>(ws + L.off[10]);
+            int64_t *d_sizes = reinterpret_cast<int64_t *>(ws + L.off[11]);
+            if (rc == 0 && dd.n) rc = zlz4_launch_load_dict(st, dd.dict, dd.off, dd.len, d_tables, d_sizes, dd.n);
+            if (rc == 0)
+                rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_a, slots, out_off, out_cap, dd.dict, a_off,
+                                                          a_len, d_tables, a_tix, csize, max_blocks, in_max, max_dict_len, 1);
+            if (rc == 0 && link_b) {
+                uint32_t *tables = reinterpret_cast<uint32_t *>(ws + L.off[17]);
+                uint64_t *b_off = reinterpret_cast<uint64_t *>(ws + L.off[18]);
+                uint32_t *b_len = reinterpret_cast<uint32_t *>(ws + L.off[19]);
+                int64_t *b_size = reinterpret_cast<int64_t *>(ws + L.off[20]);
+                int64_t *csize_b = reinterpret_cast<int64_t *>(ws + L.off[21]);
+                rc = zlz4_launch_bfl_dict_desc(st, fr, nframes, max_blocks, d_src_off, in_off, len_b, b_off, b_len);
+                if (rc == 0) rc = zlz4_launch_load_dict(st, d_src, b_off, b_len, tables, b_size, max_blocks);
+                if (rc == 0)
+                    rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_b, slots, out_off, out_cap, d_src, b_off,
+                                                              b_len, tables, nullptr, csize_b, max_blocks, (uint32_t)bs,
+                                                              65536u, 1);
+                if (rc == 0) rc = zlz4_launch_bfcd_merge(st, len_b, csize_b, csize, max_blocks);
+            }
         }
         if (rc != 0) return ZLZ4_ERR_DEVICE;
         hipLaunchKernelGGL(k_bfc_plan, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, csize, in_len,
@@ -1936,15 +1998,16 @@ __global__ void k_bf_dict_id(const uint8_t *__restrict__ src, const uint64_t *__
     dict_id[f] = (ph.flg & 0x01u) ? (int64_t)zx_rd32(head + 6 + ((ph.flg & 0x08u) ? 8 : 0)) : 0;
 }
 
-// One frame with one dictionary through zlz4f_batch_compress_frame_using_dict, device pointers (single_compress_frame_ex)
+// One frame with one dictionary through zlz4f_batch_compress_frame_using_dict (ex: .._using_dict_ex), device pointers
+// (single_compress_frame_ex)
 int64_t single_compress_frame_dict(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
-                                   const zlz4f_prefs &p, const uint8_t *d_dict, uint32_t dict_len) {
+                                   const zlz4f_prefs &p, const uint8_t *d_dict, uint32_t dict_len, bool ex) {
     const size_t bs = block_size_of(p.block_size_id);
     const uint64_t nb = (uint64_t)n / bs + (n % bs != 0);
     if (nb > 0x7FFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const uint32_t max_blocks = (uint32_t)nb;
     DeviceCall dc(st);
-    const size_t ws = bfcd_layout(1, max_blocks, p, 1, n).bytes;
+    const size_t ws = bfcd_layout(1, max_blocks, p, 1, n, dict_len, bfcd_hc(p, ex)).bytes;
     struct Rec { FrameRec f; uint64_t dict_off; uint32_t dict_len; };
     Staged<Rec> rec(&dc);
     DevBuf d_ws(ws, &dc);
@@ -1955,11 +2018,30 @@ int64_t single_compress_frame_dict(hipStream_t st, const uint8_t *d_src, size_t 
     FrameRec *r = &rec.d->f;
     const BfDict dd = {d_dict, &rec.d->dict_off, &rec.d->dict_len, 1u, nullptr};
     const int32_t rc = batch_compress_frame_dict_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap,
-                                                      &r->result, 1, max_blocks, &p, 0, dd, n, dict_len, d_ws.p, ws);
+                                                      &r->result, 1, max_blocks, &p, 0, dd, n, dict_len, d_ws.p, ws, ex);
     if (rc != 0) return rc;
     int64_t result = 0;
     if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
     return result;
+}
+
+// the host-pointer call of both entry points: the refusals are host arithmetic and come before the device check
+int64_t host_compress_frame_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const zlz4f_prefs *prefs,
+                                 const uint8_t *dict, size_t dict_len, bool ex) {
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    const int32_t refused = bfcd_refusal(p, 0, ex);
+    if (refused != 0) return refused;
+    if ((!src && n) || (!dst && cap) || (!dict && dict_len)) return ZLZ4_ERR_INVALID_STATE;
+    const size_t bound = zlz4f_compress_frame_bound(n, &p);
+    if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const size_t D = dict_tail(dict_len);
+    DevBuf d_dict(D);
+    if (!d_dict.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (D && hipMemcpy(d_dict.p, dict + (dict_len - D), D, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
+        return single_compress_frame_dict(nullptr, d_src, n, d_dst, bound, p, d_dict.as<uint8_t>(), (uint32_t)D, ex);
+    });
 }
 
 }  // namespace
@@ -1983,7 +2065,30 @@ int32_t zlz4f_batch_compress_frame_using_dict(void *stream, const uint8_t *d_src
     const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
     return batch_compress_frame_dict_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
                                           max_blocks, prefs, batch_flags, dd, max_src_len, max_dict_len, d_workspace,
-                                          workspace_bytes);
+                                          workspace_bytes, false);
+}
+
+// the same, and the HC levels 3..9
+size_t zlz4f_batch_compress_frame_using_dict_workspace_ex(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs,
+                                                          uint32_t batch_flags, uint32_t ndicts, uint64_t max_src_len,
+                                                          uint32_t max_dict_len) {
+    (void)batch_flags;
+    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
+    return bfcd_layout(nframes, max_blocks, p, ndicts, max_src_len, max_dict_len, bfcd_hc(p, true)).bytes;
+}
+
+int32_t zlz4f_batch_compress_frame_using_dict_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                 const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                                 const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes,
+                                                 uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                                 const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                 const uint32_t *d_dict_len, uint32_t ndicts, const uint32_t *d_dict_idx,
+                                                 uint64_t max_src_len, uint32_t max_dict_len, void *d_workspace,
+                                                 size_t workspace_bytes) {
+    const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
+    return batch_compress_frame_dict_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
+                                          max_blocks, prefs, batch_flags, dd, max_src_len, max_dict_len, d_workspace,
+                                          workspace_bytes, true);
 }
 
 size_t zlz4f_batch_decompress_frame_using_dict_workspace(uint32_t nframes, uint32_t max_blocks) {
@@ -2030,20 +2135,12 @@ int32_t zlz4f_batch_frame_dict_id(void *stream, const uint8_t *d_src, const uint
 // host pointers: the frame, the dictionary's tail and a batch of one (zlz4f_compress_frame_ex)
 int64_t zlz4f_compress_frame_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const zlz4f_prefs *prefs,
                                         const uint8_t *dict, size_t dict_len) {
-    const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
-    const int32_t refused = bfcd_refusal(p, 0);
-    if (refused != 0) return refused;
-    if ((!src && n) || (!dst && cap) || (!dict && dict_len)) return ZLZ4_ERR_INVALID_STATE;
-    const size_t bound = zlz4f_compress_frame_bound(n, &p);
-    if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
-    if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const size_t D = dict_tail(dict_len);
-    DevBuf d_dict(D);
-    if (!d_dict.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    if (D && hipMemcpy(d_dict.p, dict + (dict_len - D), D, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
-        return single_compress_frame_dict(nullptr, d_src, n, d_dst, bound, p, d_dict.as<uint8_t>(), (uint32_t)D);
-    });
+    return host_compress_frame_dict(src, n, dst, cap, prefs, dict, dict_len, false);
+}
+
+int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const zlz4f_prefs *prefs,
+                                           const uint8_t *dict, size_t dict_len) {
+    return host_compress_frame_dict(src, n, dst, cap, prefs, dict, dict_len, true);
 }
 
 int64_t zlz4f_decompress_frame_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const uint8_t *dict,

@@ -84,13 +84,16 @@ extern "c" fn zlz4f_decompress_frame_device_ex(stream: ?*anyopaque, d_src: [*]co
 extern "c" fn zlz4f_decompress_frame_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
 extern "c" fn zlz4f_frame_decompressed_size_ex(src: [*]const u8, src_len: usize, decode_flags: u32) i64;
 extern "c" fn zlz4f_batch_compress_frame_using_dict_workspace(nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, ndicts: u32, max_src_len: u64, max_dict_len: u32) usize;
+extern "c" fn zlz4f_batch_compress_frame_using_dict_workspace_ex(nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, ndicts: u32, max_src_len: u64, max_dict_len: u32) usize;
 extern "c" fn zlz4f_batch_compress_frame_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, max_src_len: u64, max_dict_len: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_compress_frame_using_dict_ex(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, prefs: ?*const CPrefs, batch_flags: u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, max_src_len: u64, max_dict_len: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_batch_decompress_frame_using_dict_workspace(nframes: u32, max_blocks: u32) usize;
 extern "c" fn zlz4f_batch_decompress_frame_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_batch_frame_decompressed_size_using_dict_workspace(nframes: u32, max_blocks: u32) usize;
 extern "c" fn zlz4f_batch_frame_decompressed_size_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_size: [*]i64, nframes: u32, max_blocks: u32, d_dict_len: [*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_batch_frame_dict_id(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dict_id: [*]i64, nframes: u32) i32;
 extern "c" fn zlz4f_compress_frame_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4f_compress_frame_using_dict_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4f_decompress_frame_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4f_frame_decompressed_size_using_dict(src: [*]const u8, src_len: usize, dict_len: usize) i64;
 extern "c" fn zlz4f_batch_decompress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
@@ -741,6 +744,19 @@ pub const lz4f = struct {
         }
         return mapBatch(zlz4f_batch_compress_frame_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, null, batch_flags, d.dict, d.off, d.len, d.ndicts, d.idx, max_src_len, max_dict_len, workspace, workspace_bytes));
     }
+    // the same calls, and prefs.compression_level 3..9 (HC blocks against the dictionary; include/zlz4_amd.h); at those levels
+    // max_dict_len changes the workspace size
+    pub fn compressFrameBatchUsingDictWorkspaceEx(nframes: u32, max_blocks: u32, prefs: ?Preferences, batch_flags: u32, ndicts: u32, max_src_len: u64, max_dict_len: u32) usize {
+        if (prefs) |p| { const c = toC(p); return zlz4f_batch_compress_frame_using_dict_workspace_ex(nframes, max_blocks, &c, batch_flags, ndicts, max_src_len, max_dict_len); }
+        return zlz4f_batch_compress_frame_using_dict_workspace_ex(nframes, max_blocks, null, batch_flags, ndicts, max_src_len, max_dict_len);
+    }
+    pub fn compressFrameBatchUsingDictEx(stream: ?*anyopaque, f: Frames, max_blocks: u32, prefs: ?Preferences, batch_flags: u32, d: Dicts, max_src_len: u64, max_dict_len: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        if (prefs) |p| {
+            const c = toC(p);
+            return mapBatch(zlz4f_batch_compress_frame_using_dict_ex(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, &c, batch_flags, d.dict, d.off, d.len, d.ndicts, d.idx, max_src_len, max_dict_len, workspace, workspace_bytes));
+        }
+        return mapBatch(zlz4f_batch_compress_frame_using_dict_ex(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, max_blocks, null, batch_flags, d.dict, d.off, d.len, d.ndicts, d.idx, max_src_len, max_dict_len, workspace, workspace_bytes));
+    }
     pub fn decompressFrameBatchUsingDictWorkspace(nframes: u32, max_blocks: u32) usize {
         return zlz4f_batch_decompress_frame_using_dict_workspace(nframes, max_blocks);
     }
@@ -760,6 +776,10 @@ pub const lz4f = struct {
     pub fn compressFrameUsingDict(src: []const u8, dst: []u8, prefs: ?Preferences, dict: []const u8) Error!usize {
         if (prefs) |p| { const c = toC(p); return mapFrame(zlz4f_compress_frame_using_dict(src.ptr, src.len, dst.ptr, dst.len, &c, dict.ptr, dict.len)); }
         return mapFrame(zlz4f_compress_frame_using_dict(src.ptr, src.len, dst.ptr, dst.len, null, dict.ptr, dict.len));
+    }
+    pub fn compressFrameUsingDictEx(src: []const u8, dst: []u8, prefs: ?Preferences, dict: []const u8) Error!usize {
+        if (prefs) |p| { const c = toC(p); return mapFrame(zlz4f_compress_frame_using_dict_ex(src.ptr, src.len, dst.ptr, dst.len, &c, dict.ptr, dict.len)); }
+        return mapFrame(zlz4f_compress_frame_using_dict_ex(src.ptr, src.len, dst.ptr, dst.len, null, dict.ptr, dict.len));
     }
     pub fn decompressFrameUsingDict(src: []const u8, dst: []u8, dict: []const u8) Error!usize {
         return mapFrame(zlz4f_decompress_frame_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len));
