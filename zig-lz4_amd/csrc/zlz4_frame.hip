@@ -1174,11 +1174,26 @@ __global__ __launch_bounds__(256) void k_bfq_total(const BFrame *__restrict__ fr
 }
 
 // ------------------------------------------------------------------ workspace layout
-struct BatchLayout {
-    size_t off[24];
+// A region of the caller's workspace: a typed pointer and `bytes`, the room it holds up to the next region.  A layout
+// function carves its regions in the order the workspace holds them, each rounded up to 256 bytes, and is the only place
+// that knows that order; the _workspace functions and the call itself both go through it.  A region the call's branch does
+// not have is never carved and stays null.
+template <typename T> struct Region {
+    T *p = nullptr;
     size_t bytes = 0;
-    int n = 0;
-    size_t add(size_t b) { const size_t o = bytes; off[n++] = o; bytes = (o + b + 255) & ~(size_t)255; return o; }
+    operator T *() const { return p; }
+};
+
+struct Carver {
+    uint8_t *ws;           // null: the _workspace functions, which want the total alone
+    size_t bytes = 0;
+    template <typename T> void one(size_t count, Region<T> &r) {
+        const size_t off = bytes;
+        bytes = (off + count * sizeof(T) + 255) & ~(size_t)255;
+        r.p = ws ? reinterpret_cast<T *>(ws + off) : nullptr;
+        r.bytes = bytes - off;
+    }
+    template <typename... R> void take(size_t count, R &...r) { (one(count, r), ...); }   // `count` elements each
 };
 
 int32_t bf_hc_level(const zlz4f_prefs &p) {   // compress_frame_impl's routing (:393-404, src/lz4hc.zig:1445)
@@ -1188,89 +1203,151 @@ int32_t bf_hc_level(const zlz4f_prefs &p) {   // compress_frame_impl's routing (
 
 uint64_t bf_slot(size_t bs) { return (zlz4_compress_bound(bs) + 15) & ~15ull; }
 
-// compress: frames | in_off out_off dst_off (u64) | in_len out_cap hdr cks (u32) | csize (i64) | slots | HC workspace
-// with ZLZ4F_BATCH_LINK_BLOCKS also: | loadDict tables | dict_off (u64) | dict_len (u32) | dictSize (i64)
-// with ZLZ4F_BATCH_LINK_BLOCKS at levels 3..9 instead: frames ... slots | links, results, visited bits of
-// zlz4_launch_compress_hc_linked | v_off (u64) | { v_len, start } (2 x u32) | v_len (u32)
+// what every compress call starts with: the frame records, the block table (`m` entries) and a compressBound slot per entry
+struct CompressCore {
+    Region<BFrame> frames;
+    Region<uint64_t> in_off, out_off, dst_off;
+    Region<uint32_t> in_len, out_cap, hdr, cks;
+    Region<int64_t> csize;
+    Region<uint8_t> slots;
+    void carve(Carver &c, uint32_t nframes, size_t m, size_t bs) {
+        c.take(nframes, frames);
+        c.take(m, in_off, out_off, dst_off, in_len, out_cap, hdr, cks, csize);
+        c.take(m * bf_slot(bs), slots);
+    }
+};
+
+// linked blocks at the fast level: a loadDict table per entry, where the entry's dictionary lies
+// in the input, and what loadDict reports
+struct LinkedFastTail {
+    Region<uint32_t> tables, len;
+    Region<uint64_t> off;
+    Region<int64_t> dict_size;
+    void carve(Carver &c, size_t m) { c.take(m * ZLZ4_STREAM_TABLE_ENTRIES, tables); c.take(m, off, len, dict_size); }
+};
+
+// linked blocks at the HC levels 3..9: the V descriptors of zlz4_launch_compress_hc_linked (v_pair = { v_len, start })
+struct LinkedHcTail {
+    Region<uint64_t> v_off;
+    Region<uint32_t> v_pair, v_len;
+    void carve(Carver &c, size_t m) { c.take(m, v_off); c.take(m * 2, v_pair); c.take(m, v_len); }
+};
+
 bool bf_hc_linked(const zlz4f_prefs &p, uint32_t batch_flags) {
     const int32_t lv = bf_hc_level(p);
     return (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) && lv >= 3 && lv <= 9;
 }
 
-BatchLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t batch_flags = 0) {
-    const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
-    BatchLayout L;
-    L.add((size_t)nframes * sizeof(BFrame));
-    for (int k = 0; k < 3; k++) L.add(m * sizeof(uint64_t));
-    for (int k = 0; k < 4; k++) L.add(m * sizeof(uint32_t));
-    L.add(m * sizeof(int64_t));
-    L.add(m * bf_slot(bs));
-    if (bf_hc_linked(p, batch_flags)) {
-        L.add(zlz4_hc_linked_workspace_bytes(max_blocks, (uint32_t)bs));
-        L.add(m * sizeof(uint64_t));
-        L.add(m * 2 * sizeof(uint32_t));
-        L.add(m * sizeof(uint32_t));
-        return L;
-    }
-    L.add(bf_hc_level(p) ? zlz4_hc_workspace_bytes(max_blocks, (uint32_t)bs) : 0);
-    if (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) {
-        L.add(m * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
-        L.add(m * sizeof(uint64_t));
-        L.add(m * sizeof(uint32_t));
-        L.add(m * sizeof(int64_t));
-    }
-    return L;
-}
-
-// decompress: frames | data_off cks_off out_off x_off (u64) | data_len flags fidx cks_ok out_cap dec_len x_cap x_len (u32)
-// | sizes (i64); with ZLZ4F_DECODE_LINKED also: | walk_err (i64 per frame)
-// with a dictionary (the _using_dict calls, always history-aware) also: | fd_end (u64 per frame) | fd_len (u32 per frame)
-// | e_off (u64 per entry) | e_len (u32 per entry)
-BatchLayout bfd_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0, bool dict = false) {
-    const size_t m = max_blocks;
-    BatchLayout L;
-    L.add((size_t)nframes * sizeof(BFrame));
-    for (int k = 0; k < 4; k++) L.add(m * sizeof(uint64_t));
-    for (int k = 0; k < 8; k++) L.add(m * sizeof(uint32_t));
-    L.add(m * sizeof(int64_t));
-    if (decode_flags & ZLZ4F_DECODE_LINKED) L.add((size_t)nframes * sizeof(int64_t));
-    if (dict) {
-        L.add((size_t)nframes * sizeof(uint64_t));
-        L.add((size_t)nframes * sizeof(uint32_t));
-        L.add(m * sizeof(uint64_t));
-        L.add(m * sizeof(uint32_t));
-    }
-    return L;
-}
-
-// size query: frames | data_off cks_off (u64) | data_len flags fidx cks_ok dec_len (u32) | sizes (i64); with
-// ZLZ4F_DECODE_LINKED also: | walk_err (i64 per frame)
-// with a dictionary also: | fd_len (u32 per frame) | e_len (u32 per entry)
-BatchLayout bfq_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags = 0, bool dict = false) {
-    const size_t m = max_blocks;
-    BatchLayout L;
-    L.add((size_t)nframes * sizeof(BFrame));
-    for (int k = 0; k < 2; k++) L.add(m * sizeof(uint64_t));
-    for (int k = 0; k < 5; k++) L.add(m * sizeof(uint32_t));
-    L.add(m * sizeof(int64_t));
-    if (decode_flags & ZLZ4F_DECODE_LINKED) L.add((size_t)nframes * sizeof(int64_t));
-    if (dict) {
-        L.add((size_t)nframes * sizeof(uint32_t));
-        L.add(m * sizeof(uint32_t));
-    }
-    return L;
-}
-
-// the dictionary arguments of the _using_dict calls (include/zlz4_amd.h); a null BfDict * is a call without them
-struct BfDict {
-    const uint8_t *dict;
-    const uint64_t *off;
-    const uint32_t *len;
-    uint32_t n;
-    const uint32_t *idx;
+// zlz4f_batch_compress_frame / _ex.  hc: the workspace of the HC launcher the call uses (empty at the fast level);
+// ZLZ4F_BATCH_LINK_BLOCKS adds the trailer of its level.
+struct BfcLayout {
+    CompressCore c;
+    Region<uint8_t> hc;
+    LinkedFastTail lf;
+    LinkedHcTail lh;
+    size_t bytes = 0;
 };
 
+BfcLayout bfc_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t batch_flags = 0,
+                     void *ws = nullptr) {
+    const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
+    BfcLayout L;
+    Carver c{static_cast<uint8_t *>(ws)};
+    L.c.carve(c, nframes, m, bs);
+    if (bf_hc_linked(p, batch_flags)) {
+        c.take(zlz4_hc_linked_workspace_bytes(max_blocks, (uint32_t)bs), L.hc);
+        L.lh.carve(c, m);
+    } else {
+        c.take(bf_hc_level(p) ? zlz4_hc_workspace_bytes(max_blocks, (uint32_t)bs) : 0, L.hc);
+        if (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) L.lf.carve(c, m);
+    }
+    L.bytes = c.bytes;
+    return L;
+}
+
+// The decode-side calls, zlz4f_batch_decompress_frame and (query) zlz4f_batch_frame_decompressed_size, share one layout.
+struct BfdLayout {
+    // the block table both walk the frames into (walk_err: ZLZ4F_DECODE_LINKED, one per frame)
+    Region<BFrame> frames;
+    Region<uint64_t> data_off, cks_off;
+    Region<uint32_t> data_len, flags, fidx, cks_ok, dec_len;
+    Region<int64_t> sizes, walk_err;
+    // decode only: where the blocks go, speculative (out_) and exact (x_)
+    Region<uint64_t> out_off, x_off;
+    Region<uint32_t> out_cap, x_cap, x_len;
+    // the dictionary of the _using_dict calls per frame (fd_) and per entry (e_); the query reads no dictionary byte and
+    // has the lengths alone
+    Region<uint64_t> fd_end, e_off;
+    Region<uint32_t> fd_len, e_len;
+    size_t bytes = 0;
+};
+
+constexpr bool kDecode = false, kQuery = true;
+
+BfdLayout bfd_layout(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags, bool dict, bool query,
+                     void *ws = nullptr) {
+    const size_t m = max_blocks;
+    BfdLayout L;
+    Carver c{static_cast<uint8_t *>(ws)};
+    c.take(nframes, L.frames);
+    c.take(m, L.data_off, L.cks_off);
+    if (!query) c.take(m, L.out_off, L.x_off);
+    c.take(m, L.data_len, L.flags, L.fidx, L.cks_ok);
+    if (!query) c.take(m, L.out_cap);
+    c.take(m, L.dec_len);
+    if (!query) c.take(m, L.x_cap, L.x_len);
+    c.take(m, L.sizes);
+    if (decode_flags & ZLZ4F_DECODE_LINKED) c.take(nframes, L.walk_err);
+    if (dict && !query) c.take(nframes, L.fd_end);
+    if (dict) c.take(nframes, L.fd_len);
+    if (dict && !query) c.take(m, L.e_off);
+    if (dict) c.take(m, L.e_len);
+    L.bytes = c.bytes;
+    return L;
+}
+
+// ------------------------------------------------------------------ arguments
+// the caller's per-frame arrays (include/zlz4_amd.h); the size query and the dictID call have no destination
+struct BfArrays {
+    const uint8_t *src; const uint64_t *src_off, *src_len;
+    uint8_t *dst; const uint64_t *dst_off, *dst_cap;
+    int64_t *result; uint32_t nframes, max_blocks;
+};
+
+// the dictionary arguments of the _using_dict calls; a null BfDict * is a call without them
+struct BfDict { const uint8_t *dict; const uint64_t *off; const uint32_t *len; uint32_t n; const uint32_t *idx; };
+
 inline bool bf_misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// Every refusal of a device array or of the workspace answers ZLZ4_ERR_INVALID_STATE.  Which of them an entry point makes,
+// and where among its other refusals (flags, no device, nframes == 0) they stand, differs from call to call and is what
+// callers see: each entry point names its own set here and keeps its own order.
+enum : uint32_t {
+    kArgSrc = 1u,          // d_src, d_src_off, d_src_len and the result array are not null
+    kArgDst = 2u,          // d_dst, d_dst_off, d_dst_cap are not null
+    kArgDictLen = 4u,      // with ndicts != 0: d_dict_len is not null
+    kArgDictOff = 8u,      //                   d_dict_off is not null
+    kArgDictBytes = 16u,   //                   d_dict is not null (when max_dict_len != 0)
+    kArgAligned = 32u,     // the 64-bit arrays are 8-aligned, the dictionary's 32-bit arrays 4-aligned
+    kArgWs = 64u,          // the workspace is not null and holds `need` bytes
+    kArgWs16 = 128u,       // the workspace is 16-aligned
+};
+
+bool bf_args_refused(uint32_t want, const BfArrays &a, const BfDict *dd = nullptr, uint32_t max_dict_len = 0,
+                     const void *ws = nullptr, size_t ws_bytes = 0, size_t need = 0) {
+    if ((want & kArgSrc) && (!a.src || !a.src_off || !a.src_len || !a.result)) return true;
+    if ((want & kArgDst) && (!a.dst || !a.dst_off || !a.dst_cap)) return true;
+    if (dd && dd->n && (((want & kArgDictLen) && !dd->len) || ((want & kArgDictOff) && !dd->off) ||
+                        ((want & kArgDictBytes) && max_dict_len && !dd->dict)))
+        return true;
+    if ((want & kArgAligned) &&
+        (bf_misaligned(a.src_off, 8) || bf_misaligned(a.src_len, 8) || bf_misaligned(a.dst_off, 8) ||
+         bf_misaligned(a.dst_cap, 8) || bf_misaligned(a.result, 8) ||
+         (dd && (bf_misaligned(dd->off, 8) || bf_misaligned(dd->len, 4) || bf_misaligned(dd->idx, 4)))))
+        return true;
+    if ((want & kArgWs) && (!ws || ws_bytes < need)) return true;
+    return (want & kArgWs16) && bf_misaligned(ws, 16);
+}
 
 inline uint32_t bf_grid(uint64_t items, uint32_t threads, uint32_t cap = 0xFFFFFFFFu) {
     const uint64_t g = (items + threads - 1) / threads;
@@ -1291,16 +1368,79 @@ size_t zlz4f_batch_compress_frame_workspace_ex(uint32_t nframes, uint32_t max_bl
 }
 
 size_t zlz4f_batch_decompress_frame_workspace(uint32_t nframes, uint32_t max_blocks) {
-    return bfd_layout(nframes, max_blocks).bytes;
+    return bfd_layout(nframes, max_blocks, 0, false, kDecode).bytes;
 }
 
 size_t zlz4f_batch_decompress_frame_workspace_ex(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags) {
-    return bfd_layout(nframes, max_blocks, decode_flags).bytes;
+    return bfd_layout(nframes, max_blocks, decode_flags, false, kDecode).bytes;
 }
 
 }  // extern "C"
 
 namespace {
+
+// ------------------------------------------------------------------ compress: the launch sequences both calls share
+// Open: block count and capacity check per frame, the dictionary call's preconditions (dd; the one early return), the
+// scan, and -- with a table -- the block descriptors.
+int32_t bfc_open(hipStream_t st, const BfArrays &a, const zlz4f_prefs &p, const CompressCore &C, const BfDict *dd = nullptr,
+                 uint64_t max_src_len = 0, uint32_t max_dict_len = 0) {
+    const size_t bs = block_size_of(p.block_size_id);
+    const uint64_t per_block = 4 + zlz4_compress_bound(bs) + (p.block_checksum == 1 ? 4 : 0);   // zlz4f_compress_frame_bound
+    const uint64_t fixed = 19 + 4 + (p.content_checksum == 1 ? 4 : 0);
+    hipLaunchKernelGGL(k_bfc_count, dim3(bf_grid(a.nframes, 256)), dim3(256), 0, st, a.src_len, a.dst_cap, a.nframes,
+                       (uint64_t)bs, per_block, fixed, C.frames);
+    if (dd && zlz4_launch_bfcd_pre(st, C.frames, a.nframes, a.src_len, dd->len, dd->n, dd->idx, max_src_len, max_dict_len) != 0)
+        return ZLZ4_ERR_DEVICE;
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, C.frames, a.nframes);
+    if (a.max_blocks)
+        hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(a.max_blocks, 256, 4096)), dim3(256), 0, st, C.frames, a.nframes,
+                           a.max_blocks, a.src_off, a.src_len, (uint64_t)bs, bf_slot(bs), C.in_off, C.in_len, C.out_off,
+                           C.out_cap, C.hdr);
+    return 0;
+}
+
+// Close: with a table the dstPos plan per frame, the block checksums and the scatter; then header, end mark, content
+// checksum and result of every frame.
+int32_t bfc_close(hipStream_t st, const BfArrays &a, const zlz4f_prefs &p, uint32_t cs_from_len, const CompressCore &C) {
+    const uint32_t bc = p.block_checksum == 1 ? 1u : 0u;
+    if (a.max_blocks) {
+        hipLaunchKernelGGL(k_bfc_plan, dim3(bf_grid(a.nframes, 4)), dim3(256), 0, st, C.frames, a.nframes, a.max_blocks,
+                           C.csize, C.in_len, bc, p, cs_from_len, a.src_len, a.dst_off, C.dst_off, C.hdr);
+        if (bc)
+            hipLaunchKernelGGL(k_block_xxh32, dim3(bf_grid(a.max_blocks, 64)), dim3(64), 0, st, a.src, C.in_off, C.slots,
+                               C.out_off, C.hdr, a.max_blocks, C.cks);
+        hipLaunchKernelGGL(k_bf_scatter, dim3(a.max_blocks), dim3(256), 0, st, a.src, C.in_off, C.slots, C.out_off, C.hdr,
+                           C.dst_off, C.cks, bc, a.dst);
+    }
+    hipLaunchKernelGGL(k_bfc_head_tail, dim3(bf_grid(a.nframes, 64)), dim3(64), 0, st, C.frames, a.nframes, a.max_blocks, p,
+                       cs_from_len, a.src, a.src_off, a.src_len, a.dst, a.dst_off, a.result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+// Linked blocks at the fast level: the entries with len[i] != 0 against the 64 KiB of input in front of them.  Descriptors,
+// one loadDict table per entry, then the dictionary compressor over the table (block 0 of a frame has an empty dictionary:
+// compressDefault's bytes).  Answers the first failing launcher's code.
+int bfc_linked_fast(hipStream_t st, const BfArrays &a, const CompressCore &C, const LinkedFastTail &T, const uint32_t *len,
+                    int64_t *csize, size_t bs) {
+    int rc = zlz4_launch_bfl_dict_desc(st, C.frames, a.nframes, a.max_blocks, a.src_off, C.in_off, len, T.off, T.len);
+    if (rc == 0) rc = zlz4_launch_load_dict(st, a.src, T.off, T.len, T.tables, T.dict_size, a.max_blocks);
+    if (rc == 0)
+        rc = zlz4_launch_compress_fast_using_dict(st, a.src, C.in_off, len, C.slots, C.out_off, C.out_cap, a.src, T.off, T.len,
+                                                  T.tables, nullptr, csize, a.max_blocks, (uint32_t)bs, 65536u, 1);
+    return rc;
+}
+
+// Linked blocks at the levels 3..9: block k is compressHCUsingDict against the same 64 KiB; V_k = tail ++ block lies
+// contiguous in d_src, so the descriptors point the HC kernels at the input itself (no staged copy, no loadDict table).
+int bfc_linked_hc(hipStream_t st, const BfArrays &a, const CompressCore &C, const LinkedHcTail &T, const Region<uint8_t> &hc,
+                  const uint32_t *len, int64_t *csize, size_t bs, int32_t level) {
+    int rc = zlz4_launch_bfl_hc_desc(st, C.frames, a.nframes, a.max_blocks, a.src_off, C.in_off, len, T.v_off, T.v_len,
+                                     T.v_pair);
+    if (rc == 0)
+        rc = zlz4_launch_compress_hc_linked(st, a.src, T.v_off, T.v_len, T.v_pair, C.slots, C.out_off, C.out_cap, csize,
+                                            a.max_blocks, (uint32_t)bs, level, hc, hc.bytes);
+    return rc;
+}
 
 // the refusals of both compress calls that need no device, in their order.  ex: zlz4f_batch_compress_frame_ex, which links
 // blocks at the HC levels 3..9 (the levels zlz4_batch_compress_hc_using_dict takes); the plain call refuses every HC level.
@@ -1313,87 +1453,39 @@ int32_t bfc_refusal(const zlz4f_prefs &p, uint32_t batch_flags, bool ex) {
     return 0;
 }
 
-int32_t batch_compress_frame_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
-                                  uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
-                                  uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
-                                  void *d_workspace, size_t workspace_bytes, bool ex) {
+// The compressors answer their own code on the paths without links; a failing launcher of a linked path is a DeviceError.
+int32_t batch_compress_frame_impl(void *stream_, const BfArrays &a, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                  void *ws, size_t workspace_bytes, bool ex) {
     const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
     const int32_t refused = bfc_refusal(p, batch_flags, ex);
     if (refused != 0) return refused;
     const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
     const bool link = (batch_flags & ZLZ4F_BATCH_LINK_BLOCKS) != 0;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const BatchLayout L = bfc_layout(nframes, max_blocks, p, batch_flags);
-    if (nframes == 0) return 0;
-    if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
-    if (ex && (reinterpret_cast<uintptr_t>(d_workspace) & 15u)) return ZLZ4_ERR_INVALID_STATE;
+    const BfcLayout L = bfc_layout(a.nframes, a.max_blocks, p, batch_flags, ws);
+    if (a.nframes == 0) return 0;
+    if (bf_args_refused(kArgWs | (ex ? kArgWs16 : 0u), a, nullptr, 0, ws, workspace_bytes, L.bytes))
+        return ZLZ4_ERR_INVALID_STATE;
     hipStream_t st = (hipStream_t)stream_;
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
-    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
-    uint64_t *in_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *out_off = reinterpret_cast<uint64_t *>(ws + L.off[2]),
-             *dst_off = reinterpret_cast<uint64_t *>(ws + L.off[3]);
-    uint32_t *in_len = reinterpret_cast<uint32_t *>(ws + L.off[4]), *out_cap = reinterpret_cast<uint32_t *>(ws + L.off[5]),
-             *hdr = reinterpret_cast<uint32_t *>(ws + L.off[6]), *cks = reinterpret_cast<uint32_t *>(ws + L.off[7]);
-    int64_t *csize = reinterpret_cast<int64_t *>(ws + L.off[8]);
-    uint8_t *slots = ws + L.off[9];
-    void *hc_ws = ws + L.off[10];
-    const size_t hc_bytes = L.bytes - L.off[10];
+    const CompressCore &C = L.c;
     const size_t bs = block_size_of(p.block_size_id);
     const int32_t hc_level = bf_hc_level(p);
-    const uint32_t bc = p.block_checksum == 1 ? 1u : 0u;
-    const uint64_t slot = bf_slot(bs);
-    const uint64_t per_block = 4 + zlz4_compress_bound(bs) + (bc ? 4 : 0);       // zlz4f_compress_frame_bound
-    const uint64_t fixed = 19 + 4 + (p.content_checksum == 1 ? 4 : 0);
-    hipLaunchKernelGGL(k_bfc_count, dim3(bf_grid(nframes, 256)), dim3(256), 0, st, d_src_len, d_dst_cap, nframes,
-                       (uint64_t)bs, per_block, fixed, fr);
-    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
-    if (max_blocks) {
-        hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, fr, nframes, max_blocks,
-                           d_src_off, d_src_len, (uint64_t)bs, slot, in_off, in_len, out_off, out_cap, hdr);
+    (void)bfc_open(st, a, p, C);             // (its one failure is the dictionary call's)
+    if (a.max_blocks) {
         int rc;
-        if (link && hc_level != 0) {
-            // levels 3..9: block k is compressHCUsingDict against the same 64 KiB; V_k = tail ++ block lies contiguous in
-            // d_src, so the descriptors point the HC kernels at the input itself (no staged copy, no loadDict table)
-            uint64_t *v_off = reinterpret_cast<uint64_t *>(ws + L.off[11]);
-            uint32_t *v_pair = reinterpret_cast<uint32_t *>(ws + L.off[12]);
-            uint32_t *v_len = reinterpret_cast<uint32_t *>(ws + L.off[13]);
-            rc = zlz4_launch_bfl_hc_desc(st, fr, nframes, max_blocks, d_src_off, in_off, in_len, v_off, v_len, v_pair);
-            if (rc == 0)
-                rc = zlz4_launch_compress_hc_linked(st, d_src, v_off, v_len, v_pair, slots, out_off, out_cap, csize, max_blocks,
-                                                    (uint32_t)bs, hc_level, hc_ws, L.off[11] - L.off[10]);
-            if (rc != 0) rc = ZLZ4_ERR_DEVICE;
-        } else if (link) {
-            // block k against the 64 KiB of input in front of it: descriptors, one loadDict table per entry, then the
-            // dictionary compressor over the table (block 0 of a frame has an empty dictionary: compressDefault's bytes)
-            uint32_t *tables = reinterpret_cast<uint32_t *>(ws + L.off[11]);
-            uint64_t *dict_off = reinterpret_cast<uint64_t *>(ws + L.off[12]);
-            uint32_t *dict_len = reinterpret_cast<uint32_t *>(ws + L.off[13]);
-            int64_t *dict_size = reinterpret_cast<int64_t *>(ws + L.off[14]);
-            rc = zlz4_launch_bfl_dict_desc(st, fr, nframes, max_blocks, d_src_off, in_off, in_len, dict_off, dict_len);
-            if (rc == 0) rc = zlz4_launch_load_dict(st, d_src, dict_off, dict_len, tables, dict_size, max_blocks);
-            if (rc == 0)
-                rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, in_len, slots, out_off, out_cap, d_src, dict_off,
-                                                          dict_len, tables, nullptr, csize, max_blocks, (uint32_t)bs, 65536u,
-                                                          1);
+        if (link) {
+            rc = hc_level != 0 ? bfc_linked_hc(st, a, C, L.lh, L.hc, C.in_len, C.csize, bs, hc_level)
+                               : bfc_linked_fast(st, a, C, L.lf, C.in_len, C.csize, bs);
             if (rc != 0) rc = ZLZ4_ERR_DEVICE;
         } else if (hc_level == 0)
-            rc = zlz4_launch_compress_fast(st, d_src, in_off, in_len, slots, out_off, out_cap, csize, max_blocks,
+            rc = zlz4_launch_compress_fast(st, a.src, C.in_off, C.in_len, C.slots, C.out_off, C.out_cap, C.csize, a.max_blocks,
                                            (uint32_t)bs, 1);                                               // :400-404
         else
-            rc = zlz4_launch_compress_hc(st, d_src, in_off, in_len, slots, out_off, out_cap, csize, max_blocks,
-                                         (uint32_t)bs, hc_level, hc_ws, hc_bytes);                         // :394-398
+            rc = zlz4_launch_compress_hc(st, a.src, C.in_off, C.in_len, C.slots, C.out_off, C.out_cap, C.csize, a.max_blocks,
+                                         (uint32_t)bs, hc_level, L.hc, L.hc.bytes);                        // :394-398
         if (rc != 0) return rc;
-        hipLaunchKernelGGL(k_bfc_plan, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, csize, in_len,
-                           bc, p, cs_from_len, d_src_len, d_dst_off, dst_off, hdr);
-        if (bc)
-            hipLaunchKernelGGL(k_block_xxh32, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, in_off, slots, out_off,
-                               hdr, max_blocks, cks);
-        hipLaunchKernelGGL(k_bf_scatter, dim3(max_blocks), dim3(256), 0, st, d_src, in_off, slots, out_off, hdr, dst_off,
-                           cks, bc, d_dst);
     }
-    hipLaunchKernelGGL(k_bfc_head_tail, dim3(bf_grid(nframes, 64)), dim3(64), 0, st, fr, nframes, max_blocks, p,
-                       cs_from_len, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_result);
-    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+    return bfc_close(st, a, p, cs_from_len, C);
 }
 
 // ------------------------------------------------------------------ dictionary frames, compress
@@ -1415,51 +1507,42 @@ uint32_t bfcd_in_max(size_t bs, uint64_t max_src_len) {
     return max_src_len != 0 && max_src_len < bs ? (uint32_t)max_src_len : (uint32_t)bs;
 }
 
-// frames | in_off out_off dst_off (u64) | in_len out_cap hdr cks (u32) | csize (i64) | slots | loadDict tables of the
-// dictionaries | their dictSize (i64) | len_a (u32) | a_off (u64) | a_len a_tix (u32); with launch B also: | len_b (u32) |
-// loadDict tables per entry | b_off (u64) | b_len (u32) | dictSize (i64) | csize_b (i64)
-// hc (bfcd_hc): frames ... slots | len_a (u32) | a_off (u64) | a_len a_tix (u32) | HC scratch; with launch B also: | len_b
-// (u32) | v_off (u64) | { v_len, start } (2 x u32) | v_len (u32) | csize_b (i64).  The HC scratch is ONE region, the larger
-// of zlz4_hc_dict_workspace_bytes (launch A) and zlz4_hc_linked_workspace_bytes (launch B): both launchers join their side
-// stream into the caller's before they return, so launch B's first memset is ordered behind all of launch A's work.
-BatchLayout bfcd_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t ndicts, uint64_t max_src_len,
-                        uint32_t max_dict_len = 0, bool hc = false) {
+// zlz4f_batch_compress_frame_using_dict / _ex.  d_tables, d_sizes: loadDict over the ndicts dictionaries (fast level only).
+// len_a ... a_tix: launch A's lengths and dictionary descriptors.  With launch B: len_b, the linked trailer of the level and
+// B's results.  hc (bfcd_hc) is ONE region, the larger of zlz4_hc_dict_workspace_bytes (launch A) and
+// zlz4_hc_linked_workspace_bytes (launch B): both launchers join their side stream into the caller's before they return,
+// so launch B's first memset is ordered behind all of launch A's work.
+struct BfcdLayout {
+    CompressCore c;
+    Region<uint32_t> d_tables, len_a, a_len, a_tix, len_b;
+    Region<uint64_t> a_off;
+    Region<int64_t> d_sizes, csize_b;
+    Region<uint8_t> hc;
+    LinkedFastTail lf;
+    LinkedHcTail lh;
+    size_t bytes = 0;
+};
+
+BfcdLayout bfcd_layout(uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs &p, uint32_t ndicts, uint64_t max_src_len,
+                       uint32_t max_dict_len = 0, bool hc = false, void *ws = nullptr) {
     const size_t bs = block_size_of(p.block_size_id), m = max_blocks;
-    BatchLayout L;
-    L.add((size_t)nframes * sizeof(BFrame));
-    for (int k = 0; k < 3; k++) L.add(m * sizeof(uint64_t));
-    for (int k = 0; k < 4; k++) L.add(m * sizeof(uint32_t));
-    L.add(m * sizeof(int64_t));
-    L.add(m * bf_slot(bs));
+    const bool link_b = bfcd_link_b(p, max_src_len);
+    BfcdLayout L;
+    Carver c{static_cast<uint8_t *>(ws)};
+    L.c.carve(c, nframes, m, bs);
+    if (!hc) { c.take((size_t)ndicts * ZLZ4_STREAM_TABLE_ENTRIES, L.d_tables); c.take(ndicts, L.d_sizes); }
+    c.take(m, L.len_a, L.a_off, L.a_len, L.a_tix);
     if (hc) {
-        const bool link_b = bfcd_link_b(p, max_src_len);
-        L.add(m * sizeof(uint32_t));
-        L.add(m * sizeof(uint64_t));
-        for (int k = 0; k < 2; k++) L.add(m * sizeof(uint32_t));
         const size_t scratch_a = zlz4_hc_dict_workspace_bytes(max_blocks, bfcd_in_max(bs, max_src_len), max_dict_len);
         const size_t scratch_b = link_b ? zlz4_hc_linked_workspace_bytes(max_blocks, (uint32_t)bs) : 0;
-        L.add(scratch_a > scratch_b ? scratch_a : scratch_b);
-        if (link_b) {
-            L.add(m * sizeof(uint32_t));
-            L.add(m * sizeof(uint64_t));
-            L.add(m * 2 * sizeof(uint32_t));
-            L.add(m * sizeof(uint32_t));
-            L.add(m * sizeof(int64_t));
-        }
-        return L;
+        c.take(scratch_a > scratch_b ? scratch_a : scratch_b, L.hc);
     }
-    L.add((size_t)ndicts * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
-    L.add((size_t)ndicts * sizeof(int64_t));
-    L.add(m * sizeof(uint32_t));
-    L.add(m * sizeof(uint64_t));
-    for (int k = 0; k < 2; k++) L.add(m * sizeof(uint32_t));
-    if (bfcd_link_b(p, max_src_len)) {
-        L.add(m * sizeof(uint32_t));
-        L.add(m * ZLZ4_STREAM_TABLE_ENTRIES * sizeof(uint32_t));
-        L.add(m * sizeof(uint64_t));
-        L.add(m * sizeof(uint32_t));
-        for (int k = 0; k < 2; k++) L.add(m * sizeof(int64_t));
+    if (link_b) {
+        c.take(m, L.len_b);
+        if (hc) L.lh.carve(c, m); else L.lf.carve(c, m);
+        c.take(m, L.csize_b);
     }
+    L.bytes = c.bytes;
     return L;
 }
 
@@ -1481,134 +1564,95 @@ int32_t bfcd_refusal(const zlz4f_prefs &p, uint32_t batch_flags, bool ex = false
 // zlz4_launch_compress_hc_dict over len_a / a_off / a_len (an entry that takes no part has record and dictionary length 0:
 // nothing staged, result 0), launch B zlz4_launch_compress_hc_linked over the V descriptors k_bfl_hc_desc derives from
 // len_b (block 0 and the empty entries get an empty V).  No loadDict table is built.
-int32_t batch_compress_frame_dict_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
-                                       const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
-                                       const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
-                                       const zlz4f_prefs *prefs, uint32_t batch_flags, const BfDict &dd, uint64_t max_src_len,
-                                       uint32_t max_dict_len, void *d_workspace, size_t workspace_bytes, bool ex) {
+// Every failing launcher is a DeviceError here.
+int32_t batch_compress_frame_dict_impl(void *stream_, const BfArrays &a, const zlz4f_prefs *prefs, uint32_t batch_flags,
+                                       const BfDict &dd, uint64_t max_src_len, uint32_t max_dict_len, void *ws,
+                                       size_t workspace_bytes, bool ex) {
     const zlz4f_prefs p = prefs ? *prefs : kDefaultPrefs;
     const int32_t refused = bfcd_refusal(p, batch_flags, ex);
     if (refused != 0) return refused;
     const uint32_t cs_from_len = (batch_flags & ZLZ4F_BATCH_CONTENT_SIZE) ? 1u : 0u;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     const bool hc = bfcd_hc(p, ex);
-    const BatchLayout L = bfcd_layout(nframes, max_blocks, p, dd.n, max_src_len, max_dict_len, hc);
-    if (nframes == 0) return 0;
-    if (!d_src || !d_src_off || !d_src_len || !d_dst || !d_dst_off || !d_dst_cap || !d_result ||
-        (dd.n && (!dd.off || !dd.len)) || (dd.n && max_dict_len && !dd.dict) || bf_misaligned(d_src_off, 8) ||
-        bf_misaligned(d_src_len, 8) || bf_misaligned(d_dst_off, 8) || bf_misaligned(d_dst_cap, 8) || bf_misaligned(d_result, 8) ||
-        bf_misaligned(dd.off, 8) || bf_misaligned(dd.len, 4) || bf_misaligned(dd.idx, 4))
+    const BfcdLayout L = bfcd_layout(a.nframes, a.max_blocks, p, dd.n, max_src_len, max_dict_len, hc, ws);
+    if (a.nframes == 0) return 0;
+    if (bf_args_refused(kArgSrc | kArgDst | kArgDictLen | kArgDictOff | kArgDictBytes | kArgAligned | kArgWs | kArgWs16, a, &dd,
+                        max_dict_len, ws, workspace_bytes, L.bytes))
         return ZLZ4_ERR_INVALID_STATE;
-    if (workspace_bytes < L.bytes || !d_workspace || bf_misaligned(d_workspace, 16)) return ZLZ4_ERR_INVALID_STATE;
     hipStream_t st = (hipStream_t)stream_;
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
-    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
-    uint64_t *in_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *out_off = reinterpret_cast<uint64_t *>(ws + L.off[2]),
-             *dst_off = reinterpret_cast<uint64_t *>(ws + L.off[3]);
-    uint32_t *in_len = reinterpret_cast<uint32_t *>(ws + L.off[4]), *out_cap = reinterpret_cast<uint32_t *>(ws + L.off[5]),
-             *hdr = reinterpret_cast<uint32_t *>(ws + L.off[6]), *cks = reinterpret_cast<uint32_t *>(ws + L.off[7]);
-    int64_t *csize = reinterpret_cast<int64_t *>(ws + L.off[8]);
-    uint8_t *slots = ws + L.off[9];
-    const int a0 = hc ? 10 : 12;                                   // launch A's descriptors (bfcd_layout)
-    uint32_t *len_a = reinterpret_cast<uint32_t *>(ws + L.off[a0]);
-    uint64_t *a_off = reinterpret_cast<uint64_t *>(ws + L.off[a0 + 1]);
-    uint32_t *a_len = reinterpret_cast<uint32_t *>(ws + L.off[a0 + 2]), *a_tix = reinterpret_cast<uint32_t *>(ws + L.off[a0 + 3]);
+    const CompressCore &C = L.c;
     const bool link_b = bfcd_link_b(p, max_src_len);
     const size_t bs = block_size_of(p.block_size_id);
-    const uint32_t bc = p.block_checksum == 1 ? 1u : 0u;
-    const uint64_t slot = bf_slot(bs);
-    const uint64_t per_block = 4 + zlz4_compress_bound(bs) + (bc ? 4 : 0);       // zlz4f_compress_frame_bound
-    const uint64_t fixed = 19 + 4 + (p.content_checksum == 1 ? 4 : 0);
-    hipLaunchKernelGGL(k_bfc_count, dim3(bf_grid(nframes, 256)), dim3(256), 0, st, d_src_len, d_dst_cap, nframes,
-                       (uint64_t)bs, per_block, fixed, fr);
-    if (zlz4_launch_bfcd_pre(st, fr, nframes, d_src_len, dd.len, dd.n, dd.idx, max_src_len, max_dict_len) != 0)
-        return ZLZ4_ERR_DEVICE;
-    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
-    if (max_blocks) {
-        hipLaunchKernelGGL(k_bfc_desc, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, fr, nframes, max_blocks,
-                           d_src_off, d_src_len, (uint64_t)bs, slot, in_off, in_len, out_off, out_cap, hdr);
-        uint32_t *len_b = link_b ? reinterpret_cast<uint32_t *>(ws + L.off[hc ? 15 : 16]) : nullptr;
+    if (bfc_open(st, a, p, C, &dd, max_src_len, max_dict_len) != 0) return ZLZ4_ERR_DEVICE;
+    if (a.max_blocks) {
         // (without launch B every frame has one block at most: all entries are launch A's, len_b does not exist)
-        int rc = zlz4_launch_bfcd_desc(st, fr, nframes, max_blocks, link_b, dd.off, dd.len, dd.idx, in_len, len_a, len_b, a_off,
-                                       a_len, a_tix);
+        int rc = zlz4_launch_bfcd_desc(st, C.frames, a.nframes, a.max_blocks, link_b, dd.off, dd.len, dd.idx, C.in_len, L.len_a,
+                                       L.len_b, L.a_off, L.a_len, L.a_tix);
         const uint32_t in_max = bfcd_in_max(bs, max_src_len);
         if (hc) {
-            const int32_t level = bf_hc_level(p);
-            void *hc_ws = ws + L.off[14];
-            const size_t hc_bytes = (link_b ? L.off[15] : L.bytes) - L.off[14];
             if (rc == 0)
-                rc = zlz4_launch_compress_hc_dict(st, d_src, in_off, len_a, slots, out_off, out_cap, dd.dict, a_off, a_len, csize,
-                                                  max_blocks, in_max, max_dict_len, level, hc_ws, hc_bytes);
-            if (rc == 0 && link_b) {
-                uint64_t *v_off = reinterpret_cast<uint64_t *>(ws + L.off[16]);
-                uint32_t *v_pair = reinterpret_cast<uint32_t *>(ws + L.off[17]);
-                uint32_t *v_len = reinterpret_cast<uint32_t *>(ws + L.off[18]);
-                int64_t *csize_b = reinterpret_cast<int64_t *>(ws + L.off[19]);
-                rc = zlz4_launch_bfl_hc_desc(st, fr, nframes, max_blocks, d_src_off, in_off, len_b, v_off, v_len, v_pair);
-                if (rc == 0)
-                    rc = zlz4_launch_compress_hc_linked(st, d_src, v_off, v_len, v_pair, slots, out_off, out_cap, csize_b,
-                                                        max_blocks, (uint32_t)bs, level, hc_ws, hc_bytes);
-                if (rc == 0) rc = zlz4_launch_bfcd_merge(st, len_b, csize_b, csize, max_blocks);
-            }
+                rc = zlz4_launch_compress_hc_dict(st, a.src, C.in_off, L.len_a, C.slots, C.out_off, C.out_cap, dd.dict, L.a_off,
+                                                  L.a_len, C.csize, a.max_blocks, in_max, max_dict_len, bf_hc_level(p), L.hc,
+                                                  L.hc.bytes);
+            if (rc == 0 && link_b) rc = bfc_linked_hc(st, a, C, L.lh, L.hc, L.len_b, L.csize_b, bs, bf_hc_level(p));
         } else {
-            uint32_t *d_tables = reinterpret_cast<uint32_t *>(ws + L.off[10]);
-            int64_t *d_sizes = reinterpret_cast<int64_t *>(ws + L.off[11]);
-            if (rc == 0 && dd.n) rc = zlz4_launch_load_dict(st, dd.dict, dd.off, dd.len, d_tables, d_sizes, dd.n);
+            if (rc == 0 && dd.n) rc = zlz4_launch_load_dict(st, dd.dict, dd.off, dd.len, L.d_tables, L.d_sizes, dd.n);
             if (rc == 0)
-                rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_a, slots, out_off, out_cap, dd.dict, a_off,
-                                                          a_len, d_tables, a_tix, csize, max_blocks, in_max, max_dict_len, 1);
-            if (rc == 0 && link_b) {
-                uint32_t *tables = reinterpret_cast<uint32_t *>(ws + L.off[17]);
-                uint64_t *b_off = reinterpret_cast<uint64_t *>(ws + L.off[18]);
-                uint32_t *b_len = reinterpret_cast<uint32_t *>(ws + L.off[19]);
-                int64_t *b_size = reinterpret_cast<int64_t *>(ws + L.off[20]);
-                int64_t *csize_b = reinterpret_cast<int64_t *>(ws + L.off[21]);
-                rc = zlz4_launch_bfl_dict_desc(st, fr, nframes, max_blocks, d_src_off, in_off, len_b, b_off, b_len);
-                if (rc == 0) rc = zlz4_launch_load_dict(st, d_src, b_off, b_len, tables, b_size, max_blocks);
-                if (rc == 0)
-                    rc = zlz4_launch_compress_fast_using_dict(st, d_src, in_off, len_b, slots, out_off, out_cap, d_src, b_off,
-                                                              b_len, tables, nullptr, csize_b, max_blocks, (uint32_t)bs,
-                                                              65536u, 1);
-                if (rc == 0) rc = zlz4_launch_bfcd_merge(st, len_b, csize_b, csize, max_blocks);
-            }
+                rc = zlz4_launch_compress_fast_using_dict(st, a.src, C.in_off, L.len_a, C.slots, C.out_off, C.out_cap, dd.dict,
+                                                          L.a_off, L.a_len, L.d_tables, L.a_tix, C.csize, a.max_blocks, in_max,
+                                                          max_dict_len, 1);
+            if (rc == 0 && link_b) rc = bfc_linked_fast(st, a, C, L.lf, L.len_b, L.csize_b, bs);
         }
+        if (rc == 0 && link_b) rc = zlz4_launch_bfcd_merge(st, L.len_b, L.csize_b, C.csize, a.max_blocks);
         if (rc != 0) return ZLZ4_ERR_DEVICE;
-        hipLaunchKernelGGL(k_bfc_plan, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, csize, in_len,
-                           bc, p, cs_from_len, d_src_len, d_dst_off, dst_off, hdr);
-        if (bc)
-            hipLaunchKernelGGL(k_block_xxh32, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, in_off, slots, out_off,
-                               hdr, max_blocks, cks);
-        hipLaunchKernelGGL(k_bf_scatter, dim3(max_blocks), dim3(256), 0, st, d_src, in_off, slots, out_off, hdr, dst_off,
-                           cks, bc, d_dst);
     }
-    hipLaunchKernelGGL(k_bfc_head_tail, dim3(bf_grid(nframes, 64)), dim3(64), 0, st, fr, nframes, max_blocks, p,
-                       cs_from_len, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_result);
-    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+    return bfc_close(st, a, p, cs_from_len, C);
 }
 
-// One frame through zlz4f_batch_compress_frame_ex, device pointers: a batch of one with max_blocks = ceil(n / bs) and a
-// workspace from the device cache; synchronises `st` (as single_frame_ex of the decode side)
-int64_t single_compress_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
-                                 const zlz4f_prefs &p, uint32_t batch_flags) {
+// One frame through zlz4f_batch_compress_frame_ex or, with a dictionary of dict_len bytes at d_dict, through
+// zlz4f_batch_compress_frame_using_dict (ex: .._using_dict_ex); device pointers: a batch of one with max_blocks =
+// ceil(n / bs), a staged record and a workspace from the device cache; synchronises `st` (as single_frame_ex of the
+// decode side)
+struct OneDict { const uint8_t *d_dict; uint32_t dict_len; bool ex; };
+
+int64_t single_compress_frame(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap, const zlz4f_prefs &p,
+                              uint32_t batch_flags, const OneDict *dict = nullptr) {
     const size_t bs = block_size_of(p.block_size_id);
     const uint64_t nb = (uint64_t)n / bs + (n % bs != 0);
     if (nb > 0x7FFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const uint32_t max_blocks = (uint32_t)nb;
     DeviceCall dc(st);
-    const size_t ws = bfc_layout(1, max_blocks, p, batch_flags).bytes;
-    Staged<FrameRec> rec(&dc);
+    const size_t ws = dict ? bfcd_layout(1, max_blocks, p, 1, n, dict->dict_len, bfcd_hc(p, dict->ex)).bytes
+                           : bfc_layout(1, max_blocks, p, batch_flags).bytes;
+    struct Rec { FrameRec f; uint64_t dict_off; uint32_t dict_len; };
+    Staged<Rec> rec(&dc);
     DevBuf d_ws(ws, &dc);
     if (!rec.d || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    rec.h.src_len = n; rec.h.dst_cap = cap;
+    rec.h.f.src_len = n; rec.h.f.dst_cap = cap; rec.h.dict_len = dict ? dict->dict_len : 0;
     dc.launched();
-    if (!rec.upload(st)) return ZLZ4_ERR_DEVICE;
-    FrameRec *r = rec.d;
-    const int32_t rc = batch_compress_frame_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap, &r->result,
-                                                 1, max_blocks, &p, batch_flags, d_ws.p, ws, true);
+    if (!rec.upload(st, dict ? sizeof(Rec) : sizeof(FrameRec))) return ZLZ4_ERR_DEVICE;   // (the dictionary fields follow f)
+    FrameRec *r = &rec.d->f;
+    const BfArrays a = {d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap, &r->result, 1, max_blocks};
+    int32_t rc;
+    if (dict) {
+        const BfDict dd = {dict->d_dict, &rec.d->dict_off, &rec.d->dict_len, 1u, nullptr};
+        rc = batch_compress_frame_dict_impl(st, a, &p, 0, dd, n, dict->dict_len, d_ws.p, ws, dict->ex);
+    } else {
+        rc = batch_compress_frame_impl(st, a, &p, batch_flags, d_ws.p, ws, true);
+    }
     if (rc != 0) return rc;
     int64_t result = 0;
     if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
     return result;
+}
+
+// the last 64 KiB of a host dictionary on the device, for the call that then runs with it
+template <typename Call> int64_t with_dict_tail(const uint8_t *dict, size_t dict_len, Call call) {
+    const size_t D = dict_tail(dict_len);
+    DevBuf d_dict(D);
+    if (!d_dict.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (D && hipMemcpy(d_dict.p, dict + (dict_len - D), D, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    return call(d_dict.as<uint8_t>(), (uint32_t)D);
 }
 
 }  // namespace
@@ -1619,8 +1663,8 @@ int32_t zlz4f_batch_compress_frame(void *stream, const uint8_t *d_src, const uin
                                    uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
                                    uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
                                    void *d_workspace, size_t workspace_bytes) {
-    return batch_compress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
-                                     max_blocks, prefs, batch_flags, d_workspace, workspace_bytes, false);
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, max_blocks};
+    return batch_compress_frame_impl(stream, a, prefs, batch_flags, d_workspace, workspace_bytes, false);
 }
 
 // zlz4f_batch_compress_frame, and ZLZ4F_BATCH_LINK_BLOCKS at the HC levels 3..9
@@ -1628,8 +1672,8 @@ int32_t zlz4f_batch_compress_frame_ex(void *stream, const uint8_t *d_src, const 
                                       uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result,
                                       uint32_t nframes, uint32_t max_blocks, const zlz4f_prefs *prefs, uint32_t batch_flags,
                                       void *d_workspace, size_t workspace_bytes) {
-    return batch_compress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
-                                     max_blocks, prefs, batch_flags, d_workspace, workspace_bytes, true);
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, max_blocks};
+    return batch_compress_frame_impl(stream, a, prefs, batch_flags, d_workspace, workspace_bytes, true);
 }
 
 // one frame through zlz4f_batch_compress_frame_ex (the result is the batch call's for that frame); synchronises `stream`
@@ -1640,7 +1684,7 @@ int64_t zlz4f_compress_frame_device_ex(void *stream, const uint8_t *d_src, size_
     if (refused != 0) return refused;
     if ((!d_src && n) || (!d_dst && cap)) return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    return single_compress_frame_ex((hipStream_t)stream, d_src, n, d_dst, cap, p, batch_flags);
+    return single_compress_frame((hipStream_t)stream, d_src, n, d_dst, cap, p, batch_flags);
 }
 
 // host pointers: stage -> the device call -> copy the frame back
@@ -1654,7 +1698,7 @@ int64_t zlz4f_compress_frame_ex(const uint8_t *src, size_t n, uint8_t *dst, size
     if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
-        return single_compress_frame_ex(nullptr, d_src, n, d_dst, bound, p, batch_flags);
+        return single_compress_frame(nullptr, d_src, n, d_dst, bound, p, batch_flags);
     });
 }
 
@@ -1662,191 +1706,138 @@ int64_t zlz4f_compress_frame_ex(const uint8_t *src, size_t n, uint8_t *dst, size
 
 namespace {
 
+// ------------------------------------------------------------------ decode: what both decode-side calls share
+// with a dictionary the block decoders take a descriptor per entry
+int bfd_decode_safe(hipStream_t st, const BfArrays &a, const BfDict *dd, const BfdLayout &L, const uint32_t *len,
+                    const uint64_t *off, const uint32_t *cap) {
+    return dd ? zlz4_launch_decompress_safe_using_dict(st, a.src, L.data_off, len, a.dst, off, cap, L.sizes, a.max_blocks,
+                                                       dd->dict, L.e_off, L.e_len)
+              : zlz4_launch_decompress_safe(st, a.src, L.data_off, len, a.dst, off, cap, L.sizes, a.max_blocks);
+}
+
+int bfd_decode_sizes(hipStream_t st, const BfArrays &a, const BfDict *dd, const BfdLayout &L, const uint32_t *len,
+                     const uint64_t *off, const uint32_t *cap) {
+    return dd ? zlz4_launch_decompress_sizes_using_dict(st, a.src, L.data_off, len, off, cap, L.sizes, a.max_blocks, L.e_off,
+                                                        L.e_len)
+              : zlz4_launch_decompress_sizes(st, a.src, L.data_off, len, off, cap, L.sizes, a.max_blocks);
+}
+
+// the entries of the frames k_bfl_decode takes leave a length / capacity array (ZLZ4F_DECODE_LINKED only)
+int bfd_mask_serial(hipStream_t st, const BfDict *dd, const BfdLayout &L, uint32_t max_blocks, uint32_t *cap, uint32_t *len) {
+    return (dd ? zlz4_launch_bfdd_mask : zlz4_launch_bfl_mask)(st, L.frames, L.fidx, max_blocks, cap, len);
+}
+
+// The prelude: clear the table, count every frame's blocks, (dictionary) the frame's dictionary, scan, (linked) keep the
+// walk's error, and -- with a table -- record the blocks, (dictionary) the entry's dictionary, verify the block checksums.
+// The size query has no fd_end / e_off and passes no dictionary offsets.  0 or ZLZ4_ERR_DEVICE.
+int32_t bfd_prelude(hipStream_t st, const BfArrays &a, bool linked, const BfDict *dd, const BfdLayout &L) {
+    const uint32_t gf = bf_grid(a.nframes, 256), gb = bf_grid(a.max_blocks, 256, 4096);
+    if (a.max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, L.data_len, L.flags, L.fidx, a.max_blocks);
+    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, a.src, a.src_off, a.src_len, a.nframes, a.max_blocks,
+                       L.frames, L.data_off, L.data_len, L.flags, L.cks_off, L.fidx);
+    if (dd && zlz4_launch_bfdd_frame(st, L.frames, a.nframes, L.fd_end ? dd->off : nullptr, dd->len, dd->n, dd->idx, L.fd_end,
+                                     L.fd_len) != 0)
+        return ZLZ4_ERR_DEVICE;
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, L.frames, a.nframes);
+    if (linked && zlz4_launch_bfl_save(st, L.frames, a.nframes, L.walk_err) != 0) return ZLZ4_ERR_DEVICE;
+    if (a.max_blocks) {
+        hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, a.src, a.src_off, a.src_len, a.nframes, a.max_blocks,
+                           L.frames, L.data_off, L.data_len, L.flags, L.cks_off, L.fidx);
+        if (dd && zlz4_launch_bfdd_entry(st, L.frames, L.fidx, a.max_blocks, L.fd_end, L.fd_len, L.e_off, L.e_len) != 0)
+            return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(a.max_blocks, 64)), dim3(64), 0, st, a.src, L.data_off, L.data_len,
+                           L.flags, L.cks_off, a.max_blocks, L.cks_ok);
+    }
+    return 0;
+}
+
+// The frames that are decoded in block order by one wavefront each: with a dictionary the linked-declared frames of several
+// blocks (with the external tail), else -- ZLZ4F_DECODE_LINKED -- the linked-declared ones.  write: decode into a.dst and
+// leave F.total / F.err; else the size query, whose results go to a.result.
+int32_t bfd_serial(hipStream_t st, int write, const BfArrays &a, bool linked, const BfDict *dd, const BfdLayout &L) {
+    int64_t *d_size = write ? nullptr : a.result;
+    if (dd)
+        return zlz4_launch_bfl_decode_dict(st, write, L.frames, a.nframes, a.max_blocks, a.src, L.data_off, L.data_len, L.flags,
+                                           L.cks_ok, L.walk_err, a.dst, a.dst_off, a.dst_cap, a.src_len, d_size,
+                                           write ? dd->dict : nullptr, L.fd_end, L.fd_len);
+    if (!linked) return 0;
+    return zlz4_launch_bfl_decode(st, write, L.frames, a.nframes, a.max_blocks, a.src, L.data_off, L.data_len, L.flags, L.cks_ok,
+                                  L.walk_err, a.dst, a.dst_off, a.dst_cap, a.src_len, d_size);
+}
+
 // decode_flags 0: zlz4f_batch_decompress_frame.  ZLZ4F_DECODE_LINKED: the frames whose FLG declares linked blocks leave the
-// parallel decodes (k_bfl_mask after each kernel that fills a length / capacity array) and are decoded in block order by
-// k_bfl_decode, which leaves F.total / F.err for k_bfd_finish; the sequence of launches stays fixed.
-int32_t batch_decompress_frame_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
-                                    const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
-                                    const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
-                                    uint32_t decode_flags, void *d_workspace, size_t workspace_bytes,
+// parallel decodes (bfd_mask_serial after each kernel that fills a length / capacity array) and are decoded in block order
+// by k_bfl_decode, which leaves F.total / F.err for k_bfd_finish; the sequence of launches stays fixed.
+// Dictionary frames (dd): the linked-declared frames of several blocks go through k_bfl_decode with
+// the external tail, the others stay on the parallel decodes, which get a dictionary descriptor per entry.
+int32_t batch_decompress_frame_impl(void *stream_, const BfArrays &a, uint32_t decode_flags, void *ws, size_t workspace_bytes,
                                     const BfDict *dd = nullptr) {
     if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
     const bool linked = (decode_flags & ZLZ4F_DECODE_LINKED) != 0;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const BatchLayout L = bfd_layout(nframes, max_blocks, decode_flags, dd != nullptr);
-    if (nframes == 0) return 0;
-    if (workspace_bytes < L.bytes || !d_workspace) return ZLZ4_ERR_INVALID_STATE;
-    if (dd) {
-        if (!d_src || !d_src_off || !d_src_len || !d_dst || !d_dst_off || !d_dst_cap || !d_result ||
-            (dd->n && (!dd->off || !dd->len)) || bf_misaligned(d_workspace, 16) || bf_misaligned(d_src_off, 8) ||
-            bf_misaligned(d_src_len, 8) || bf_misaligned(d_dst_off, 8) || bf_misaligned(d_dst_cap, 8) ||
-            bf_misaligned(d_result, 8) || bf_misaligned(dd->off, 8) || bf_misaligned(dd->len, 4) || bf_misaligned(dd->idx, 4))
-            return ZLZ4_ERR_INVALID_STATE;
-    }
-    // dictionary frames: the linked-declared frames of several blocks go through k_bfl_decode with
-    // the external tail, the others stay on the parallel decodes, which get a dictionary descriptor per entry
-    uint64_t *fd_end = dd ? reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_workspace) + L.off[15]) : nullptr;
-    uint32_t *fd_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[16]) : nullptr;
-    uint64_t *e_off = dd ? reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_workspace) + L.off[17]) : nullptr;
-    uint32_t *e_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[18]) : nullptr;
+    const BfdLayout L = bfd_layout(a.nframes, a.max_blocks, decode_flags, dd != nullptr, kDecode, ws);
+    if (a.nframes == 0) return 0;
+    if (bf_args_refused(kArgWs | (dd ? kArgSrc | kArgDst | kArgDictLen | kArgDictOff | kArgAligned | kArgWs16 : 0u), a, dd, 0, ws,
+                        workspace_bytes, L.bytes))
+        return ZLZ4_ERR_INVALID_STATE;
     hipStream_t st = (hipStream_t)stream_;
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
-    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
-    uint64_t *data_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *cks_off = reinterpret_cast<uint64_t *>(ws + L.off[2]),
-             *out_off = reinterpret_cast<uint64_t *>(ws + L.off[3]), *x_off = reinterpret_cast<uint64_t *>(ws + L.off[4]);
-    uint32_t *data_len = reinterpret_cast<uint32_t *>(ws + L.off[5]), *flags = reinterpret_cast<uint32_t *>(ws + L.off[6]),
-             *fidx = reinterpret_cast<uint32_t *>(ws + L.off[7]), *cks_ok = reinterpret_cast<uint32_t *>(ws + L.off[8]),
-             *out_cap = reinterpret_cast<uint32_t *>(ws + L.off[9]), *dec_len = reinterpret_cast<uint32_t *>(ws + L.off[10]),
-             *x_cap = reinterpret_cast<uint32_t *>(ws + L.off[11]), *x_len = reinterpret_cast<uint32_t *>(ws + L.off[12]);
-    int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[13]);
-    int64_t *walk_err = linked ? reinterpret_cast<int64_t *>(ws + L.off[14]) : nullptr;
-    const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
-    const auto mask_serial = dd ? zlz4_launch_bfdd_mask : zlz4_launch_bfl_mask;   // (the frames k_bfl_decode takes)
-    if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
-    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
-                       data_off, data_len, flags, cks_off, fidx);
-    if (dd && zlz4_launch_bfdd_frame(st, fr, nframes, dd->off, dd->len, dd->n, dd->idx, fd_end, fd_len) != 0)
-        return ZLZ4_ERR_DEVICE;
-    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
-    if (linked && zlz4_launch_bfl_save(st, fr, nframes, walk_err) != 0) return ZLZ4_ERR_DEVICE;
-    if (max_blocks) {
-        hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
-                           data_off, data_len, flags, cks_off, fidx);
-        if (dd && zlz4_launch_bfdd_entry(st, fr, fidx, max_blocks, fd_end, fd_len, e_off, e_len) != 0) return ZLZ4_ERR_DEVICE;
+    const uint32_t gf = bf_grid(a.nframes, 256), gb = bf_grid(a.max_blocks, 256, 4096), mb = a.max_blocks;
+    if (bfd_prelude(st, a, linked, dd, L) != 0) return ZLZ4_ERR_DEVICE;
+    if (mb) {
         // speculative layout, proven per frame
-        hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, data_off, data_len, flags,
-                           cks_off, max_blocks, cks_ok);
-        hipLaunchKernelGGL(k_bfd_spec, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, d_dst_off, d_dst_cap, max_blocks,
-                           out_off, out_cap, dec_len);
-        if (linked && mask_serial(st, fr, fidx, max_blocks, out_cap, dec_len) != 0) return ZLZ4_ERR_DEVICE;
-        int rc = dd ? zlz4_launch_decompress_safe_using_dict(st, d_src, data_off, dec_len, d_dst, out_off, out_cap, sizes,
-                                                             max_blocks, dd->dict, e_off, e_len)
-                    : zlz4_launch_decompress_safe(st, d_src, data_off, dec_len, d_dst, out_off, out_cap, sizes, max_blocks);
-        if (rc != 0) return ZLZ4_ERR_DEVICE;
-        hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, out_off,
-                           out_cap, d_dst);
-        hipLaunchKernelGGL(k_bfd_check, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags,
-                           sizes, cks_ok, out_cap);
+        hipLaunchKernelGGL(k_bfd_spec, dim3(gb), dim3(256), 0, st, L.frames, L.fidx, L.data_len, L.flags, a.dst_off, a.dst_cap,
+                           mb, L.out_off, L.out_cap, L.dec_len);
+        if (linked && bfd_mask_serial(st, dd, L, mb, L.out_cap, L.dec_len) != 0) return ZLZ4_ERR_DEVICE;
+        if (bfd_decode_safe(st, a, dd, L, L.dec_len, L.out_off, L.out_cap) != 0) return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bf_copy_stored, dim3(mb), dim3(256), 0, st, a.src, L.data_off, L.data_len, L.flags, L.out_off,
+                           L.out_cap, a.dst);
+        hipLaunchKernelGGL(k_bfd_check, dim3(bf_grid(a.nframes, 4)), dim3(256), 0, st, L.frames, a.nframes, mb, L.data_len,
+                           L.flags, L.sizes, L.cks_ok, L.out_cap);
         // exact path for the frames whose layout was not proven (always enqueued: the sequence does not depend on data)
-        hipLaunchKernelGGL(k_bfd_mask, dim3(gb), dim3(256), 0, st, fr, fidx, data_len, flags, max_blocks, x_off, x_cap, x_len);
-        if (linked && mask_serial(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
-        rc = dd ? zlz4_launch_decompress_sizes_using_dict(st, d_src, data_off, x_len, x_off, x_cap, sizes, max_blocks, e_off,
-                                                          e_len)
-                : zlz4_launch_decompress_sizes(st, d_src, data_off, x_len, x_off, x_cap, sizes, max_blocks);
-        if (rc != 0) return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bfd_mask, dim3(gb), dim3(256), 0, st, L.frames, L.fidx, L.data_len, L.flags, mb, L.x_off, L.x_cap,
+                           L.x_len);
+        if (linked && bfd_mask_serial(st, dd, L, mb, L.x_cap, L.x_len) != 0) return ZLZ4_ERR_DEVICE;
+        if (bfd_decode_sizes(st, a, dd, L, L.x_len, L.x_off, L.x_cap) != 0) return ZLZ4_ERR_DEVICE;
     }
-    hipLaunchKernelGGL(k_bfd_plan, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags, sizes, cks_ok,
-                       d_dst_off, d_dst_cap, x_off, x_cap, x_len);
-    if (max_blocks) {
+    hipLaunchKernelGGL(k_bfd_plan, dim3(gf), dim3(256), 0, st, L.frames, a.nframes, mb, L.data_len, L.flags, L.sizes, L.cks_ok,
+                       a.dst_off, a.dst_cap, L.x_off, L.x_cap, L.x_len);
+    if (mb) {
         // (k_bfd_plan laid out the unproven frames, a linked one among them from sizes that mean nothing: masked again)
-        if (linked && mask_serial(st, fr, fidx, max_blocks, x_cap, x_len) != 0) return ZLZ4_ERR_DEVICE;
-        const int rc = dd ? zlz4_launch_decompress_safe_using_dict(st, d_src, data_off, x_len, d_dst, x_off, x_cap, sizes,
-                                                                   max_blocks, dd->dict, e_off, e_len)
-                          : zlz4_launch_decompress_safe(st, d_src, data_off, x_len, d_dst, x_off, x_cap, sizes, max_blocks);
-        if (rc != 0) return ZLZ4_ERR_DEVICE;
-        hipLaunchKernelGGL(k_bf_copy_stored, dim3(max_blocks), dim3(256), 0, st, d_src, data_off, data_len, flags, x_off,
-                           x_cap, d_dst);
+        if (linked && bfd_mask_serial(st, dd, L, mb, L.x_cap, L.x_len) != 0) return ZLZ4_ERR_DEVICE;
+        if (bfd_decode_safe(st, a, dd, L, L.x_len, L.x_off, L.x_cap) != 0) return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bf_copy_stored, dim3(mb), dim3(256), 0, st, a.src, L.data_off, L.data_len, L.flags, L.x_off,
+                           L.x_cap, a.dst);
     }
-    if (dd) {
-        if (zlz4_launch_bfl_decode_dict(st, 1, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err, d_dst,
-                                        d_dst_off, d_dst_cap, d_src_len, nullptr, dd->dict, fd_end, fd_len) != 0)
-            return ZLZ4_ERR_DEVICE;
-    } else if (linked && zlz4_launch_bfl_decode(st, 1, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok,
-                                                walk_err, d_dst, d_dst_off, d_dst_cap, d_src_len, nullptr) != 0)
-        return ZLZ4_ERR_DEVICE;
-    hipLaunchKernelGGL(k_bfd_finish, dim3(gf), dim3(256), 0, st, fr, nframes, max_blocks, d_src, d_src_off, d_src_len, d_dst,
-                       d_dst_off, d_dst_cap, d_result);
+    if (bfd_serial(st, 1, a, linked, dd, L) != 0) return ZLZ4_ERR_DEVICE;
+    hipLaunchKernelGGL(k_bfd_finish, dim3(gf), dim3(256), 0, st, L.frames, a.nframes, mb, a.src, a.src_off, a.src_len, a.dst,
+                       a.dst_off, a.dst_cap, a.result);
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t zlz4f_batch_decompress_frame(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
-                                     const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
-                                     const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
-                                     void *d_workspace, size_t workspace_bytes) {
-    return batch_decompress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
-                                       max_blocks, 0, d_workspace, workspace_bytes);
-}
-
-int32_t zlz4f_batch_decompress_frame_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
-                                        const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
-                                        const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
-                                        uint32_t decode_flags, void *d_workspace, size_t workspace_bytes) {
-    return batch_decompress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
-                                       max_blocks, decode_flags, d_workspace, workspace_bytes);
-}
-
-size_t zlz4f_batch_frame_decompressed_size_workspace(uint32_t nframes, uint32_t max_blocks) {
-    return bfq_layout(nframes, max_blocks).bytes;
-}
-
-size_t zlz4f_batch_frame_decompressed_size_workspace_ex(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags) {
-    return bfq_layout(nframes, max_blocks, decode_flags).bytes;
-}
-
-}  // extern "C"
-
-namespace {
-
-// the walk, scan and block-checksum passes of zlz4f_batch_decompress_frame, then the size kernel over the block table and
-// the per-frame total; nothing but d_size and the workspace is written.  ZLZ4F_DECODE_LINKED: the entries of the linked-
-// declared frames are masked out of the size kernel and k_bfl_decode<false> replaces their results.
-int32_t batch_frame_decompressed_size_impl(void *stream_, const uint8_t *d_src, const uint64_t *d_src_off,
-                                           const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
-                                           uint32_t max_blocks, uint32_t decode_flags, void *d_workspace,
+// The prelude of zlz4f_batch_decompress_frame, then the size kernel over the block table and the per-frame total; nothing
+// but a.result (d_size) and the workspace is written.  ZLZ4F_DECODE_LINKED: the entries of the linked-declared frames are
+// masked out of the size kernel and k_bfl_decode<false> replaces their results.  No device is the LAST refusal here.
+int32_t batch_frame_decompressed_size_impl(void *stream_, const BfArrays &a, uint32_t decode_flags, void *ws,
                                            size_t workspace_bytes, const BfDict *dd = nullptr) {
     if (decode_flags & ~ZLZ4F_DECODE_LINKED) return ZLZ4F_ERR_PARAMETER_INVALID;
     const bool linked = (decode_flags & ZLZ4F_DECODE_LINKED) != 0;
-    if (nframes == 0) return 0;
-    const BatchLayout L = bfq_layout(nframes, max_blocks, decode_flags, dd != nullptr);
-    if (!d_src || !d_src_off || !d_src_len || !d_size || !d_workspace || ((uintptr_t)d_workspace & 15u) || workspace_bytes < L.bytes)
-        return ZLZ4_ERR_INVALID_STATE;
-    if (dd && ((dd->n && !dd->len) || bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) || bf_misaligned(d_size, 8) ||
-               bf_misaligned(dd->len, 4) || bf_misaligned(dd->idx, 4)))
+    if (a.nframes == 0) return 0;
+    const BfdLayout L = bfd_layout(a.nframes, a.max_blocks, decode_flags, dd != nullptr, kQuery, ws);
+    if (bf_args_refused(kArgSrc | kArgWs | kArgWs16 | (dd ? kArgDictLen | kArgAligned : 0u), a, dd, 0, ws, workspace_bytes,
+                        L.bytes))
         return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    uint32_t *fd_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[10]) : nullptr;
-    uint32_t *e_len = dd ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_workspace) + L.off[11]) : nullptr;
     hipStream_t st = (hipStream_t)stream_;
-    uint8_t *ws = static_cast<uint8_t *>(d_workspace);
-    BFrame *fr = reinterpret_cast<BFrame *>(ws + L.off[0]);
-    uint64_t *data_off = reinterpret_cast<uint64_t *>(ws + L.off[1]), *cks_off = reinterpret_cast<uint64_t *>(ws + L.off[2]);
-    uint32_t *data_len = reinterpret_cast<uint32_t *>(ws + L.off[3]), *flags = reinterpret_cast<uint32_t *>(ws + L.off[4]),
-             *fidx = reinterpret_cast<uint32_t *>(ws + L.off[5]), *cks_ok = reinterpret_cast<uint32_t *>(ws + L.off[6]),
-             *dec_len = reinterpret_cast<uint32_t *>(ws + L.off[7]);
-    int64_t *sizes = reinterpret_cast<int64_t *>(ws + L.off[8]);
-    int64_t *walk_err = linked ? reinterpret_cast<int64_t *>(ws + L.off[9]) : nullptr;
-    const uint32_t gf = bf_grid(nframes, 256), gb = bf_grid(max_blocks, 256, 4096);
-    const auto mask_serial = dd ? zlz4_launch_bfdd_mask : zlz4_launch_bfl_mask;   // (the frames k_bfl_decode takes)
-    if (max_blocks) hipLaunchKernelGGL(k_bfd_init, dim3(gb), dim3(256), 0, st, data_len, flags, fidx, max_blocks);
-    hipLaunchKernelGGL(k_bfd_walk<false>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
-                       data_off, data_len, flags, cks_off, fidx);
-    if (dd && zlz4_launch_bfdd_frame(st, fr, nframes, nullptr, dd->len, dd->n, dd->idx, nullptr, fd_len) != 0)
-        return ZLZ4_ERR_DEVICE;
-    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, st, fr, nframes);
-    if (linked && zlz4_launch_bfl_save(st, fr, nframes, walk_err) != 0) return ZLZ4_ERR_DEVICE;
-    if (max_blocks) {
-        hipLaunchKernelGGL(k_bfd_walk<true>, dim3(gf), dim3(256), 0, st, d_src, d_src_off, d_src_len, nframes, max_blocks, fr,
-                           data_off, data_len, flags, cks_off, fidx);
-        if (dd && zlz4_launch_bfdd_entry(st, fr, fidx, max_blocks, nullptr, fd_len, nullptr, e_len) != 0) return ZLZ4_ERR_DEVICE;
-        hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(max_blocks, 64)), dim3(64), 0, st, d_src, data_off, data_len, flags,
-                           cks_off, max_blocks, cks_ok);
-        hipLaunchKernelGGL(k_bfq_len, dim3(gb), dim3(256), 0, st, data_len, flags, max_blocks, dec_len);
-        if (linked && mask_serial(st, fr, fidx, max_blocks, nullptr, dec_len) != 0) return ZLZ4_ERR_DEVICE;
-        if (zlz4_launch_decompressed_size(st, d_src, data_off, dec_len, e_len, sizes, max_blocks) != 0) return ZLZ4_ERR_DEVICE;
+    const uint32_t mb = a.max_blocks;
+    if (bfd_prelude(st, a, linked, dd, L) != 0) return ZLZ4_ERR_DEVICE;
+    if (mb) {
+        hipLaunchKernelGGL(k_bfq_len, dim3(bf_grid(mb, 256, 4096)), dim3(256), 0, st, L.data_len, L.flags, mb, L.dec_len);
+        if (linked && bfd_mask_serial(st, dd, L, mb, nullptr, L.dec_len) != 0) return ZLZ4_ERR_DEVICE;
+        if (zlz4_launch_decompressed_size(st, a.src, L.data_off, L.dec_len, L.e_len, L.sizes, mb) != 0) return ZLZ4_ERR_DEVICE;
     }
-    hipLaunchKernelGGL(k_bfq_total, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, fr, nframes, max_blocks, data_len, flags,
-                       sizes, cks_ok, d_src_len, d_size);
-    if (dd) {
-        if (zlz4_launch_bfl_decode_dict(st, 0, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok, walk_err,
-                                        nullptr, nullptr, nullptr, d_src_len, d_size, nullptr, nullptr, fd_len) != 0)
-            return ZLZ4_ERR_DEVICE;
-    } else if (linked && zlz4_launch_bfl_decode(st, 0, fr, nframes, max_blocks, d_src, data_off, data_len, flags, cks_ok,
-                                                walk_err, nullptr, nullptr, nullptr, d_src_len, d_size) != 0)
-        return ZLZ4_ERR_DEVICE;
+    hipLaunchKernelGGL(k_bfq_total, dim3(bf_grid(a.nframes, 4)), dim3(256), 0, st, L.frames, a.nframes, mb, L.data_len, L.flags,
+                       L.sizes, L.cks_ok, a.src_len, a.result);
+    if (bfd_serial(st, 0, a, linked, dd, L) != 0) return ZLZ4_ERR_DEVICE;
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
@@ -1873,17 +1864,16 @@ int64_t single_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t 
     if (F.status < 0) return F.status;
     if (F.nb > 0x7FFFFFFFull) return ZLZ4F_ERR_FRAME_SIZE_WRONG;
     const uint32_t max_blocks = (uint32_t)F.nb;
-    const size_t ws = want_size ? bfq_layout(1, max_blocks, decode_flags, with_dict).bytes
-                                : bfd_layout(1, max_blocks, decode_flags, with_dict).bytes;
+    const size_t ws = bfd_layout(1, max_blocks, decode_flags, with_dict, want_size).bytes;
     DevBuf d_ws(ws, &dc);
     if (!d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     dc.launched();
     const BfDict one = {d_dict, &rec.d->dict_off, &rec.d->dict_len, 1u, nullptr};
     const BfDict *dd = with_dict ? &one : nullptr;
-    const int32_t rc = want_size
-        ? batch_frame_decompressed_size_impl(st, d_src, &r->src_off, &r->src_len, &r->result, 1, max_blocks, decode_flags, d_ws.p, ws, dd)
-        : batch_decompress_frame_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap, &r->result, 1,
-                                      max_blocks, decode_flags, d_ws.p, ws, dd);
+    const BfArrays a = {d_src, &r->src_off, &r->src_len, want_size ? nullptr : d_dst, want_size ? nullptr : &r->dst_off,
+                        want_size ? nullptr : &r->dst_cap, &r->result, 1, max_blocks};
+    const int32_t rc = want_size ? batch_frame_decompressed_size_impl(st, a, decode_flags, d_ws.p, ws, dd)
+                                 : batch_decompress_frame_impl(st, a, decode_flags, d_ws.p, ws, dd);
     if (rc != 0) return rc;
     int64_t result = 0;
     if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
@@ -1894,19 +1884,43 @@ int64_t single_frame_ex(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t 
 
 extern "C" {
 
+int32_t zlz4f_batch_decompress_frame(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                     const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                     const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                     void *d_workspace, size_t workspace_bytes) {
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, max_blocks};
+    return batch_decompress_frame_impl(stream, a, 0, d_workspace, workspace_bytes);
+}
+
+int32_t zlz4f_batch_decompress_frame_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                        const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                        const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                        uint32_t decode_flags, void *d_workspace, size_t workspace_bytes) {
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, max_blocks};
+    return batch_decompress_frame_impl(stream, a, decode_flags, d_workspace, workspace_bytes);
+}
+
+size_t zlz4f_batch_frame_decompressed_size_workspace(uint32_t nframes, uint32_t max_blocks) {
+    return bfd_layout(nframes, max_blocks, 0, false, kQuery).bytes;
+}
+
+size_t zlz4f_batch_frame_decompressed_size_workspace_ex(uint32_t nframes, uint32_t max_blocks, uint32_t decode_flags) {
+    return bfd_layout(nframes, max_blocks, decode_flags, false, kQuery).bytes;
+}
+
 int32_t zlz4f_batch_frame_decompressed_size(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
                                             const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
                                             uint32_t max_blocks, void *d_workspace, size_t workspace_bytes) {
-    return batch_frame_decompressed_size_impl(stream, d_src, d_src_off, d_src_len, d_size, nframes, max_blocks, 0,
-                                              d_workspace, workspace_bytes);
+    const BfArrays a = {d_src, d_src_off, d_src_len, nullptr, nullptr, nullptr, d_size, nframes, max_blocks};
+    return batch_frame_decompressed_size_impl(stream, a, 0, d_workspace, workspace_bytes);
 }
 
 int32_t zlz4f_batch_frame_decompressed_size_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
                                                const uint64_t *d_src_len, int64_t *d_size, uint32_t nframes,
                                                uint32_t max_blocks, uint32_t decode_flags, void *d_workspace,
                                                size_t workspace_bytes) {
-    return batch_frame_decompressed_size_impl(stream, d_src, d_src_off, d_src_len, d_size, nframes, max_blocks, decode_flags,
-                                              d_workspace, workspace_bytes);
+    const BfArrays a = {d_src, d_src_off, d_src_len, nullptr, nullptr, nullptr, d_size, nframes, max_blocks};
+    return batch_frame_decompressed_size_impl(stream, a, decode_flags, d_workspace, workspace_bytes);
 }
 
 // one frame through zlz4f_batch_decompress_frame_ex / zlz4f_batch_frame_decompressed_size_ex (the result is the batch
@@ -1998,33 +2012,6 @@ __global__ void k_bf_dict_id(const uint8_t *__restrict__ src, const uint64_t *__
     dict_id[f] = (ph.flg & 0x01u) ? (int64_t)zx_rd32(head + 6 + ((ph.flg & 0x08u) ? 8 : 0)) : 0;
 }
 
-// One frame with one dictionary through zlz4f_batch_compress_frame_using_dict (ex: .._using_dict_ex), device pointers
-// (single_compress_frame_ex)
-int64_t single_compress_frame_dict(hipStream_t st, const uint8_t *d_src, size_t n, uint8_t *d_dst, size_t cap,
-                                   const zlz4f_prefs &p, const uint8_t *d_dict, uint32_t dict_len, bool ex) {
-    const size_t bs = block_size_of(p.block_size_id);
-    const uint64_t nb = (uint64_t)n / bs + (n % bs != 0);
-    if (nb > 0x7FFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
-    const uint32_t max_blocks = (uint32_t)nb;
-    DeviceCall dc(st);
-    const size_t ws = bfcd_layout(1, max_blocks, p, 1, n, dict_len, bfcd_hc(p, ex)).bytes;
-    struct Rec { FrameRec f; uint64_t dict_off; uint32_t dict_len; };
-    Staged<Rec> rec(&dc);
-    DevBuf d_ws(ws, &dc);
-    if (!rec.d || !d_ws.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    rec.h.f.src_len = n; rec.h.f.dst_cap = cap; rec.h.dict_len = dict_len;
-    dc.launched();
-    if (!rec.upload(st)) return ZLZ4_ERR_DEVICE;
-    FrameRec *r = &rec.d->f;
-    const BfDict dd = {d_dict, &rec.d->dict_off, &rec.d->dict_len, 1u, nullptr};
-    const int32_t rc = batch_compress_frame_dict_impl(st, d_src, &r->src_off, &r->src_len, d_dst, &r->dst_off, &r->dst_cap,
-                                                      &r->result, 1, max_blocks, &p, 0, dd, n, dict_len, d_ws.p, ws, ex);
-    if (rc != 0) return rc;
-    int64_t result = 0;
-    if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
-    return result;
-}
-
 // the host-pointer call of both entry points: the refusals are host arithmetic and come before the device check
 int64_t host_compress_frame_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const zlz4f_prefs *prefs,
                                  const uint8_t *dict, size_t dict_len, bool ex) {
@@ -2035,12 +2022,11 @@ int64_t host_compress_frame_dict(const uint8_t *src, size_t n, uint8_t *dst, siz
     const size_t bound = zlz4f_compress_frame_bound(n, &p);
     if (cap < bound) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;                                            // :363-366
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const size_t D = dict_tail(dict_len);
-    DevBuf d_dict(D);
-    if (!d_dict.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    if (D && hipMemcpy(d_dict.p, dict + (dict_len - D), D, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
-        return single_compress_frame_dict(nullptr, d_src, n, d_dst, bound, p, d_dict.as<uint8_t>(), (uint32_t)D, ex);
+    return with_dict_tail(dict, dict_len, [&](const uint8_t *d_dict, uint32_t D) {
+        return host_frame_call(src, n, dst, cap, bound, [&](const uint8_t *d_src, uint8_t *d_dst) {
+            const OneDict one = {d_dict, D, ex};
+            return single_compress_frame(nullptr, d_src, n, d_dst, bound, p, 0, &one);
+        });
     });
 }
 
@@ -2062,9 +2048,9 @@ int32_t zlz4f_batch_compress_frame_using_dict(void *stream, const uint8_t *d_src
                                               const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,
                                               uint32_t ndicts, const uint32_t *d_dict_idx, uint64_t max_src_len,
                                               uint32_t max_dict_len, void *d_workspace, size_t workspace_bytes) {
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, max_blocks};
     const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
-    return batch_compress_frame_dict_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
-                                          max_blocks, prefs, batch_flags, dd, max_src_len, max_dict_len, d_workspace,
+    return batch_compress_frame_dict_impl(stream, a, prefs, batch_flags, dd, max_src_len, max_dict_len, d_workspace,
                                           workspace_bytes, false);
 }
 
@@ -2085,14 +2071,14 @@ int32_t zlz4f_batch_compress_frame_using_dict_ex(void *stream, const uint8_t *d_
                                                  const uint32_t *d_dict_len, uint32_t ndicts, const uint32_t *d_dict_idx,
                                                  uint64_t max_src_len, uint32_t max_dict_len, void *d_workspace,
                                                  size_t workspace_bytes) {
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, max_blocks};
     const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
-    return batch_compress_frame_dict_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
-                                          max_blocks, prefs, batch_flags, dd, max_src_len, max_dict_len, d_workspace,
+    return batch_compress_frame_dict_impl(stream, a, prefs, batch_flags, dd, max_src_len, max_dict_len, d_workspace,
                                           workspace_bytes, true);
 }
 
 size_t zlz4f_batch_decompress_frame_using_dict_workspace(uint32_t nframes, uint32_t max_blocks) {
-    return bfd_layout(nframes, max_blocks, ZLZ4F_DECODE_LINKED, true).bytes;
+    return bfd_layout(nframes, max_blocks, ZLZ4F_DECODE_LINKED, true, kDecode).bytes;
 }
 
 int32_t zlz4f_batch_decompress_frame_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
@@ -2101,13 +2087,13 @@ int32_t zlz4f_batch_decompress_frame_using_dict(void *stream, const uint8_t *d_s
                                                 uint32_t max_blocks, const uint8_t *d_dict, const uint64_t *d_dict_off,
                                                 const uint32_t *d_dict_len, uint32_t ndicts, const uint32_t *d_dict_idx,
                                                 void *d_workspace, size_t workspace_bytes) {
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, max_blocks};
     const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
-    return batch_decompress_frame_impl(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes,
-                                       max_blocks, ZLZ4F_DECODE_LINKED, d_workspace, workspace_bytes, &dd);
+    return batch_decompress_frame_impl(stream, a, ZLZ4F_DECODE_LINKED, d_workspace, workspace_bytes, &dd);
 }
 
 size_t zlz4f_batch_frame_decompressed_size_using_dict_workspace(uint32_t nframes, uint32_t max_blocks) {
-    return bfq_layout(nframes, max_blocks, ZLZ4F_DECODE_LINKED, true).bytes;
+    return bfd_layout(nframes, max_blocks, ZLZ4F_DECODE_LINKED, true, kQuery).bytes;
 }
 
 int32_t zlz4f_batch_frame_decompressed_size_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
@@ -2115,17 +2101,16 @@ int32_t zlz4f_batch_frame_decompressed_size_using_dict(void *stream, const uint8
                                                        uint32_t max_blocks, const uint32_t *d_dict_len, uint32_t ndicts,
                                                        const uint32_t *d_dict_idx, void *d_workspace,
                                                        size_t workspace_bytes) {
+    const BfArrays a = {d_src, d_src_off, d_src_len, nullptr, nullptr, nullptr, d_size, nframes, max_blocks};
     const BfDict dd = {nullptr, nullptr, d_dict_len, ndicts, d_dict_idx};
-    return batch_frame_decompressed_size_impl(stream, d_src, d_src_off, d_src_len, d_size, nframes, max_blocks,
-                                              ZLZ4F_DECODE_LINKED, d_workspace, workspace_bytes, &dd);
+    return batch_frame_decompressed_size_impl(stream, a, ZLZ4F_DECODE_LINKED, d_workspace, workspace_bytes, &dd);
 }
 
 int32_t zlz4f_batch_frame_dict_id(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
                                   int64_t *d_dict_id, uint32_t nframes) {
     if (nframes == 0) return 0;
-    if (!d_src || !d_src_off || !d_src_len || !d_dict_id || bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) ||
-        bf_misaligned(d_dict_id, 8))
-        return ZLZ4_ERR_INVALID_STATE;
+    const BfArrays a = {d_src, d_src_off, d_src_len, nullptr, nullptr, nullptr, d_dict_id, nframes, 0};
+    if (bf_args_refused(kArgSrc | kArgAligned, a)) return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     hipLaunchKernelGGL(k_bf_dict_id, dim3(bf_grid(nframes, 256)), dim3(256), 0, (hipStream_t)stream, d_src, d_src_off,
                        d_src_len, nframes, d_dict_id);
@@ -2149,12 +2134,10 @@ int64_t zlz4f_decompress_frame_using_dict(const uint8_t *src, size_t n, uint8_t 
     const ParsedHeader ph = parse_header(src, n);      // header errors need no device
     if (ph.size < 0) return ph.size;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const size_t D = dict_tail(dict_len);
-    DevBuf d_dict(D);
-    if (!d_dict.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
-    if (D && hipMemcpy(d_dict.p, dict + (dict_len - D), D, hipMemcpyHostToDevice) != hipSuccess) return ZLZ4_ERR_DEVICE;
-    return host_frame_call(src, n, dst, cap, cap, [&](const uint8_t *d_src, uint8_t *d_dst) {
-        return single_frame_ex(nullptr, d_src, n, d_dst, cap, ZLZ4F_DECODE_LINKED, false, true, d_dict.as<uint8_t>(), (uint32_t)D);
+    return with_dict_tail(dict, dict_len, [&](const uint8_t *d_dict, uint32_t D) {
+        return host_frame_call(src, n, dst, cap, cap, [&](const uint8_t *d_src, uint8_t *d_dst) {
+            return single_frame_ex(nullptr, d_src, n, d_dst, cap, ZLZ4F_DECODE_LINKED, false, true, d_dict, D);
+        });
     });
 }
 

@@ -71,7 +71,10 @@ template <typename Rec> struct Staged {
     explicit Staged(DeviceCall *dc, size_t bytes = 64) : buf(bytes, dc), d(buf.as<Rec>()) {
         static_assert(sizeof(Rec) <= 256, "record");
     }
-    bool upload(hipStream_t st) { return hipMemcpyAsync(d, &h, sizeof h, hipMemcpyHostToDevice, st) == hipSuccess; }
+    // (bytes: the leading fields alone, for a call that has no use for the rest)
+    bool upload(hipStream_t st, size_t bytes = sizeof(Rec)) {
+        return hipMemcpyAsync(d, &h, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+    }
 };
 
 // n host bytes into `d`, in stream order; nothing to copy is no call
