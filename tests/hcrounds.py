@@ -47,6 +47,28 @@ def small_blocks():
     return items
 
 
+def round_blocks(n, chunk):
+    """blocks per round of a call with n blocks whose chunk holds `chunk`: half a chunk once there is more than one round"""
+    return chunk // 2 if chunk >= 2 and n > chunk // 2 else chunk
+
+
+def boundary_blocks(n, sub, seed, empty=True):
+    """n blocks of 200..599 bytes for rounds of `sub` blocks (tests/test_gpu_hc_round_boundaries.py).  Block i lies in
+    result slot (round & 1) * sub + i % sub; the blocks that share a slot have the same length; rounds 0 and 1 hold
+    D-reptext, the rounds that reuse a half hold random bytes: a match left behind by the earlier round would be emitted
+    where the reference has literals.  Block 1 has 13 bytes; block sub + 1 (round 1) is empty if `empty` and n >= 5."""
+    lens = np.random.default_rng(seed).integers(200, 600, 2 * sub)
+    items = []
+    for i in range(n):
+        k = int(lens[((i // sub) & 1) * sub + i % sub])
+        items.append(bytes((dg.random_bytes if i // sub >= 2 else dg.reptext_bytes)(k, seed + 1 + i)))
+    if n >= 2:
+        items[1] = b"abcabcabcabcd"
+    if empty and n >= 5:
+        items[sub + 1] = b""
+    return items
+
+
 def periodic_items(level):
     """Blocks with a period (random content repeated every 1 .. 40000 bytes, some with noise in the middle or two periods
     in a row): the inputs of test_gpu_parity.test_compress_hc_periodic_inputs."""

@@ -54,3 +54,13 @@ t2 = time.perf_counter()
 assert out == blk
 print("single-block host calls, 64 KiB: compressDefault %.0f us/call, decompressSafe %.0f us/call (ctypes overhead included)"
       % ((t1 - t0) / reps * 1e6, (t2 - t1) / reps * 1e6))
+# one-block HC calls: a call is mostly host code (workspace, launches, the side stream is not used), so this is where a
+# change of the HC launchers' host side would show
+for level in (9, 11):
+    zl.compressHC(blk, level)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        hc = zl.compressHC(blk, level)
+    t1 = time.perf_counter()
+    assert len(hc) > 0 and (level > 9 or zl.decompressSafe(hc, 65536) == blk)   # (levels 10-12 are never round-tripped)
+    print("single-block host calls, 64 KiB: compressHC level %d %.0f us/call" % (level, (t1 - t0) / reps * 1e6))

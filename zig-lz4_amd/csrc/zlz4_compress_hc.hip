@@ -31,6 +31,15 @@
 //   K3  k_hc_parse_emit   one wavefront per block: the greedy walk of :1009-1032 over the stored results,
 //                         encodeSequence with its limitedOutput checks, final literals; runs on a side stream beside
 //                         K1 / K2s of the next round.
+//
+// Host side (behind the kernels)
+// ------------------------------
+// A call works in chunks of blocks (hc_chunk_blocks: about 6 GiB of workspace, at most 8192 blocks) and in rounds of half
+// a chunk.  HcRounds owns the rounds: the side stream, the two halves, the event waits before a half is reused, the fork in
+// front of the consumer, the join at the end and the error exit.  hc_seg_rounds is the one K1 / K2s / K3 loop of levels
+// 3-9; an HcSegJob says what differs between its three users: launch_hc_chunked (plain; it also holds the loop of levels
+// 10-12, which takes its ordering from HcRounds too) and launch_hc_dict_chunked with a staging pass per round (dictionary
+// records) or without one (linked frame blocks).
 #include <cstdlib>
 #include <type_traits>
 
@@ -1289,79 +1298,162 @@ static HcSideStream *hc_side_stream() {
     return per_device[dev].init() ? &per_device[dev] : nullptr;
 }
 
-// K1 + K2 (+ K3 for the greedy levels, or the price-based parse for levels 10-12) in rounds of `chunk` blocks
+// ------------------------------------------------------------------ host side: what every HC pipeline shares
+namespace {
+// The round choreography, once.  A call's blocks go in rounds of `sub`.  With a side stream a round is half a chunk: the
+// producer of round r + 1 (K1 and the search, on `stream`) runs beside the consumer of round r (K3 or the price-based
+// parse, on the side stream), and what the consumer reads alternates between two halves of its area.  Without one a round
+// is a whole chunk, half 0, all on `stream`.  The ordering rules:
+//   claim()    before a round writes its half: the consumer of round - 2, which read it, is done
+//   fork()     the consumer goes behind everything the round has put on `stream` so far
+//   release()  the consumer is enqueued: its half is free once it has run
+//   join()     everything enqueued here is ordered before whatever the caller enqueues on `stream` next (zlz4_frame.hip
+//              runs two launchers on one workspace region and relies on it)
+//   fail()     error exit: the consumer may still be running on the side stream and the caller parks the workspace as soon
+//              as `stream` is idle -- wait for the side stream first
+struct HcRounds {
+    hipStream_t stream;
+    HcSideStream *side;              // nullptr: no overlap
+    uint32_t sub, round = 0;         // blocks per round; the round that is being enqueued
+    HcRounds(hipStream_t stream_, uint32_t chunk, uint32_t nblocks, bool overlap)
+        : stream(stream_), side(overlap && chunk >= 2u && nblocks > chunk / 2u ? hc_side_stream() : nullptr),
+          sub(side ? chunk / 2u : chunk) {}
+    uint32_t blocks(uint32_t b0, uint32_t nblocks) const { return nblocks - b0 < sub ? nblocks - b0 : sub; }
+    uint32_t half_of(uint32_t r) const { return side ? (r & 1u) : 0u; }
+    uint32_t slot_of(uint32_t r) const { return half_of(r) * sub; }   // first block slot of round r's half
+    uint32_t slot() const { return slot_of(round); }
+    bool claim() { return !side || round < 2u || hipStreamWaitEvent(stream, side->emitted[half_of(round)], 0) == hipSuccess; }
+    bool fork(hipStream_t *consumer) {
+        *consumer = side ? side->st : stream;
+        return !side || (hipEventRecord(side->searched[half_of(round)], stream) == hipSuccess &&
+                         hipStreamWaitEvent(side->st, side->searched[half_of(round)], 0) == hipSuccess);
+    }
+    bool release() { return !side || hipEventRecord(side->emitted[half_of(round)], side->st) == hipSuccess; }
+    int join() {
+        for (uint32_t k = 0; side && k < 2u && k < round; k++)
+            if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail();
+        return hipGetLastError() == hipSuccess ? 0 : -7;
+    }
+    int fail(int rc = -7) { if (side) (void)hipStreamSynchronize(side->st); return rc; }
+};
+
+// blocks per chunk: the workspace stays around 6 GiB for big blocks, a chunk at 8192 blocks (3.5 GiB for 64 KiB blocks;
+// 4096 / 8192 / 14043: 52.3 / 50.5 / 51.5 ms on configs[3])
+uint32_t hc_chunk_blocks(uint64_t bytes_per_block, uint32_t nblocks) {
+    uint64_t c = (6ull << 30) / bytes_per_block;
+    if (c < 1) c = 1;
+    if (c > 8192u) c = 8192u;
+    if (c > nblocks) c = nblocks ? nblocks : 1;
+    return (uint32_t)c;
+}
+int32_t hc_attempts(int32_t level) { return 1 << (level - 1); }                 // levels 3..9: nbSearches 4 ... 256
+uint32_t hc_np_max(uint32_t max_n) { return max_n < 13u ? 1u : max_n - 11u; }   // positions of the longest block
+// K1's LDS: 128 KiB of the CU's 160 KiB for the 32-bit table, the staged links, the turn counter
+template <typename T> constexpr uint32_t kBuildLinksLds = kHcTableSize * 4u + 4096u * sizeof(T) + 16u;
+void hc_allow_lds(const void *kernel, uint32_t bytes) { (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
+
+// what the kernels of a call read: block b is len[b] bytes at base + off[b], none longer than max_n (the strides come from
+// it; K1 and the searches skip a longer one, K3 reports it).  pair = len, or { v_len, start } per block for the kDict
+// instantiations of K2s and K3, which take it in their d_in_len argument.  HcOut: the four output arguments of K3
+struct HcIn { const uint8_t *base; const uint64_t *off; const uint32_t *len, *pair; uint32_t max_n; };
+struct HcOut { uint8_t *base; const uint64_t *off; const uint32_t *cap; int64_t *result; };
+
+// launch shape of k_hc_seg_search: thr_div start points per lane (`nseg` of them in the longest block) and at least
+// min_threads (the lanes also copy the block's links into LDS).  LDS links: links, counted runs, bitmap and `words` scalars
+// (3, + kDict's `start`); HBM links: the scalars and the counted runs
+struct HcSegShape { uint32_t threads, lk_bytes, lds; };
+HcSegShape hc_seg_shape(bool lds_links, uint32_t np_max, uint32_t nseg, uint32_t thr_div, uint32_t min_threads, uint32_t words) {
+    HcSegShape s;
+    s.threads = (nseg / thr_div + 63u) & ~63u;
+    if (s.threads > 1024u) s.threads = 1024u;
+    if (s.threads < min_threads) s.threads = min_threads;
+    s.lk_bytes = ((np_max * 2u + 15u) & ~15u) + 16u;                         // + padding: the walk reads 3 links ahead
+    s.lds = lds_links ? s.lk_bytes + 64u + ((np_max + 31u) / 32u + words) * 4u : 16u + 64u;
+    return s;
+}
+
+// what differs between the parse-aware pipelines of levels 3-9 (plain, dictionary, linked frame blocks)
+template <typename T, typename R> struct HcSegJob {
+    HcIn in;
+    HcOut out;
+    T *d_link;                       // links of one round, results of a chunk: `stride` entries per block in both
+    R *d_res;
+    uint64_t stride;
+    uint32_t *d_bitmap;              // visited bits of one round, bm_stride words per block (HBM links only)
+    uint64_t bm_stride;
+    decltype(&k_hc_seg_search<4, true, false>) kern;   // (every instantiation has this type)
+    HcSegShape shape;
+    uint32_t seg_len;                // start points of the speculative walks
+    int fetch_rounds;
+    int32_t max_attempts;
+};
+
+// K1 + K2s + K3 in rounds.  stage(b0, nb, slot): an optional pass in front of a round that writes the round's input into
+// the block slots from `slot` on of an area of its own (the dictionary call's V); false = error
+template <bool kDict, typename T, typename R, typename Stage>
+int hc_seg_rounds(HcRounds rd, const HcSegJob<T, R> &j, uint32_t nblocks, Stage stage) {
+    constexpr bool kLds = sizeof(T) == 2;
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += rd.sub, rd.round++) {
+        const uint32_t nb = rd.blocks(b0, nblocks);
+        R *res = j.d_res + (uint64_t)rd.slot() * j.stride;
+        if (!rd.claim() || !stage(b0, nb, rd.slot())) return rd.fail();
+        // K2s stores matches only: every other position of the parse must read "no match"
+        if (hipMemsetAsync(res, 0, (size_t)nb * j.stride * sizeof(R), rd.stream) != hipSuccess) return rd.fail();
+        if (!kLds && hipMemsetAsync(j.d_bitmap, 0, (size_t)nb * j.bm_stride * 4u, rd.stream) != hipSuccess) return rd.fail();
+        hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), kBuildLinksLds<T>, rd.stream, j.in.base,
+                           j.in.off, j.in.len, j.d_link, j.stride, b0, nb, j.in.max_n);
+        hipLaunchKernelGGL(j.kern, dim3(nb), dim3(j.shape.threads), j.shape.lds, rd.stream, j.in.base, j.in.off, j.in.pair,
+                           static_cast<const void *>(j.d_link), j.stride, static_cast<void *>(res), j.d_bitmap, j.bm_stride, b0,
+                           nb, j.max_attempts, j.in.max_n, j.shape.lk_bytes, j.seg_len, j.fetch_rounds);
+        hipStream_t emit_on;
+        if (!rd.fork(&emit_on)) return rd.fail();
+        hipLaunchKernelGGL((k_hc_parse_emit<R, kDict>), dim3((nb + 3u) / 4u), dim3(256), 0, emit_on, j.in.base, j.in.off, j.in.pair,
+                           j.out.base, j.out.off, j.out.cap, j.out.result, static_cast<const R *>(res), j.stride, b0, nb, j.in.max_n);
+        if (!rd.release()) return rd.fail();
+    }
+    return rd.join();
+}
+}  // namespace
+
+// ------------------------------------------------------------------ levels 3..12, plain
+// K1 + K2s + K3 for the greedy levels; K1 + K2 + the price-based parse for levels 10-12.
 // (A per-wavefront work-queue form of the search-every-position K2 -- a lane that finishes its chain takes the next
 //  unassigned position -- was bit-exact but ran 2.3x SLOWER in round 1: neighbouring positions walk neighbouring chains, so
 //  the lock-step kernel's 64 gathers of a trip fall into a few cache lines, while the queue's lanes drift apart.  With
 //  the links in LDS and only the parse's positions searched, k_hc_seg_search is exactly such a queue and wins.)
+// The tuning knobs (ZLZ4_HC_*; the tuning and stamps builds read them) act on this call only.
 template <typename T, typename R>
 int launch_hc_chunked(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
                       uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap, int64_t *d_result,
                       uint32_t nblocks, uint32_t max_in_len, int32_t max_attempts, void *ws, uint32_t chunk,
                       bool optimal, uint32_t sufficient_len) {
+    constexpr bool kLds = sizeof(T) == 2;
     const uint64_t stride = ((uint64_t)max_in_len + 15u) & ~15ull;           // entries per block in both arrays
     T *d_link = static_cast<T *>(ws);
     uint8_t *after_link = static_cast<uint8_t *>(ws) + (uint64_t)chunk * stride * sizeof(T);
     R *d_res = reinterpret_cast<R *>(after_link);
     void *d_opt = after_link + (uint64_t)chunk * stride * sizeof(R);
-    const uint32_t np_max = max_in_len < 13u ? 1u : max_in_len - 11u;
-    // 128 KiB of the CU's 160 KiB LDS for the 32-bit table
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hc_build_links<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kHcTableSize * 4u + 4096u * sizeof(T) + 16u));
+    const uint32_t np_max = hc_np_max(max_in_len);
+    hc_allow_lds(reinterpret_cast<const void *>(&k_hc_build_links<T>), kBuildLinksLds<T>);
     static const bool legacy_search = zlz4_tune_env("ZLZ4_HC_LEGACY_SEARCH") != nullptr;   // A/B switch for profiles/
-    const bool seg_search = !optimal && !legacy_search;
-    if (seg_search) {
-        // parse-aware search (k_hc_seg_search).  Rounds of half a chunk, results in the two halves of the result
-        // area in turn: K3 of round r runs on the side stream while K1 / K2s of round r + 1 run on `stream`.
-        constexpr bool kLds = sizeof(T) == 2;
-        static const uint32_t seg_len = [] { const char *e = zlz4_tune_env("ZLZ4_HC_SEG"); return e ? (uint32_t)atoi(e) : 32u; }();   // start points of the speculative walks
+    if (!optimal && !legacy_search) {
+        // parse-aware search (k_hc_seg_search): K3 of round r runs beside K1 / K2s of round r + 1
+        static const uint32_t seg_len = [] { const char *e = zlz4_tune_env("ZLZ4_HC_SEG"); return e ? (uint32_t)atoi(e) : 32u; }();
         static const uint32_t thr_div = [] { const char *e = zlz4_tune_env("ZLZ4_HC_LPS"); return e ? (uint32_t)atoi(e) : 2u; }();
         static const bool no_overlap = zlz4_tune_env("ZLZ4_HC_NO_OVERLAP") != nullptr;          // A/B switch for profiles/
         static const int fetch_rounds = [] { const char *e = zlz4_tune_env("ZLZ4_HC_FETCH"); const int v = e ? atoi(e) : 1; return v >= 1 && v <= 8 ? v : 1; }();
-        const uint32_t nseg_max = (np_max + seg_len - 1u) / seg_len;
-        uint32_t threads = (nseg_max / thr_div + 63u) & ~63u;                // ~2 start points per lane
-        if (threads > 1024u) threads = 1024u;
-        if (threads < 64u) threads = 64u;
-        const uint32_t lk_bytes = ((np_max * 2u + 15u) & ~15u) + 16u;        // + padding: the walk reads 3 links ahead
-        const uint32_t lds = kLds ? lk_bytes + 64u + ((np_max + 31u) / 32u + 3u) * 4u : 16u + 64u;   // links, counted runs, bitmap, 3 words | 3 words, counted runs
         static const int cands = [] { const char *e = zlz4_tune_env("ZLZ4_HC_CANDS"); return e ? atoi(e) : 4; }();
-        auto kern = cands == 8 ? &k_hc_seg_search<8, kLds> : cands == 4 ? &k_hc_seg_search<4, kLds> : cands == 2 ? &k_hc_seg_search<2, kLds> : &k_hc_seg_search<1, kLds>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const uint64_t bm_stride = (stride + 31u) / 32u + 1u;                // bitmap words per block (HBM links only)
-        uint32_t *d_bitmap = static_cast<uint32_t *>(d_opt);                 // (the area of the price-based parse is idle here)
-        HcSideStream *side = (chunk >= 2u && nblocks > chunk / 2u && !no_overlap) ? hc_side_stream() : nullptr;
-        const uint32_t sub = side ? chunk / 2u : chunk;
-        uint32_t round = 0;
-        // error exit: K3 may still be running on the side stream and the caller parks the workspace as soon as `stream` is
-        // idle -- wait for the side stream first
-        auto fail = [&]() -> int { if (side) (void)hipStreamSynchronize(side->st); return -7; };
-        for (uint32_t b0 = 0; b0 < nblocks; b0 += sub, round++) {
-            const uint32_t nb = nblocks - b0 < sub ? nblocks - b0 : sub;
-            const uint32_t half = side ? (round & 1u) : 0u;
-            R *res = d_res + (uint64_t)half * sub * stride;
-            if (side && round >= 2u && hipStreamWaitEvent(stream, side->emitted[half], 0) != hipSuccess) return fail();   // K3 of round - 2 read this half
-            // K2s stores matches only: every other position of the parse must read "no match"
-            if (hipMemsetAsync(res, 0, (size_t)nb * stride * sizeof(R), stream) != hipSuccess) return fail();
-            if (!kLds && hipMemsetAsync(d_bitmap, 0, (size_t)nb * bm_stride * 4u, stream) != hipSuccess) return fail();
-            hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), kHcTableSize * 4u + 4096u * sizeof(T) + 16u, stream, d_in,
-                               d_in_off, d_in_len, d_link, stride, b0, nb, max_in_len);
-            hipLaunchKernelGGL(kern, dim3(nb), dim3(threads), lds, stream, d_in, d_in_off, d_in_len,
-                               static_cast<const void *>(d_link), stride, static_cast<void *>(res), d_bitmap, bm_stride, b0, nb,
-                               max_attempts, max_in_len, lk_bytes, seg_len, fetch_rounds);
-            hipStream_t emit_on = stream;
-            if (side) {
-                if (hipEventRecord(side->searched[half], stream) != hipSuccess ||
-                    hipStreamWaitEvent(side->st, side->searched[half], 0) != hipSuccess) return fail();
-                emit_on = side->st;
-            }
-            hipLaunchKernelGGL((k_hc_parse_emit<R>), dim3((nb + 3u) / 4u), dim3(256), 0, emit_on, d_in, d_in_off, d_in_len,
-                               d_out, d_out_off, d_out_cap, d_result, static_cast<const R *>(res), stride, b0, nb, max_in_len);
-            if (side && hipEventRecord(side->emitted[half], side->st) != hipSuccess) return fail();
-        }
-        if (side)     // join: everything enqueued here is ordered before whatever the caller enqueues on `stream` next
-            for (uint32_t k = 0; k < 2u && k < round; k++)
-                if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail();
-        return hipGetLastError() == hipSuccess ? 0 : -7;
+        HcSegJob<T, R> j = {{d_in, d_in_off, d_in_len, d_in_len, max_in_len}, {d_out, d_out_off, d_out_cap, d_result}, d_link, d_res, stride};
+        j.d_bitmap = static_cast<uint32_t *>(d_opt);                         // (the area of the price-based parse is idle here)
+        j.bm_stride = (stride + 31u) / 32u + 1u;
+        j.kern = cands == 8 ? &k_hc_seg_search<8, kLds> : cands == 4 ? &k_hc_seg_search<4, kLds> : cands == 2 ? &k_hc_seg_search<2, kLds> : &k_hc_seg_search<1, kLds>;
+        j.shape = hc_seg_shape(kLds, np_max, (np_max + seg_len - 1u) / seg_len, thr_div, 64u, 3u);
+        j.seg_len = seg_len;
+        j.fetch_rounds = fetch_rounds;
+        j.max_attempts = max_attempts;
+        hc_allow_lds(reinterpret_cast<const void *>(j.kern), j.shape.lds);
+        return hc_seg_rounds<false>(HcRounds(stream, chunk, nblocks, !no_overlap), j, nblocks,
+                                    [](uint32_t, uint32_t, uint32_t) { return true; });
     }
     // search-every-position pipeline (levels 10-12, and the A/B switch).  The price-based parse of round r runs on the
     // side stream beside K2 of round r + 1: the parse keeps its records in LDS and leaves the vector memory path alone,
@@ -1369,56 +1461,46 @@ int launch_hc_chunked(hipStream_t stream, const uint8_t *d_in, const uint64_t *d
     // small workgroups keep refilling never has it free: K1 launched beside the parse waited 30-45 ms per round), so
     // links and results both alternate between two halves of their areas:
     //   stream: K1(0) K2(0) K1(1) | K2(1) K1(2) | K2(2) ...        side: parse(0) | parse(1) | ...
-    static const bool opt_no_overlap = zlz4_tune_env("ZLZ4_HC_NO_OVERLAP") != nullptr;
-    HcSideStream *side = (optimal && chunk >= 2u && nblocks > chunk / 2u && !opt_no_overlap) ? hc_side_stream() : nullptr;
-    const uint32_t sub = side ? chunk / 2u : chunk;
-    auto fail = [&](int rc) -> int { if (side) (void)hipStreamSynchronize(side->st); return rc; };
-    auto links_of = [&](uint32_t round) { return d_link + (uint64_t)(side ? (round & 1u) : 0u) * sub * stride; };
+    static const bool opt_no_overlap = zlz4_tune_env("ZLZ4_HC_NO_OVERLAP") != nullptr;   // (this pipeline's own static, as the library's symbols have it)
+    HcRounds rd(stream, chunk, nblocks, optimal && !opt_no_overlap);
+    auto links_of = [&](uint32_t round) { return d_link + (uint64_t)rd.slot_of(round) * stride; };
     auto launch_k1 = [&](uint32_t round, uint32_t b0) {
-        const uint32_t nb = nblocks - b0 < sub ? nblocks - b0 : sub;
-        hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), kHcTableSize * 4u + 4096u * sizeof(T) + 16u, stream, d_in, d_in_off,
+        const uint32_t nb = rd.blocks(b0, nblocks);
+        hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), kBuildLinksLds<T>, stream, d_in, d_in_off,
                            d_in_len, links_of(round), stride, b0, nb, max_in_len);
     };
-    uint32_t round = 0;
     if (nblocks) launch_k1(0, 0);
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += sub, round++) {
-        const uint32_t nb = nblocks - b0 < sub ? nblocks - b0 : sub;
-        const uint32_t half = side ? (round & 1u) : 0u;
-        R *res = d_res + (uint64_t)half * sub * stride;
-        if (side && round >= 2u && hipStreamWaitEvent(stream, side->emitted[half], 0) != hipSuccess) return fail(-7);   // parse(round - 2) read this half
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += rd.sub, rd.round++) {
+        const uint32_t nb = rd.blocks(b0, nblocks);
+        R *res = d_res + (uint64_t)rd.slot() * stride;
+        if (!rd.claim()) return rd.fail();
         // every position (the price-based parse of levels 10-12 looks results up everywhere; blocks > 64 KiB)
         // (one-wave workgroups: 376 / 401 / 416 ms for 64 / 128 / 256 threads on configs[3] -- the wavefronts of a
         //  workgroup finish at very different times and a four-wave workgroup keeps its slots until the last one is done)
         hipLaunchKernelGGL((k_hc_search<T, R>), dim3((np_max + 63u) / 64u, nb), dim3(64), 0, stream, d_in,
-                           d_in_off, d_in_len, links_of(round), stride, res, b0, nb, max_attempts, optimal ? 1 : 0, max_in_len);
-        if (side && b0 + sub < nblocks) launch_k1(round + 1u, b0 + sub);      // (its half of the links was last read by K2(round - 1))
+                           d_in_off, d_in_len, links_of(rd.round), stride, res, b0, nb, max_attempts, optimal ? 1 : 0, max_in_len);
+        if (rd.side && b0 + rd.sub < nblocks) launch_k1(rd.round + 1u, b0 + rd.sub);   // (its half of the links was last read by K2(round - 1))
+        hipStream_t parse_on;
+        if (!rd.fork(&parse_on)) return rd.fail();
         if (optimal) {
-            hipStream_t parse_on = stream;
-            if (side) {
-                if (hipEventRecord(side->searched[half], stream) != hipSuccess ||
-                    hipStreamWaitEvent(side->st, side->searched[half], 0) != hipSuccess) return fail(-7);
-                parse_on = side->st;
-            }
             const int rc = zlz4_launch_hc_opt_parse(parse_on, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result,
                                                     res, stride, sizeof(R) == 8 ? 1 : 0, d_opt, b0, nb, sufficient_len, max_in_len);
-            if (rc != 0) return fail(rc);
-            if (side && hipEventRecord(side->emitted[half], side->st) != hipSuccess) return fail(-7);
+            if (rc != 0) return rd.fail(rc);
         } else {
-            hipLaunchKernelGGL((k_hc_parse_emit<R>), dim3((nb + 3u) / 4u), dim3(256), 0, stream, d_in, d_in_off, d_in_len,
+            hipLaunchKernelGGL((k_hc_parse_emit<R>), dim3((nb + 3u) / 4u), dim3(256), 0, parse_on, d_in, d_in_off, d_in_len,
                                d_out, d_out_off, d_out_cap, d_result, res, stride, b0, nb, max_in_len);
         }
-        if (!side && b0 + sub < nblocks) launch_k1(round + 1u, b0 + sub);
+        if (!rd.release()) return rd.fail();
+        if (!rd.side && b0 + rd.sub < nblocks) launch_k1(rd.round + 1u, b0 + rd.sub);
     }
-    if (side)     // join
-        for (uint32_t k = 0; k < 2u && k < round; k++)
-            if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail(-7);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return rd.join();
 }
 
 }  // namespace zlz4
 
 namespace {
-constexpr uint32_t kHcChunkBlocks = 8192;   // blocks per round (bounds the workspace: 3.5 GiB for 64 KiB blocks; 4096 / 8192 / 14043: 52.3 / 50.5 / 51.5 ms on configs[3])
+using namespace zlz4;
+
 bool hc_small(uint32_t max_in_len) {
     // ZLZ4_HC_HBM_LINKS (A/B switch for profiles/): blocks <= 64 KiB through the variant that keeps the links in HBM
     static const bool force_hbm = zlz4_tune_env("ZLZ4_HC_HBM_LINKS") != nullptr;
@@ -1432,14 +1514,7 @@ uint64_t hc_per_block_bytes(uint32_t max_in_len) {
     const uint64_t mid = zlz4_hc_mid_workspace_bytes(1);                                                     // level 2
     return chain + opt > mid ? chain + opt : mid;
 }
-uint32_t hc_chunk(uint32_t nblocks, uint32_t max_in_len) {
-    // keep the workspace around <= 6 GiB for big blocks
-    uint64_t c = (6ull << 30) / hc_per_block_bytes(max_in_len);
-    if (c < 1) c = 1;
-    if (c > kHcChunkBlocks) c = kHcChunkBlocks;
-    if (c > nblocks) c = nblocks ? nblocks : 1;
-    return (uint32_t)c;
-}
+uint32_t hc_chunk(uint32_t nblocks, uint32_t max_in_len) { return hc_chunk_blocks(hc_per_block_bytes(max_in_len), nblocks); }
 }  // namespace
 
 // one workspace size for every level (the caller need not know which strategy a level maps to)
@@ -1467,7 +1542,7 @@ extern "C" int zlz4_launch_compress_hc(hipStream_t stream, const uint8_t *d_in, 
     const bool optimal = level >= 10;
     static const int32_t opt_nb[3] = {96, 512, 16384};
     static const uint32_t opt_target[3] = {64, 128, 4096};
-    const int32_t max_attempts = optimal ? opt_nb[level - 10] : 1 << (level - 1);   // 3 -> 4 ... 9 -> 256
+    const int32_t max_attempts = optimal ? opt_nb[level - 10] : hc_attempts(level);
     const uint32_t sufficient = optimal ? opt_target[level - 10] : 0;
     if (hc_small(max_in_len))
         return zlz4::launch_hc_chunked<uint16_t, uint32_t>(stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
@@ -1478,113 +1553,70 @@ extern "C" int zlz4_launch_compress_hc(hipStream_t stream, const uint8_t *d_in, 
                                                        sufficient);
 }
 
-// ------------------------------------------------------------------ levels 3..9 with a dictionary
-// zlz4_batch_compress_hc_using_dict: compressHashChain on V = dictionary tail ++ record with ip = anchor = D.  A staging
-// kernel (zlz4_compress_hc_dict.hip) writes V per block into the workspace; K1 runs on V as it is, K2s and K3 in their
-// kDict instantiations.  Rounds, side stream and result halves as in launch_hc_chunked; V alternates between two halves
-// with the results, because K3 of round r takes its literals from V while round r + 1 is staged.
-//
-// workspace: v_off u64[nblocks] | { v_len, start } u32[2 nblocks] | v_len u32[nblocks] | (16-byte boundary)
-//            links T[chunk * stride] | results R[chunk * stride] | visited bits (HBM links) | V [chunk * stride]
+// ------------------------------------------------------------------ levels 3..9 on V = tail ++ record (DESIGN.md sections 4.3c, 4.4c)
+// compressHashChain on V with ip = anchor = start = the tail's length: K1 runs on V as it is, K2s and K3 in their kDict
+// instantiations, through hc_seg_rounds.  Two callers:
+//  * zlz4_batch_compress_hc_using_dict: V = the dictionary's last 64 KiB ++ the record.  A staging kernel
+//    (zlz4_compress_hc_dict.hip) writes it per block into the workspace in front of every round; V alternates between two
+//    halves with the results, because K3 of round r takes its literals from V while round r + 1 is staged.
+//    workspace: v_off u64[nblocks] | { v_len, start } u32[2 nblocks] | v_len u32[nblocks] | (16-byte boundary)
+//               links T[chunk * stride] | results R[chunk * stride] | visited bits (HBM links) | V [chunk * stride]
+//  * linked frame blocks: block k is compressHCUsingDict(block_k, dict = the 64 KiB of input in front of it), and V_k
+//    already lies contiguous in the caller's input, so nothing is staged and V has no halves.  k_bfl_hc_desc
+//    (zlz4_frame_linked.hip) has written v_off (absolute in d_in), v_len and the pairs.  max_n = 65536 + max_block_len:
+//    HBM links (u32 / u64) always.
+//    workspace: links u32[chunk * stride] | results u64[chunk * stride] | visited bits u32[chunk * bm_stride]
 
 namespace {
 struct HcDictPlan {
-    uint32_t dmax, max_n;            // longest tail, longest V
+    uint32_t dmax, max_rec, max_n;   // longest tail, longest record, longest V
     bool lds;                        // LDS links (u16 / u32 results) or HBM links (u32 / u64)
     uint64_t stride;                 // entries per block in links and results = bytes per block of V
     uint64_t bm_stride;              // visited-bitmap words per block (HBM links)
     uint64_t head, per_block;
     uint32_t chunk;
+    uint64_t bytes() const { return head + (uint64_t)chunk * per_block; }
 };
-HcDictPlan hc_dict_plan(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len) {
+HcDictPlan hc_dict_plan(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len, bool staged) {
     HcDictPlan p;
     p.dmax = max_dict_len < 65536u ? max_dict_len : 65536u;
     // (a record over ZLZ4_MAX_INPUT_SIZE is refused by the staging kernel: it never needs room)
-    p.max_n = p.dmax + (max_in_len < zlz4::kMaxInput ? max_in_len : zlz4::kMaxInput);
-    p.lds = p.max_n <= 65536u;
+    p.max_rec = max_in_len < kMaxInput ? max_in_len : kMaxInput;
+    p.max_n = p.dmax + p.max_rec;
+    p.lds = staged && p.max_n <= 65536u;
     p.stride = ((uint64_t)p.max_n + 15u) & ~15ull;
     if (p.stride == 0) p.stride = 16;                            // (a batch of empty records)
     p.bm_stride = p.lds ? 0 : ((p.stride + 31u) / 32u + 1u + 3u) & ~3ull;   // (whole 16 bytes: V, which follows, stays aligned)
-    p.head = ((uint64_t)nblocks * 20u + 15u) & ~15ull;
-    p.per_block = p.stride * (p.lds ? 6u : 12u) + p.bm_stride * 4u + p.stride;
-    uint64_t c = (6ull << 30) / p.per_block;                     // as hc_chunk: around 6 GiB at most
-    if (c < 1) c = 1;
-    if (c > kHcChunkBlocks) c = kHcChunkBlocks;
-    if (c > nblocks) c = nblocks ? nblocks : 1;
-    p.chunk = (uint32_t)c;
+    p.head = staged ? ((uint64_t)nblocks * 20u + 15u) & ~15ull : 0;
+    p.per_block = p.stride * (p.lds ? 6u : 12u) + p.bm_stride * 4u + (staged ? p.stride : 0);
+    p.chunk = hc_chunk_blocks(p.per_block, nblocks);
     return p;
+}
+
+// `body`: the workspace from the links on
+template <typename T, typename R, typename Stage>
+int launch_hc_dict_chunked(hipStream_t stream, const HcIn &in, const HcOut &out, uint32_t nblocks, int32_t level,
+                           uint8_t *body, const HcDictPlan &pl, Stage stage) {
+    constexpr bool kLds = sizeof(T) == 2;
+    const uint64_t entries = (uint64_t)pl.chunk * pl.stride;
+    HcSegJob<T, R> j = {in, out, reinterpret_cast<T *>(body), reinterpret_cast<R *>(body + entries * sizeof(T)), pl.stride};
+    j.d_bitmap = reinterpret_cast<uint32_t *>(body + entries * (sizeof(T) + sizeof(R)));
+    j.bm_stride = pl.bm_stride;
+    j.kern = &k_hc_seg_search<4, kLds, true>;
+    j.seg_len = 32u;
+    // start points counted over the record (nothing below `start` is one); at least four wavefronts, which also copy the
+    // links of the whole of V into LDS
+    j.shape = hc_seg_shape(kLds, hc_np_max(pl.max_n), pl.max_rec / j.seg_len + 1u, 2u, 256u, 4u);
+    j.fetch_rounds = 1;
+    j.max_attempts = hc_attempts(level);
+    hc_allow_lds(reinterpret_cast<const void *>(&k_hc_build_links<T>), kBuildLinksLds<T>);
+    hc_allow_lds(reinterpret_cast<const void *>(j.kern), j.shape.lds);
+    return hc_seg_rounds<true>(HcRounds(stream, pl.chunk, nblocks, true), j, nblocks, stage);
 }
 }  // namespace
 
-namespace zlz4 {
-template <typename T, typename R>
-int launch_hc_dict_chunked(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
-                           uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap, const uint8_t *d_dict,
-                           const uint64_t *d_dict_off, const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks,
-                           uint32_t max_in_len, int32_t max_attempts, void *ws, const HcDictPlan &pl) {
-    constexpr bool kLds = sizeof(T) == 2;
-    const uint64_t stride = pl.stride;
-    const uint32_t chunk = pl.chunk;
-    uint64_t *v_off = static_cast<uint64_t *>(ws);
-    uint32_t *v_pair = reinterpret_cast<uint32_t *>(v_off + nblocks);
-    uint32_t *v_len = v_pair + 2u * (uint64_t)nblocks;
-    uint8_t *body = static_cast<uint8_t *>(ws) + pl.head;
-    T *d_link = reinterpret_cast<T *>(body);
-    R *d_res = reinterpret_cast<R *>(body + (uint64_t)chunk * stride * sizeof(T));
-    uint32_t *d_bitmap = reinterpret_cast<uint32_t *>(body + (uint64_t)chunk * stride * (sizeof(T) + sizeof(R)));
-    uint8_t *d_v = reinterpret_cast<uint8_t *>(d_bitmap) + (uint64_t)chunk * pl.bm_stride * 4u;
-    const uint32_t np_max = pl.max_n < 13u ? 1u : pl.max_n - 11u;
-    const uint32_t k1_lds = kHcTableSize * 4u + 4096u * sizeof(T) + 16u;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hc_build_links<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1_lds);
-    constexpr uint32_t seg_len = 32u;
-    // ~2 start points per lane, counted over the record (nothing below `start` is a start point); at least four
-    // wavefronts, which also copy the links of the whole of V into LDS
-    const uint32_t nseg_max = (max_in_len < zlz4::kMaxInput ? max_in_len : zlz4::kMaxInput) / seg_len + 1u;
-    uint32_t threads = (nseg_max / 2u + 63u) & ~63u;
-    if (threads > 1024u) threads = 1024u;
-    if (threads < 256u) threads = 256u;
-    const uint32_t lk_bytes = ((np_max * 2u + 15u) & ~15u) + 16u;            // + padding: the walk reads 3 links ahead
-    const uint32_t lds = kLds ? lk_bytes + 64u + ((np_max + 31u) / 32u + 4u) * 4u : 16u + 64u;   // as launch_hc_chunked, + the word for `start`
-    auto kern = &k_hc_seg_search<4, kLds, true>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    HcSideStream *side = (chunk >= 2u && nblocks > chunk / 2u) ? hc_side_stream() : nullptr;
-    const uint32_t sub = side ? chunk / 2u : chunk;
-    uint32_t round = 0;
-    auto fail = [&]() -> int { if (side) (void)hipStreamSynchronize(side->st); return -7; };
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += sub, round++) {
-        const uint32_t nb = nblocks - b0 < sub ? nblocks - b0 : sub;
-        const uint32_t half = side ? (round & 1u) : 0u;
-        R *res = d_res + (uint64_t)half * sub * stride;
-        if (side && round >= 2u && hipStreamWaitEvent(stream, side->emitted[half], 0) != hipSuccess) return fail();   // K3 of round - 2 read this half of V and of the results
-        if (zlz4_launch_hc_dict_stage(stream, d_in, d_in_off, d_in_len, d_dict, d_dict_off, d_dict_len, d_v, stride, v_off,
-                                      v_len, v_pair, b0, nb, half * sub, max_in_len, pl.dmax) != 0) return fail();
-        if (hipMemsetAsync(res, 0, (size_t)nb * stride * sizeof(R), stream) != hipSuccess) return fail();
-        if (!kLds && hipMemsetAsync(d_bitmap, 0, (size_t)nb * pl.bm_stride * 4u, stream) != hipSuccess) return fail();
-        hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), k1_lds, stream, d_v, v_off, v_len, d_link,
-                           stride, b0, nb, pl.max_n);
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(threads), lds, stream, d_v, v_off, v_pair, static_cast<const void *>(d_link),
-                           stride, static_cast<void *>(res), d_bitmap, pl.bm_stride, b0, nb, max_attempts, pl.max_n, lk_bytes,
-                           seg_len, 1);
-        hipStream_t emit_on = stream;
-        if (side) {
-            if (hipEventRecord(side->searched[half], stream) != hipSuccess ||
-                hipStreamWaitEvent(side->st, side->searched[half], 0) != hipSuccess) return fail();
-            emit_on = side->st;
-        }
-        hipLaunchKernelGGL((k_hc_parse_emit<R, true>), dim3((nb + 3u) / 4u), dim3(256), 0, emit_on, d_v, v_off, v_pair, d_out,
-                           d_out_off, d_out_cap, d_result, static_cast<const R *>(res), stride, b0, nb, pl.max_n);
-        if (side && hipEventRecord(side->emitted[half], side->st) != hipSuccess) return fail();
-    }
-    if (side)     // join
-        for (uint32_t k = 0; k < 2u && k < round; k++)
-            if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail();
-    return hipGetLastError() == hipSuccess ? 0 : -7;
-}
-}  // namespace zlz4
-
 extern "C" size_t zlz4_hc_dict_workspace_bytes(uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len) {
-    const HcDictPlan p = hc_dict_plan(nblocks, max_in_len, max_dict_len);
-    return (size_t)(p.head + (uint64_t)p.chunk * p.per_block);
+    return (size_t)hc_dict_plan(nblocks, max_in_len, max_dict_len, true).bytes();
 }
 
 // `level` is normalised (3..9) by the caller
@@ -1596,50 +1628,25 @@ extern "C" int zlz4_launch_compress_hc_dict(hipStream_t stream, const uint8_t *d
                                             size_t ws_bytes) {
     if (nblocks == 0) return 0;
     if (level < 3 || level > 9) return -8;
-    const HcDictPlan p = hc_dict_plan(nblocks, max_in_len, max_dict_len);
-    if (ws_bytes < p.head + (uint64_t)p.chunk * p.per_block) return -5;
-    const int32_t max_attempts = 1 << (level - 1);                              // 3 -> 4 ... 9 -> 256
-    if (p.lds)
-        return zlz4::launch_hc_dict_chunked<uint16_t, uint32_t>(stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_dict,
-                                                                d_dict_off, d_dict_len, d_result, nblocks, max_in_len,
-                                                                max_attempts, ws, p);
-    return zlz4::launch_hc_dict_chunked<uint32_t, uint64_t>(stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_dict,
-                                                            d_dict_off, d_dict_len, d_result, nblocks, max_in_len, max_attempts,
-                                                            ws, p);
+    const HcDictPlan p = hc_dict_plan(nblocks, max_in_len, max_dict_len, true);
+    if (ws_bytes < p.bytes()) return -5;
+    uint64_t *v_off = static_cast<uint64_t *>(ws);
+    uint32_t *v_pair = reinterpret_cast<uint32_t *>(v_off + nblocks);
+    uint32_t *v_len = v_pair + 2u * (uint64_t)nblocks;
+    uint8_t *body = static_cast<uint8_t *>(ws) + p.head;
+    uint8_t *d_v = body + (uint64_t)p.chunk * (p.per_block - p.stride);      // behind links, results and visited bits
+    auto stage = [=](uint32_t b0, uint32_t nb, uint32_t slot) {
+        return zlz4_launch_hc_dict_stage(stream, d_in, d_in_off, d_in_len, d_dict, d_dict_off, d_dict_len, d_v, p.stride, v_off,
+                                         v_len, v_pair, b0, nb, slot, max_in_len, p.dmax) == 0;
+    };
+    const HcIn in = {d_v, v_off, v_len, v_pair, p.max_n};
+    const HcOut out = {d_out, d_out_off, d_out_cap, d_result};
+    if (p.lds) return launch_hc_dict_chunked<uint16_t, uint32_t>(stream, in, out, nblocks, level, body, p, stage);
+    return launch_hc_dict_chunked<uint32_t, uint64_t>(stream, in, out, nblocks, level, body, p, stage);
 }
-
-// ------------------------------------------------------------------ levels 3..9 on linked frame blocks
-// Block k of a linked frame is compressHCUsingDict(block_k, dict = the 64 KiB of input in front of it): V_k = tail ++ block
-// already lies contiguous in the caller's input, so nothing is staged.  k_bfl_hc_desc (zlz4_frame_linked.hip) has written
-// v_off (absolute in d_in), v_len and the pairs { v_len, start }; K1, K2s and K3 run on d_in in the instantiations
-// launch_hc_dict_chunked uses.  Rounds, side stream and result halves as there; V has no halves: K3 takes its literals
-// from the caller's input, which does not move.  max_n = 65536 + max_block_len > 65536: HBM links (u32 / u64) always.
-//
-// workspace: links u32[chunk * stride] | results u64[chunk * stride] | visited bits u32[chunk * bm_stride]
-namespace {
-struct HcLinkedPlan {
-    uint32_t max_n;
-    uint64_t stride, bm_stride, per_block;
-    uint32_t chunk;
-};
-HcLinkedPlan hc_linked_plan(uint32_t nblocks, uint32_t max_block_len) {
-    HcLinkedPlan p;
-    p.max_n = 65536u + (max_block_len < zlz4::kMaxInput ? max_block_len : zlz4::kMaxInput);
-    p.stride = ((uint64_t)p.max_n + 15u) & ~15ull;
-    p.bm_stride = ((p.stride + 31u) / 32u + 1u + 3u) & ~3ull;
-    p.per_block = p.stride * 12u + p.bm_stride * 4u;
-    uint64_t c = (6ull << 30) / p.per_block;                     // as hc_chunk: around 6 GiB at most
-    if (c < 1) c = 1;
-    if (c > kHcChunkBlocks) c = kHcChunkBlocks;
-    if (c > nblocks) c = nblocks ? nblocks : 1;
-    p.chunk = (uint32_t)c;
-    return p;
-}
-}  // namespace
 
 extern "C" size_t zlz4_hc_linked_workspace_bytes(uint32_t nblocks, uint32_t max_block_len) {
-    const HcLinkedPlan p = hc_linked_plan(nblocks, max_block_len);
-    return (size_t)((uint64_t)p.chunk * p.per_block);
+    return (size_t)hc_dict_plan(nblocks, max_block_len, 65536u, false).bytes();
 }
 
 // `level` is normalised (3..9) by the caller; ws is 16-byte aligned
@@ -1648,61 +1655,12 @@ extern "C" int zlz4_launch_compress_hc_linked(hipStream_t stream, const uint8_t 
                                               const uint64_t *d_out_off, const uint32_t *d_out_cap, int64_t *d_result,
                                               uint32_t nblocks, uint32_t max_block_len, int32_t level, void *ws,
                                               size_t ws_bytes) {
-    using namespace zlz4;
-    typedef uint32_t T;
-    typedef uint64_t R;
     if (nblocks == 0) return 0;
     if (level < 3 || level > 9) return -8;
-    const HcLinkedPlan pl = hc_linked_plan(nblocks, max_block_len);
-    if (ws_bytes < (uint64_t)pl.chunk * pl.per_block) return -5;
-    const int32_t max_attempts = 1 << (level - 1);                              // 3 -> 4 ... 9 -> 256
-    const uint64_t stride = pl.stride;
-    const uint32_t chunk = pl.chunk;
-    uint8_t *body = static_cast<uint8_t *>(ws);
-    T *d_link = reinterpret_cast<T *>(body);
-    R *d_res = reinterpret_cast<R *>(body + (uint64_t)chunk * stride * sizeof(T));
-    uint32_t *d_bitmap = reinterpret_cast<uint32_t *>(body + (uint64_t)chunk * stride * (sizeof(T) + sizeof(R)));
-    const uint32_t np_max = pl.max_n - 11u;
-    const uint32_t k1_lds = kHcTableSize * 4u + 4096u * sizeof(T) + 16u;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hc_build_links<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k1_lds);
-    constexpr uint32_t seg_len = 32u;
-    // ~2 start points per lane, counted over the block (nothing below `start` is a start point), as launch_hc_dict_chunked
-    const uint32_t nseg_max = (max_block_len < kMaxInput ? max_block_len : kMaxInput) / seg_len + 1u;
-    uint32_t threads = (nseg_max / 2u + 63u) & ~63u;
-    if (threads > 1024u) threads = 1024u;
-    if (threads < 256u) threads = 256u;
-    const uint32_t lk_bytes = ((np_max * 2u + 15u) & ~15u) + 16u;            // (unused by the HBM-link instantiation)
-    const uint32_t lds = 16u + 64u;                                          // 4 words (the last one is `start`), counted runs
-    auto kern = &k_hc_seg_search<4, false, true>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    HcSideStream *side = (chunk >= 2u && nblocks > chunk / 2u) ? hc_side_stream() : nullptr;
-    const uint32_t sub = side ? chunk / 2u : chunk;
-    uint32_t round = 0;
-    auto fail = [&]() -> int { if (side) (void)hipStreamSynchronize(side->st); return -7; };
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += sub, round++) {
-        const uint32_t nb = nblocks - b0 < sub ? nblocks - b0 : sub;
-        const uint32_t half = side ? (round & 1u) : 0u;
-        R *res = d_res + (uint64_t)half * sub * stride;
-        if (side && round >= 2u && hipStreamWaitEvent(stream, side->emitted[half], 0) != hipSuccess) return fail();   // K3 of round - 2 read this half of the results
-        if (hipMemsetAsync(res, 0, (size_t)nb * stride * sizeof(R), stream) != hipSuccess) return fail();
-        if (hipMemsetAsync(d_bitmap, 0, (size_t)nb * pl.bm_stride * 4u, stream) != hipSuccess) return fail();
-        hipLaunchKernelGGL((k_hc_build_links<T>), dim3(nb), dim3(64 * kLinkWaves), k1_lds, stream, d_in, v_off, v_len, d_link,
-                           stride, b0, nb, pl.max_n);
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(threads), lds, stream, d_in, v_off, v_pair, static_cast<const void *>(d_link),
-                           stride, static_cast<void *>(res), d_bitmap, pl.bm_stride, b0, nb, max_attempts, pl.max_n, lk_bytes,
-                           seg_len, 1);
-        hipStream_t emit_on = stream;
-        if (side) {
-            if (hipEventRecord(side->searched[half], stream) != hipSuccess ||
-                hipStreamWaitEvent(side->st, side->searched[half], 0) != hipSuccess) return fail();
-            emit_on = side->st;
-        }
-        hipLaunchKernelGGL((k_hc_parse_emit<R, true>), dim3((nb + 3u) / 4u), dim3(256), 0, emit_on, d_in, v_off, v_pair, d_out,
-                           d_out_off, d_out_cap, d_result, static_cast<const R *>(res), stride, b0, nb, pl.max_n);
-        if (side && hipEventRecord(side->emitted[half], side->st) != hipSuccess) return fail();
-    }
-    if (side)     // join
-        for (uint32_t k = 0; k < 2u && k < round; k++)
-            if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail();
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    const HcDictPlan p = hc_dict_plan(nblocks, max_block_len, 65536u, false);
+    if (ws_bytes < p.bytes()) return -5;
+    const HcIn in = {d_in, v_off, v_len, v_pair, p.max_n};
+    const HcOut out = {d_out, d_out_off, d_out_cap, d_result};
+    return launch_hc_dict_chunked<uint32_t, uint64_t>(stream, in, out, nblocks, level, static_cast<uint8_t *>(ws), p,
+                                                      [](uint32_t, uint32_t, uint32_t) { return true; });
 }
