@@ -6,6 +6,8 @@ batch call, warm-up, median of --reps.  Cases (profiles/r08_stream_decode.md):
   c  4 KiB records as runs of 64 with a shared 64 KiB dictionary pending at each run's start
   d  (a) with 1 % corrupt blocks
   e  per-call latency of zlz4_decompress_safe_continue against zlz4_decompress_safe (host buffers)
+  w  the serial walk of k_sd_finish: 64 runs that open with 70 corrupt calls (more than k_sd_plan looks back), then 32 x
+     (a corrupt call, a 64 KiB block); every block is re-decoded by its run's one wavefront
 Prints one line per case."""
 import argparse
 import os
@@ -89,6 +91,34 @@ def main():
     bad = rng.random(n) < 0.01
     comp_bad_len = [1 if bad[i] else clen[i % uniq] for i in range(n)]   # a 1-byte stream with a literal run: corrupt
     stream_case("(d) one run, 1 % corrupt", i32([0, n]), i32(comp_bad_len), 1)
+
+    # (w) the good blocks go to ascending slots, each behind a corrupt call whose slot lies above them all: a block's true
+    # entry bound is 0, the guessed one (from the call in front of it) is not, and no plan round sees a success
+    W, G = 64, 32
+    per = 70 + 2 * G
+    blk, slot = [], []
+    for s in range(W):
+        for j in range(per):
+            good = j >= 70 and (j - 70) % 2 == 1
+            blk.append((s * G + (j - 70) // 2) % uniq if good else -1)
+            slot.append(s * G + (j - 70) // 2 if good else W * G)
+    w_in_off = i64([max(b, 0) * cap for b in blk])
+    w_in_len = i32([clen[b] if b >= 0 else 1 for b in blk])
+    w_out = torch.empty((W * G + 1) * B, dtype=torch.uint8, device=dev)
+    w_out_off, w_out_cap = i64([k * B for k in slot]), i32([B] * len(blk))
+    w_res = torch.empty(len(blk), dtype=torch.int64, device=dev)
+    w_state = torch.zeros((W, 4), dtype=torch.int64, device=dev)
+    w_ws = torch.empty(zl.batch_decompress_safe_continue_workspace(len(blk), W), dtype=torch.uint8, device=dev)
+    w_runs = i32([per * s for s in range(W + 1)])
+
+    def gow():
+        w_state.zero_()
+        zl.batch_decompress_safe_continue(comp, w_in_off, w_in_len, w_out, w_out_off, w_out_cap, w_runs, w_state, w_res, w_ws)
+    t = timed(gow, a.warmup, a.reps)
+    wr = w_res.cpu()
+    wgib = W * G * B / 2**30
+    print("(w) %d runs of 70 corrupt calls + %d x (corrupt, 64 KiB), the serial walk: %.3f ms  %.2f GiB/s  (%d ok, %d failed)" %
+          (W, G, t, wgib / t * 1e3, int((wr >= 0).sum()), int((wr < 0).sum())))
 
     # (c) 4 KiB records, runs of 64, a shared 64 KiB dictionary pending at each run's start.  The records are compressed
     # without the dictionary (no device dict encoder): the dictionary path is taken and consumed, bytes as plain.

@@ -685,5 +685,5 @@ extern "C" int zlz4_launch_compress_fast_using_dict(hipStream_t stream, const ui
     if ((uint64_t)dmax + max_in_len <= 65536u + 11u) ZLZ4_LAUNCH_DICT(uint16_t);
     else ZLZ4_LAUNCH_DICT(uint32_t);
 #undef ZLZ4_LAUNCH_DICT
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }

@@ -954,7 +954,7 @@ extern "C" int zlz4_launch_compress_fast(hipStream_t stream, const uint8_t *d_in
         else ZLZ4_LAUNCH_FAST(k_compress_fast, uint32_t, 0, wpw, wpw * 4096 * sizeof(uint32_t) + lds_pad);
     }
 #undef ZLZ4_LAUNCH_FAST
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 // Stream.compressFastContinue per block (see k_compress_fast, kSeed).  The same table widths as the launcher above, with
@@ -974,7 +974,7 @@ extern "C" int zlz4_launch_compress_fast_continue(hipStream_t stream, const uint
     else if (tune_tag != 0 && max_in_len <= (1u << 24)) ZLZ4_LAUNCH_SEEDED(uint32_t, 2);
     else ZLZ4_LAUNCH_SEEDED(uint32_t, 0);
 #undef ZLZ4_LAUNCH_SEEDED
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_load_dict(hipStream_t stream, const uint8_t *d_dict, const uint64_t *d_dict_off,
@@ -982,15 +982,15 @@ extern "C" int zlz4_launch_load_dict(hipStream_t stream, const uint8_t *d_dict, 
     if (ndicts == 0) return 0;
     hipLaunchKernelGGL(zlz4::k_load_dict, dim3(ndicts), dim3(256), 0, stream, d_dict, d_dict_off, d_dict_len, d_tables,
                        d_result, ndicts);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 #ifdef ZLZ4_STAMPS
 extern "C" int zlz4_debug_read_stamps(unsigned long long *out16, int reset) {
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_zlz4_stamps), 24 * sizeof(unsigned long long)) != hipSuccess) return -7;
+    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_zlz4_stamps), 24 * sizeof(unsigned long long)) != hipSuccess) return ZLZ4_ERR_DEVICE;
     if (reset) {
         unsigned long long z[24] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_zlz4_stamps), z, sizeof z) != hipSuccess) return -7;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_zlz4_stamps), z, sizeof z) != hipSuccess) return ZLZ4_ERR_DEVICE;
     }
     return 0;
 }

@@ -49,7 +49,7 @@
 #ifdef ZLZ4_STAMPS
 __device__ unsigned long long g_zlz4_hstamps[16];
 extern "C" int zlz4_debug_read_hstamps(unsigned long long *out4) {
-    return hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_zlz4_hstamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : -7;
+    return hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_zlz4_hstamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 #endif
 
@@ -1332,9 +1332,9 @@ struct HcRounds {
     int join() {
         for (uint32_t k = 0; side && k < 2u && k < round; k++)
             if (hipStreamWaitEvent(stream, side->emitted[k], 0) != hipSuccess) return fail();
-        return hipGetLastError() == hipSuccess ? 0 : -7;
+        return zlz4_launch_status();
     }
-    int fail(int rc = -7) { if (side) (void)hipStreamSynchronize(side->st); return rc; }
+    int fail(int rc = ZLZ4_ERR_DEVICE) { if (side) (void)hipStreamSynchronize(side->st); return rc; }
 };
 
 // blocks per chunk: the workspace stays around 6 GiB for big blocks, a chunk at 8192 blocks (3.5 GiB for 64 KiB blocks;

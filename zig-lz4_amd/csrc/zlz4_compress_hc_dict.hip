@@ -61,5 +61,5 @@ extern "C" int zlz4_launch_hc_dict_stage(hipStream_t stream, const uint8_t *d_in
                                          uint32_t max_in_len, uint32_t dmax) {
     hipLaunchKernelGGL(zlz4::k_hc_dict_stage, dim3(nblocks), dim3(256), 0, stream, d_in, d_in_off, d_in_len, d_dict, d_dict_off,
                        d_dict_len, d_v, v_stride, v_off, v_len, v_pair, blk0, nblocks, slot0, max_in_len, dmax);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }

@@ -628,14 +628,14 @@ extern "C" int zlz4_launch_hc_mid(hipStream_t stream, const uint8_t *d_in, const
                                   uint32_t nblocks, void *ws, uint32_t chunk, uint32_t max_in_len) {
     for (uint32_t b0 = 0; b0 < nblocks; b0 += chunk) {
         const uint32_t nb = nblocks - b0 < chunk ? nblocks - b0 : chunk;
-        if (hipMemsetAsync(ws, 0, zlz4_hc_mid_workspace_bytes(nb), stream) != hipSuccess) return -7;   // :725-726
+        if (hipMemsetAsync(ws, 0, zlz4_hc_mid_workspace_bytes(nb), stream) != hipSuccess) return ZLZ4_ERR_DEVICE;   // :725-726
         // blocks per wavefront: two walk in lock step (the probe loop re-converges every iteration, a match is handled by
         // the lanes that have one); 1 / 2 / 4 / 8: 124.7 / 106.2 / 133.6 / 153.7 ms on 16 384 blocks, 516 / 474 / 498 / 508 on 65 536
         static const uint32_t lanes = [] { const char *e = zlz4_tune_env("ZLZ4_MID_LANES"); const uint32_t v = e ? (uint32_t)atoi(e) : 2u; return v >= 1u && v <= 64u ? v : 2u; }();
         hipLaunchKernelGGL(zlz4::k_hc_mid_serial, dim3((nb + lanes - 1u) / lanes), dim3(lanes), 0, stream, d_in, d_in_off, d_in_len, d_out,
                            d_out_off, d_out_cap, d_result, static_cast<uint32_t *>(ws), b0, nb, max_in_len);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 // parse of one chunk whose K2 results are already in d_res (called from zlz4_compress_hc.hip's chunk loop)
@@ -652,7 +652,7 @@ extern "C" int zlz4_launch_hc_opt_parse(hipStream_t stream, const uint8_t *d_in,
         hipLaunchKernelGGL(zlz4::k_hc_opt_parse_wave, dim3(nb), dim3(64), 0, stream, d_in, d_in_off, d_in_len, d_out, d_out_off,
                            d_out_cap, d_result, static_cast<const uint32_t *>(d_res), res_stride,
                            static_cast<zlz4::OptEntry *>(d_opt), b0, nb, sufficient_len, max_in_len);
-        return hipGetLastError() == hipSuccess ? 0 : -7;
+        return zlz4_launch_status();
     }
     if (wide)
         hipLaunchKernelGGL(zlz4::k_hc_opt_parse<uint64_t>, dim3((nb + lanes - 1u) / lanes), dim3(lanes), 0, stream, d_in, d_in_off, d_in_len,
@@ -662,5 +662,5 @@ extern "C" int zlz4_launch_hc_opt_parse(hipStream_t stream, const uint8_t *d_in,
         hipLaunchKernelGGL(zlz4::k_hc_opt_parse<uint32_t>, dim3((nb + lanes - 1u) / lanes), dim3(lanes), 0, stream, d_in, d_in_off, d_in_len,
                            d_out, d_out_off, d_out_cap, d_result, static_cast<const uint32_t *>(d_res), res_stride,
                            static_cast<zlz4::OptEntry *>(d_opt), b0, nb, sufficient_len, max_in_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }

@@ -43,17 +43,6 @@ namespace zlz4 {
 __device__ __forceinline__ uint32_t ld16(const uint8_t *p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
 __device__ __forceinline__ uint64_t ld64u(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 
-// inclusive prefix sum over the 64 lanes (DPP: Hillis-Steele inside each row of 16, then row broadcasts)
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);    // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);    // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);    // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);    // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-    return x;
-}
-
 // kWrite == false: size pass (no stores) -- used by the frame decoder to learn every block's
 // decompressed size before placing the blocks (lz4f.decompressFrame accumulates dstPos serially).
 // kLaneCopy: short matches are moved four bytes per lane (batches that fill the chip); false = 16 bytes per sequence lane
@@ -768,115 +757,120 @@ __global__ __launch_bounds__(64) void k_decompress_lane(
 
 }  // namespace zlz4
 
+namespace {
+
 constexpr uint32_t kLaneCopyMinBlocks = 6144;   // (crossover measured between 4096 and 8192 blocks; the chip holds 8192 wavefronts)
+
+// an integer knob of the tuning build; `dflt` in the shipped library, which reads no environment
+long long tune_int(const char *name, long long dflt) { const char *e = zlz4_tune_env(name); return e ? atoll(e) : dflt; }
+
+// the arguments every k_decompress_safe build takes, but for min_phase_tokens (the launch shape's)
+struct SafeArgs {
+    const uint8_t *d_in; const uint64_t *d_in_off; const uint32_t *d_in_len;
+    uint8_t *d_out; const uint64_t *d_out_off; const uint32_t *d_out_cap;
+    int64_t *d_result; uint32_t nblocks;
+    const uint8_t *d_dict; const uint64_t *d_dict_off; const uint32_t *d_dict_len;
+};
+
+// How k_decompress_safe is launched: one wavefront per block, four per workgroup; from kLaneCopyMinBlocks blocks on (the
+// batch fills the chip) the lane-copy build with copy phases, below it 16 bytes per sequence lane.  `knobs`: the launcher
+// reads the tuning build's ZLZ4_DECOMP_WPW and ZLZ4_DECOMP_PHASE_MIN (zlz4_launch_decompress_safe and _using_dict); the
+// other launchers keep the fixed shape whatever the environment says.
+struct SafeShape {
+    uint32_t grid, threads, lds, min_phase_tokens;   // min_phase_tokens: tokens that must be left for another copy phase
+    bool lane_copy;                                  // to be worth its wait (0 in the size passes, which copy nothing)
+};
+SafeShape safe_shape(uint32_t nblocks, bool knobs, uint32_t min_phase_tokens = 3u) {
+    static const uint32_t wpw_env = [] { const uint32_t v = (uint32_t)tune_int("ZLZ4_DECOMP_WPW", 4);
+                                         return (v == 1u || v == 2u || v == 4u) ? v : 4u; }();
+    static const uint32_t phase_min_env = (uint32_t)tune_int("ZLZ4_DECOMP_PHASE_MIN", 3);
+    const uint32_t waves_per_wg = knobs ? wpw_env : 4u;
+    return {grid_of(nblocks, waves_per_wg), 64u * waves_per_wg, 0u, knobs ? phase_min_env : min_phase_tokens,
+            nblocks >= kLaneCopyMinBlocks};
+}
+
+template <bool kWrite, bool kLaneCopy, bool kPhases = kLaneCopy, bool kDict = false, bool kBound = false>
+int launch_safe(hipStream_t stream, const SafeShape &sh, const SafeArgs &a) {
+    hipLaunchKernelGGL((zlz4::k_decompress_safe<kWrite, kLaneCopy, kPhases, kDict, kBound>), dim3(sh.grid), dim3(sh.threads),
+                       sh.lds, stream, a.d_in, a.d_in_off, a.d_in_len, a.d_out, a.d_out_off, a.d_out_cap, a.d_result, a.nblocks,
+                       sh.min_phase_tokens, a.d_dict, a.d_dict_off, a.d_dict_len);
+    return zlz4_launch_status();
+}
+
+}  // namespace
+
 extern "C" int zlz4_launch_decompress_safe(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
                                            const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
                                            const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks) {
     if (nblocks == 0) return 0;
     // one wavefront per block (batch path) is the faster decoder at every batch size measured on MI355X; the
     // one-lane-per-block kernel stays available behind ZLZ4_DECOMP_LANE_MIN (tests/test_gpu_lane_decoder.py)
-    static const uint32_t lane_min = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_LANE_MIN"); return e ? (uint32_t)atoll(e) : 0xFFFFFFFFu; }();
+    static const uint32_t lane_min = (uint32_t)tune_int("ZLZ4_DECOMP_LANE_MIN", 0xFFFFFFFFll);
     if (nblocks >= lane_min) {
         // the kernel is latency-bound: with few blocks use fewer lanes per wavefront so that ~8192 wavefronts exist
-        static const uint32_t lanes_env = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_LANES"); return e ? (uint32_t)atoi(e) : 0u; }();
+        static const uint32_t lanes_env = (uint32_t)tune_int("ZLZ4_DECOMP_LANES", 0);
         // measured on MI355X (65 536 blocks): 16 or 32 active lanes per wavefront are ~5 % faster than 64
         uint32_t lanes = nblocks >= 524288u ? 64u : (nblocks >= 262144u ? 32u : 16u);
         if (lanes_env >= 1 && lanes_env <= 64) lanes = lanes_env;
-        static const uint32_t max_lanes = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_MAXLANES"); return e ? (uint32_t)atoll(e) : 0u; }();
+        static const uint32_t max_lanes = (uint32_t)tune_int("ZLZ4_DECOMP_MAXLANES", 0);
         uint32_t grid = (nblocks + lanes - 1u) / lanes;
         if (max_lanes && (uint64_t)grid * lanes > max_lanes) grid = (max_lanes + lanes - 1u) / lanes;
         hipLaunchKernelGGL(zlz4::k_decompress_lane, dim3(grid), dim3(lanes), 0, stream, d_in, d_in_off,
                            d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks);
-        return hipGetLastError() == hipSuccess ? 0 : -7;
+        return zlz4_launch_status();
     }
-    static const uint32_t waves_per_wg = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_WPW"); const uint32_t v = e ? (uint32_t)atoi(e) : 4u;
-                                              return (v == 1u || v == 2u || v == 4u) ? v : 4u; }();
-    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
-    // experiment knob: dynamic LDS per workgroup only to limit the number of resident wavefronts per CU
-    static const uint32_t dyn_lds = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_LDS"); return e ? (uint32_t)atoll(e) : 0u; }();
-    // short matches four bytes per lane once the batch fills the chip (see the kernel); ZLZ4_DECOMP_SHORT forces 0 / 32
-    static const int short_env = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_SHORT"); return e ? atoi(e) : -1; }();
-    const uint32_t short_max = short_env >= 0 ? (uint32_t)short_env : (nblocks >= kLaneCopyMinBlocks ? 32u : 0u);
-    // A/B switch for profiles/ (tuning build): the lane-copy decoder without copy phases
-    static const bool no_phases = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_PHASES"); return e && atoi(e) == 0; }();
-    // tokens that must be left for another copy phase to be worth its wait (ZLZ4_DECOMP_PHASE_MIN in the tuning build)
-    static const uint32_t min_phase_tokens = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_PHASE_MIN"); return e ? (uint32_t)atoi(e) : 3u; }();
-    if (short_max && no_phases)
-        hipLaunchKernelGGL((zlz4::k_decompress_safe<true, true, false>), dim3(grid), dim3(64 * waves_per_wg), dyn_lds, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
-                           nullptr, nullptr, nullptr);
-    else if (short_max)
-        hipLaunchKernelGGL((zlz4::k_decompress_safe<true, true>), dim3(grid), dim3(64 * waves_per_wg), dyn_lds, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
-                           nullptr, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((zlz4::k_decompress_safe<true, false>), dim3(grid), dim3(64 * waves_per_wg), dyn_lds, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
-                           nullptr, nullptr, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    SafeShape sh = safe_shape(nblocks, true);
+    // this launcher's own experiment knobs: dynamic LDS per workgroup only to limit the number of resident wavefronts per
+    // CU; ZLZ4_DECOMP_SHORT forces the lane copy off / on (0 / 32); ZLZ4_DECOMP_PHASES=0 is the lane copy without phases
+    static const uint32_t dyn_lds = (uint32_t)tune_int("ZLZ4_DECOMP_LDS", 0);
+    static const int short_env = (int)tune_int("ZLZ4_DECOMP_SHORT", -1);
+    static const bool no_phases = tune_int("ZLZ4_DECOMP_PHASES", 1) == 0;
+    sh.lds = dyn_lds;
+    if (short_env >= 0) sh.lane_copy = short_env != 0;
+    const SafeArgs a = {d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, nullptr, nullptr, nullptr};
+    if (sh.lane_copy && no_phases) return launch_safe<true, true, false>(stream, sh, a);
+    return sh.lane_copy ? launch_safe<true, true>(stream, sh, a) : launch_safe<true, false>(stream, sh, a);
 }
 
-// decompressSafeUsingDict over a batch: the grid and the build choice of zlz4_launch_decompress_safe (16 bytes per
-// sequence lane below kLaneCopyMinBlocks blocks, lane copy with phases from there on); block i reads the dictionary
-// d_dict[d_dict_off[i] .. + d_dict_len[i]) (any length; only its last 65536 bytes can be reached).  The tuning knobs of
-// the no-dict launcher (lane decoder, phases off, LDS) do not apply here.
+// decompressSafeUsingDict over a batch: block i reads the dictionary d_dict[d_dict_off[i] .. + d_dict_len[i]) (any length;
+// only its last 65536 bytes can be reached).  The no-dict launcher's own knobs (lane decoder, phases off, LDS) do not
+// apply here.
 extern "C" int zlz4_launch_decompress_safe_using_dict(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
                                                       const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
                                                       const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks,
                                                       const uint8_t *d_dict, const uint64_t *d_dict_off,
                                                       const uint32_t *d_dict_len) {
     if (nblocks == 0) return 0;
-    static const uint32_t waves_per_wg = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_WPW"); const uint32_t v = e ? (uint32_t)atoi(e) : 4u;
-                                              return (v == 1u || v == 2u || v == 4u) ? v : 4u; }();
-    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
-    static const uint32_t min_phase_tokens = [] { const char *e = zlz4_tune_env("ZLZ4_DECOMP_PHASE_MIN"); return e ? (uint32_t)atoi(e) : 3u; }();
-    if (nblocks >= kLaneCopyMinBlocks)
-        hipLaunchKernelGGL((zlz4::k_decompress_safe<true, true, true, true>), dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
-                           d_dict, d_dict_off, d_dict_len);
-    else
-        hipLaunchKernelGGL((zlz4::k_decompress_safe<true, false, false, true>), dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in,
-                           d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, min_phase_tokens,
-                           d_dict, d_dict_off, d_dict_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    const SafeShape sh = safe_shape(nblocks, true);
+    const SafeArgs a = {d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len};
+    return sh.lane_copy ? launch_safe<true, true, true, true>(stream, sh, a) : launch_safe<true, false, false, true>(stream, sh, a);
 }
 
-// StreamDecode builds (kBound): the grid and build choice of zlz4_launch_decompress_safe_using_dict.  d_dict_len holds
-// 2 * nblocks entries: the dictionary lengths (read only when with_dict), then one bound per block (k_decompress_safe).
-// with_dict = 0 runs the build without the dictionary path (d_dict / d_dict_off are then not read).
+// StreamDecode builds (kBound), fixed shape.  d_dict_len holds 2 * nblocks entries: the dictionary lengths (read only
+// when with_dict), then one bound per block (k_decompress_safe).  with_dict = 0 runs the build without the dictionary
+// path (d_dict / d_dict_off are then not read).
 extern "C" int zlz4_launch_decompress_safe_bound(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
                                                  const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
                                                  const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks,
                                                  const uint8_t *d_dict, const uint64_t *d_dict_off,
                                                  const uint32_t *d_dict_len, int with_dict) {
     if (nblocks == 0) return 0;
-    const uint32_t waves_per_wg = 4;
-    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
-    const uint32_t min_phase_tokens = 3;
-    const bool lane_copy = nblocks >= kLaneCopyMinBlocks;
-#define ZLZ4_BOUND_LAUNCH(LC, DICT)                                                                                      \
-    hipLaunchKernelGGL((zlz4::k_decompress_safe<true, LC, LC, DICT, true>), dim3(grid), dim3(64 * waves_per_wg), 0,      \
-                       stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks,                 \
-                       min_phase_tokens, d_dict, d_dict_off, d_dict_len)
-    if (with_dict) {
-        if (lane_copy) ZLZ4_BOUND_LAUNCH(true, true); else ZLZ4_BOUND_LAUNCH(false, true);
-    } else {
-        if (lane_copy) ZLZ4_BOUND_LAUNCH(true, false); else ZLZ4_BOUND_LAUNCH(false, false);
-    }
-#undef ZLZ4_BOUND_LAUNCH
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    const SafeShape sh = safe_shape(nblocks, false);
+    const SafeArgs a = {d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len};
+    if (with_dict)
+        return sh.lane_copy ? launch_safe<true, true, true, true, true>(stream, sh, a)
+                            : launch_safe<true, false, false, true, true>(stream, sh, a);
+    return sh.lane_copy ? launch_safe<true, true, true, false, true>(stream, sh, a)
+                        : launch_safe<true, false, false, false, true>(stream, sh, a);
 }
 
-// size pass: d_out may be null; d_out_off / d_out_cap still give (dummy offset 0, capacity) per block
+// size pass, fixed shape: no output buffer; d_out_off / d_out_cap still give (dummy offset 0, capacity) per block
 extern "C" int zlz4_launch_decompress_sizes(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
                                             const uint32_t *d_in_len, const uint64_t *d_out_off,
                                             const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks) {
     if (nblocks == 0) return 0;
-    const uint32_t waves_per_wg = 4;
-    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
-    hipLaunchKernelGGL((zlz4::k_decompress_safe<false, false>), dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in, d_in_off,
-                       d_in_len, (uint8_t *)nullptr, d_out_off, d_out_cap, d_result, nblocks, 0u, nullptr, nullptr, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    const SafeArgs a = {d_in, d_in_off, d_in_len, nullptr, d_out_off, d_out_cap, d_result, nblocks, nullptr, nullptr, nullptr};
+    return launch_safe<false, false>(stream, safe_shape(nblocks, false, 0u), a);
 }
 
 // the size pass of decompressSafeUsingDict: the kDict build without a byte written or a dictionary byte read (every
@@ -886,20 +880,16 @@ extern "C" int zlz4_launch_decompress_sizes_using_dict(hipStream_t stream, const
                                                        const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks,
                                                        const uint64_t *d_dict_off, const uint32_t *d_dict_len) {
     if (nblocks == 0) return 0;
-    const uint32_t waves_per_wg = 4;
-    const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
-    hipLaunchKernelGGL((zlz4::k_decompress_safe<false, false, false, true>), dim3(grid), dim3(64 * waves_per_wg), 0, stream,
-                       d_in, d_in_off, d_in_len, (uint8_t *)nullptr, d_out_off, d_out_cap, d_result, nblocks, 0u,
-                       (const uint8_t *)nullptr, d_dict_off, d_dict_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    const SafeArgs a = {d_in, d_in_off, d_in_len, nullptr, d_out_off, d_out_cap, d_result, nblocks, nullptr, d_dict_off, d_dict_len};
+    return launch_safe<false, false, false, true>(stream, safe_shape(nblocks, false, 0u), a);
 }
 
 #ifdef ZLZ4_STAMPS
 extern "C" int zlz4_debug_read_dstamps(unsigned long long *out16, int reset) {
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_zlz4_dstamps), 16 * sizeof(unsigned long long)) != hipSuccess) return -7;
+    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_zlz4_dstamps), 16 * sizeof(unsigned long long)) != hipSuccess) return ZLZ4_ERR_DEVICE;
     if (reset) {
         unsigned long long z[16] = {0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_zlz4_dstamps), z, sizeof z) != hipSuccess) return -7;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_zlz4_dstamps), z, sizeof z) != hipSuccess) return ZLZ4_ERR_DEVICE;
     }
     return 0;
 }

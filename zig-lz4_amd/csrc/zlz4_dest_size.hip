@@ -301,7 +301,7 @@ extern "C" int zlz4_launch_compress_dest_size(hipStream_t stream, const uint8_t 
         uint32_t *ws_cap = reinterpret_cast<uint32_t *>(ws + (uint64_t)nblocks * 16u);
         hipLaunchKernelGGL(zlz4::k_dest_size_prep, dim3((nblocks + 255u) / 256u), dim3(256), 0, stream, ws_off, ws_cap, slot,
                            nblocks);
-        if (hipGetLastError() != hipSuccess) return -7;
+        if (int rc = zlz4_launch_status()) return rc;
         d_slot_off = ws_off;
         d_slot_cap = ws_cap;
     }
@@ -312,5 +312,5 @@ extern "C" int zlz4_launch_compress_dest_size(hipStream_t stream, const uint8_t 
     // (b) the search and the output of every block
     hipLaunchKernelGGL(zlz4::k_dest_size_plan, dim3(nblocks), dim3(64), 0, stream, d_in, d_in_off, d_in_len, d_out,
                        d_out_off, d_out_cap, d_result, d_consumed, nblocks, max_in_len, ws_stream, slot, ws_res);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }

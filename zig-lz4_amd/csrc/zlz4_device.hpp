@@ -108,6 +108,117 @@ __device__ __forceinline__ void copy_bytes(uint8_t *dst, const uint8_t *src, uin
     if (t0 + lane < n && lane < 16u) dst[t0 + lane] = src[t0 + lane];
 }
 
+// inclusive prefix sum over the 64 lanes (DPP: Hillis-Steele inside each row of 16, then row broadcasts)
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);    // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);    // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);    // row_shr:4
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);    // row_shr:8
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
+    return x;
+}
+
+__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v); }
+__device__ __forceinline__ uint32_t byte_at(const uint8_t *p) { return rfl((uint32_t)*p); }   // wave-uniform address
+
+// decompressGeneric (src/lz4.zig:89-251) of one block by one wavefront, straight from the reference's loop: the serial
+// walk of the two decoders that cannot run a block per wavefront in parallel.  `out` is where the block's output starts,
+// `hist` the bytes in front of it that a match may reach (<= 65536).  :181-192 with dict.len = hist: CorruptedData iff
+// offset > op + hist; every other match is a copy to out + op, in the output from out + op - offset (overlap rule
+// included), its byte stores following the general path of k_decompress_safe.
+// kWrite false: the same walk without a byte written or read from the output (the size query).
+// kDict: the `hist` bytes are the tail of T ++ (the `inframe` bytes directly in front of `out`), T an external buffer that
+// ends at `tend`.  A match that starts more than `inframe` bytes in front of the block starts in T: its first bytes come
+// from tend - a (a = offset - op - inframe), it may end there or run across T's end into the bytes that follow it, from
+// where it is the in-output match at distance `offset`.
+// kBound: `lo` is a floor inside the output: a match at op with offset o is CorruptedData unless op - o >= lo (:181-185
+// without a dictionary; lo <= kBoundMax, so offset + lo cannot wrap).
+// Callers:
+//   k_bfl_decode (zlz4_frame_linked.hip, DESIGN.md sections 4.4c / 4.4d): block k of a linked frame at out = dst + pos,
+//     inframe = min(pos, 65536); <kWrite> with hist = inframe, <kWrite, true> with T the frame's dictionary tail of D
+//     bytes and hist = min(pos + D, 65536).
+//   k_sd_finish (zlz4_stream_decode.hip): a call re-decoded with its true entry state;
+//     <true, true> with a pending dictionary (lowPrefix = dst: inframe = 0, hist = its reachable length, tend = its end),
+//     <true, false, true> with lowPrefix = dst + lo and no dictionary (hist = 0).
+template <bool kWrite, bool kDict = false, bool kBound = false>
+__device__ int64_t decode_block_wave(const uint8_t *src, uint32_t iend, uint8_t *out, uint32_t oend, uint32_t hist,
+                                     uint32_t lane, const uint8_t *tend = nullptr, uint32_t inframe = 0, uint32_t lo = 0) {
+    if (iend == 0 || oend == 0) return 0;                              // :97-98
+    uint32_t ip = 0, op = 0;
+    for (;;) {
+        if (ip >= iend) break;                                         // :113
+        const uint32_t token = byte_at(src + ip++);                    // :116
+        uint32_t lit = token >> 4;
+        if (lit == 15u) {                                              // :123-131
+            for (;;) {
+                if (ip >= iend) return kErrCorrupted;
+                const uint32_t b = byte_at(src + ip++);
+                lit += b;
+                if (lit > 0xFFFF0000u) lit = 0xFFFF0000u;
+                if (b != 255u) break;
+            }
+        }
+        if (lit > 0) {                                                 // :134-144
+            if (lit > iend - ip) return kErrCorrupted;
+            if (lit > oend - op) return kErrOutputTooSmall;
+            if (kWrite) copy_bytes(out + op, src + ip, lit, lane);
+            ip += lit; op += lit;
+        }
+        if (ip >= iend) break;                                         // :146
+        if (iend - ip < 2u) return kErrCorrupted;                      // :149
+        const uint32_t offset = byte_at(src + ip) | (byte_at(src + ip + 1) << 8);
+        ip += 2;
+        if (offset == 0) return kErrCorrupted;                         // :154
+        uint32_t ml = token & 15u;
+        if (ml == 15u) {                                               // :160-168
+            for (;;) {
+                if (ip >= iend) return kErrCorrupted;
+                const uint32_t b = byte_at(src + ip++);
+                ml += b;
+                if (ml > 0xFFFF0000u) ml = 0xFFFF0000u;
+                if (b != 255u) break;
+            }
+        }
+        ml += kMinMatch;                                               // :171
+        if (ml > oend - op) return kErrOutputTooSmall;                 // :174
+        if (offset > op && offset - op > hist) return kErrCorrupted;   // :181-192: in front of the history
+        if constexpr (kBound) {
+            if (offset + lo > op) return kErrCorrupted;                // :183-185: below lowPrefix, no dictionary
+        }
+        if (kWrite) {                                                  // :195-248: out[op + k] = out[op - offset + k]
+            uint8_t *o = out + op;
+            uint32_t n = ml;
+            if constexpr (kDict) {
+                if (offset > op + inframe) {                           // :199-225: the part that lies in T comes first
+                    const uint32_t a = offset - op - inframe, n1 = a < n ? a : n;
+                    copy_bytes(o, tend - a, n1, lane);
+                    o += n1;
+                    n -= n1;
+                }
+            }
+            const uint8_t *m = o - offset;
+            if (n == 0) {
+                // (the match ended inside T)
+            } else if (offset >= n || offset >= 1024u) {
+                copy_bytes(o, m, n, lane);
+            } else {
+                // overlap (:235-241): what is made so far is copied again as a whole -- offset bytes, then 2 x, 4 x ... --
+                // each copy disjoint from its source, and `made` a multiple of offset until the last one
+                uint32_t made = 0;
+                while (made < n) {
+                    const uint32_t have = made + offset, left = n - made;
+                    const uint32_t n1 = have < left ? have : left;
+                    copy_bytes(o + made, m, n1, lane);
+                    made += n1;
+                }
+            }
+        }
+        op += ml;
+    }
+    return (int64_t)op;                                                // :250
+}
+
 // number of extension bytes the LZ4 length code needs for a value v >= 15 (token nibble saturated)
 __device__ __forceinline__ uint32_t ext_len_bytes(uint32_t v) { return v >= 15u ? 1u + (v - 15u) / 255u : 0u; }
 

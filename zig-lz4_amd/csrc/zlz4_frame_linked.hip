@@ -32,94 +32,6 @@ namespace {
 
 using namespace zlz4;
 
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v); }
-__device__ __forceinline__ uint32_t byte_at(const uint8_t *p) { return rfl((uint32_t)*p); }   // wave-uniform address
-
-// decompressGeneric (src/lz4.zig:89-251) of one block by one wavefront, after decode_wave of zlz4_stream_decode.hip.
-// `out` is where the block's output starts, `hist` the bytes of the same frame that lie directly in front of it and may
-// be referenced (<= 65536).  :181-192 with dict.len = hist: CorruptedData iff offset > op + hist; every other match is a
-// plain copy from out + op - offset, whether it starts in the history, spans its end or lies in the block.
-// kWrite false: the same walk without a byte written or read from the output (the size query).
-// kDict (dictionary frames): the history is the tail of T ++ dst[0..pos), T the frame's dictionary
-// tail of D bytes that ends at `tend`.  `hist` then counts min(pos + D, 65536) and `inframe` = min(pos, 65536) of it lie
-// directly in front of `out`; the rest is T.  A match that starts more than `inframe` bytes in front of the block starts
-// in T: its first bytes come from tend - a (a = offset - op - inframe), it may end there or run across T's end into the
-// frame's first output byte, from where it is the in-output match at distance `offset` (overlap rule included).
-template <bool kWrite, bool kDict = false>
-__device__ int64_t decode_linked_block(const uint8_t *src, uint32_t iend, uint8_t *out, uint32_t oend, uint32_t hist,
-                                       uint32_t lane, const uint8_t *tend = nullptr, uint32_t inframe = 0) {
-    if (iend == 0 || oend == 0) return 0;                              // :97-98
-    uint32_t ip = 0, op = 0;
-    for (;;) {
-        if (ip >= iend) break;                                         // :113
-        const uint32_t token = byte_at(src + ip++);                    // :116
-        uint32_t lit = token >> 4;
-        if (lit == 15u) {                                              // :123-131
-            for (;;) {
-                if (ip >= iend) return kErrCorrupted;
-                const uint32_t b = byte_at(src + ip++);
-                lit += b;
-                if (lit > 0xFFFF0000u) lit = 0xFFFF0000u;
-                if (b != 255u) break;
-            }
-        }
-        if (lit > 0) {                                                 // :134-144
-            if (lit > iend - ip) return kErrCorrupted;
-            if (lit > oend - op) return kErrOutputTooSmall;
-            if (kWrite) copy_bytes(out + op, src + ip, lit, lane);
-            ip += lit; op += lit;
-        }
-        if (ip >= iend) break;                                         // :146
-        if (iend - ip < 2u) return kErrCorrupted;                      // :149
-        const uint32_t offset = byte_at(src + ip) | (byte_at(src + ip + 1) << 8);
-        ip += 2;
-        if (offset == 0) return kErrCorrupted;                         // :154
-        uint32_t ml = token & 15u;
-        if (ml == 15u) {                                               // :160-168
-            for (;;) {
-                if (ip >= iend) return kErrCorrupted;
-                const uint32_t b = byte_at(src + ip++);
-                ml += b;
-                if (ml > 0xFFFF0000u) ml = 0xFFFF0000u;
-                if (b != 255u) break;
-            }
-        }
-        ml += kMinMatch;                                               // :171
-        if (ml > oend - op) return kErrOutputTooSmall;                 // :174
-        if (offset > op && offset - op > hist) return kErrCorrupted;   // :181-192: in front of the history
-        if (kWrite) {                                                  // :195-248: out[op + k] = out[op - offset + k]
-            uint8_t *o = out + op;
-            uint32_t n = ml;
-            if constexpr (kDict) {
-                if (offset > op + inframe) {                           // :199-225: the part that lies in T comes first
-                    const uint32_t a = offset - op - inframe, n1 = a < n ? a : n;
-                    copy_bytes(o, tend - a, n1, lane);
-                    o += n1;
-                    n -= n1;
-                }
-            }
-            const uint8_t *m = o - offset;
-            if (n == 0) {
-                // (the match ended inside T)
-            } else if (offset >= n || offset >= 1024u) {
-                copy_bytes(o, m, n, lane);
-            } else {
-                // overlap (:235-241): what is made so far is copied again as a whole -- offset bytes, then 2 x, 4 x ... --
-                // each copy disjoint from its source
-                uint32_t made = 0;
-                while (made < n) {
-                    const uint32_t have = made + offset, left = n - made;
-                    const uint32_t n1 = have < left ? have : left;
-                    copy_bytes(o + made, m, n1, lane);
-                    made += n1;
-                }
-            }
-        }
-        op += ml;
-    }
-    return (int64_t)op;                                                // :250
-}
-
 // One wavefront per linked-declared frame, four per workgroup: src/lz4f.zig:563-621 in block order with the history-aware
 // decode; the error order is k_bfd_plan's (:591, :596, a stored block's DstMaxSizeTooSmall, :611), then the walk's error.
 // kWrite: decodes into the frame's slot and leaves F.total / F.err for k_bfd_finish.  !kWrite: a destination that is
@@ -170,7 +82,7 @@ __global__ __launch_bounds__(256) void k_bfl_decode(BFrame *__restrict__ fr, uin
             const uint32_t oend = rem < 0xFFFFFFFFull ? (uint32_t)rem : 0xFFFFFFFFu;
             const uint32_t inframe = pos < 65536u ? (uint32_t)pos : 65536u;
             const uint32_t hist = inframe + D < 65536u ? inframe + D : 65536u;
-            const int64_t r = decode_linked_block<kWrite, kDict>(p, len, kWrite ? out + pos : nullptr, oend, hist, lane, tend,
+            const int64_t r = decode_block_wave<kWrite, kDict>(p, len, kWrite ? out + pos : nullptr, oend, hist, lane, tend,
                                                                  inframe);
             if (r < 0) { err = ZLZ4F_ERR_DECOMPRESSION_FAILED; break; }             // :611
             pos += (uint64_t)r;
@@ -369,18 +281,13 @@ __global__ void k_bfcd_merge(const uint32_t *__restrict__ len_b, const int64_t *
         if (len_b[i] != 0) csize[i] = csize_b[i];
 }
 
-inline uint32_t grid_of(uint64_t items, uint32_t threads, uint32_t cap = 0xFFFFFFFFu) {
-    const uint64_t g = (items + threads - 1) / threads;
-    return g == 0 ? 1u : (g > cap ? cap : (uint32_t)g);
-}
-
 }  // namespace
 
-// `frames` is the pipeline's BFrame array.  All launchers: 0, or -7 when a launch fails.
+// `frames` is the pipeline's BFrame array.  All launchers: 0, or ZLZ4_ERR_DEVICE when a launch fails.
 extern "C" int zlz4_launch_bfl_save(hipStream_t st, const void *frames, uint32_t nframes, int64_t *walk_err) {
     hipLaunchKernelGGL(k_bfl_save, dim3(grid_of(nframes, 256)), dim3(256), 0, st, static_cast<const BFrame *>(frames), nframes,
                        walk_err);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfl_mask(hipStream_t st, const void *frames, const uint32_t *fidx, uint32_t max_blocks,
@@ -388,7 +295,7 @@ extern "C" int zlz4_launch_bfl_mask(hipStream_t st, const void *frames, const ui
     if (max_blocks == 0) return 0;
     hipLaunchKernelGGL(k_bfl_mask, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
                        static_cast<const BFrame *>(frames), fidx, max_blocks, cap, len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 // write != 0: the decode (F.total / F.err); write == 0: the size query (d_size receives the frame's result)
@@ -405,7 +312,7 @@ extern "C" int zlz4_launch_bfl_decode(hipStream_t st, int write, void *frames, u
     else
         hipLaunchKernelGGL(k_bfl_decode<false>, grid, block, 0, st, fr, nframes, max_blocks, src, data_off, data_len, flags,
                            cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size, nullptr, nullptr, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 // the same with a dictionary per frame: fd_end / fd_len are k_bfdd_frame's
@@ -423,7 +330,7 @@ extern "C" int zlz4_launch_bfl_decode_dict(hipStream_t st, int write, void *fram
     else
         hipLaunchKernelGGL((k_bfl_decode<false, true>), grid, block, 0, st, fr, nframes, max_blocks, src, data_off, data_len,
                            flags, cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size, dict, fd_end, fd_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfdd_frame(hipStream_t st, void *frames, uint32_t nframes, const uint64_t *dict_off,
@@ -431,7 +338,7 @@ extern "C" int zlz4_launch_bfdd_frame(hipStream_t st, void *frames, uint32_t nfr
                                       uint32_t *fd_len) {
     hipLaunchKernelGGL(k_bfdd_frame, dim3(grid_of(nframes, 256)), dim3(256), 0, st, static_cast<BFrame *>(frames), nframes,
                        dict_off, dict_len, ndicts, dict_idx, fd_end, fd_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfdd_entry(hipStream_t st, const void *frames, const uint32_t *fidx, uint32_t max_blocks,
@@ -439,7 +346,7 @@ extern "C" int zlz4_launch_bfdd_entry(hipStream_t st, const void *frames, const 
     if (max_blocks == 0) return 0;
     hipLaunchKernelGGL(k_bfdd_entry, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
                        static_cast<const BFrame *>(frames), fidx, max_blocks, fd_end, fd_len, e_off, e_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfdd_mask(hipStream_t st, const void *frames, const uint32_t *fidx, uint32_t max_blocks,
@@ -447,7 +354,7 @@ extern "C" int zlz4_launch_bfdd_mask(hipStream_t st, const void *frames, const u
     if (max_blocks == 0) return 0;
     hipLaunchKernelGGL(k_bfdd_mask, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
                        static_cast<const BFrame *>(frames), fidx, max_blocks, cap, len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfcd_pre(hipStream_t st, void *frames, uint32_t nframes, const uint64_t *src_len,
@@ -455,7 +362,7 @@ extern "C" int zlz4_launch_bfcd_pre(hipStream_t st, void *frames, uint32_t nfram
                                     uint32_t max_dict_len) {
     hipLaunchKernelGGL(k_bfcd_pre, dim3(grid_of(nframes, 256)), dim3(256), 0, st, static_cast<BFrame *>(frames), nframes,
                        src_len, dict_len, ndicts, dict_idx, max_src_len, max_dict_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfcd_desc(hipStream_t st, const void *frames, uint32_t nframes, uint32_t max_blocks, int with_b,
@@ -463,11 +370,11 @@ extern "C" int zlz4_launch_bfcd_desc(hipStream_t st, const void *frames, uint32_
                                      const uint32_t *in_len, uint32_t *len_a, uint32_t *len_b, uint64_t *a_off,
                                      uint32_t *a_len, uint32_t *a_tix) {
     if (max_blocks == 0) return 0;
-    if (with_b && !len_b) return -5;
+    if (with_b && !len_b) return ZLZ4_ERR_INVALID_STATE;
     hipLaunchKernelGGL(k_bfcd_desc, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
                        static_cast<const BFrame *>(frames), nframes, max_blocks, with_b != 0, dict_off, dict_len, dict_idx,
                        in_len, len_a, len_b, a_off, a_len, a_tix);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfcd_merge(hipStream_t st, const uint32_t *len_b, const int64_t *csize_b, int64_t *csize,
@@ -475,7 +382,7 @@ extern "C" int zlz4_launch_bfcd_merge(hipStream_t st, const uint32_t *len_b, con
     if (max_blocks == 0) return 0;
     hipLaunchKernelGGL(k_bfcd_merge, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st, len_b, csize_b, csize,
                        max_blocks);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfl_dict_desc(hipStream_t st, const void *frames, uint32_t nframes, uint32_t max_blocks,
@@ -484,7 +391,7 @@ extern "C" int zlz4_launch_bfl_dict_desc(hipStream_t st, const void *frames, uin
     if (max_blocks == 0) return 0;
     hipLaunchKernelGGL(k_bfl_dict_desc, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
                        static_cast<const BFrame *>(frames), nframes, max_blocks, src_off, in_off, in_len, dict_off, dict_len);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 extern "C" int zlz4_launch_bfl_hc_desc(hipStream_t st, const void *frames, uint32_t nframes, uint32_t max_blocks,
@@ -493,5 +400,5 @@ extern "C" int zlz4_launch_bfl_hc_desc(hipStream_t st, const void *frames, uint3
     if (max_blocks == 0) return 0;
     hipLaunchKernelGGL(k_bfl_hc_desc, dim3(grid_of(max_blocks, 256, 4096)), dim3(256), 0, st,
                        static_cast<const BFrame *>(frames), nframes, max_blocks, src_off, in_off, in_len, v_off, v_len, v_pair);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }

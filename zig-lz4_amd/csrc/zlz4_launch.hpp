@@ -9,6 +9,17 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/zlz4_amd.h"
+
+// how a launcher ends: 0, or ZLZ4_ERR_DEVICE when the launch (or an earlier asynchronous call) failed
+inline int zlz4_launch_status() { return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE; }
+
+// workgroups of `threads` items that cover `items` (at least one, at most `cap`)
+inline uint32_t grid_of(uint64_t items, uint32_t threads, uint32_t cap = 0xFFFFFFFFu) {
+    const uint64_t g = (items + threads - 1) / threads;
+    return g == 0 ? 1u : (g > cap ? cap : (uint32_t)g);
+}
+
 extern "C" {
 
 // zlz4_compress_fast.hip

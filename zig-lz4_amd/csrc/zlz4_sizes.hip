@@ -27,17 +27,6 @@ namespace {
 
 constexpr uint32_t kSizeCap = 0xFFFFFFFFu;
 
-// inclusive prefix sum over the 64 lanes (DPP: Hillis-Steele inside each row of 16, then row broadcasts)
-__device__ __forceinline__ uint32_t size_incl_scan(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);    // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);    // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);    // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);    // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-    return x;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_decompressed_size(
@@ -206,7 +195,7 @@ __global__ __launch_bounds__(256) void k_decompressed_size(
                 if (R != 0) {
                     const bool real0 = (R >> lane) & 1ull;
                     const uint32_t x = real0 ? ol : 0u;
-                    const uint32_t relv = size_incl_scan(x) - x;    // output offset of the sequence inside the batch
+                    const uint32_t relv = wave_incl_scan(x) - x;    // output offset of the sequence inside the batch
                     const uint32_t pr = op + relv + lit;
                     const uint64_t vm = ballot(real0 && off > pr && off - pr > dlen);
                     if (vm != 0) {
@@ -329,7 +318,7 @@ extern "C" int zlz4_launch_decompressed_size(hipStream_t stream, const uint8_t *
     const uint32_t grid = (nblocks + waves_per_wg - 1) / waves_per_wg;
     hipLaunchKernelGGL(zlz4::k_decompressed_size, dim3(grid), dim3(64 * waves_per_wg), 0, stream, d_in, d_in_off, d_in_len,
                        d_dict_len, d_size, nblocks);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
 
 // align: a power of two >= 1 (the caller checks).  n == 0 stores a total of 0.
@@ -337,5 +326,5 @@ extern "C" int zlz4_launch_plan_outputs(hipStream_t stream, const int64_t *d_siz
                                         uint64_t *d_out_off, uint32_t *d_out_cap, uint64_t *d_total) {
     hipLaunchKernelGGL(zlz4::k_plan_outputs, dim3(1), dim3(1024), 0, stream, d_size, n, (uint64_t)align, d_out_off,
                        d_out_cap, d_total);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }

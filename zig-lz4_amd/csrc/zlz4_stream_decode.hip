@@ -16,7 +16,7 @@
 // (from the results so far) differs from the key they ran with; k_sd_plan<kCheck> flags the runs that still differ
 // (or whose look-back ran past kLookback calls) and marks, per run, its last success and whether a success had a
 // mode-B entry; k_sd_finish walks the flagged runs one call after another (one wavefront per run, re-decoding with
-// decode_wave below where needed) and writes every run's final state.
+// decode_block_wave of zlz4_device.hpp where needed) and writes every run's final state.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -149,79 +149,6 @@ __global__ __launch_bounds__(256) void k_sd_plan(uint8_t *d_out, const uint64_t 
     if (hb && !(prev_hb && prev_s == s)) atomicOr(&w.run_flags[s], (uint32_t)kRunHadB);
 }
 
-// decompressGeneric (src/lz4.zig:89-251) by one wavefront, straight from the reference's loop: lowPrefix = dst + lo and
-// no dictionary, or lowPrefix = dst and the dictionary ending at dend (dlen = its reachable length, <= 65536).  The slow
-// path of k_sd_finish only; the byte stores of copies follow the general path of k_decompress_safe.
-__device__ int64_t decode_wave(const uint8_t *src, uint32_t iend, uint8_t *dst, uint32_t oend, uint32_t lo,
-                               const uint8_t *dend, uint32_t dlen, uint32_t lane) {
-    if (iend == 0 || oend == 0) return 0;                              // :97-98
-    uint32_t ip = 0, op = 0;
-    for (;;) {
-        if (ip >= iend) break;                                         // :113
-        const uint32_t token = src[ip++];                              // :116
-        uint32_t lit = token >> 4;
-        if (lit == 15u) {                                              // :123-131
-            for (;;) {
-                if (ip >= iend) return kErrCorrupted;
-                const uint32_t b = src[ip++];
-                lit += b;
-                if (lit > 0xFFFF0000u) lit = 0xFFFF0000u;
-                if (b != 255u) break;
-            }
-        }
-        if (lit > 0) {                                                 // :134-144
-            if (lit > iend - ip) return kErrCorrupted;
-            if (lit > oend - op) return kErrOutputTooSmall;
-            copy_bytes(dst + op, src + ip, lit, lane);
-            ip += lit; op += lit;
-        }
-        if (ip >= iend) break;                                         // :146
-        if (iend - ip < 2u) return kErrCorrupted;                      // :149
-        const uint32_t offset = (uint32_t)src[ip] | ((uint32_t)src[ip + 1] << 8);
-        ip += 2;
-        if (offset == 0) return kErrCorrupted;                         // :154
-        uint32_t ml = token & 15u;
-        if (ml == 15u) {                                               // :160-168
-            for (;;) {
-                if (ip >= iend) return kErrCorrupted;
-                const uint32_t b = src[ip++];
-                ml += b;
-                if (ml > 0xFFFF0000u) ml = 0xFFFF0000u;
-                if (b != 255u) break;
-            }
-        }
-        ml += kMinMatch;                                               // :171
-        if (ml > oend - op) return kErrOutputTooSmall;                 // :174
-        if (offset > op) {                                             // :181-192
-            if (!dend || offset - op > dlen) return kErrCorrupted;
-            const uint32_t a = offset - op, n1 = a < ml ? a : ml;      // :195-225: dictionary part first
-            copy_bytes(dst + op, dend - a, n1, lane);
-            op += n1; ml -= n1;
-            if (ml == 0) continue;
-        } else if (offset + lo > op) {
-            return kErrCorrupted;                                      // below lowPrefix, no dictionary (:183-185)
-        }
-        // :227-248 (and the rest of a spanning match, an in-block match at op == offset): out[op+k] = out[op-offset+k]
-        uint8_t *o = dst + op;
-        const uint8_t *m = o - offset;
-        if (offset >= ml || offset >= 1024u) {
-            copy_bytes(o, m, ml, lane);
-        } else {
-            // overlap (:235-241): what is made so far is copied again as a whole -- offset bytes, then 2 x, 4 x ... --
-            // each copy disjoint from its source, and `made` a multiple of offset until the last one
-            uint32_t made = 0;
-            while (made < ml) {
-                const uint32_t have = made + offset, left = ml - made;
-                const uint32_t n1 = have < left ? have : left;
-                copy_bytes(o + made, m, n1, lane);
-                made += n1;
-            }
-        }
-        op += ml;
-    }
-    return (int64_t)op;                                                // :250
-}
-
 // One wavefront per run: the final state; a run flagged by k_sd_plan<kCheck> is first walked call by call with the
 // reference's state machine, re-decoding every call whose true key differs from the one its result was decoded with.
 __global__ __launch_bounds__(64) void k_sd_finish(const uint8_t *d_in, const uint64_t *__restrict__ d_in_off,
@@ -261,11 +188,16 @@ __global__ __launch_bounds__(64) void k_sd_finish(const uint8_t *d_in, const uin
                     if (key == kKeyInvalid) {
                         r = kErrInvalidState;
                     } else {
-                        const bool dict = key == kKeyDict;
-                        const uint32_t dlen = dict ? (uint32_t)(st.dict_len < 65536u ? st.dict_len : 65536u) : 0u;
-                        r = decode_wave(d_in + d_in_off[j], rfl(d_in_len[j]), (uint8_t *)(uintptr_t)dst, rfl(d_out_cap[j]),
-                                        dict ? 0u : (uint32_t)key,
-                                        dict ? (const uint8_t *)(uintptr_t)(st.dict + st.dict_len) : nullptr, dlen, lane);
+                        const uint8_t *src = d_in + d_in_off[j];
+                        uint8_t *out = (uint8_t *)(uintptr_t)dst;
+                        const uint32_t iend = rfl(d_in_len[j]), oend = rfl(d_out_cap[j]);
+                        if (key == kKeyDict) {                        // lowPrefix = dst, the dictionary's reachable tail
+                            const uint32_t dlen = (uint32_t)(st.dict_len < 65536u ? st.dict_len : 65536u);
+                            r = decode_block_wave<true, true>(src, iend, out, oend, dlen, lane,
+                                                              (const uint8_t *)(uintptr_t)(st.dict + st.dict_len), 0u);
+                        } else {                                      // lowPrefix = dst + key, no dictionary
+                            r = decode_block_wave<true, false, true>(src, iend, out, oend, 0u, lane, nullptr, 0u, (uint32_t)key);
+                        }
                     }
                     if (lane == 0) { d_result[j] = r; w.key[j] = key; }
                 }
@@ -308,7 +240,7 @@ extern "C" int zlz4_launch_stream_decode(hipStream_t stream, const uint8_t *d_in
     w.bl = reinterpret_cast<uint32_t *>(p); p += align16(8 * n);
     w.run_last = reinterpret_cast<uint32_t *>(p); p += align16(4 * (size_t)nstreams);
     w.run_flags = reinterpret_cast<uint32_t *>(p);
-    if (hipMemsetAsync(w.run_last, 0, align16(4 * (size_t)nstreams) * 2, stream) != hipSuccess) return -7;
+    if (hipMemsetAsync(w.run_last, 0, align16(4 * (size_t)nstreams) * 2, stream) != hipSuccess) return ZLZ4_ERR_DEVICE;
     const uint32_t pgrid = (nblocks + 255u) / 256u;
     auto decode = [&]() {
         int rc = zlz4_launch_decompress_safe_bound(stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result,
@@ -321,19 +253,19 @@ extern "C" int zlz4_launch_stream_decode(hipStream_t stream, const uint8_t *d_in
     if (nblocks) {
         hipLaunchKernelGGL(k_sd_plan<kSpec>, dim3(pgrid), dim3(256), 0, stream, d_out, d_out_off, d_run_start, d_state,
                            d_result, nblocks, nstreams, w);
-        if (hipGetLastError() != hipSuccess) return -7;
+        if (int rc = zlz4_launch_status()) return rc;
         if (int rc = decode()) return rc;
         for (int round = 0; round < 2; round++) {
             hipLaunchKernelGGL(k_sd_plan<kRedo>, dim3(pgrid), dim3(256), 0, stream, d_out, d_out_off, d_run_start,
                                d_state, d_result, nblocks, nstreams, w);
-            if (hipGetLastError() != hipSuccess) return -7;
+            if (int rc = zlz4_launch_status()) return rc;
             if (int rc = decode()) return rc;
         }
         hipLaunchKernelGGL(k_sd_plan<kCheck>, dim3(pgrid), dim3(256), 0, stream, d_out, d_out_off, d_run_start, d_state,
                            d_result, nblocks, nstreams, w);
-        if (hipGetLastError() != hipSuccess) return -7;
+        if (int rc = zlz4_launch_status()) return rc;
     }
     hipLaunchKernelGGL(k_sd_finish, dim3(nstreams), dim3(64), 0, stream, d_in, d_in_off, d_in_len, d_out, d_out_off,
                        d_out_cap, d_run_start, d_state, d_result, nstreams, w);
-    return hipGetLastError() == hipSuccess ? 0 : -7;
+    return zlz4_launch_status();
 }
