@@ -48,15 +48,16 @@ __device__ __forceinline__ uint64_t ld64u(const uint8_t *p) { uint64_t v; __buil
 // kLaneCopy: short matches are moved four bytes per lane (batches that fill the chip); false = 16 bytes per sequence lane
 // for every match (few blocks: the shorter latency chain)
 // (the decoder is bound by vector issue and lives on occupancy: eight wavefronts per SIMD = at most 64 VGPRs.  The copy
-//  phases brought the lane-copy build to 66 and the seventh-of-eight cost D-text 7 %; it is back at 62 since the lane
-//  copy keeps two rounds of registers instead of three.)
+//  phases brought the lane-copy build to 66 and the seventh-of-eight cost D-text 7 %; it went back to 62 when the lane
+//  copy kept two rounds of registers instead of three, and is at 54 with the wave-uniform lane masks.)
 // kDict: decompressSafeUsingDict (src/lz4.zig:960-969): a match whose offset reaches in front of dst reads the virtual
 // buffer dict ++ dst (:181-225).  Only the last min(dict.len, 65536) bytes can be reached (offset <= 65535), so dend /
 // dlen below are that tail; the dictionary is read-only and must not overlap dst.  The dictionary arguments come last so
 // that the kernel-argument layout of the no-dict instantiations is unchanged.  The dict instantiations are held to eight
 // wavefronts per SIMD (64 VGPRs; the lane-copy build would take 67 and spills two to scratch instead): measured on
 // MI355X, 7 -> 8 wavefronts beat the spill on every case of tools/time_dict_decompress.py (configs[1] with an empty
-// dictionary 10.96 -> 10.46 ms); the no-dict instantiations are compiled exactly as before.
+// dictionary 10.96 -> 10.46 ms); the no-dict instantiations are compiled exactly as before.  (With the wave-uniform lane
+// masks the lane-copy dict build takes 58 and spills nothing; the attribute stays as the bound.)
 // kBound: StreamDecode.decompressSafeContinue (src/lz4.zig:912-939) with a previous output at prefix: a match at output
 // position op with offset o is CorruptedData unless op - o >= lo = max(0, prefix - dst) (:181-185 without a dictionary,
 // then :231), tested where the other builds test offset > op.  lo is d_dict_len[nblocks + blk] (the arguments stay
@@ -131,7 +132,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                 //  spends vector instructions on 64-bit pointer arithmetic)
                 if (pml >= 16u) {
                     st128(dst + po, pa);
-                    for (uint32_t k = 16u; k + 16u <= pml; k += 16u)
+                    // (a token lane only, and only past 96 bytes: the lanes above it hold bytes [16, 80) -- copy_side)
+                    for (uint32_t k = 80u; k + 16u <= pml; k += 16u)
                         st128(dst + (po + k), ld128(kDict && po < pof ? dend - (pof - po) + k : dst + (po - pof + k)));
                     st128(dst + (po + pml - 16u), pb);
                 } else if (pml >= 8u) {
@@ -295,7 +297,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                 bool viol_err = false;                              // :181-186 / :231 offset > op: never copied here
                 const uint32_t op0 = op;                            // output position of the batch
                 if (R != 0) {
-                    const bool real0 = (R >> lane) & 1ull;
+                    const bool real0 = in_mask(R);
                     const uint32_t x = real0 ? ol : 0u;
                     relv = wave_incl_scan(x) - x;                   // output offset of the sequence inside the batch
                     // :181-186 / :231 offset > op, and (copy pass) a match source that reaches into this batch's
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                     }
                     bool viol = viol_err;
                     if (kWrite) viol = viol || (off + lit0 < relv + ol);
-                    const uint64_t vm = ballot(real0 && viol);
+                    const uint64_t vm = R & ballot(viol);
                     if (vm != 0) {
                         const uint32_t fb = first_lane(vm);
                         R &= (1ull << fb) - 1ull;
@@ -336,11 +338,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                 auto cap_short = [&]() {
                     if constexpr (kWrite && kLaneCopy) {
                         if ((uint32_t)__popcll(R) <= 16u) return;    // (scalar: the usual batch has 8 tokens)
-                        const bool sh = ((R >> lane) & 1ull) && ml <= short_max;
-                        const uint64_t S = ballot(sh);
+                        const uint64_t S = R & ballot(ml <= short_max);
                         if ((uint32_t)__popcll(S) > 16u) {
-                            const uint32_t rk = (uint32_t)__popcll(S & ((1ull << lane) - 1ull));
-                            const uint32_t fb = first_lane(ballot(sh && rk == 16u));
+                            const uint32_t fb = first_lane(S & ballot(lane_rank(S) == 16u));
                             R &= (1ull << fb) - 1ull;
                             T = rdlane(relv, fb);
                             pos = fb;
@@ -364,34 +364,54 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                     // matches (:244): source entirely older than this phase's first match, no overlap.  One or two
                     // 16-byte loads per sequence lane; the data is stored by flush_pending() after the next batch
                     // has been parsed (or when the next phase begins).
-                    const bool real = (R >> lane) & 1ull;
-                    const uint32_t po_t = op0 + relv + lit, mo_t = po_t - off;      // (off <= 65535, ml <= 273)
+                    // (the masks are wave-uniform: a lane's role is its bit, ballots of single compares combined in scalar)
+                    const uint64_t Sm = R & ballot(ml <= short_max), Lm = R & ~Sm;   // short: the lane copy; long: 16-byte pieces
+                    const uint32_t po_t = op0 + relv + lit;                         // (off <= 65535, ml <= 273)
                     // short_max = 32 when the chip is full (the address path is what bounds the kernel then), 0 with few
                     // blocks (one wavefront per SIMD: the permutes are four more dependent steps of a latency chain, and
                     // 16 bytes per sequence lane is the shorter chain: 38.3 against 43.4 ms on 1024 x 4 MiB)
-                    [[maybe_unused]] const bool shortm = real && ml <= short_max;
-                    if (!kLaneCopy || ballot(real && ml > short_max)) {   // long matches: 16-byte pieces per sequence lane
-                        if (real && ml > short_max) {
-                            if constexpr (kDict) {
-                                // one load per piece from a per-lane address: the source is wholly in the dictionary
-                                // (see viol_err) or wholly in dst (two exec-masked loads would write pa twice in flight)
-                                const uint64_t ma = off > po_t ? (uint64_t)(uintptr_t)dbase + (mo_t + 65536u)
-                                                               : (uint64_t)(uintptr_t)dst + mo_t;
-                                asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(pa) : "v"(ma) : "memory");
-                                if (ml >= 16u)
-                                    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(pb) : "v"(ma + (ml - 16u)) : "memory");
-                            } else {
-                                asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pa) : "v"(mo_t), "s"(dst) : "memory");
-                                if (ml >= 16u)
-                                    asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pb) : "v"(mo_t + ml - 16u), "s"(dst) : "memory");
-                            }
-                            pml = ml; po = po_t; pof = off;
+                    [[maybe_unused]] const bool shortm = in_mask(Sm);
+                    // long matches: 16-byte pieces.  A sequence takes >= 3 window bytes, so the two lanes above a token lane t
+                    // are never token lanes and their pa / pb are idle: they hold the middle of a match of more than 32
+                    // bytes, and no match of <= 96 bytes needs a blocking load -> store loop in flush_pending().
+                    //   lane t: pa = bytes [0, 16), pb = the last 16;  t + 1 (ml > 32): [16, 48);  t + 2 (ml > 64): [48, 80)
+                    // A helper with fewer than 32 bytes to cover ends 16 bytes before the match does (the token lane's pb
+                    // takes over) but holds at least 16, so its two pieces overlap like pa / pb of a 16..32-byte match and
+                    // flush_pending() stores all three roles alike.  The helpers read the token's (po_t, off, ml) one / two
+                    // lanes down (DPP wave_shr:1 crosses the 16-lane rows); a lane's role is its bit of a wave-uniform mask.
+                    // (The shifts run in every batch: behind a wave-uniform `Lm != 0` the allocator copied pa / pb at the join.)
+                    const uint64_t H1 = (Lm & ballot(ml > 32u)) << 1, H2 = (Lm & ballot(ml > 64u)) << 2;
+                    const uint32_t om = off | (ml << 16);
+                    const uint32_t om1 = wave_shr1(om), po1 = wave_shr1(po_t);
+                    const uint32_t om2 = wave_shr1(om1), po2 = wave_shr1(po1);
+                    if (in_mask(Lm | H1 | H2)) {
+                        const bool h1 = in_mask(H1), h2 = in_mask(H2);
+                        const uint32_t t_om = h1 ? om1 : (h2 ? om2 : om), t_po = h1 ? po1 : (h2 ? po2 : po_t);
+                        const uint32_t t_off = t_om & 0xFFFFu, t_ml = t_om >> 16;
+                        const uint32_t pf = h1 ? 16u : (h2 ? 48u : 0u);             // first match byte this lane holds
+                        const uint32_t rest = t_ml - 16u - pf;                      // (helpers: >= 1 by H1 / H2)
+                        const uint32_t pl = pf == 0u ? t_ml : (rest < 16u ? 16u : (rest < 32u ? rest : 32u));
+                        // (the lane-copy build loads pb unconditionally: a token lane there has ml > short_max)
+                        static_assert(!kLaneCopy || short_max >= 15u, "a lane-copy token lane must hold >= 16 bytes");
+                        if constexpr (kDict) {
+                            // one load per piece from a per-lane address: the source is wholly in the dictionary
+                            // (see viol_err) or wholly in dst (two exec-masked loads would write pa twice in flight)
+                            const uint64_t ma = (t_off > t_po ? (uint64_t)(uintptr_t)dbase + (t_po - t_off + 65536u)
+                                                              : (uint64_t)(uintptr_t)dst + (t_po - t_off)) + pf;
+                            asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(pa) : "v"(ma) : "memory");
+                            if (kLaneCopy || pl >= 16u)             // (the lane-copy build: every role holds >= 16 bytes)
+                                asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(pb) : "v"(ma + (pl - 16u)) : "memory");
+                        } else {
+                            const uint32_t mo = t_po - t_off + pf;
+                            asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pa) : "v"(mo), "s"(dst) : "memory");
+                            if (kLaneCopy || pl >= 16u)             // (the lane-copy build: every role holds >= 16 bytes)
+                                asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(pb) : "v"(mo + pl - 16u), "s"(dst) : "memory");
                         }
+                        pml = pl; po = t_po + pf; pof = t_off;
                     }
                     if constexpr (kLaneCopy) {
-                        const uint64_t S = ballot(shortm);
-                        const uint32_t ns = (uint32_t)__popcll(S);                       // <= 21 sequences per batch
-                        const uint32_t rk = (uint32_t)__popcll(S & ((1ull << lane) - 1ull));
+                        const uint32_t ns = (uint32_t)__popcll(Sm);                      // <= 21 sequences per batch
+                        const uint32_t rk = lane_rank(Sm);
                         const uint32_t lead = (lane & ~7u) << 2, k4 = (lane & 7u) * 4u, grp = lane >> 3;
                         // one round: the sequences of rank g0 .. g0 + 7 send (source, destination, length) to the first lane
                         // of their group of eight (ds_permute; everybody else sends to lane 63, which leads no group), the
@@ -434,10 +454,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                         const uint32_t first = pos, tbase = T;      // first token (lane) / output offset of the new phase
                         const uint64_t Rn = R_walk & ~((1ull << first) - 1ull);
                         if ((uint32_t)__builtin_popcountll(Rn) < min_phase_tokens) break;
-                        const bool realn = (Rn >> lane) & 1ull;
                         const uint32_t lit_f = rdlane(lit, first);
                         const bool violn = viol_err || (off + lit_f < (relv - tbase) + ol);
-                        const uint64_t vmn = ballot(realn && violn);
+                        const uint64_t vmn = Rn & ballot(violn);
                         if ((vmn >> first) & 1ull) break;           // single-sequence path for that token
                         if (vmn != 0) {
                             const uint32_t fb = first_lane(vmn);

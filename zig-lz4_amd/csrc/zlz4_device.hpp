@@ -55,6 +55,11 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
 // (the inverse of a ballot), nothing is computed per lane
 __device__ __forceinline__ bool in_mask(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 
+// lane i reads lane i - 1 (lane 0 reads 0): DPP wave_shr:1, which crosses the 16-lane rows
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
+}
+
 // (a + kOff) & 0xFF in one instruction: SDWA keeps the low byte of the sum and pads the rest with zeros.  For ds_bpermute
 // addresses (4 * lane index): in a byte they wrap modulo 64 lanes.  Only ds_bpermute may read the result (the compiler
 // does not see the partial write inside the statement, so no VALU instruction should consume it right behind).
