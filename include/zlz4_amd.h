@@ -124,7 +124,8 @@ int64_t zlz4_compress_hc_ext_state(void *state, size_t state_len, const uint8_t 
 int64_t zlz4_decompress_safe(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap);
 
 /* replaces lz4.decompressSafePartial, src/lz4.zig:619-621: decompressGeneric with targetOutputSize as the
- * output limit (:99, :109) -- i.e. OutputTooSmall as soon as a sequence would pass `target_output_size`. */
+ * output limit (:99, :109) -- i.e. OutputTooSmall as soon as a sequence would pass `target_output_size`.  The call that
+ * returns the first bytes of a block instead is zlz4_decompress_safe_prefix. */
 int64_t zlz4_decompress_safe_partial(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                      size_t target_output_size);
 
@@ -137,9 +138,34 @@ int64_t zlz4_decompress_safe_using_dict(const uint8_t *src, size_t src_len, uint
                                         const uint8_t *dict, size_t dict_len);
 
 /* replaces lz4.decompressSafePartialUsingDict, src/lz4.zig:967-969: the same with target_output_size as the output
- * limit (:99, :109), as zlz4_decompress_safe_partial. */
+ * limit (:99, :109), as zlz4_decompress_safe_partial.  The call that returns the first bytes of a block instead is
+ * zlz4_decompress_safe_prefix_using_dict. */
 int64_t zlz4_decompress_safe_partial_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                                 size_t target_output_size, const uint8_t *dict, size_t dict_len);
+
+/* Prefix decoding: the first dst_cap bytes of a block (no counterpart in the reference; what liblz4's
+ * LZ4_decompress_safe_partial(src, dst, src_len, dst_cap, dst_cap) gives for a valid block).  dst_cap is both the number
+ * of bytes wanted and the size of dst.  The walk is decompressGeneric's (src/lz4.zig:89-251) with oend = dst_cap and these
+ * changes:
+ *   - it stops and returns dst_cap as soon as dst_cap bytes are out: tested at the top of the loop (beside :113), right
+ *     after the literal copy and right after the match copy.  Nothing behind that point is read: after literals that end
+ *     exactly at dst_cap, the offset and match length of that sequence are not validated;
+ *   - literals: the length bytes and :136 are unchanged (a run that passes the end of src is CorruptedData even when the
+ *     cut falls inside it); instead of :137, min(lit, dst_cap - op) bytes are copied;
+ *   - match: :146, :149, :154 (offset 0) and the extension bytes (:160-168) are unchanged, :174 is dropped, CorruptedData
+ *     iff offset > op + dict_len (:181-192 / :231) on the full offset, then the first min(ml, dst_cap - op) bytes of the
+ *     match are copied with the reference's byte-by-byte meaning (it may start in the dictionary, cross its end and run
+ *     over itself).
+ * The result is never OutputTooSmall: it is dst_cap (cut), the decoded size S < dst_cap (the block ended first), or
+ * CorruptedData for a defect met before dst_cap bytes were out.  src_len == 0 or dst_cap == 0 gives 0 (:97-98).
+ * Consequences: where zlz4_decompressed_size gives S >= 0 the result is min(S, dst_cap) and the bytes are the first
+ * min(S, dst_cap) bytes of the full decode; for dst_cap >= S the result and the first S bytes are those of
+ * zlz4_decompress_safe(_using_dict).  One limit, the size query's: a single literal or match length saturates at
+ * 0xFFFF0000 as in the decoders, so this holds for blocks in which no single run or match is longer than that.
+ * The _using_dict call stages only the last min(dict_len, 65536) bytes; dict == NULL with dict_len > 0 -> InvalidState. */
+int64_t zlz4_decompress_safe_prefix(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap);
+int64_t zlz4_decompress_safe_prefix_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                               const uint8_t *dict, size_t dict_len);
 
 /* Streaming compression, lz4.Stream (src/lz4.zig:751-866).  `table` is Stream.hashTable: ZLZ4_STREAM_TABLE_ENTRIES
  * u32 in HOST memory, staged with the data (correct, not fast -- the batch calls of section 2 are the fast path).  The
@@ -290,6 +316,25 @@ int32_t zlz4_batch_decompress_safe_using_dict(void *stream,
                                               uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
                                               const uint8_t *d_dict, const uint64_t *d_dict_off,
                                               const uint32_t *d_dict_len, int64_t *d_result, uint32_t nblocks);
+
+/* Prefix decoding per block (zlz4_decompress_safe_prefix above): the argument lists of the two
+ * decode calls above, with d_out_cap[i] both the number of bytes wanted of block i and the size of its slot.
+ * d_result[i] = min(decoded size, d_out_cap[i]), or CorruptedData for a defect met before d_out_cap[i] bytes were out;
+ * never OutputTooSmall.  The walk of block i ends where its prefix does: a 4 KiB prefix of a 64 KiB block costs about a
+ * sixteenth of the full decode's walk.  No byte outside [d_out_off[i], d_out_off[i] + d_out_cap[i]) is written; bytes of
+ * the slot behind d_result[i] are left as they were.  Same contract as the decode calls: device pointers, asynchronous,
+ * no allocation, no read-back (graph-capturable).  A null array (d_dict may be null: dictionaries of length 0) or a
+ * misaligned one (8 bytes for the 64-bit arrays, 4 for the 32-bit ones) returns InvalidState and launches nothing. */
+int32_t zlz4_batch_decompress_safe_prefix(void *stream,
+                                          const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
+                                          uint8_t *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                          int64_t *d_result, uint32_t nblocks);
+int32_t zlz4_batch_decompress_safe_prefix_using_dict(void *stream,
+                                                     const uint8_t *d_in, const uint64_t *d_in_off,
+                                                     const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                                     const uint32_t *d_out_cap, const uint8_t *d_dict,
+                                                     const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                                     int64_t *d_result, uint32_t nblocks);
 
 /* Decompressed sizes, for compressed blocks whose decoded size the caller does not know (an LZ4 block does not carry it;
  * no counterpart in the reference).  d_size[i] = what decompressSafe (src/lz4.zig:257-259) returns for block i into a

@@ -73,6 +73,10 @@ SYMBOLS = {
     "zlz4_batch_compress_fast": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U32]),
     "zlz4_batch_decompress_safe": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_decompress_safe_using_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_decompress_safe_prefix": (_I64, [_VP, _SZ, _VP, _SZ]),
+    "zlz4_decompress_safe_prefix_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ]),
+    "zlz4_batch_decompress_safe_prefix": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "zlz4_batch_decompress_safe_prefix_using_dict": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_decompressed_size": (_I64, [_VP, _SZ, _SZ]),
     "zlz4_batch_decompressed_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _U32]),
     "zlz4_batch_plan_outputs": (_I32, [_VP, _VP, _U32, _U32, _VP, _VP, _VP]),
@@ -253,6 +257,21 @@ def decompressSafePartialUsingDict(src, dst_cap, target_output_size, dict):
     """lz4.decompressSafePartialUsingDict(src, dst, targetOutputSize, dict), src/lz4.zig:967-969."""
     dk, dn = _in(dict)
     return _run(lib().zlz4_decompress_safe_partial_using_dict, src, dst_cap, target_output_size, C.addressof(dk), dn)
+
+
+def decompressSafePrefix(src, n):
+    """zlz4_decompress_safe_prefix (no counterpart in the reference): the first n bytes of the block, or all of it where it
+    decodes to fewer; never OutputTooSmall (include/zlz4_amd.h)."""
+    return _run(lib().zlz4_decompress_safe_prefix, src, n)
+
+
+def decompressSafePrefixUsingDict(src, n, dict):
+    """zlz4_decompress_safe_prefix_using_dict: decompressSafePrefix with the external dictionary `dict` in front of the
+    output; dict None with nothing to stage is the empty dictionary."""
+    if dict is None:
+        return _run(lib().zlz4_decompress_safe_prefix_using_dict, src, n, None, 0)
+    dk, dn = _in(dict)
+    return _run(lib().zlz4_decompress_safe_prefix_using_dict, src, n, C.addressof(dk), dn)
 
 
 def compressFastUsingDict(src, dict, acceleration=1, dst_cap=None):
@@ -986,6 +1005,52 @@ def decompressBlocks(blocks, dicts=None, device="cuda"):
     sizes = size.cpu().tolist()
     out = _unstage(d_dst, out_off.cpu().tolist(), result)
     return [o if s >= 0 else s for o, s in zip(out, sizes)]      # (a failed block has capacity 0: the query's code stands)
+
+
+def batch_decompress_safe_prefix(d_in, in_off, in_len, d_out, out_off, out_cap, result):
+    """zlz4_batch_decompress_safe_prefix: the tensors of batch_decompress_safe; out_cap[i] is the number of bytes wanted of
+    block i and the size of its slot, result[i] = min(decoded size, out_cap[i]) or CorruptedData."""
+    _check(lib().zlz4_batch_decompress_safe_prefix(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(d_out),
+                                                   _ptr(out_off), _ptr(out_cap), _ptr(result), in_len.numel()))
+
+
+def batch_decompress_safe_prefix_using_dict(d_in, in_off, in_len, d_out, out_off, out_cap, d_dict, dict_off, dict_len,
+                                            result):
+    """zlz4_batch_decompress_safe_prefix_using_dict: the tensors of batch_decompress_safe_using_dict, out_cap as in
+    batch_decompress_safe_prefix."""
+    _check(lib().zlz4_batch_decompress_safe_prefix_using_dict(_stream(), _ptr(d_in), _ptr(in_off), _ptr(in_len),
+                                                              _ptr(d_out), _ptr(out_off), _ptr(out_cap), _ptr(d_dict),
+                                                              _ptr(dict_off), _ptr(dict_len), _ptr(result),
+                                                              in_len.numel()))
+
+
+def decompressBlockPrefixes(blocks, n, dicts=None, device="cuda"):
+    """The first n bytes of every compressed block of `blocks` (n: one int for all, or one per block), staged like
+    decompressBlocks but without a size query: block i's slot is n[i] bytes.  dicts[i] (bytes or None) is block i's
+    dictionary.  -> list of prefixes (bytes; a block that decodes to fewer bytes gives all of them) or error codes."""
+    import torch
+    nb = len(blocks)
+    if nb == 0:
+        return []
+    want = [int(n)] * nb if isinstance(n, int) else [int(x) for x in n]
+    if len(want) != nb or any(w < 0 or w > 0xFFFFFFFF for w in want):
+        raise ValueError("n: one length per block, each in [0, 0xFFFFFFFF]")
+    d_src, src_off, src_len = _stage(blocks, device)
+    in_len = src_len.to(torch.int32)
+    offs = _offsets(want)
+    out_off = torch.tensor(offs, dtype=torch.int64, device=device)
+    # (int32 tensors carry the u32 capacities bit for bit)
+    out_cap = torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in want], dtype=torch.int32, device=device)
+    d_dst = torch.empty(max(1, sum(want)), dtype=torch.uint8, device=device)
+    result = torch.empty(nb, dtype=torch.int64, device=device)
+    if dicts is None:
+        batch_decompress_safe_prefix(d_src, src_off, in_len, d_dst, out_off, out_cap, result)
+    else:
+        dbytes = [bytes(d) if d is not None else b"" for d in dicts]
+        d_dict, dict_off, dl = _stage(dbytes, device)
+        batch_decompress_safe_prefix_using_dict(d_src, src_off, in_len, d_dst, out_off, out_cap, d_dict, dict_off,
+                                                dl.to(torch.int32), result)
+    return _unstage(d_dst, offs, result)
 
 
 def batch_load_dict(d_dict, dict_off, dict_len, tables, result):

@@ -53,6 +53,15 @@ inline Result decompressSafePartialUsingDict(const std::uint8_t *src, std::size_
                                              std::size_t target, const std::uint8_t *dict, std::size_t dict_len) {
     return wrap(zlz4_decompress_safe_partial_using_dict(src, n, dst, cap, target, dict, dict_len));
 }
+// no counterpart in the reference: the first `cap` bytes of the block (all of it where it decodes to fewer), never
+// OutputTooSmall; the result is min(decoded size, cap) (include/zlz4_amd.h)
+inline Result decompressSafePrefix(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap) {
+    return wrap(zlz4_decompress_safe_prefix(src, n, dst, cap));
+}
+inline Result decompressSafePrefixUsingDict(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                                            const std::uint8_t *dict, std::size_t dict_len) {
+    return wrap(zlz4_decompress_safe_prefix_using_dict(src, n, dst, cap, dict, dict_len));
+}
 // no counterpart in the reference (its Stream never refers to a loaded dictionary): compressFast's loop on the last 64 KiB
 // of `dict` followed by `src`, from the table Stream.loadDict(dict) leaves; decodes with decompressSafeUsingDict
 inline Result compressFastUsingDict(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
@@ -165,6 +174,14 @@ struct DictBlocks {
 inline Result decompressSafeUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d) {
     return wrap(zlz4_batch_decompress_safe_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
                                                       d.dict_off, d.dict_len, b.result, b.nblocks));
+}
+// prefix decoding: b.out_cap[i] is the number of bytes wanted of block i and the size of its slot
+inline Result decompressSafePrefixBatch(void *stream, const Blocks &b) {
+    return wrap(zlz4_batch_decompress_safe_prefix(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks));
+}
+inline Result decompressSafePrefixUsingDictBatch(void *stream, const Blocks &b, const DictBlocks &d) {
+    return wrap(zlz4_batch_decompress_safe_prefix_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap,
+                                                             d.dict, d.dict_off, d.dict_len, b.result, b.nblocks));
 }
 // decompressed sizes: size[i] = what decompressSafeBatch returns for block i into 0xFFFFFFFF bytes, or
 // decompressSafeUsingDictBatch with a dictionary of dict_len[i] bytes (nullptr = no dictionary); only b.in* and b.nblocks

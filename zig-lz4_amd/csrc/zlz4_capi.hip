@@ -18,14 +18,18 @@ using namespace zlz4host;
 
 namespace {
 
-enum class Op { Fast, Hc, Decompress, DecompressDict, DecompressBound };
+enum class Op { Fast, Hc, Decompress, DecompressDict, DecompressBound, DecompressPrefix, DecompressPrefixDict };
 
 // One block, host pointers: stage -> kernel -> copy back.  Op::DecompressDict stages the tail of `dict` (dict_tail,
 // zlz4_host.hpp).  Op::DecompressBound decodes with the StreamDecode bound `bound` (k_decompress_safe, kBound).
+// Op::DecompressPrefix / DecompressPrefixDict: the prefix decoder (kPartial), dst_cap bytes wanted; the second stages the
+// dictionary's tail like Op::DecompressDict.
 int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t accel,
                    int32_t level, const uint8_t *dict = nullptr, size_t dict_len = 0, uint32_t bound = 0) {
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    if (src_len > 0xFFFFFFFFull) return op == Op::Decompress ? ZLZ4_ERR_CORRUPTED_DATA : ZLZ4_ERR_INPUT_TOO_LARGE;
+    if (src_len > 0xFFFFFFFFull)
+        return op == Op::Decompress || op == Op::DecompressPrefix || op == Op::DecompressPrefixDict ? ZLZ4_ERR_CORRUPTED_DATA
+                                                                                                  : ZLZ4_ERR_INPUT_TOO_LARGE;
     const uint32_t cap32 = clamp_cap32(dst_cap), len32 = (uint32_t)src_len;
 
     // scratch from the parked-buffer cache (zlz4_host.hpp): a caller that loops over single blocks does not pay a
@@ -33,7 +37,7 @@ int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size
     hipStream_t st = nullptr;
     DeviceCall dc(st);
     const size_t ws = op == Op::Hc ? zlz4_hc_workspace_bytes(1, len32) : 0;
-    const size_t dtail = op == Op::DecompressDict ? dict_tail(dict_len) : 0;
+    const size_t dtail = op == Op::DecompressDict || op == Op::DecompressPrefixDict ? dict_tail(dict_len) : 0;
     DevBuf d_in(src_len, &dc), d_out(cap32, &dc);
     Staged<BlockRec> rec(&dc);
     DevBuf d_ws(ws, &dc), d_dict(dtail, &dc);
@@ -57,6 +61,11 @@ int64_t run_single(Op op, const uint8_t *src, size_t src_len, uint8_t *dst, size
     } else if (op == Op::DecompressBound) {
         rc = zlz4_launch_decompress_safe_bound(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap, &r->result, 1,
                                                nullptr, &r->dict_off, &r->dict_len, 0);
+    } else if (op == Op::DecompressPrefix) {
+        rc = zlz4_launch_decompress_safe_prefix(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap, &r->result, 1);
+    } else if (op == Op::DecompressPrefixDict) {
+        rc = zlz4_launch_decompress_safe_prefix_using_dict(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap,
+                                                           &r->result, 1, d_dict.as<uint8_t>(), &r->dict_off, &r->dict_len);
     } else {
         rc = zlz4_launch_decompress_safe_using_dict(st, in, &r->in_off, &r->in_len, out, &r->out_off, &r->out_cap,
                                                     &r->result, 1, d_dict.as<uint8_t>(), &r->dict_off, &r->dict_len);
@@ -354,6 +363,21 @@ int64_t zlz4_decompress_safe_partial_using_dict(const uint8_t *src, size_t n, ui
     return partial_target_zero(src, n);
 }
 
+// prefix decoding (include/zlz4_amd.h): dst_cap is the number of bytes wanted and the size of dst
+int64_t zlz4_decompress_safe_prefix(const uint8_t *src, size_t n, uint8_t *dst, size_t cap) {
+    if (n == 0) return 0;                                           // src/lz4.zig:97
+    if (cap == 0) return 0;                                         // :98
+    return run_single(Op::DecompressPrefix, src, n, dst, cap, 0, 0);
+}
+
+int64_t zlz4_decompress_safe_prefix_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const uint8_t *dict,
+                                               size_t dict_len) {
+    if (n == 0) return 0;                                           // :97
+    if (cap == 0) return 0;                                         // :98
+    if (!dict && dict_len) return ZLZ4_ERR_INVALID_STATE;
+    return run_single(Op::DecompressPrefixDict, src, n, dst, cap, 0, 0, dict, dict_len);
+}
+
 void zlz4_stream_decode_init(zlz4_stream_decode_t *sd) {          // src/lz4.zig:893-901
     if (sd) *sd = zlz4_stream_decode_t{0, 0, 0, 0};
 }
@@ -575,6 +599,37 @@ int32_t zlz4_batch_decompress_safe_using_dict(void *stream, const uint8_t *d_in,
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     return zlz4_launch_decompress_safe_using_dict((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off,
                                                   d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len);
+}
+
+// prefix decoding per block: d_out_cap[i] = bytes wanted = slot size (k_decompress_safe, kPartial)
+int32_t zlz4_batch_decompress_safe_prefix(void *stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                          const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                          const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks) {
+    if (nblocks == 0) return 0;
+    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_result) return ZLZ4_ERR_INVALID_STATE;
+    if (((uintptr_t)d_in_off | (uintptr_t)d_out_off | (uintptr_t)d_result) & 7u ||
+        ((uintptr_t)d_in_len | (uintptr_t)d_out_cap) & 3u)
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_decompress_safe_prefix((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
+                                              d_result, nblocks);
+}
+
+int32_t zlz4_batch_decompress_safe_prefix_using_dict(void *stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                     const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                                     const uint32_t *d_out_cap, const uint8_t *d_dict,
+                                                     const uint64_t *d_dict_off, const uint32_t *d_dict_len,
+                                                     int64_t *d_result, uint32_t nblocks) {
+    if (nblocks == 0) return 0;
+    // (d_dict may be null: every dictionary empty)
+    if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_dict_off || !d_dict_len || !d_result)
+        return ZLZ4_ERR_INVALID_STATE;
+    if (((uintptr_t)d_in_off | (uintptr_t)d_out_off | (uintptr_t)d_dict_off | (uintptr_t)d_result) & 7u ||
+        ((uintptr_t)d_in_len | (uintptr_t)d_out_cap | (uintptr_t)d_dict_len) & 3u)
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_decompress_safe_prefix_using_dict((hipStream_t)stream, d_in, d_in_off, d_in_len, d_out, d_out_off,
+                                                         d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len);
 }
 
 int32_t zlz4_batch_load_dict(void *stream, const uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_len,

@@ -65,7 +65,13 @@ __device__ __forceinline__ uint64_t ld64u(const uint8_t *p) { uint64_t v; __buil
 // kBoundInvalid stores InvalidState and decodes nothing (zlz4_batch_decompress_safe_continue, DESIGN.md section 4.2c;
 // the constants are in zlz4_device.hpp).
 // With kDict too, a block decodes with its dictionary or with its bound, never both (d_dict_len[blk] == 0 or lo == 0).
-template <bool kWrite, bool kLaneCopy = false, bool kPhases = kLaneCopy, bool kDict = false, bool kBound = false>
+// kPartial: prefix decoding: oend is the number of bytes wanted, and the sequence that would pass
+// it is cut there instead of being OutputTooSmall -- the walk stops with op == oend as soon as that many bytes are out (at
+// the top of the loop, after the literals, after the match), and nothing behind that point is read or validated.  The
+// batch path stays 32 bytes clear of oend (room0), so every sequence that reaches the end is one of the single-sequence
+// paths', and only their :137 / :174 exits change: the lengths of their copies are clamped to oend - op, exactly.
+template <bool kWrite, bool kLaneCopy = false, bool kPhases = kLaneCopy, bool kDict = false, bool kBound = false,
+          bool kPartial = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 : 1))) void k_decompress_safe(
     const uint8_t *__restrict__ d_in, const uint64_t *__restrict__ d_in_off,
     const uint32_t *__restrict__ d_in_len, uint8_t *d_out, const uint64_t *__restrict__ d_out_off,
@@ -163,6 +169,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
 
         for (;;) {
             if (ip >= iend) break;                                  // :113
+            if constexpr (kPartial) { if (op >= oend) break; }      // (prefix: every byte wanted is out)
             // ---- batch path: every lane parses the 64-byte window as if a token started at its byte; a scalar walk
             //      over next(i) picks the real token starts, and all sequences that lie entirely inside the window
             //      (typically 6-9 on text) are copied together: one store writes every literal of the batch straight
@@ -506,13 +513,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                 const uint32_t in_rem = iend - ip - 1u;             // bytes after the token
                 if (lit != 15u && mlc != 15u && in_rem >= lit + 2u) {
                     // (in_rem >= lit + 2 : literals fit (:136) and the offset is present (:146, :149))
+                    if constexpr (kPartial) {
+                        // prefix: the literals that fit; when they fill the output, the offset behind them is not read
+                        if (lit >= oend - op) {
+                            if (lane > i0 && lane <= i0 + (oend - op)) dst[op + (lane - i0 - 1u)] = (uint8_t)w;
+                            op = oend;
+                            break;
+                        }
+                    } else
                     if (lit > oend - op) { res = kErrOutputTooSmall; break; }            // :137
                     if (kWrite && lane > i0 && lane <= i0 + lit) dst[op + (lane - i0 - 1u)] = (uint8_t)w;   // :140
                     op += lit;
                     const uint32_t offset = rdlane(w, i0 + 1u + lit) | (rdlane(w, i0 + 2u + lit) << 8);   // :150
                     ip += 3u + lit;
                     if (offset == 0) { res = kErrCorrupted; break; }                     // :154
-                    const uint32_t ml = mlc + kMinMatch;                                 // :171 (4..18)
+                    uint32_t ml = mlc + kMinMatch;                                       // :171 (4..18)
+                    if constexpr (kPartial) { if (ml > oend - op) ml = oend - op; } else   // (prefix: what fits, >= 1)
                     if (ml > oend - op) { res = kErrOutputTooSmall; break; }             // :174
                     if (offset > op) {                                                   // :181-186 / :231
                         if (!kDict || offset - op > dlen) { res = kErrCorrupted; break; }   // (dict: :189-192)
@@ -554,18 +570,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
             }
             if (lit > 0) {                                          // :134
                 if (lit > iend - ip) { res = kErrCorrupted; break; }        // :136
-                if (lit > oend - op) { res = kErrOutputTooSmall; break; }   // :137
+                if constexpr (!kPartial) { if (lit > oend - op) { res = kErrOutputTooSmall; break; } }   // :137
+                const uint32_t nl = kPartial && lit > oend - op ? oend - op : lit;   // (prefix: the literals that fit)
                 if (!kWrite) {
                     // size pass: literals are skipped, the window follows lazily
                 } else if (lit <= 64u) {
                     if (ip - wbase + lit > 64u) reload(ip);
                     const uint32_t j0 = ip - wbase;
-                    if (lane >= j0 && lane < j0 + lit) dst[op + (lane - j0)] = (uint8_t)w;
+                    if (lane >= j0 && lane < j0 + nl) dst[op + (lane - j0)] = (uint8_t)w;
                 } else {
-                    copy_bytes(dst + op, src + ip, lit, lane);      // :140
+                    copy_bytes(dst + op, src + ip, nl, lane);       // :140
                 }
                 ip += lit;
-                op += lit;
+                op += nl;
+                if constexpr (kPartial) { if (op >= oend) break; }  // (prefix: nothing behind the literals is read)
             }
             if (ip >= iend) break;                                  // :146
             if (iend - ip < 2u) { res = kErrCorrupted; break; }     // :149
@@ -586,7 +604,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDict ? 8 :
                 if (bad) { res = kErrCorrupted; break; }
             }
             ml += kMinMatch;                                        // :171
-            if (ml > oend - op) { res = kErrOutputTooSmall; break; }   // :174
+            if constexpr (kPartial) {
+                // prefix: the first oend - op (>= 1) bytes of the match.  Every copy below moves exactly ml bytes with
+                // the byte-by-byte meaning of :235-241, so the clamped length cuts the dictionary part, the disjoint copy
+                // and both overlap paths alike; the loop's top then ends the walk
+                if (ml > oend - op) ml = oend - op;
+            } else if (ml > oend - op) { res = kErrOutputTooSmall; break; }   // :174
             if (offset > op) {                                      // :181-186 (no dict) / :231
                 if (!kDict || offset - op > dlen) { res = kErrCorrupted; break; }   // (dict: :189-192)
             } else if (kBound && offset + lo > op) { res = kErrCorrupted; break; }   // (match below prefix)
@@ -808,9 +831,10 @@ SafeShape safe_shape(uint32_t nblocks, bool knobs, uint32_t min_phase_tokens = 3
             nblocks >= kLaneCopyMinBlocks};
 }
 
-template <bool kWrite, bool kLaneCopy, bool kPhases = kLaneCopy, bool kDict = false, bool kBound = false>
+template <bool kWrite, bool kLaneCopy, bool kPhases = kLaneCopy, bool kDict = false, bool kBound = false,
+          bool kPartial = false>
 int launch_safe(hipStream_t stream, const SafeShape &sh, const SafeArgs &a) {
-    hipLaunchKernelGGL((zlz4::k_decompress_safe<kWrite, kLaneCopy, kPhases, kDict, kBound>), dim3(sh.grid), dim3(sh.threads),
+    hipLaunchKernelGGL((zlz4::k_decompress_safe<kWrite, kLaneCopy, kPhases, kDict, kBound, kPartial>), dim3(sh.grid), dim3(sh.threads),
                        sh.lds, stream, a.d_in, a.d_in_off, a.d_in_len, a.d_out, a.d_out_off, a.d_out_cap, a.d_result, a.nblocks,
                        sh.min_phase_tokens, a.d_dict, a.d_dict_off, a.d_dict_len);
     return zlz4_launch_status();
@@ -863,6 +887,30 @@ extern "C" int zlz4_launch_decompress_safe_using_dict(hipStream_t stream, const 
     const SafeShape sh = safe_shape(nblocks, true);
     const SafeArgs a = {d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len};
     return sh.lane_copy ? launch_safe<true, true, true, true>(stream, sh, a) : launch_safe<true, false, false, true>(stream, sh, a);
+}
+
+// Prefix decoding (kPartial): d_out_cap[i] is the number of bytes wanted of block i and the size of
+// its slot.  Fixed shape: the tuning knobs stay with the two launchers above.
+extern "C" int zlz4_launch_decompress_safe_prefix(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                  const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                                  const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks) {
+    if (nblocks == 0) return 0;
+    const SafeShape sh = safe_shape(nblocks, false);
+    const SafeArgs a = {d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, nullptr, nullptr, nullptr};
+    return sh.lane_copy ? launch_safe<true, true, true, false, false, true>(stream, sh, a)
+                        : launch_safe<true, false, false, false, false, true>(stream, sh, a);
+}
+
+extern "C" int zlz4_launch_decompress_safe_prefix_using_dict(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                             const uint32_t *d_in_len, uint8_t *d_out,
+                                                             const uint64_t *d_out_off, const uint32_t *d_out_cap,
+                                                             int64_t *d_result, uint32_t nblocks, const uint8_t *d_dict,
+                                                             const uint64_t *d_dict_off, const uint32_t *d_dict_len) {
+    if (nblocks == 0) return 0;
+    const SafeShape sh = safe_shape(nblocks, false);
+    const SafeArgs a = {d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_result, nblocks, d_dict, d_dict_off, d_dict_len};
+    return sh.lane_copy ? launch_safe<true, true, true, true, false, true>(stream, sh, a)
+                        : launch_safe<true, false, false, true, false, true>(stream, sh, a);
 }
 
 // StreamDecode builds (kBound), fixed shape.  d_dict_len holds 2 * nblocks entries: the dictionary lengths (read only

@@ -96,6 +96,15 @@ int zlz4_launch_decompress_safe_bound(hipStream_t stream, const uint8_t *d_in, c
                                       const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
                                       const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks, const uint8_t *d_dict,
                                       const uint64_t *d_dict_off, const uint32_t *d_dict_len, int with_dict);
+// prefix decoding (k_decompress_safe, kPartial): d_out_cap[i] = bytes wanted of block i = size of its slot
+int zlz4_launch_decompress_safe_prefix(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                       const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                       const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks);
+int zlz4_launch_decompress_safe_prefix_using_dict(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off,
+                                                  const uint32_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                                  const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks,
+                                                  const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                  const uint32_t *d_dict_len);
 int zlz4_launch_decompress_sizes(hipStream_t stream, const uint8_t *d_in, const uint64_t *d_in_off, const uint32_t *d_in_len,
                                  const uint64_t *d_out_off, const uint32_t *d_out_cap, int64_t *d_result, uint32_t nblocks);
 

@@ -28,6 +28,10 @@ extern "c" fn zlz4_compress_hc_ext_state(state: [*]u8, state_len: usize, src: [*
 
 // the data-parallel hot path: device pointers, one wavefront (HC: one workgroup) per block, results per block
 extern "c" fn zlz4_batch_compress_fast(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, acceleration: u32) i32;
+extern "c" fn zlz4_decompress_safe_prefix(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize) i64;
+extern "c" fn zlz4_decompress_safe_prefix_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4_batch_decompress_safe_prefix(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
+extern "c" fn zlz4_batch_decompress_safe_prefix_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
 extern "c" fn zlz4_batch_decompress_safe(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
 extern "c" fn zlz4_batch_decompress_safe_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: [*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_result: [*]i64, nblocks: u32) i32;
 extern "c" fn zlz4_decompress_safe_continue(sd: *CStreamDecode, src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize) i64;
@@ -158,6 +162,16 @@ pub fn decompressSafeUsingDict(src: []const u8, dst: []u8, dict: []const u8) Err
 /// reference src/lz4.zig:967-969
 pub fn decompressSafePartialUsingDict(src: []const u8, dst: []u8, targetOutputSize: usize, dict: []const u8) Error!usize {
     return mapBlock(zlz4_decompress_safe_partial_using_dict(src.ptr, src.len, dst.ptr, dst.len, targetOutputSize, dict.ptr, dict.len));
+}
+/// No counterpart in the reference: the first dst.len bytes of the block (all of it where it decodes to fewer), never
+/// OutputTooSmall -- decompressGeneric with oend = dst.len, a walk that stops once dst is full and copies of the last
+/// sequence cut there (include/zlz4_amd.h).  Returns min(decoded size, dst.len).
+pub fn decompressSafePrefix(src: []const u8, dst: []u8) Error!usize {
+    return mapBlock(zlz4_decompress_safe_prefix(src.ptr, src.len, dst.ptr, dst.len));
+}
+/// decompressSafePrefix with `dict` in front of dst, as decompressSafeUsingDict
+pub fn decompressSafePrefixUsingDict(src: []const u8, dst: []u8, dict: []const u8) Error!usize {
+    return mapBlock(zlz4_decompress_safe_prefix_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len));
 }
 /// No counterpart in the reference (its Stream never refers to a loaded dictionary): compressFastWithHashTable's loop
 /// (src/lz4.zig:624-740) on the last 64 KiB of `dict` followed by `src`, from the table Stream.loadDict(dict) leaves
@@ -434,6 +448,10 @@ pub const device = struct {
     pub fn decompressSafeBatch(stream: ?*anyopaque, b: Blocks) Error!void {
         return mapLaunch(zlz4_batch_decompress_safe(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks));
     }
+    /// batch form of decompressSafePrefix: b.out_cap[i] is the number of bytes wanted of block i and the size of its slot
+    pub fn decompressSafePrefixBatch(stream: ?*anyopaque, b: Blocks) Error!void {
+        return mapLaunch(zlz4_batch_decompress_safe_prefix(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, b.result, b.nblocks));
+    }
     /// decompressed sizes (zlz4_batch_decompressed_size): size[i] = what decompressSafeBatch returns for block i into
     /// 0xFFFFFFFF bytes, or decompressSafeUsingDictBatch with a dictionary of dict_len[i] bytes (null = no dictionary)
     pub fn decompressedSizeBatch(stream: ?*anyopaque, in: [*]const u8, in_off: [*]const u64, in_len: [*]const u32, dict_len: ?[*]const u32, size: [*]i64, nblocks: u32) Error!void {
@@ -516,6 +534,10 @@ pub const DictBlocks = struct {
 /// batch form of decompressSafeUsingDict (src/lz4.zig:960-962); dictionaries are read-only and must not overlap `b.out`
 pub fn decompressSafeUsingDictBatch(stream: ?*anyopaque, b: device.Blocks, d: DictBlocks) Error!void {
     return device.mapLaunch(zlz4_batch_decompress_safe_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict, d.dict_off, d.dict_len, b.result, b.nblocks));
+}
+/// batch form of decompressSafePrefixUsingDict; b.out_cap as in device.decompressSafePrefixBatch
+pub fn decompressSafePrefixUsingDictBatch(stream: ?*anyopaque, b: device.Blocks, d: DictBlocks) Error!void {
+    return device.mapLaunch(zlz4_batch_decompress_safe_prefix_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict, d.dict_off, d.dict_len, b.result, b.nblocks));
 }
 
 /// Mirror of the `lz4f` namespace (reference src/lz4f.zig); enum/struct shapes as in :64-122.
