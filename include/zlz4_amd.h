@@ -786,6 +786,57 @@ int64_t zlz4f_decompress_frame_using_dict(const uint8_t *src, size_t src_len, ui
                                           const uint8_t *dict, size_t dict_len);
 int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t src_len, size_t dict_len);
 
+/* ---- frame prefix decoding: the first n bytes of every frame (no counterpart in the reference; what liblz4's
+ * LZ4F_decompress(_usingDict) leaves in a destination of n bytes).  FP(frame, n, T), DESIGN.md section 4.4f: n =
+ * d_dst_cap[f] is both the number of bytes wanted and the size of the slot, T the last D = min(dict_len, 65536) bytes of
+ * the frame's dictionary (D = 0 without one), pos the bytes out so far.
+ *   1. The header is parsed as by the decode calls (src/lz4f.zig:547); a header error is the result, also when n == 0.
+ *      After a good header n == 0 gives 0.
+ *   2. Stop rule: at the top of the block loop, in front of its condition and of the next block header, pos == n returns n.
+ *      Nothing behind that point is read or validated: later block headers, checksums, the end mark, the content checksum.
+ *   3. The chain is that of the decode calls (:563-600): input ending at a block boundary ends the loop, srcPos + 4 > len
+ *      is FrameSizeWrong (:565), a zero word is the end mark, srcPos + sz > len is FrameSizeWrong (:582).
+ *   4. With FLG bit 0x10: a missing checksum word is FrameSizeWrong (:591), a mismatch BlockChecksumInvalid (:596).  The
+ *      checksum covers the block's whole data, also when only part of it will be decoded, and is checked in front of the
+ *      decode.  Only blocks the walk reaches are hashed.
+ *   5. A stored block: min(sz, n - pos) bytes are copied, and they are history.  Never DstMaxSizeTooSmall.
+ *   6. A compressed block is the prefix decode of zlz4_decompress_safe_prefix_using_dict (section 4.2e) with n - pos bytes
+ *      wanted (at most 0xFFFFFFFF); any error from it is DecompressionFailed (:611).  History is always on, as in
+ *      zlz4f_batch_decompress_frame_using_dict: FLG bit 0x20 set, every block sees T alone; clear, the last 65536 bytes of
+ *      T ++ dst[0 .. pos) -- a match may start in T, cross into the frame's output and run over itself.  CorruptedData iff
+ *      offset > op + hist, on the full offset.
+ *   7. The chain ended with pos < n (the whole frame is out): the chain's error; then, with FLG bit 0x04, FrameSizeWrong for
+ *      a missing checksum word (:626), then ContentChecksumInvalid (:631) over dst[0 .. pos).  The result is pos.
+ * The result is n (the frame was cut), S < n (the frame ended first) or a frame error for a defect met before n bytes were
+ * out; never DstMaxSizeTooSmall, never OutputTooSmall.  Bytes of the slot behind the result are left as they were; no byte
+ * outside [d_dst_off[f], d_dst_off[f] + n) is written.
+ * Consequences.  Let R be the result of zlz4f_batch_decompress_frame_using_dict with a capacity that is large enough (D == 0:
+ * of zlz4f_batch_decompress_frame_ex(.., ZLZ4F_DECODE_LINKED, ..)).  R = S >= 0: the result is min(S, n) and the bytes are
+ * the first min(S, n) bytes of that decode.  For n > S, and for a failing frame once n exceeds the bytes that decode in
+ * front of the defect, the result is R itself, error codes included.  At n == S exactly the result is S and a defect
+ * behind the last byte (a bad content checksum, a broken chain tail) is not reported.  A single literal or match length
+ * saturates at 0xFFFF0000 as in the decoders.
+ * Batch calls: device pointers, one fixed launch (one wavefront per frame), no workspace, no max_blocks; asynchronous,
+ * nothing allocated, nothing read back: graph-capturable.  Dictionary arguments as in the calls above (d_dict_idx == NULL:
+ * dictionary 0; d_dict_idx[f] >= ndicts: ZLZ4_ERR_INVALID_STATE for that frame in front of every other status, nothing
+ * written, the other frames unaffected; d_dict may be NULL when every dictionary is empty).  ndicts == 0 is the plain call:
+ * no frame has a dictionary and no dictionary argument is read.  nframes == 0 returns 0.  A null array or a misaligned one
+ * (8 bytes for the 64-bit arrays, 4 for the 32-bit ones) returns ZLZ4_ERR_INVALID_STATE and launches nothing.
+ * The host calls stage the frame and the dictionary's last 64 KiB and run a batch of one; dict == NULL with dict_len > 0
+ * gives InvalidState.  No start offset; the StreamDecode calls and the segment calls have no prefix form. */
+int32_t zlz4f_batch_decompress_frame_prefix(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                            const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                            const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes);
+int32_t zlz4f_batch_decompress_frame_prefix_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                       const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                                       const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes,
+                                                       const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                       const uint32_t *d_dict_len, uint32_t ndicts,
+                                                       const uint32_t *d_dict_idx);
+int64_t zlz4f_decompress_frame_prefix(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap);
+int64_t zlz4f_decompress_frame_prefix_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                                 const uint8_t *dict, size_t dict_len);
+
 /* ---- dictionary frames at the HC levels 3..9 (what `lz4 -9 -D dict` and LZ4F_compressFrame_usingCDict with a level
  * produce; no counterpart in the reference).  The _ex calls are the calls they are named after, with the same argument
  * lists; the plain calls keep refusing every level > 0.  L = prefs->compression_level as the frame calls read it (<= 0:

@@ -138,6 +138,10 @@ SYMBOLS = {
     "zlz4f_batch_compress_frame_using_dict_ex": (_I32, [_VP] * 8 + [_U32, _U32, _PP, _U32, _VP, _VP, _VP, _U32, _VP,
                                                         C.c_uint64, _U32, _VP, _SZ]),
     "zlz4f_compress_frame_using_dict_ex": (_I64, [_VP, _SZ, _VP, _SZ, _PP, _VP, _SZ]),
+    "zlz4f_batch_decompress_frame_prefix": (_I32, [_VP] * 8 + [_U32]),
+    "zlz4f_batch_decompress_frame_prefix_using_dict": (_I32, [_VP] * 8 + [_U32, _VP, _VP, _VP, _U32, _VP]),
+    "zlz4f_decompress_frame_prefix": (_I64, [_VP, _SZ, _VP, _SZ]),
+    "zlz4f_decompress_frame_prefix_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -887,6 +891,43 @@ class lz4f:
             out = [o if s >= 0 else s for o, s in zip(out, sizes)]
         return out
 
+    # frame prefix decoding (include/zlz4_amd.h)
+    @staticmethod
+    def decompressFramePrefix(src, n, dict=None):
+        """zlz4f_decompress_frame_prefix(_using_dict with `dict`): the first n bytes of the frame's content, or all of it
+        where the frame holds fewer; a defect met before n bytes were out raises Lz4Error, one behind the cut does not."""
+        if dict is None:
+            return _run(lib().zlz4f_decompress_frame_prefix, src, n)
+        d, dn = _in(dict)
+        return _run(lib().zlz4f_decompress_frame_prefix_using_dict, src, n, C.addressof(d) if dn else None, dn)
+
+    @staticmethod
+    def decompressFramePrefixes(frames, n, dicts=None, dict_index=None, device="cuda"):
+        """The first n bytes of every frame of `frames` (n: one int for all, or one per frame) in one launch, without a size
+        query, a block table or a workspace: frame f's slot is n[f] bytes.  dicts / dict_index as in
+        decompressFramesUsingDict.  -> list of prefixes (bytes; a frame that holds fewer bytes gives all of them) or error
+        codes."""
+        import torch
+        nf = len(frames)
+        if nf == 0:
+            return []
+        want = [int(n)] * nf if isinstance(n, int) else [int(x) for x in n]
+        if len(want) != nf or any(w < 0 for w in want):
+            raise ValueError("n: one length per frame, each >= 0")
+        d_src, src_off, src_len = _stage(frames, device)
+        offs = _offsets(want)
+        d_dst = torch.empty(max(1, sum(want)), dtype=torch.uint8, device=device)
+        result = torch.empty(nf, dtype=torch.int64, device=device)
+        dst_off = torch.tensor(offs, dtype=torch.int64, device=device)
+        dst_cap = torch.tensor(want, dtype=torch.int64, device=device)
+        if dicts is None:
+            batch_decompress_frame_prefix(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result)
+        else:
+            d_dict, dict_off, dict_len, idx, _ = lz4f._stage_dicts(dicts, dict_index, nf, device)
+            batch_decompress_frame_prefix(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, d_dict, dict_off,
+                                          dict_len, idx)
+        return _unstage(d_dst, offs, result)
+
 
 def _offsets(lens):
     out, pos = [], 0
@@ -1022,6 +1063,21 @@ def batch_decompress_safe_prefix_using_dict(d_in, in_off, in_len, d_out, out_off
                                                               _ptr(d_out), _ptr(out_off), _ptr(out_cap), _ptr(d_dict),
                                                               _ptr(dict_off), _ptr(dict_len), _ptr(result),
                                                               in_len.numel()))
+
+
+def batch_decompress_frame_prefix(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, d_dict=None, dict_off=None,
+                                  dict_len=None, dict_idx=None):
+    """zlz4f_batch_decompress_frame_prefix (dict_len None) / _using_dict on torch CUDA tensors: the layout of
+    lz4f.decompressFrameBatch (int64 offsets, lengths and capacities) without max_blocks and workspace; dst_cap[f] is the
+    number of bytes wanted of frame f and the size of its slot, result[f] = min(content size, dst_cap[f]) or the frame's
+    error code.  Dictionaries as in lz4f.decompressFrameUsingDictBatch.  One launch on the current stream."""
+    if dict_len is None:
+        _check(lib().zlz4f_batch_decompress_frame_prefix(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                         _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel()))
+    else:
+        _check(lib().zlz4f_batch_decompress_frame_prefix_using_dict(
+            _stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst), _ptr(dst_off), _ptr(dst_cap), _ptr(result),
+            src_len.numel(), _ptr(d_dict), _ptr(dict_off), _ptr(dict_len), dict_len.numel(), _ptr(dict_idx)))
 
 
 def decompressBlockPrefixes(blocks, n, dicts=None, device="cuda"):

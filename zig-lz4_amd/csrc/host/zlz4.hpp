@@ -366,6 +366,29 @@ inline Result decompressFrameDeviceEx(void *stream, const std::uint8_t *d_src, s
 inline Result frameDecompressedSizeEx(const std::uint8_t *src, std::size_t n, std::uint32_t decode_flags) {
     return wrap(zlz4f_frame_decompressed_size_ex(src, n, decode_flags));
 }
+// frame prefix decoding (include/zlz4_amd.h; no counterpart in the reference): the first `cap` bytes of the frame's content
+// (all of it where the frame holds fewer), history-aware; the result is min(content size, cap), a defect behind the cut is
+// not reported.  Batch: f.dst_cap[i] is the number of bytes wanted of frame i and the size of its slot; one launch, no
+// workspace, no max_blocks.  FrameDicts: dictionary d is dict + off[d], len[d] bytes; frame i uses dictionary idx[i]
+// (nullptr: dictionary 0); ndicts == 0 is the plain call.
+struct FrameDicts {
+    const std::uint8_t *dict; const std::uint64_t *off; const std::uint32_t *len; std::uint32_t ndicts; const std::uint32_t *idx;
+};
+inline Result decompressFramePrefix(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap) {
+    return wrap(zlz4f_decompress_frame_prefix(src, n, dst, cap));
+}
+inline Result decompressFramePrefixUsingDict(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                                             const std::uint8_t *dict, std::size_t dict_len) {
+    return wrap(zlz4f_decompress_frame_prefix_using_dict(src, n, dst, cap, dict, dict_len));
+}
+inline Result decompressFramePrefixBatch(void *stream, const Frames &f) {
+    return wrap(zlz4f_batch_decompress_frame_prefix(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result,
+                                                    f.nframes));
+}
+inline Result decompressFramePrefixBatchUsingDict(void *stream, const Frames &f, const FrameDicts &d) {
+    return wrap(zlz4f_batch_decompress_frame_prefix_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap,
+                                                               f.result, f.nframes, d.dict, d.off, d.len, d.ndicts, d.idx));
+}
 }  // namespace lz4f
 
 }  // namespace zlz4

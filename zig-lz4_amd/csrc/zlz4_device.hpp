@@ -139,6 +139,12 @@ __device__ __forceinline__ uint32_t byte_at(const uint8_t *p) { return rfl((uint
 // where it is the in-output match at distance `offset`.
 // kBound: `lo` is a floor inside the output: a match at op with offset o is CorruptedData unless op - o >= lo (:181-185
 // without a dictionary; lo <= kBoundMax, so offset + lo cannot wrap).
+// kPartial: prefix decoding (DESIGN.md sections 4.2e / 4.4f): oend is the number of bytes wanted and the sequence that would
+// pass it is cut there instead of being OutputTooSmall.  The walk stops with op == oend as soon as that many bytes are out
+// -- at the top of the loop, behind the literal copy, behind the match copy -- and nothing behind that point is read or
+// validated.  The two OutputTooSmall exits become clamps of the length about to be copied (the T part of a dictionary match
+// takes its share of the clamped length); every copy moves exactly the bytes asked for, so no store lands at or past
+// out + oend.
 // Callers:
 //   k_bfl_decode (zlz4_frame_linked.hip, DESIGN.md sections 4.4c / 4.4d): block k of a linked frame at out = dst + pos,
 //     inframe = min(pos, 65536); <kWrite> with hist = inframe, <kWrite, true> with T the frame's dictionary tail of D
@@ -146,13 +152,16 @@ __device__ __forceinline__ uint32_t byte_at(const uint8_t *p) { return rfl((uint
 //   k_sd_finish (zlz4_stream_decode.hip): a call re-decoded with its true entry state;
 //     <true, true> with a pending dictionary (lowPrefix = dst: inframe = 0, hist = its reachable length, tend = its end),
 //     <true, false, true> with lowPrefix = dst + lo and no dictionary (hist = 0).
-template <bool kWrite, bool kDict = false, bool kBound = false>
+//   k_bfp_decode (zlz4_frame_linked.hip): the blocks of a frame up to the cut, <true, kDict, false,
+//     true> with oend = the bytes still wanted.
+template <bool kWrite, bool kDict = false, bool kBound = false, bool kPartial = false>
 __device__ int64_t decode_block_wave(const uint8_t *src, uint32_t iend, uint8_t *out, uint32_t oend, uint32_t hist,
                                      uint32_t lane, const uint8_t *tend = nullptr, uint32_t inframe = 0, uint32_t lo = 0) {
     if (iend == 0 || oend == 0) return 0;                              // :97-98
     uint32_t ip = 0, op = 0;
     for (;;) {
         if (ip >= iend) break;                                         // :113
+        if constexpr (kPartial) { if (op >= oend) break; }             // (prefix: every byte wanted is out)
         const uint32_t token = byte_at(src + ip++);                    // :116
         uint32_t lit = token >> 4;
         if (lit == 15u) {                                              // :123-131
@@ -166,9 +175,16 @@ __device__ int64_t decode_block_wave(const uint8_t *src, uint32_t iend, uint8_t 
         }
         if (lit > 0) {                                                 // :134-144
             if (lit > iend - ip) return kErrCorrupted;
-            if (lit > oend - op) return kErrOutputTooSmall;
-            if (kWrite) copy_bytes(out + op, src + ip, lit, lane);
-            ip += lit; op += lit;
+            if constexpr (kPartial) {                                  // (prefix: the literals that fit; when they fill
+                const uint32_t nl = lit < oend - op ? lit : oend - op; //  the output, nothing behind them is read)
+                if (kWrite) copy_bytes(out + op, src + ip, nl, lane);
+                ip += lit; op += nl;
+                if (op >= oend) break;
+            } else {
+                if (lit > oend - op) return kErrOutputTooSmall;
+                if (kWrite) copy_bytes(out + op, src + ip, lit, lane);
+                ip += lit; op += lit;
+            }
         }
         if (ip >= iend) break;                                         // :146
         if (iend - ip < 2u) return kErrCorrupted;                      // :149
@@ -186,7 +202,11 @@ __device__ int64_t decode_block_wave(const uint8_t *src, uint32_t iend, uint8_t 
             }
         }
         ml += kMinMatch;                                               // :171
-        if (ml > oend - op) return kErrOutputTooSmall;                 // :174
+        if constexpr (kPartial) {
+            if (ml > oend - op) ml = oend - op;                        // (prefix: the first oend - op >= 1 bytes)
+        } else {
+            if (ml > oend - op) return kErrOutputTooSmall;             // :174
+        }
         if (offset > op && offset - op > hist) return kErrCorrupted;   // :181-192: in front of the history
         if constexpr (kBound) {
             if (offset + lo > op) return kErrCorrupted;                // :183-185: below lowPrefix, no dictionary

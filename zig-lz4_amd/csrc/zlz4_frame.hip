@@ -42,41 +42,6 @@ size_t block_size_of(uint32_t id) {
     }
 }
 
-// ------------------------------------------------------------------ XXH32 (host + device)
-#define ZX_P1 2654435761u
-#define ZX_P2 2246822519u
-#define ZX_P3 3266489917u
-#define ZX_P4 668265263u
-#define ZX_P5 374761393u
-
-__host__ __device__ inline uint32_t zx_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-__host__ __device__ inline uint32_t zx_rd32(const uint8_t *p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__host__ __device__ inline uint32_t zx_round(uint32_t acc, uint32_t in) { return zx_rotl(acc + in * ZX_P2, 13) * ZX_P1; }
-
-__host__ __device__ inline uint32_t xxh32(const uint8_t *p, uint64_t len, uint32_t seed) {
-    const uint8_t *const end = p + len;
-    uint32_t h;
-    if (len >= 16) {
-        uint32_t v1 = seed + ZX_P1 + ZX_P2, v2 = seed + ZX_P2, v3 = seed, v4 = seed - ZX_P1;
-        const uint8_t *const limit = end - 16;
-        do {
-            v1 = zx_round(v1, zx_rd32(p)); v2 = zx_round(v2, zx_rd32(p + 4));
-            v3 = zx_round(v3, zx_rd32(p + 8)); v4 = zx_round(v4, zx_rd32(p + 12));
-            p += 16;
-        } while (p <= limit);
-        h = zx_rotl(v1, 1) + zx_rotl(v2, 7) + zx_rotl(v3, 12) + zx_rotl(v4, 18);
-    } else {
-        h = seed + ZX_P5;
-    }
-    h += (uint32_t)len;
-    while (p + 4 <= end) { h = zx_rotl(h + zx_rd32(p) * ZX_P3, 17) * ZX_P4; p += 4; }
-    while (p < end) { h = zx_rotl(h + (*p) * ZX_P5, 11) * ZX_P1; p += 1; }
-    h ^= h >> 15; h *= ZX_P2; h ^= h >> 13; h *= ZX_P3; h ^= h >> 16;
-    return h;
-}
-
 // ------------------------------------------------------------------ frame header (host side, <= 19 bytes)
 struct HeaderBytes { uint8_t b[20]; uint32_t n; };
 
@@ -107,39 +72,6 @@ __host__ __device__ inline HeaderBytes encode_header_cs(const zlz4f_prefs &p, ui
 }
 
 HeaderBytes encode_header(const zlz4f_prefs &p) { return encode_header_cs(p, p.content_size); }
-
-struct ParsedHeader { int64_t size; uint8_t flg; size_t block_size; };
-
-// parseFrameHeader, src/lz4f.zig:483-538 (decodeFLG :187-221, decodeBD :235-249); `have` = bytes available
-__host__ __device__ inline ParsedHeader parse_header(const uint8_t *src, size_t have) {
-    ParsedHeader r = {0, 0, 0};
-    if (have < 7) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; }
-    const uint32_t magic = zx_rd32(src);
-    if (magic != ZLZ4F_MAGICNUMBER) { r.size = ZLZ4F_ERR_FRAME_TYPE_UNKNOWN; return r; }
-    size_t pos = 4;
-    const uint8_t flg = src[pos];
-    if (((flg >> 6) & 3) != 1) { r.size = ZLZ4F_ERR_HEADER_VERSION_WRONG; return r; }
-    if (flg & 0x02) { r.size = ZLZ4F_ERR_RESERVED_FLAG_SET; return r; }
-    pos += 1;
-    const uint8_t bd = src[pos];
-    if (bd & 0x8F) { r.size = ZLZ4F_ERR_RESERVED_FLAG_SET; return r; }
-    switch ((bd >> 4) & 7) {
-        case 0: case 4: r.block_size = 64u * 1024; break;
-        case 5: r.block_size = 256u * 1024; break;
-        case 6: r.block_size = 1024u * 1024; break;
-        case 7: r.block_size = 4u * 1024 * 1024; break;
-        default: r.size = ZLZ4F_ERR_MAX_BLOCK_SIZE_INVALID; return r;
-    }
-    pos += 1;
-    if (flg & 0x08) { if (have < pos + 8) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; } pos += 8; }
-    if (flg & 0x01) { if (have < pos + 4) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; } pos += 4; }
-    if (have < pos + 1) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; }
-    if (src[pos] != (uint8_t)((xxh32(src + 4, pos - 4, 0) >> 8) & 0xFF)) { r.size = ZLZ4F_ERR_HEADER_CHECKSUM_INVALID; return r; }
-    pos += 1;
-    r.size = (int64_t)pos;
-    r.flg = flg;
-    return r;
-}
 
 // ------------------------------------------------------------------ compress-side kernels
 // block descriptors for the batch kernels: block i = src[i*bs, min(n, (i+1)*bs)) -> slot i
@@ -2139,6 +2071,66 @@ int64_t zlz4f_decompress_frame_using_dict(const uint8_t *src, size_t n, uint8_t 
             return single_frame_ex(nullptr, d_src, n, d_dst, cap, ZLZ4F_DECODE_LINKED, false, true, d_dict, D);
         });
     });
+}
+
+// ---- frame prefix decoding (include/zlz4_amd.h): d_dst_cap[f] = bytes wanted = slot size; one
+// launch of k_bfp_decode, no workspace.  The plain call is the dictionary call without dictionaries.
+int32_t zlz4f_batch_decompress_frame_prefix_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                       const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                                       const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes,
+                                                       const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                       const uint32_t *d_dict_len, uint32_t ndicts,
+                                                       const uint32_t *d_dict_idx) {
+    if (nframes == 0) return 0;
+    const BfArrays a = {d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result, nframes, 0};
+    const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
+    // (d_dict may be null: every dictionary empty)
+    if (bf_args_refused(kArgSrc | kArgDst | kArgDictLen | kArgDictOff | kArgAligned, a, &dd)) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return zlz4_launch_bfp_decode_dict((hipStream_t)stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_result,
+                                       nframes, d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx);
+}
+
+int32_t zlz4f_batch_decompress_frame_prefix(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                            const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                            const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes) {
+    return zlz4f_batch_decompress_frame_prefix_using_dict(stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap,
+                                                          d_result, nframes, nullptr, nullptr, nullptr, 0, nullptr);
+}
+
+// host pointers: the frame, the dictionary's tail and a batch of one.  dst_cap == 0 needs no destination.
+int64_t zlz4f_decompress_frame_prefix_using_dict(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const uint8_t *dict,
+                                                 size_t dict_len) {
+    if ((!src && n) || (!dst && cap) || (!dict && dict_len)) return ZLZ4_ERR_INVALID_STATE;
+    const ParsedHeader ph = parse_header(src, n);      // header errors need no device
+    if (ph.size < 0) return ph.size;
+    if (cap == 0) return 0;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return with_dict_tail(dict, dict_len, [&](const uint8_t *d_dict, uint32_t D) {
+        return host_frame_call(src, n, dst, cap, cap, [&](const uint8_t *d_src, uint8_t *d_dst) -> int64_t {
+            hipStream_t st = nullptr;
+            DeviceCall dc(st);
+            struct Rec { FrameRec f; uint64_t dict_off; uint32_t dict_len; };
+            Staged<Rec> rec(&dc);
+            if (!rec.d) return ZLZ4F_ERR_ALLOCATION_FAILED;
+            rec.h.f.src_len = n; rec.h.f.dst_cap = cap; rec.h.dict_len = D;
+            dc.launched();
+            if (!rec.upload(st)) return ZLZ4_ERR_DEVICE;
+            FrameRec *r = &rec.d->f;
+            const int32_t rc = zlz4f_batch_decompress_frame_prefix_using_dict(st, d_src, &r->src_off, &r->src_len, d_dst,
+                                                                              &r->dst_off, &r->dst_cap, &r->result, 1, d_dict,
+                                                                              &rec.d->dict_off, &rec.d->dict_len, D ? 1u : 0u,
+                                                                              nullptr);
+            if (rc != 0) return rc;
+            int64_t result = 0;
+            if (!read_result(dc, &r->result, result)) return ZLZ4_ERR_DEVICE;
+            return result;
+        });
+    });
+}
+
+int64_t zlz4f_decompress_frame_prefix(const uint8_t *src, size_t n, uint8_t *dst, size_t cap) {
+    return zlz4f_decompress_frame_prefix_using_dict(src, n, dst, cap, nullptr, 0);
 }
 
 int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t n, size_t dict_len) {

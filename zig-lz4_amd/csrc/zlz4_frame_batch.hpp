@@ -1,8 +1,11 @@
 // zlz4_frame_batch.hpp -- the per-frame record and the block flags of the batch frame calls,
-// shared by zlz4_frame.hip (the pipeline) and zlz4_frame_linked.hip (the linked-block kernels of section 4.4c).
+// XXH32 and the frame header parse, shared by zlz4_frame.hip (the pipeline) and zlz4_frame_linked.hip (the linked-block
+// kernels of section 4.4c, the frame prefix decoder of section 4.4f).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/zlz4_amd.h"
 
 namespace {
 
@@ -20,6 +23,75 @@ struct BFrame {
     uint32_t flg;       // decompress: FLG
     uint32_t proven;    // decompress: 1 = the speculative layout is proven
 };
+
+// ------------------------------------------------------------------ XXH32 (host + device)
+#define ZX_P1 2654435761u
+#define ZX_P2 2246822519u
+#define ZX_P3 3266489917u
+#define ZX_P4 668265263u
+#define ZX_P5 374761393u
+
+__host__ __device__ inline uint32_t zx_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+__host__ __device__ inline uint32_t zx_rd32(const uint8_t *p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+__host__ __device__ inline uint32_t zx_round(uint32_t acc, uint32_t in) { return zx_rotl(acc + in * ZX_P2, 13) * ZX_P1; }
+
+__host__ __device__ inline uint32_t xxh32(const uint8_t *p, uint64_t len, uint32_t seed) {
+    const uint8_t *const end = p + len;
+    uint32_t h;
+    if (len >= 16) {
+        uint32_t v1 = seed + ZX_P1 + ZX_P2, v2 = seed + ZX_P2, v3 = seed, v4 = seed - ZX_P1;
+        const uint8_t *const limit = end - 16;
+        do {
+            v1 = zx_round(v1, zx_rd32(p)); v2 = zx_round(v2, zx_rd32(p + 4));
+            v3 = zx_round(v3, zx_rd32(p + 8)); v4 = zx_round(v4, zx_rd32(p + 12));
+            p += 16;
+        } while (p <= limit);
+        h = zx_rotl(v1, 1) + zx_rotl(v2, 7) + zx_rotl(v3, 12) + zx_rotl(v4, 18);
+    } else {
+        h = seed + ZX_P5;
+    }
+    h += (uint32_t)len;
+    while (p + 4 <= end) { h = zx_rotl(h + zx_rd32(p) * ZX_P3, 17) * ZX_P4; p += 4; }
+    while (p < end) { h = zx_rotl(h + (*p) * ZX_P5, 11) * ZX_P1; p += 1; }
+    h ^= h >> 15; h *= ZX_P2; h ^= h >> 13; h *= ZX_P3; h ^= h >> 16;
+    return h;
+}
+
+// ------------------------------------------------------------------ frame header
+struct ParsedHeader { int64_t size; uint8_t flg; size_t block_size; };
+
+// parseFrameHeader, src/lz4f.zig:483-538 (decodeFLG :187-221, decodeBD :235-249); `have` = bytes available
+__host__ __device__ inline ParsedHeader parse_header(const uint8_t *src, size_t have) {
+    ParsedHeader r = {0, 0, 0};
+    if (have < 7) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; }
+    const uint32_t magic = zx_rd32(src);
+    if (magic != ZLZ4F_MAGICNUMBER) { r.size = ZLZ4F_ERR_FRAME_TYPE_UNKNOWN; return r; }
+    size_t pos = 4;
+    const uint8_t flg = src[pos];
+    if (((flg >> 6) & 3) != 1) { r.size = ZLZ4F_ERR_HEADER_VERSION_WRONG; return r; }
+    if (flg & 0x02) { r.size = ZLZ4F_ERR_RESERVED_FLAG_SET; return r; }
+    pos += 1;
+    const uint8_t bd = src[pos];
+    if (bd & 0x8F) { r.size = ZLZ4F_ERR_RESERVED_FLAG_SET; return r; }
+    switch ((bd >> 4) & 7) {
+        case 0: case 4: r.block_size = 64u * 1024; break;
+        case 5: r.block_size = 256u * 1024; break;
+        case 6: r.block_size = 1024u * 1024; break;
+        case 7: r.block_size = 4u * 1024 * 1024; break;
+        default: r.size = ZLZ4F_ERR_MAX_BLOCK_SIZE_INVALID; return r;
+    }
+    pos += 1;
+    if (flg & 0x08) { if (have < pos + 8) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; } pos += 8; }
+    if (flg & 0x01) { if (have < pos + 4) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; } pos += 4; }
+    if (have < pos + 1) { r.size = ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE; return r; }
+    if (src[pos] != (uint8_t)((xxh32(src + 4, pos - 4, 0) >> 8) & 0xFF)) { r.size = ZLZ4F_ERR_HEADER_CHECKSUM_INVALID; return r; }
+    pos += 1;
+    r.size = (int64_t)pos;
+    r.flg = flg;
+    return r;
+}
 
 __device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { return F.nb == 0 || F.base + F.nb <= max_blocks; }
 

@@ -99,6 +99,95 @@ __global__ __launch_bounds__(256) void k_bfl_decode(BFrame *__restrict__ fr, uin
     }
 }
 
+// Frame prefix decoding, FP(frame, n, T) of DESIGN.md section 4.4f: the first n = dst_cap[f] bytes of frame f.  One
+// wavefront per frame, four per workgroup, and the wavefront does all of it in one serial walk that ends at the cut: the
+// header (:547), the chain (:563-600, k_bfd_walk's loop), a reached block's checksum (one lane hashes, the verdict is
+// broadcast), the stored copy, the history-aware decode cut at the bytes still wanted, and -- only when the chain ended
+// first -- the content checksum (:625-635).  No block table, no workspace; every scalar is wave-uniform (rfl / byte_at).
+// The stop rule stands in front of the loop's own condition: once n bytes are out nothing more of the source is read.
+// kDict: frame f's dictionary is number dict_idx[f] (nullptr: 0) of ndicts; an index that names none gives InvalidState
+// in front of every other status.  The kDict == false instantiation never reads the dictionary arguments.
+template <bool kDict>
+__global__ __launch_bounds__(256) void k_bfp_decode(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                                    const uint64_t *__restrict__ src_len, uint8_t *dst,
+                                                    const uint64_t *__restrict__ dst_off,
+                                                    const uint64_t *__restrict__ dst_cap, int64_t *__restrict__ result,
+                                                    uint32_t nframes, const uint8_t *__restrict__ dict,
+                                                    const uint64_t *__restrict__ dict_off,
+                                                    const uint32_t *__restrict__ dict_len, uint32_t ndicts,
+                                                    const uint32_t *__restrict__ dict_idx) {
+    const uint32_t f = rfl(blockIdx.x * 4u + threadIdx.x / 64u), lane = threadIdx.x & 63u;
+    if (f >= nframes) return;
+    uint32_t D = 0;
+    const uint8_t *tend = nullptr;
+    if constexpr (kDict) {
+        const uint32_t d = dict_idx ? rfl(dict_idx[f]) : 0u;
+        if (d >= ndicts) {
+            if (lane == 0) result[f] = ZLZ4_ERR_INVALID_STATE;
+            return;
+        }
+        const uint32_t len = rfl(dict_len[d]);
+        D = len < 65536u ? len : 65536u;
+        tend = dict + rfl64(dict_off[d]) + len;
+    }
+    const uint64_t n = rfl64(src_len[f]), want = rfl64(dst_cap[f]);
+    const uint8_t *s = src + rfl64(src_off[f]);
+    uint8_t *out = dst + rfl64(dst_off[f]);
+    const ParsedHeader ph = parse_header(s, n < 19u ? (size_t)n : (size_t)19u);   // :547, every lane the same bytes
+    const int64_t hs = (int64_t)rfl64((uint64_t)ph.size);
+    if (hs < 0) {
+        if (lane == 0) result[f] = hs;
+        return;
+    }
+    const uint32_t flg = rfl((uint32_t)ph.flg);
+    const bool bc = (flg & 0x10u) != 0, indep = (flg & 0x20u) != 0;
+    uint64_t sp = (uint64_t)hs, pos = 0;
+    int64_t err = 0;
+    bool cut = false;
+    for (;;) {
+        if (pos == want) { cut = true; break; }                        // the stop rule: nothing behind is read
+        if (sp >= n) break;                                            // :563
+        if (sp + 4 > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }   // :565
+        const uint32_t h = byte_at(s + sp) | (byte_at(s + sp + 1) << 8) | (byte_at(s + sp + 2) << 16) |
+                           (byte_at(s + sp + 3) << 24);
+        sp += 4;
+        if (h == 0) break;                                             // :573
+        const uint32_t sz = h & 0x7FFFFFFFu;
+        if (sp + sz > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }  // :582
+        const uint8_t *p = s + sp;
+        sp += sz;
+        if (bc) {                                                      // :590: over the whole block, in front of the decode
+            if (sp + 4 > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }            // :591
+            uint32_t ok = 0;
+            if (lane == 0) ok = xxh32(p, sz, 0) == zx_rd32(s + sp) ? 1u : 0u;
+            if (rfl(ok) == 0u) { err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID; break; }   // :596
+            sp += 4;
+        }
+        const uint64_t rem = want - pos;                               // >= 1
+        if (h >> 31) {                                                 // :603-608: the bytes that fit; history
+            const uint32_t c = sz < rem ? sz : (uint32_t)rem;
+            copy_bytes(out + pos, p, c, lane);
+            pos += c;
+        } else {                                                       // :610
+            const uint32_t oend = rem < 0xFFFFFFFFull ? (uint32_t)rem : 0xFFFFFFFFu;
+            const uint32_t inframe = indep ? 0u : (pos < 65536u ? (uint32_t)pos : 65536u);
+            const uint32_t hist = inframe + D < 65536u ? inframe + D : 65536u;
+            const int64_t r = decode_block_wave<true, kDict, false, true>(p, sz, out + pos, oend, hist, lane, tend, inframe);
+            if (r < 0) { err = ZLZ4F_ERR_DECOMPRESSION_FAILED; break; }             // :611
+            pos += (uint64_t)r;
+        }
+    }
+    if (!cut && !err && (flg & 0x04u)) {                               // the whole frame is out: :625-635
+        if (sp + 4 > n) err = ZLZ4F_ERR_FRAME_SIZE_WRONG;              // :626
+        else {
+            uint32_t ok = 0;
+            if (lane == 0) ok = xxh32(out, pos, 0) == zx_rd32(s + sp) ? 1u : 0u;
+            if (rfl(ok) == 0u) err = ZLZ4F_ERR_CONTENT_CHECKSUM_INVALID;            // :631
+        }
+    }
+    if (lane == 0) result[f] = err ? err : (int64_t)pos;
+}
+
 // one lane per frame: the chain walk's error, before k_bfd_plan replaces F.err
 __global__ void k_bfl_save(const BFrame *__restrict__ fr, uint32_t nframes, int64_t *__restrict__ walk_err) {
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
@@ -330,6 +419,31 @@ extern "C" int zlz4_launch_bfl_decode_dict(hipStream_t st, int write, void *fram
     else
         hipLaunchKernelGGL((k_bfl_decode<false, true>), grid, block, 0, st, fr, nframes, max_blocks, src, data_off, data_len,
                            flags, cks_ok, walk_err, dst, dst_off, dst_cap, src_len, d_size, dict, fd_end, fd_len);
+    return zlz4_launch_status();
+}
+
+// Frame prefix decoding: one launch, no workspace.  d_dst_cap[f] is the number of bytes wanted of
+// frame f and the size of its slot.  ndicts == 0: no dictionaries (the plain call; the dictionary arguments are not read).
+extern "C" int zlz4_launch_bfp_decode(hipStream_t st, const uint8_t *src, const uint64_t *src_off, const uint64_t *src_len,
+                                      uint8_t *dst, const uint64_t *dst_off, const uint64_t *dst_cap, int64_t *result,
+                                      uint32_t nframes) {
+    return zlz4_launch_bfp_decode_dict(st, src, src_off, src_len, dst, dst_off, dst_cap, result, nframes, nullptr, nullptr,
+                                       nullptr, 0, nullptr);
+}
+
+extern "C" int zlz4_launch_bfp_decode_dict(hipStream_t st, const uint8_t *src, const uint64_t *src_off,
+                                           const uint64_t *src_len, uint8_t *dst, const uint64_t *dst_off,
+                                           const uint64_t *dst_cap, int64_t *result, uint32_t nframes, const uint8_t *dict,
+                                           const uint64_t *dict_off, const uint32_t *dict_len, uint32_t ndicts,
+                                           const uint32_t *dict_idx) {
+    if (nframes == 0) return 0;
+    const dim3 grid(grid_of(nframes, 4)), block(256);
+    if (ndicts == 0)
+        hipLaunchKernelGGL(k_bfp_decode<false>, grid, block, 0, st, src, src_off, src_len, dst, dst_off, dst_cap, result,
+                           nframes, nullptr, nullptr, nullptr, 0u, nullptr);
+    else
+        hipLaunchKernelGGL(k_bfp_decode<true>, grid, block, 0, st, src, src_off, src_len, dst, dst_off, dst_cap, result,
+                           nframes, dict, dict_off, dict_len, ndicts, dict_idx);
     return zlz4_launch_status();
 }
 

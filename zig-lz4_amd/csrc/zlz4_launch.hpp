@@ -141,6 +141,14 @@ int zlz4_launch_bfl_decode_dict(hipStream_t st, int write, void *frames, uint32_
                                 const uint32_t *cks_ok, const int64_t *walk_err, uint8_t *dst, const uint64_t *dst_off,
                                 const uint64_t *dst_cap, const uint64_t *src_len, int64_t *d_size, const uint8_t *dict,
                                 const uint64_t *fd_end, const uint32_t *fd_len);
+// frame prefix decoding (k_bfp_decode): one launch, no workspace; dst_cap[f] = bytes wanted of frame
+// f = size of its slot.  The plain call is the dictionary call with ndicts == 0 (no dictionary argument is read then).
+int zlz4_launch_bfp_decode(hipStream_t st, const uint8_t *src, const uint64_t *src_off, const uint64_t *src_len, uint8_t *dst,
+                           const uint64_t *dst_off, const uint64_t *dst_cap, int64_t *result, uint32_t nframes);
+int zlz4_launch_bfp_decode_dict(hipStream_t st, const uint8_t *src, const uint64_t *src_off, const uint64_t *src_len,
+                                uint8_t *dst, const uint64_t *dst_off, const uint64_t *dst_cap, int64_t *result,
+                                uint32_t nframes, const uint8_t *dict, const uint64_t *dict_off, const uint32_t *dict_len,
+                                uint32_t ndicts, const uint32_t *dict_idx);
 // dictionary frames: per-frame and per-entry dictionary descriptors of the decode, the
 // preconditions, descriptors and result merge of the compress call
 int zlz4_launch_bfdd_frame(hipStream_t st, void *frames, uint32_t nframes, const uint64_t *dict_off, const uint32_t *dict_len,

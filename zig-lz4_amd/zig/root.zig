@@ -100,6 +100,10 @@ extern "c" fn zlz4f_compress_frame_using_dict(src: [*]const u8, src_len: usize, 
 extern "c" fn zlz4f_compress_frame_using_dict_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, prefs: ?*const CPrefs, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4f_decompress_frame_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4f_frame_decompressed_size_using_dict(src: [*]const u8, src_len: usize, dict_len: usize) i64;
+extern "c" fn zlz4f_batch_decompress_frame_prefix(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32) i32;
+extern "c" fn zlz4f_batch_decompress_frame_prefix_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, d_dict: ?[*]const u8, d_dict_off: ?[*]const u64, d_dict_len: ?[*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32) i32;
+extern "c" fn zlz4f_decompress_frame_prefix(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize) i64;
+extern "c" fn zlz4f_decompress_frame_prefix_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
 extern "c" fn zlz4f_batch_decompress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 
 // ---- constants (reference src/lz4.zig:12-25, src/lz4hc.zig:28-31) ----
@@ -805,6 +809,24 @@ pub const lz4f = struct {
     }
     pub fn decompressFrameUsingDict(src: []const u8, dst: []u8, dict: []const u8) Error!usize {
         return mapFrame(zlz4f_decompress_frame_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len));
+    }
+    /// No counterpart in the reference: the first dst.len bytes of the frame's content (all of it where the frame holds
+    /// fewer), history-aware; a defect behind the cut is not reported (include/zlz4_amd.h, frame prefix decoding).
+    /// Returns min(content size, dst.len).
+    pub fn decompressFramePrefix(src: []const u8, dst: []u8) Error!usize {
+        return mapFrame(zlz4f_decompress_frame_prefix(src.ptr, src.len, dst.ptr, dst.len));
+    }
+    /// decompressFramePrefix with the frame's dictionary, as decompressFrameUsingDict
+    pub fn decompressFramePrefixUsingDict(src: []const u8, dst: []u8, dict: []const u8) Error!usize {
+        return mapFrame(zlz4f_decompress_frame_prefix_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len));
+    }
+    /// batch forms: f.dst_cap[i] is the number of bytes wanted of frame i and the size of its slot; one launch, no
+    /// workspace, no max_blocks
+    pub fn decompressFramePrefixBatch(stream: ?*anyopaque, f: Frames) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_frame_prefix(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes));
+    }
+    pub fn decompressFramePrefixBatchUsingDict(stream: ?*anyopaque, f: Frames, d: Dicts) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_frame_prefix_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, d.dict, d.off, d.len, d.ndicts, d.idx));
     }
     pub fn frameDecompressedSizeUsingDict(src: []const u8, dict_len: usize) Error!usize {
         return mapFrame(zlz4f_frame_decompressed_size_using_dict(src.ptr, src.len, dict_len));
