@@ -823,7 +823,8 @@ int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t src_
  * no frame has a dictionary and no dictionary argument is read.  nframes == 0 returns 0.  A null array or a misaligned one
  * (8 bytes for the 64-bit arrays, 4 for the 32-bit ones) returns ZLZ4_ERR_INVALID_STATE and launches nothing.
  * The host calls stage the frame and the dictionary's last 64 KiB and run a batch of one; dict == NULL with dict_len > 0
- * gives InvalidState.  No start offset; the StreamDecode calls and the segment calls have no prefix form. */
+ * gives InvalidState.  The cut is at the end only (a start offset: the frame range calls below); the StreamDecode calls
+ * and the segment calls have no prefix form. */
 int32_t zlz4f_batch_decompress_frame_prefix(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
                                             const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
                                             const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes);
@@ -836,6 +837,92 @@ int32_t zlz4f_batch_decompress_frame_prefix_using_dict(void *stream, const uint8
 int64_t zlz4f_decompress_frame_prefix(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap);
 int64_t zlz4f_decompress_frame_prefix_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                                  const uint8_t *dict, size_t dict_len);
+
+/* ---- frame index and range decoding: bytes [a, b) of frames whose blocks decode on their own (no counterpart in the
+ * reference).  A frame is a chain of blocks; the INDEX says where block k lies and at which decoded
+ * offset it starts, the RANGE DECODE decodes only the blocks that overlap [a, b), one wavefront per block.
+ *
+ * zlz4f_batch_frame_index: frame f with nb blocks in its chain gets nb + 1 entries at d_index + d_idx_off[f] (offsets and
+ *   capacities count entries): entry k < nb = { pos: the byte position of block k's header word inside the frame, dec: the
+ *   decoded offset at which block k starts }, entry nb = { pos: where the chain ended (the end mark, or the end of the
+ *   input), dec: S, the decoded size }; d_result[f] = nb.  Statuses are exactly those of zlz4f_batch_frame_decompressed_size
+ *   (flags 0: every block is sized as an independent block, the content checksum is set aside): wherever that query
+ *   answers an error the index answers the same error and writes no entry, wherever it answers S the last entry's dec is
+ *   S.  nb + 1 > d_idx_cap[f]: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL, no entry written.  max_blocks and ZLZ4_ERR_INVALID_STATE
+ *   per frame as there.  Workspace: zlz4f_batch_frame_index_workspace (= the query's), 16-byte aligned.  A null array, a
+ *   d_index / d_idx_off / d_idx_cap that is not 8-byte aligned or a refused workspace return ZLZ4_ERR_INVALID_STATE and
+ *   launch nothing; no device is the last refusal.  nframes == 0 returns 0.
+ *
+ * zlz4f_batch_plan_frame_ranges reads the index alone (d_idx_n = the index call's d_result).  Range r = { frame, reserved
+ *   (0), a, b } of a frame with decoded size S = entry[nb].dec: a' = min(a, S), b' = min(b, S); k0 = the block that holds
+ *   byte a', k1 the block that holds byte b' - 1 (k = the last entry of 0..nb with dec <= the byte, found by bisection; a
+ *   block that decodes to nothing never holds a byte).  d_dst_cap[r] = b' - dec[k0], the slot the decode call needs; it is
+ *   0, with no items, when a' == b', d_idx_n[frame] < 0, a > b or frame >= nframes (the decode call reports those), and
+ *   when the entries found are no such blocks (an index that is not sorted).  d_dst_off = the exclusive scan of the slot
+ *   sizes rounded up to `align` (0, 1 or a power of two up to 4096, as zlz4_batch_plan_outputs); d_totals[0] = the arena
+ *   size, d_totals[1] = the sum of k1 - k0 + 1 = the max_items of the decode call.  One 16-byte read-back sizes everything.
+ *   nranges == 0 stores two zeros.  Null or misaligned (8 bytes) arrays: ZLZ4_ERR_INVALID_STATE, nothing launched.
+ *
+ * zlz4f_batch_decompress_frame_range.  OUTPUT (zero-copy, block-aligned): slot r receives the decode of blocks k0..k1 from
+ *   the start of block k0 up to byte b'; the wanted bytes stand at d_dst + d_dst_off[r] + d_skip[r], d_skip[r] = a' -
+ *   dec[k0], and d_result[r] = b' - a'.  (The head of block k0 has to exist somewhere, the bytes behind it refer to it;
+ *   left in the slot it costs no scratch and no second pass.)  No byte outside [d_dst_off[r], d_dst_off[r] + b' - dec[k0])
+ *   is written; on any error d_skip[r] = 0 and nothing of the slot is promised.  The index is the caller's data and is NOT
+ *   trusted: every position taken from it is checked against the frame before it is used as an address.  FLG and the block
+ *   size come from the frame's own header.  Per range, in this order:
+ *   1. ZLZ4_ERR_INVALID_STATE for frame >= nframes, a > b, reserved != 0.  Then d_idx_n[frame] < 0: that code.  Then a
+ *      header error of the frame: that code.  Then ZLZ4_ERR_INVALID_STATE when entry 0's pos is not the header size, or
+ *      -- a' < b' -- the entries k0..k1+1 are not a chain: k0 / k1 not found or k1 < k0, dec[k0] > a', dec[k1] >= b',
+ *      dec[k1+1] < b', or for a k in k0..k1 pos[k+1] <= pos[k], pos[k] + 4 > src_len, pos[k+1] > src_len, dec[k+1] < dec[k],
+ *      dec[k+1] - dec[k] above the header's block size.
+ *   2. a' == b': 0, d_skip[r] = 0; nothing of the frame behind the header is read.
+ *   3. d_dst_cap[r] < b' - dec[k0]: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL.
+ *   4. The range's k1 - k0 + 1 items do not fit max_items (items are laid out in range order; a range that does not fit
+ *      still takes its room, as a frame in max_blocks): ZLZ4_ERR_INVALID_STATE.
+ *   5. The first failing block in block order decides.  Block k, header word w at pos[k], sz = w & 0x7FFFFFFF:
+ *      w == 0 (the end mark) or pos[k] + 4 + sz (+ 4 with FLG 0x10) != pos[k+1]: ZLZ4_ERR_INVALID_STATE (not this frame's index).  A block
+ *      checksum mismatch: ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID (over the whole block, also for a cut block).  A stored block:
+ *      sz != dec[k+1] - dec[k] is ZLZ4_ERR_INVALID_STATE, else the wanted part is copied.  A compressed block wanted in full
+ *      (dec[k+1] <= b'): zlz4_batch_decompress_safe with capacity dec[k+1] - dec[k]; an error or another result is
+ *      ZLZ4F_ERR_DECOMPRESSION_FAILED, so a wrong dec of a full block is caught (one exception: a step of 0 is a capacity
+ *      of 0, which the decoder answers with 0 without reading, src/lz4.zig:98).  The one block that b' cuts:
+ *      zlz4_batch_decompress_safe_prefix with b' - dec[k1] bytes wanted; an error, or fewer bytes than wanted, is
+ *      ZLZ4F_ERR_DECOMPRESSION_FAILED; nothing behind the cut is validated.
+ *   6. Otherwise b' - a'.
+ *   NOTHING outside blocks k0..k1 is read or validated: a defect elsewhere in the frame is not reported, the content
+ *   checksum is never checked.  A linked-declared frame (FLG 0x20 clear) is taken as it is: a touched block that refers to
+ *   earlier output answers ZLZ4F_ERR_DECOMPRESSION_FAILED, as zlz4f_batch_decompress_frame does (and zlz4f_batch_frame_index
+ *   answers that for the frame).  Dictionary frames, a start offset inside one block and the segment calls are not served.
+ *   Workspace: zlz4f_batch_decompress_frame_range_workspace(nranges, max_items) bytes, 16-byte aligned.  Null arrays
+ *   (d_dst may be null only when max_items == 0), misaligned (8 bytes) arrays or a refused workspace: ZLZ4_ERR_INVALID_STATE,
+ *   nothing launched; then the device.  nranges == 0 returns 0.
+ * All three: asynchronous on `stream`, a fixed launch sequence, nothing allocated, nothing read back (graph-capturable).
+ * The index stays valid for every later read of the same frame bytes.
+ *
+ * zlz4f_decompress_frame_range: one frame in HOST memory; exactly the b' - a' wanted bytes arrive at dst[0..).  Header errors
+ *   are answered on the host, then a > b (ZLZ4_ERR_INVALID_STATE); the frame is staged, a host walk of the chain sizes the
+ *   table, then index, plan and range run as a batch of one.  An index error is the result; dst_cap < b' - a' gives
+ *   ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.  It BUILDS THE INDEX ON EVERY CALL (one size query of the whole
+ *   frame): a caller with several reads of one frame keeps the index and uses the batch calls. */
+typedef struct { uint64_t pos; uint64_t dec; } zlz4f_index_entry;                            /* 16 bytes */
+typedef struct { uint32_t frame; uint32_t reserved; uint64_t a; uint64_t b; } zlz4f_range;   /* 24 bytes */
+size_t  zlz4f_batch_frame_index_workspace(uint32_t nframes, uint32_t max_blocks);
+int32_t zlz4f_batch_frame_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                zlz4f_index_entry *d_index, const uint64_t *d_idx_off, const uint64_t *d_idx_cap,
+                                int64_t *d_result, uint32_t nframes, uint32_t max_blocks, void *d_workspace,
+                                size_t workspace_bytes);
+int32_t zlz4f_batch_plan_frame_ranges(void *stream, const zlz4f_index_entry *d_index, const uint64_t *d_idx_off,
+                                      const int64_t *d_idx_n, uint32_t nframes, const zlz4f_range *d_range, uint32_t nranges,
+                                      uint32_t align, uint64_t *d_dst_off, uint64_t *d_dst_cap, uint64_t *d_totals);
+size_t  zlz4f_batch_decompress_frame_range_workspace(uint32_t nranges, uint32_t max_items);
+int32_t zlz4f_batch_decompress_frame_range(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                           const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
+                                           const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nframes,
+                                           const zlz4f_range *d_range, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                           const uint64_t *d_dst_cap, uint64_t *d_skip, int64_t *d_result, uint32_t nranges,
+                                           uint32_t max_items, void *d_workspace, size_t workspace_bytes);
+int64_t zlz4f_decompress_frame_range(const uint8_t *src, size_t src_len, uint64_t a, uint64_t b, uint8_t *dst,
+                                     size_t dst_cap);
 
 /* ---- dictionary frames at the HC levels 3..9 (what `lz4 -9 -D dict` and LZ4F_compressFrame_usingCDict with a level
  * produce; no counterpart in the reference).  The _ex calls are the calls they are named after, with the same argument

@@ -142,6 +142,12 @@ SYMBOLS = {
     "zlz4f_batch_decompress_frame_prefix_using_dict": (_I32, [_VP] * 8 + [_U32, _VP, _VP, _VP, _U32, _VP]),
     "zlz4f_decompress_frame_prefix": (_I64, [_VP, _SZ, _VP, _SZ]),
     "zlz4f_decompress_frame_prefix_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ]),
+    "zlz4f_batch_frame_index_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_frame_index": (_I32, [_VP] * 8 + [_U32, _U32, _VP, _SZ]),
+    "zlz4f_batch_plan_frame_ranges": (_I32, [_VP] * 4 + [_U32, _VP, _U32, _U32, _VP, _VP, _VP]),
+    "zlz4f_batch_decompress_frame_range_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_decompress_frame_range": (_I32, [_VP] * 7 + [_U32] + [_VP] * 6 + [_U32, _U32, _VP, _SZ]),
+    "zlz4f_decompress_frame_range": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -927,6 +933,124 @@ class lz4f:
             batch_decompress_frame_prefix(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, d_dict, dict_off,
                                           dict_len, idx)
         return _unstage(d_dst, offs, result)
+
+
+    # frame index and range decoding (include/zlz4_amd.h)
+    @staticmethod
+    def frameIndexBatchWorkspace(nframes, max_blocks):
+        return lib().zlz4f_batch_frame_index_workspace(nframes, max_blocks)
+
+    @staticmethod
+    def frameIndexBatch(d_src, src_off, src_len, index, idx_off, idx_cap, result, max_blocks, workspace=None):
+        """zlz4f_batch_frame_index on torch CUDA tensors: index int64 [entries, 2] = (pos, dec) per entry, idx_off / idx_cap
+        int64 per frame in entries, result int64 = the frame's block count or its error code."""
+        import torch
+        nf = src_len.numel()
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_frame_index_workspace(nf, max_blocks)), dtype=torch.uint8,
+                                    device=d_src.device)
+        _check(lib().zlz4f_batch_frame_index(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(index),
+                                             _ptr(idx_off), _ptr(idx_cap), _ptr(result), nf, max_blocks, _ptr(workspace),
+                                             workspace.numel()))
+
+    @staticmethod
+    def packRanges(ranges):
+        """[(frame, a, b)] -> numpy uint64 [n, 3], the memory layout of zlz4f_range (frame in the low word of column 0, the
+        reserved word 0)."""
+        import numpy as np
+        arr = np.zeros((len(ranges), 3), dtype=np.uint64)
+        for i, (f, a, b) in enumerate(ranges):
+            if not (0 <= f < 1 << 32 and 0 <= a < 1 << 64 and 0 <= b < 1 << 64):
+                raise ValueError("range %d: frame is a u32, a and b are u64" % i)
+            arr[i] = (f, a, b)
+        return arr
+
+    @staticmethod
+    def planFrameRanges(index, idx_off, idx_n, ranges, dst_off, dst_cap, totals, align=0):
+        """zlz4f_batch_plan_frame_ranges: ranges int64 [n, 3] (packRanges), dst_off / dst_cap int64 [n], totals int64 [2] =
+        (arena bytes, items)."""
+        _check(lib().zlz4f_batch_plan_frame_ranges(_stream(), _ptr(index), _ptr(idx_off), _ptr(idx_n), idx_n.numel(),
+                                                   _ptr(ranges), ranges.shape[0], align, _ptr(dst_off), _ptr(dst_cap),
+                                                   _ptr(totals)))
+
+    @staticmethod
+    def decompressFrameRangeBatchWorkspace(nranges, max_items):
+        return lib().zlz4f_batch_decompress_frame_range_workspace(nranges, max_items)
+
+    @staticmethod
+    def decompressFrameRangeBatch(d_src, src_off, src_len, index, idx_off, idx_n, ranges, d_dst, dst_off, dst_cap, skip,
+                                  result, max_items, workspace=None):
+        """zlz4f_batch_decompress_frame_range: range r's wanted bytes are d_dst[dst_off[r] + skip[r] ..][: result[r]]."""
+        import torch
+        nr = ranges.shape[0]
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_decompress_frame_range_workspace(nr, max_items)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_decompress_frame_range(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(index),
+                                                        _ptr(idx_off), _ptr(idx_n), idx_n.numel(), _ptr(ranges), _ptr(d_dst),
+                                                        _ptr(dst_off), _ptr(dst_cap), _ptr(skip), _ptr(result), nr,
+                                                        max_items, _ptr(workspace), workspace.numel()))
+
+    class FrameIndex:
+        """What frameIndex returns: the staged frames (d_src, src_off, src_len), the device index (index, idx_off) and the
+        per-frame results: idx_n on the device, `results` on the host (a block count or an error code per frame)."""
+
+        def __init__(self, d_src, src_off, src_len, index, idx_off, idx_n, results):
+            self.d_src, self.src_off, self.src_len = d_src, src_off, src_len
+            self.index, self.idx_off, self.idx_n, self.results = index, idx_off, idx_n, results
+
+    @staticmethod
+    def frameIndex(frames, device="cuda"):
+        """Stage `frames` and index them (zlz4f_batch_frame_index) -> FrameIndex, to be read any number of times with
+        decompressFrameRanges.  A frame the size query fails keeps its error code in .results."""
+        import torch
+        nf = len(frames)
+        d_src, src_off, src_len = _stage(frames, device)
+        blocks = [_chain_blocks(bytes(f)) for f in frames]
+        caps = [b + 1 for b in blocks]
+        index = torch.zeros((max(1, sum(caps)), 2), dtype=torch.int64, device=device)
+        idx_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+        idx_n = torch.zeros(nf, dtype=torch.int64, device=device)
+        if nf:
+            lz4f.frameIndexBatch(d_src, src_off, src_len, index, idx_off,
+                                 torch.tensor(caps, dtype=torch.int64, device=device), idx_n, sum(blocks))
+        return lz4f.FrameIndex(d_src, src_off, src_len, index, idx_off, idx_n, idx_n.cpu().tolist())
+
+    @staticmethod
+    def decompressFrameRanges(indexed, ranges, align=0):
+        """Bytes [a, b) of frame `frame` for every (frame, a, b) of `ranges` (both clamped to the frame's size) -> list of
+        bytes or error codes.  Plan, one read-back of the totals, decode, one read-back of the data."""
+        import torch
+        nr = len(ranges)
+        if nr == 0:
+            return []
+        dev = indexed.d_src.device
+        d_range = torch.from_numpy(lz4f.packRanges(ranges).view("int64")).to(dev)
+        dst_off = torch.empty(nr, dtype=torch.int64, device=dev)
+        dst_cap = torch.empty(nr, dtype=torch.int64, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        lz4f.planFrameRanges(indexed.index, indexed.idx_off, indexed.idx_n, d_range, dst_off, dst_cap, totals, align)
+        arena, items = totals.cpu().tolist()
+        d_dst = torch.empty(max(1, arena), dtype=torch.uint8, device=dev)
+        skip = torch.empty(nr, dtype=torch.int64, device=dev)
+        result = torch.empty(nr, dtype=torch.int64, device=dev)
+        lz4f.decompressFrameRangeBatch(indexed.d_src, indexed.src_off, indexed.src_len, indexed.index, indexed.idx_off,
+                                       indexed.idx_n, d_range, d_dst, dst_off, dst_cap, skip, result, items)
+        back = torch.stack((dst_off, skip, result)).cpu().tolist()
+        host = d_dst.cpu().numpy().tobytes()
+        return [host[o + s:o + s + r] if r >= 0 else r for o, s, r in zip(*back)]
+
+    @staticmethod
+    def decompressFrameRange(src, a, b):
+        """zlz4f_decompress_frame_range: bytes [a, b) of one frame in host memory (both clamped to the frame's size).  The
+        index is built on every call; several reads of one frame: frameIndex + decompressFrameRanges."""
+        s, n = _in(src)
+        cap = max(0, min(b, 1 << 62) - a)
+        if cap > 1 << 20:                              # (b may lie far behind the frame's end)
+            cap = min(cap, max(0, lz4f.frameDecompressedSize(src) - a))
+        d = (C.c_uint8 * max(1, cap))()
+        r = _check(lib().zlz4f_decompress_frame_range(C.addressof(s), n, a, b, C.addressof(d), cap))
+        return bytes(d[:r])
 
 
 def _offsets(lens):

@@ -389,6 +389,43 @@ inline Result decompressFramePrefixBatchUsingDict(void *stream, const Frames &f,
     return wrap(zlz4f_batch_decompress_frame_prefix_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap,
                                                                f.result, f.nframes, d.dict, d.off, d.len, d.ndicts, d.idx));
 }
+// frame index and range decoding (include/zlz4_amd.h; no counterpart in the reference): frameIndexBatch keeps the per-block
+// decoded sizes of the size query as (position, decoded offset) entries, planFrameRanges sizes the slots and the item table
+// from the index alone, decompressFrameRangeBatch decodes only the blocks that overlap [a, b): range r's bytes stand at
+// dst + dst_off[r] + skip[r].  The index is the caller's data and is checked against the frame.  decompressFrameRange: one
+// frame from host memory, exactly [a, b) at dst; it builds the index on every call.
+using IndexEntry = zlz4f_index_entry;
+using Range = zlz4f_range;
+struct FrameIndex { const IndexEntry *index; const std::uint64_t *idx_off; const std::int64_t *idx_n; };
+inline std::size_t frameIndexBatchWorkspace(std::uint32_t nframes, std::uint32_t max_blocks) {
+    return zlz4f_batch_frame_index_workspace(nframes, max_blocks);
+}
+inline Result frameIndexBatch(void *stream, const Frames &f, IndexEntry *d_index, const std::uint64_t *d_idx_off,
+                              const std::uint64_t *d_idx_cap, std::int64_t *d_idx_n, std::uint32_t max_blocks, void *ws,
+                              std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_frame_index(stream, f.src, f.src_off, f.src_len, d_index, d_idx_off, d_idx_cap, d_idx_n, f.nframes,
+                                        max_blocks, ws, ws_bytes));
+}
+inline Result planFrameRanges(void *stream, const FrameIndex &x, std::uint32_t nframes, const Range *d_range, std::uint32_t nranges,
+                              std::uint32_t align, std::uint64_t *d_dst_off, std::uint64_t *d_dst_cap, std::uint64_t *d_totals) {
+    return wrap(zlz4f_batch_plan_frame_ranges(stream, x.index, x.idx_off, x.idx_n, nframes, d_range, nranges, align, d_dst_off,
+                                              d_dst_cap, d_totals));
+}
+inline std::size_t decompressFrameRangeBatchWorkspace(std::uint32_t nranges, std::uint32_t max_items) {
+    return zlz4f_batch_decompress_frame_range_workspace(nranges, max_items);
+}
+// f.dst, f.dst_off, f.dst_cap, f.result are per RANGE here (nranges of them), f.src* and f.nframes per frame
+inline Result decompressFrameRangeBatch(void *stream, const Frames &f, const FrameIndex &x, const Range *d_range,
+                                        std::uint64_t *d_skip, std::uint32_t nranges, std::uint32_t max_items, void *ws,
+                                        std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_decompress_frame_range(stream, f.src, f.src_off, f.src_len, x.index, x.idx_off, x.idx_n, f.nframes,
+                                                   d_range, f.dst, f.dst_off, f.dst_cap, d_skip, f.result, nranges, max_items, ws,
+                                                   ws_bytes));
+}
+inline Result decompressFrameRange(const std::uint8_t *src, std::size_t n, std::uint64_t a, std::uint64_t b, std::uint8_t *dst,
+                                   std::size_t cap) {
+    return wrap(zlz4f_decompress_frame_range(src, n, a, b, dst, cap));
+}
 }  // namespace lz4f
 
 }  // namespace zlz4

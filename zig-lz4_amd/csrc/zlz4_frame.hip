@@ -2146,3 +2146,537 @@ int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t n, s
 }
 
 }  // extern "C"
+
+// ====================================================================== frame index and range decoding
+// zlz4f_batch_frame_index keeps what the size query computes and drops -- the per-block decoded sizes -- as a table of
+// (position, decoded offset) per block; zlz4f_batch_decompress_frame_range decodes the blocks that overlap [a, b) through
+// the block decoders, one item (= one block of one range) per wavefront.  The index is the caller's data: k_bfr_range and
+// k_bfr_expand check every entry they use against the frame before a position becomes an address.
+namespace {
+
+// one wavefront per frame: k_bfq_total's status over the same entries in the same order, then -- no error -- the nb + 1
+// index entries: 64 blocks per step with a shuffle prefix sum of their sizes (k_frame_plan's scan)
+__global__ __launch_bounds__(256) void k_bfi_index(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                                                   const uint64_t *__restrict__ data_off, const uint32_t *__restrict__ data_len,
+                                                   const uint32_t *__restrict__ flags, const int64_t *__restrict__ sizes,
+                                                   const uint32_t *__restrict__ cks_ok, const uint64_t *__restrict__ src_off,
+                                                   const uint64_t *__restrict__ src_len, zlz4f_index_entry *__restrict__ index,
+                                                   const uint64_t *__restrict__ idx_off, const uint64_t *__restrict__ idx_cap,
+                                                   int64_t *__restrict__ result) {
+    const uint32_t f = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    int64_t out = 0;
+    if (F.status < 0) out = F.status;                                                  // :547
+    else if (!bf_fits(F, max_blocks)) out = ZLZ4_ERR_INVALID_STATE;
+    else {
+        const bool bc = (F.flg & 0x10u) != 0;
+        unsigned long long bad = ~0ull;                               // this lane's first failing block
+        int32_t code = 0;
+        for (uint64_t j = lane; j < F.nb && bad == ~0ull; j += 64u) {
+            const uint64_t i = F.base + j;
+            int32_t err = 0;
+            if (bc && cks_ok[i] == 2u) err = ZLZ4F_ERR_FRAME_SIZE_WRONG;               // :591
+            else if (bc && cks_ok[i] == 0u) err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID;    // :596
+            else if (!(flags[i] & kBlkStored) && data_len[i] != 0 && sizes[i] < 0) err = ZLZ4F_ERR_DECOMPRESSION_FAILED;   // :611
+            if (err) { bad = j; code = err; }
+        }
+        unsigned long long first = bad;
+        for (uint32_t d = 32u; d >= 1u; d >>= 1) {
+            const unsigned long long o = __shfl_xor(first, (int)d);
+            first = o < first ? o : first;
+        }
+        if (first != ~0ull) out = (int64_t)(int32_t)zlz4::rdlane((uint32_t)code, zlz4::first_lane(zlz4::ballot(bad == first)));
+        if (!out) out = F.err;
+        if (!out && (F.flg & 0x04u) && F.end + 4 > src_len[f]) out = ZLZ4F_ERR_FRAME_SIZE_WRONG;   // :626
+        if (!out && F.nb + 1u > idx_cap[f]) out = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+    }
+    if (out) { if (lane == 0) result[f] = out; return; }
+    zlz4f_index_entry *e = index + idx_off[f];
+    const uint64_t so = src_off[f];
+    uint64_t run = 0, end_pos = (uint64_t)F.status;                   // (no block: the chain ends behind the header)
+    for (uint64_t b0 = 0; b0 < F.nb; b0 += 64u) {
+        const uint64_t j = b0 + lane, i = F.base + j;
+        uint64_t sz = 0;
+        if (j < F.nb) sz = (flags[i] & kBlkStored) ? data_len[i] : (data_len[i] != 0 ? (uint64_t)sizes[i] : 0u);
+        uint64_t incl = sz;                                           // inclusive scan over the 64 lanes
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t lo = __shfl_up((uint32_t)incl, d), hi = __shfl_up((uint32_t)(incl >> 32), d);
+            if (lane >= d) incl += ((uint64_t)hi << 32) | lo;
+        }
+        if (j < F.nb) {
+            zlz4f_index_entry E;
+            E.pos = data_off[i] - so - 4u;
+            E.dec = run + incl - sz;
+            e[j] = E;
+            if (j + 1u == F.nb) end_pos = data_off[i] - so + data_len[i] + ((flags[i] & kBlkCks) ? 4u : 0u);
+        }
+        run += ((uint64_t)zlz4::rdlane((uint32_t)(incl >> 32), 63) << 32) | zlz4::rdlane((uint32_t)incl, 63);
+    }
+    const uint32_t owner = F.nb ? (uint32_t)((F.nb - 1u) & 63u) : 0u;                  // the lane that saw the last block
+    end_pos = ((uint64_t)zlz4::rdlane((uint32_t)(end_pos >> 32), owner) << 32) | zlz4::rdlane((uint32_t)end_pos, owner);
+    if (lane == 0) {
+        zlz4f_index_entry E;
+        E.pos = end_pos;
+        E.dec = run;
+        e[F.nb] = E;
+        result[f] = (int64_t)F.nb;
+    }
+}
+
+// ------------------------------------------------------------------ ranges
+// what k_bfr_range leaves per range.  status < 0: the range's result; else n items (n == 0: the empty range, result 0)
+struct BRange {
+    uint64_t n;         // items = k1 - k0 + 1
+    uint64_t base;      // first item (exclusive scan of n)
+    uint64_t k0;        // first block
+    uint64_t a, b;      // a', b'
+    uint64_t d0;        // dec[k0] (the empty range: a')
+    int64_t status;
+    uint32_t bc;        // FLG 0x10 of the frame's header
+    uint32_t pad;
+};
+
+__device__ __forceinline__ bool bfr_fits(const BRange &G, uint32_t max_items) { return G.n == 0 || G.base + G.n <= max_items; }
+
+// the block that holds decoded byte t: the last entry k of 0..nb with dec[k] <= t (bisection for the first entry above t).
+// ~0 when entry 0 is already above t.  On a sorted index with t < dec[nb] the block is < nb and does not decode to nothing.
+__host__ __device__ inline uint64_t bfr_block_of(const zlz4f_index_entry *e, uint64_t nb, uint64_t t) {
+    uint64_t lo = 0, hi = nb + 1u;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2u;
+        if (e[mid].dec <= t) lo = mid + 1u; else hi = mid;
+    }
+    return lo - 1u;
+}
+
+// a', b', k0, k1 of range R from the index alone; false = nothing to decode (frame / a > b / index status / a' == b') or
+// the entries found are no blocks (an index that is not sorted)
+struct BfrSpan { uint64_t a, b, k0, k1; };
+__device__ inline bool bfr_span(const zlz4f_range &R, const zlz4f_index_entry *__restrict__ index,
+                                const uint64_t *__restrict__ idx_off, const int64_t *__restrict__ idx_n, uint32_t nframes,
+                                BfrSpan &s, const zlz4f_index_entry *&e, uint64_t &nb) {
+    s = BfrSpan{0, 0, 0, 0};
+    if (R.frame >= nframes || R.a > R.b || idx_n[R.frame] < 0) return false;
+    nb = (uint64_t)idx_n[R.frame];
+    e = index + idx_off[R.frame];
+    const uint64_t S = e[nb].dec;
+    s.a = R.a < S ? R.a : S;
+    s.b = R.b < S ? R.b : S;
+    if (s.a == s.b) return false;
+    s.k0 = bfr_block_of(e, nb, s.a);
+    s.k1 = bfr_block_of(e, nb, s.b - 1u);
+    return s.k0 < nb && s.k1 < nb && s.k0 <= s.k1 && e[s.k0].dec <= s.a;
+}
+
+// exclusive scan of one value per thread over the one workgroup of 1024 threads (k_bf_scan's LDS scan); -> the sum in
+// front of thread t, `total` = the sum of all
+__device__ inline uint64_t bfr_wg_scan(uint64_t s, uint64_t *part, uint64_t &total) {
+    const uint32_t t = threadIdx.x;
+    __syncthreads();
+    part[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {
+        const uint64_t v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    total = part[1023];
+    return part[t] - s;
+}
+
+// plan, one lane per range: dst_cap[r] = the slot size; dst_off[r] holds the item count until k_bfr_plan_scan replaces it
+__global__ void k_bfr_plan(const zlz4f_index_entry *__restrict__ index, const uint64_t *__restrict__ idx_off,
+                           const int64_t *__restrict__ idx_n, uint32_t nframes, const zlz4f_range *__restrict__ range,
+                           uint32_t nranges, uint64_t *__restrict__ dst_off, uint64_t *__restrict__ dst_cap) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nranges) return;
+    BfrSpan s;
+    const zlz4f_index_entry *e = nullptr;
+    uint64_t nb = 0;
+    const bool ok = bfr_span(range[r], index, idx_off, idx_n, nframes, s, e, nb);
+    dst_cap[r] = ok ? s.b - e[s.k0].dec : 0u;
+    dst_off[r] = ok ? s.k1 - s.k0 + 1u : 0u;
+}
+
+// one workgroup: dst_off = the exclusive scan of the slot sizes rounded up to `align`; totals = { arena bytes, items }
+__global__ __launch_bounds__(1024) void k_bfr_plan_scan(uint32_t nranges, uint64_t align, uint64_t *__restrict__ dst_off,
+                                                        const uint64_t *__restrict__ dst_cap, uint64_t *__restrict__ totals) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (nranges + 1023u) / 1024u;
+    const uint64_t b0 = (uint64_t)t * chunk;
+    const uint32_t lo = b0 < nranges ? (uint32_t)b0 : nranges;
+    const uint32_t hi = b0 + chunk < nranges ? (uint32_t)(b0 + chunk) : nranges;
+    auto slot = [&](uint64_t c) -> uint64_t { return (c + (align - 1u)) & ~(align - 1u); };
+    uint64_t bytes = 0, items = 0;
+    for (uint32_t r = lo; r < hi; r++) { bytes += slot(dst_cap[r]); items += dst_off[r]; }
+    uint64_t tot_bytes, tot_items;
+    uint64_t run = bfr_wg_scan(bytes, part, tot_bytes);
+    (void)bfr_wg_scan(items, part, tot_items);
+    for (uint32_t r = lo; r < hi; r++) { dst_off[r] = run; run += slot(dst_cap[r]); }
+    if (t == 0) { totals[0] = tot_bytes; totals[1] = tot_items; }
+}
+
+// decode step 1, one wavefront per range: statuses 1-3 of include/zlz4_amd.h and the item count.  Everything up to the
+// chain check depends on the range alone (wave-uniform); the lanes share the pairs (k, k + 1) of the chain.
+__global__ __launch_bounds__(256) void k_bfr_range(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                                   const uint64_t *__restrict__ src_len,
+                                                   const zlz4f_index_entry *__restrict__ index,
+                                                   const uint64_t *__restrict__ idx_off, const int64_t *__restrict__ idx_n,
+                                                   uint32_t nframes, const zlz4f_range *__restrict__ range,
+                                                   const uint64_t *__restrict__ dst_cap, uint32_t nranges,
+                                                   BRange *__restrict__ rg) {
+    const uint32_t r = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (r >= nranges) return;
+    const zlz4f_range R = range[r];
+    BRange G = {};
+    int64_t st = 0;
+    if (R.frame >= nframes || R.a > R.b || R.reserved != 0) st = ZLZ4_ERR_INVALID_STATE;
+    else if (idx_n[R.frame] < 0) st = idx_n[R.frame];
+    else {
+        const uint64_t n = src_len[R.frame];
+        const uint8_t *s = src + src_off[R.frame];
+        const ParsedHeader ph = parse_header(s, n < 19u ? (size_t)n : 19u);    // (reads the bytes it is given, no more)
+        if (ph.size < 0) st = ph.size;
+        else {
+            BfrSpan sp;
+            const zlz4f_index_entry *e = nullptr;
+            uint64_t nb = 0;
+            const bool found = bfr_span(R, index, idx_off, idx_n, nframes, sp, e, nb);
+            G.a = sp.a; G.b = sp.b; G.d0 = sp.a;
+            G.bc = (ph.flg & 0x10u) ? 1u : 0u;
+            if (e[0].pos != (uint64_t)ph.size) st = ZLZ4_ERR_INVALID_STATE;
+            else if (sp.a != sp.b) {
+                bool bad = !found;
+                if (found) {
+                    for (uint64_t k = sp.k0 + lane; k <= sp.k1; k += 64u) {
+                        const zlz4f_index_entry E = e[k], N = e[k + 1u];
+                        if (N.pos <= E.pos || E.pos > n || n - E.pos < 4u || N.pos > n || N.dec < E.dec ||
+                            N.dec - E.dec > ph.block_size)
+                            bad = true;
+                    }
+                    if (e[sp.k1].dec >= sp.b || e[sp.k1 + 1u].dec < sp.b) bad = true;
+                }
+                if (zlz4::ballot(bad) != 0) st = ZLZ4_ERR_INVALID_STATE;
+                else if (dst_cap[r] < sp.b - e[sp.k0].dec) st = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+                else { G.n = sp.k1 - sp.k0 + 1u; G.k0 = sp.k0; G.d0 = e[sp.k0].dec; }
+            }
+        }
+    }
+    G.status = st;
+    if (lane == 0) rg[r] = G;
+}
+
+// k_bf_scan over the ranges' item counts
+__global__ __launch_bounds__(1024) void k_bfr_scan(BRange *__restrict__ rg, uint32_t nranges) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (nranges + 1023u) / 1024u;
+    const uint64_t b0 = (uint64_t)t * chunk;
+    const uint32_t lo = b0 < nranges ? (uint32_t)b0 : nranges;
+    const uint32_t hi = b0 + chunk < nranges ? (uint32_t)(b0 + chunk) : nranges;
+    uint64_t s = 0, total;
+    for (uint32_t r = lo; r < hi; r++) s += rg[r].n;
+    uint64_t run = bfr_wg_scan(s, part, total);
+    for (uint32_t r = lo; r < hi; r++) { rg[r].base = run; run += rg[r].n; }
+}
+
+// per-item error marks of k_bfr_expand, in the order k_bfr_finish reports them around the block checksum
+constexpr uint32_t kItemChain = 1u, kItemStored = 2u;
+
+// the item tables: what the block decoders, k_bfd_verify and the copy read.  A length of 0 keeps an item out of a launch.
+struct BfrTables {
+    uint64_t *data_off, *cks_off, *out_off;
+    uint32_t *data_len, *flags, *f_len, *f_cap, *p_len, *p_cap, *c_len, *ierr;
+};
+
+// decode step 3, one lane per item: its range (the last whose base is <= i, as k_bfc_desc), block k = k0 + (i - base), the
+// chain check of that block against the frame, and the item's row in every table.  k_bfr_range has checked that the header
+// word and everything up to pos[k + 1] lie inside the frame; the block's data is only used when it ends at pos[k + 1].
+__global__ void k_bfr_expand(const BRange *__restrict__ rg, uint32_t nranges, uint32_t max_items,
+                             const zlz4f_range *__restrict__ range, const uint8_t *__restrict__ src,
+                             const uint64_t *__restrict__ src_off, const zlz4f_index_entry *__restrict__ index,
+                             const uint64_t *__restrict__ idx_off, const uint64_t *__restrict__ dst_off, BfrTables T) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_items; i += gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = nranges;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            if (rg[mid].base <= i) lo = mid + 1u; else hi = mid;
+        }
+        uint64_t d_off = 0, c_off = 0, o_off = 0;
+        uint32_t d_len = 0, fl = 0, f_len = 0, f_cap = 0, p_len = 0, p_cap = 0, c_len = 0, ierr = 0;
+        if (lo > 0) {
+            const uint32_t r = lo - 1u;
+            const BRange G = rg[r];
+            const uint64_t j = i - G.base;
+            if (j < G.n && G.status == 0 && bfr_fits(G, max_items)) {
+                const uint32_t f = range[r].frame;
+                const zlz4f_index_entry *e = index + idx_off[f];
+                const uint64_t k = G.k0 + j;
+                const zlz4f_index_entry E = e[k], N = e[k + 1u];
+                const uint64_t so = src_off[f];
+                const uint32_t w = zx_rd32(src + so + E.pos);
+                const uint32_t sz = w & 0x7FFFFFFFu;
+                if (w == 0 || E.pos + 4u + sz + (G.bc ? 4u : 0u) != N.pos) ierr = kItemChain;      // (0: the end mark, no block)
+                else {
+                    const uint32_t step = (uint32_t)(N.dec - E.dec);             // <= the block size (k_bfr_range)
+                    const uint64_t left = G.b - E.dec;                           // > 0: dec[k] <= dec[k1] < b'
+                    const uint32_t want = left < step ? (uint32_t)left : step;
+                    d_off = so + E.pos + 4u;
+                    d_len = sz;
+                    o_off = dst_off[r] + (E.dec - G.d0);
+                    if (G.bc) { fl |= kBlkCks; c_off = d_off + sz; }
+                    if (w >> 31) {
+                        fl |= kBlkStored;
+                        if (sz != step) ierr = kItemStored; else c_len = want;
+                    } else if (want == step) { f_len = sz; f_cap = step; }
+                    else { p_len = sz; p_cap = want; }
+                }
+            }
+        }
+        T.data_off[i] = d_off; T.cks_off[i] = c_off; T.out_off[i] = o_off;
+        T.data_len[i] = d_len; T.flags[i] = fl; T.f_len[i] = f_len; T.f_cap[i] = f_cap; T.p_len[i] = p_len;
+        T.p_cap[i] = p_cap; T.c_len[i] = c_len; T.ierr[i] = ierr;
+    }
+}
+
+// decode step 6, one workgroup per item: the wanted part of a stored block
+__global__ __launch_bounds__(256) void k_bfr_copy(const uint8_t *__restrict__ src, const uint64_t *__restrict__ data_off,
+                                                   const uint32_t *__restrict__ c_len, const uint64_t *__restrict__ out_off,
+                                                   uint8_t *__restrict__ dst) {
+    const uint32_t i = blockIdx.x, t = threadIdx.x;
+    const uint32_t n = c_len[i];
+    if (n == 0) return;
+    const uint8_t *p = src + data_off[i];
+    uint8_t *o = dst + out_off[i];
+    for (uint32_t k = t * 16u; k + 16u <= n; k += 256u * 16u) zlz4::st128(o + k, zlz4::ld128(p + k));
+    const uint32_t t0 = n & ~15u;
+    if (t < 16u && t0 + t < n) o[t0 + t] = p[t0 + t];
+}
+
+// decode step 7, one wavefront per range: the first failing item in block order (a min-reduction by index), else b' - a'
+__global__ __launch_bounds__(256) void k_bfr_finish(const BRange *__restrict__ rg, uint32_t nranges, uint32_t max_items,
+                                                    BfrTables T, const uint32_t *__restrict__ cks_ok,
+                                                    const int64_t *__restrict__ sizes_f, const int64_t *__restrict__ sizes_p,
+                                                    uint64_t *__restrict__ skip, int64_t *__restrict__ result) {
+    const uint32_t r = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (r >= nranges) return;
+    const BRange G = rg[r];
+    int64_t out = G.status;
+    if (!out && !bfr_fits(G, max_items)) out = ZLZ4_ERR_INVALID_STATE;
+    if (!out) {
+        unsigned long long bad = ~0ull;
+        int32_t code = 0;
+        for (uint64_t j = lane; j < G.n && bad == ~0ull; j += 64u) {
+            const uint64_t i = G.base + j;
+            int32_t err = 0;
+            if (T.ierr[i] == kItemChain) err = ZLZ4_ERR_INVALID_STATE;
+            else if ((T.flags[i] & kBlkCks) && cks_ok[i] != 1u) err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID;
+            else if (T.ierr[i] == kItemStored) err = ZLZ4_ERR_INVALID_STATE;
+            else if (T.f_len[i] != 0 && sizes_f[i] != (int64_t)T.f_cap[i]) err = ZLZ4F_ERR_DECOMPRESSION_FAILED;
+            else if (T.p_len[i] != 0 && sizes_p[i] != (int64_t)T.p_cap[i]) err = ZLZ4F_ERR_DECOMPRESSION_FAILED;
+            if (err) { bad = j; code = err; }
+        }
+        unsigned long long first = bad;
+        for (uint32_t d = 32u; d >= 1u; d >>= 1) {
+            const unsigned long long o = __shfl_xor(first, (int)d);
+            first = o < first ? o : first;
+        }
+        if (first != ~0ull) out = (int64_t)(int32_t)zlz4::rdlane((uint32_t)code, zlz4::first_lane(zlz4::ballot(bad == first)));
+    }
+    if (lane == 0) {
+        result[r] = out ? out : (int64_t)(G.b - G.a);
+        skip[r] = out ? 0u : G.a - G.d0;
+    }
+}
+
+// the range decode's workspace: the range records, the item tables, the decoders' results
+struct BfrLayout {
+    Region<BRange> ranges;
+    Region<uint64_t> data_off, cks_off, out_off;
+    Region<uint32_t> data_len, flags, cks_ok, f_len, f_cap, p_len, p_cap, c_len, ierr;
+    Region<int64_t> sizes_f, sizes_p;
+    size_t bytes = 0;
+};
+
+BfrLayout bfr_layout(uint32_t nranges, uint32_t max_items, void *ws = nullptr) {
+    const size_t m = max_items;
+    BfrLayout L;
+    Carver c{static_cast<uint8_t *>(ws)};
+    c.take(nranges, L.ranges);
+    c.take(m, L.data_off, L.cks_off, L.out_off);
+    c.take(m, L.data_len, L.flags, L.cks_ok, L.f_len, L.f_cap, L.p_len, L.p_cap, L.c_len, L.ierr);
+    c.take(m, L.sizes_f, L.sizes_p);
+    L.bytes = c.bytes;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t zlz4f_batch_frame_index_workspace(uint32_t nframes, uint32_t max_blocks) {
+    return bfd_layout(nframes, max_blocks, 0, false, kQuery).bytes;
+}
+
+// the size query's launch sequence with k_bfi_index in k_bfq_total's place; its refusals, then the device
+int32_t zlz4f_batch_frame_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                zlz4f_index_entry *d_index, const uint64_t *d_idx_off, const uint64_t *d_idx_cap,
+                                int64_t *d_result, uint32_t nframes, uint32_t max_blocks, void *d_workspace,
+                                size_t workspace_bytes) {
+    if (nframes == 0) return 0;
+    const BfArrays a = {d_src, d_src_off, d_src_len, nullptr, nullptr, nullptr, d_result, nframes, max_blocks};
+    const BfdLayout L = bfd_layout(nframes, max_blocks, 0, false, kQuery, d_workspace);
+    if (!d_index || !d_idx_off || !d_idx_cap || bf_misaligned(d_index, 8) || bf_misaligned(d_idx_off, 8) ||
+        bf_misaligned(d_idx_cap, 8) || bf_args_refused(kArgSrc | kArgWs | kArgWs16, a, nullptr, 0, d_workspace, workspace_bytes, L.bytes))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    if (bfd_prelude(st, a, false, nullptr, L) != 0) return ZLZ4_ERR_DEVICE;
+    if (max_blocks) {
+        hipLaunchKernelGGL(k_bfq_len, dim3(bf_grid(max_blocks, 256, 4096)), dim3(256), 0, st, L.data_len, L.flags, max_blocks,
+                           L.dec_len);
+        if (zlz4_launch_decompressed_size(st, d_src, L.data_off, L.dec_len, nullptr, L.sizes, max_blocks) != 0)
+            return ZLZ4_ERR_DEVICE;
+    }
+    hipLaunchKernelGGL(k_bfi_index, dim3(bf_grid(nframes, 4)), dim3(256), 0, st, L.frames, nframes, max_blocks, L.data_off,
+                       L.data_len, L.flags, L.sizes, L.cks_ok, d_src_off, d_src_len, d_index, d_idx_off, d_idx_cap, d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+int32_t zlz4f_batch_plan_frame_ranges(void *stream, const zlz4f_index_entry *d_index, const uint64_t *d_idx_off,
+                                      const int64_t *d_idx_n, uint32_t nframes, const zlz4f_range *d_range, uint32_t nranges,
+                                      uint32_t align, uint64_t *d_dst_off, uint64_t *d_dst_cap, uint64_t *d_totals) {
+    if (align > 4096u || (align & (align - 1u))) return ZLZ4_ERR_INVALID_STATE;      // 0, 1 or a power of two up to 4096
+    if (!d_totals || bf_misaligned(d_totals, 8)) return ZLZ4_ERR_INVALID_STATE;
+    if (nranges && (!d_range || !d_dst_off || !d_dst_cap || (nframes && (!d_index || !d_idx_off || !d_idx_n)))) return ZLZ4_ERR_INVALID_STATE;
+    if (bf_misaligned(d_index, 8) || bf_misaligned(d_idx_off, 8) || bf_misaligned(d_idx_n, 8) || bf_misaligned(d_range, 8) ||
+        bf_misaligned(d_dst_off, 8) || bf_misaligned(d_dst_cap, 8))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    if (nranges)
+        hipLaunchKernelGGL(k_bfr_plan, dim3(bf_grid(nranges, 256)), dim3(256), 0, st, d_index, d_idx_off, d_idx_n, nframes,
+                           d_range, nranges, d_dst_off, d_dst_cap);
+    hipLaunchKernelGGL(k_bfr_plan_scan, dim3(1), dim3(1024), 0, st, nranges, (uint64_t)(align ? align : 1u), d_dst_off,
+                       d_dst_cap, d_totals);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+size_t zlz4f_batch_decompress_frame_range_workspace(uint32_t nranges, uint32_t max_items) {
+    return bfr_layout(nranges, max_items).bytes;
+}
+
+int32_t zlz4f_batch_decompress_frame_range(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                           const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
+                                           const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nframes,
+                                           const zlz4f_range *d_range, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                           const uint64_t *d_dst_cap, uint64_t *d_skip, int64_t *d_result, uint32_t nranges,
+                                           uint32_t max_items, void *d_workspace, size_t workspace_bytes) {
+    if (nranges == 0) return 0;
+    const BfrLayout L = bfr_layout(nranges, max_items, d_workspace);
+    if (!d_range || !d_dst_off || !d_dst_cap || !d_skip || !d_result || (max_items && !d_dst) ||
+        (nframes && (!d_src || !d_src_off || !d_src_len || !d_index || !d_idx_off || !d_idx_n)))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) || bf_misaligned(d_index, 8) || bf_misaligned(d_idx_off, 8) ||
+        bf_misaligned(d_idx_n, 8) || bf_misaligned(d_range, 8) || bf_misaligned(d_dst_off, 8) || bf_misaligned(d_dst_cap, 8) ||
+        bf_misaligned(d_skip, 8) || bf_misaligned(d_result, 8))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!d_workspace || workspace_bytes < L.bytes || bf_misaligned(d_workspace, 16)) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t m = max_items, gr = bf_grid(nranges, 4);
+    const BfrTables T = {L.data_off, L.cks_off, L.out_off, L.data_len, L.flags, L.f_len, L.f_cap, L.p_len, L.p_cap, L.c_len, L.ierr};
+    hipLaunchKernelGGL(k_bfr_range, dim3(gr), dim3(256), 0, st, d_src, d_src_off, d_src_len, d_index, d_idx_off, d_idx_n, nframes,
+                       d_range, d_dst_cap, nranges, L.ranges);
+    hipLaunchKernelGGL(k_bfr_scan, dim3(1), dim3(1024), 0, st, L.ranges, nranges);
+    if (m) {
+        hipLaunchKernelGGL(k_bfr_expand, dim3(bf_grid(m, 256, 4096)), dim3(256), 0, st, L.ranges, nranges, m, d_range, d_src,
+                           d_src_off, d_index, d_idx_off, d_dst_off, T);
+        hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(m, 64)), dim3(64), 0, st, d_src, L.data_off, L.data_len, L.flags,
+                           L.cks_off, m, L.cks_ok);
+        if (zlz4_launch_decompress_safe(st, d_src, L.data_off, L.f_len, d_dst, L.out_off, L.f_cap, L.sizes_f, m) != 0 ||
+            zlz4_launch_decompress_safe_prefix(st, d_src, L.data_off, L.p_len, d_dst, L.out_off, L.p_cap, L.sizes_p, m) != 0)
+            return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bfr_copy, dim3(m), dim3(256), 0, st, d_src, L.data_off, L.c_len, L.out_off, d_dst);
+    }
+    hipLaunchKernelGGL(k_bfr_finish, dim3(gr), dim3(256), 0, st, L.ranges, nranges, m, T, L.cks_ok, L.sizes_f, L.sizes_p, d_skip,
+                       d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+// One frame from host memory: the index, the plan and the range decode as a batch of one.  The index is built on every call.
+int64_t zlz4f_decompress_frame_range(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap) {
+    if ((!src && n) || (!dst && cap)) return ZLZ4_ERR_INVALID_STATE;
+    const ParsedHeader ph = parse_header(src, n);      // header errors need no device
+    if (ph.size < 0) return ph.size;
+    if (a > b) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const bool bc = (ph.flg & 0x10u) != 0;
+    uint64_t pos = (uint64_t)ph.size, nb = 0;           // the block count for the table: k_bfd_walk's chain on the host
+    while (pos + 4 <= n) {
+        const uint32_t h = zx_rd32(src + pos);
+        const uint64_t sz = h & 0x7FFFFFFFu;
+        if (h == 0 || pos + 4 + sz > n) break;
+        pos += 4 + sz;
+        nb++;
+        if (bc) { if (pos + 4 > n) break; pos += 4; }
+    }
+    if (nb >= 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
+    const uint32_t max_blocks = (uint32_t)nb;
+    const size_t iws = zlz4f_batch_frame_index_workspace(1, max_blocks);
+    hipStream_t st = nullptr;
+    DeviceCall dc(st);
+    struct Rec {
+        FrameRec f; uint64_t idx_off, idx_cap, dst_off, dst_cap, skip, totals[2]; int64_t rres; zlz4f_range range;
+    };
+    DevBuf d_src(n, &dc), d_iws(iws, &dc), d_index((nb + 1) * sizeof(zlz4f_index_entry), &dc);
+    Staged<Rec> rec(&dc, 256);
+    if (!d_src.p || !d_iws.p || !d_index.p || !rec.d) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    rec.h.f.src_len = n; rec.h.idx_cap = nb + 1;
+    rec.h.range.a = a; rec.h.range.b = b;
+    dc.launched();
+    if (!upload(d_src, src, n, st) || !rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    Rec *r = rec.d;
+    zlz4f_index_entry *index = d_index.as<zlz4f_index_entry>();
+    int32_t rc = zlz4f_batch_frame_index(st, d_src.as<uint8_t>(), &r->f.src_off, &r->f.src_len, index, &r->idx_off, &r->idx_cap,
+                                         &r->f.result, 1, max_blocks, d_iws.p, iws);
+    if (rc != 0) return rc;
+    rc = zlz4f_batch_plan_frame_ranges(st, index, &r->idx_off, &r->f.result, 1, &r->range, 1, 0, &r->dst_off, &r->dst_cap,
+                                       r->totals);
+    if (rc != 0) return rc;
+    // one read-back: the index status, the slot and item count, and S (entry nb: the walk above is the index call's)
+    int64_t idx_n = 0;
+    uint64_t totals[2] = {0, 0};
+    zlz4f_index_entry last = {0, 0};
+    if (hipMemcpyAsync(&idx_n, &r->f.result, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(totals, r->totals, 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&last, index + nb, sizeof last, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync())
+        return ZLZ4_ERR_DEVICE;
+    if (idx_n < 0) return idx_n;
+    if ((uint64_t)idx_n != nb) return ZLZ4_ERR_DEVICE;           // cannot happen
+    const uint64_t S = last.dec, a1 = a < S ? a : S, b1 = b < S ? b : S;
+    if (cap < b1 - a1) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+    if (totals[1] > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
+    const uint32_t max_items = (uint32_t)totals[1];
+    const size_t rws = zlz4f_batch_decompress_frame_range_workspace(1, max_items);
+    DevBuf d_rws(rws, &dc), d_dst(totals[0], &dc);
+    if (!d_rws.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    dc.launched();
+    rc = zlz4f_batch_decompress_frame_range(st, d_src.as<uint8_t>(), &r->f.src_off, &r->f.src_len, index, &r->idx_off,
+                                            &r->f.result, 1, &r->range, d_dst.as<uint8_t>(), &r->dst_off, &r->dst_cap, &r->skip,
+                                            &r->rres, 1, max_items, d_rws.p, rws);
+    if (rc != 0) return rc;
+    int64_t result = 0;
+    uint64_t skip = 0;
+    if (hipMemcpyAsync(&skip, &r->skip, 8, hipMemcpyDeviceToHost, st) != hipSuccess || !read_result(dc, &r->rres, result))
+        return ZLZ4_ERR_DEVICE;
+    if (result > 0 && ((uint64_t)result > cap || skip + (uint64_t)result > totals[0] ||
+                       hipMemcpy(dst, d_dst.as<uint8_t>() + skip, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess))
+        return ZLZ4_ERR_DEVICE;
+    return result;
+}
+
+}  // extern "C"

@@ -104,6 +104,15 @@ extern "c" fn zlz4f_batch_decompress_frame_prefix(stream: ?*anyopaque, d_src: [*
 extern "c" fn zlz4f_batch_decompress_frame_prefix_using_dict(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, d_dict: ?[*]const u8, d_dict_off: ?[*]const u64, d_dict_len: ?[*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32) i32;
 extern "c" fn zlz4f_decompress_frame_prefix(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize) i64;
 extern "c" fn zlz4f_decompress_frame_prefix_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize) i64;
+extern "c" fn zlz4f_batch_frame_index_workspace(nframes: u32, max_blocks: u32) usize;
+extern "c" fn zlz4f_batch_frame_index(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_index: [*]IndexEntry, d_idx_off: [*]const u64, d_idx_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_plan_frame_ranges(stream: ?*anyopaque, d_index: [*]const IndexEntry, d_idx_off: [*]const u64, d_idx_n: [*]const i64, nframes: u32, d_range: [*]const Range, nranges: u32, alignment: u32, d_dst_off: [*]u64, d_dst_cap: [*]u64, d_totals: [*]u64) i32;
+extern "c" fn zlz4f_batch_decompress_frame_range_workspace(nranges: u32, max_items: u32) usize;
+extern "c" fn zlz4f_batch_decompress_frame_range(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_index: [*]const IndexEntry, d_idx_off: [*]const u64, d_idx_n: [*]const i64, nframes: u32, d_range: [*]const Range, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_skip: [*]u64, d_result: [*]i64, nranges: u32, max_items: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_decompress_frame_range(src: [*]const u8, src_len: usize, a: u64, b: u64, dst: [*]u8, dst_cap: usize) i64;
+/// zlz4f_index_entry / zlz4f_range of include/zlz4_amd.h
+pub const IndexEntry = extern struct { pos: u64, dec: u64 };
+pub const Range = extern struct { frame: u32, reserved: u32 = 0, a: u64, b: u64 };
 extern "c" fn zlz4f_batch_decompress_frame(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_result: [*]i64, nframes: u32, max_blocks: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 
 // ---- constants (reference src/lz4.zig:12-25, src/lz4hc.zig:28-31) ----
@@ -827,6 +836,29 @@ pub const lz4f = struct {
     }
     pub fn decompressFramePrefixBatchUsingDict(stream: ?*anyopaque, f: Frames, d: Dicts) (Error || root.Error)!void {
         return mapBatch(zlz4f_batch_decompress_frame_prefix_using_dict(stream, f.src, f.src_off, f.src_len, f.dst, f.dst_off, f.dst_cap, f.result, f.nframes, d.dict, d.off, d.len, d.ndicts, d.idx));
+    }
+    /// No counterpart in the reference: the frame index and range decoding (include/zlz4_amd.h).  frameIndexBatch keeps the
+    /// size query's per-block sizes as (pos, dec) entries; planFrameRanges sizes slots and items from the index alone;
+    /// decompressFrameRangeBatch decodes only the blocks that overlap [a, b): range r's bytes stand at dst + dst_off[r] +
+    /// skip[r].  The index is the caller's data and is checked against the frame.
+    pub fn frameIndexBatchWorkspace(nframes: u32, max_blocks: u32) usize {
+        return zlz4f_batch_frame_index_workspace(nframes, max_blocks);
+    }
+    pub fn frameIndexBatch(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, index: [*]IndexEntry, idx_off: [*]const u64, idx_cap: [*]const u64, idx_n: [*]i64, nframes: u32, max_blocks: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_frame_index(stream, src, src_off, src_len, index, idx_off, idx_cap, idx_n, nframes, max_blocks, workspace, workspace_bytes));
+    }
+    pub fn planFrameRanges(stream: ?*anyopaque, index: [*]const IndexEntry, idx_off: [*]const u64, idx_n: [*]const i64, nframes: u32, ranges: [*]const Range, nranges: u32, alignment: u32, dst_off: [*]u64, dst_cap: [*]u64, totals: [*]u64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_plan_frame_ranges(stream, index, idx_off, idx_n, nframes, ranges, nranges, alignment, dst_off, dst_cap, totals));
+    }
+    pub fn decompressFrameRangeBatchWorkspace(nranges: u32, max_items: u32) usize {
+        return zlz4f_batch_decompress_frame_range_workspace(nranges, max_items);
+    }
+    pub fn decompressFrameRangeBatch(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, index: [*]const IndexEntry, idx_off: [*]const u64, idx_n: [*]const i64, nframes: u32, ranges: [*]const Range, dst: [*]u8, dst_off: [*]const u64, dst_cap: [*]const u64, skip: [*]u64, result: [*]i64, nranges: u32, max_items: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_frame_range(stream, src, src_off, src_len, index, idx_off, idx_n, nframes, ranges, dst, dst_off, dst_cap, skip, result, nranges, max_items, workspace, workspace_bytes));
+    }
+    /// bytes [a, b) of one frame in host memory (both clamped to the frame's size) at dst[0..]; builds the index on every call
+    pub fn decompressFrameRange(src: []const u8, a: u64, b: u64, dst: []u8) Error!usize {
+        return mapFrame(zlz4f_decompress_frame_range(src.ptr, src.len, a, b, dst.ptr, dst.len));
     }
     pub fn frameDecompressedSizeUsingDict(src: []const u8, dict_len: usize) Error!usize {
         return mapFrame(zlz4f_frame_decompressed_size_using_dict(src.ptr, src.len, dict_len));
