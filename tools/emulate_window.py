@@ -9,12 +9,19 @@ oracle's output and remains the place to try a change of the lane logic on the C
 The window's epilogue is written the way the kernel has it: the lanes strictly inside a match are one mask (cov_acc)
 that every flush and every immediate emission ORs its own lanes into (run_cover / imm_cover), `ins` comes from that
 mask without another pass over the match lanes, and the table is settled by one write per lane (commit_one_write).
-tests/test_window_commit_model_cpu.py checks both against the definitions they replaced."""
+tests/test_window_commit_model_cpu.py checks both against the definitions they replaced.
+
+A window only starts behind a match (has_ins: lane 0 is the anchor's pending put), so every lane of a window reads,
+puts and reads back its slot; the block's first search, where position 0 is neither probed nor put, runs on the generic
+path (tests/test_window_entry_model_cpu.py).  ins_mask and commit_one_write keep their general forms (a mask / list of
+the written lanes) for the checks of their definitions; the window passes all 64 lanes."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 M32 = 0xFFFFFFFF
+M64 = (1 << 64) - 1
+ALL_LANES = [True] * 64
 def rd32(b, p): return int.from_bytes(b[p:p+4], "little")
 def hash4(x): return ((x * 2654435761) & M32) >> 20
 def ext_len_bytes(v): return 1 + (v - 15) // 255 if v >= 15 else 0
@@ -80,23 +87,18 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
         out[op:op+len(b)] = b; op += len(b)
     while F0 < L:
         ub = -1
-        if accel == 1 and F0 == anchor + 1 and (has_ins or anchor == 0) and anchor + 192 < L:
+        if accel == 1 and F0 == anchor + 1 and has_ins and anchor + 192 < L:
             A = anchor
             pos = [A + i for i in range(64)]
-            wr = [has_ins or i > 0 for i in range(64)]
             fwd = [[rd32(src, pos[i] + 4*k) for k in range(4)] for i in range(64)]
             h = [hash4(fwd[i][0]) for i in range(64)]
-            old = [table[h[i]] if wr[i] else 0 for i in range(64)]
+            old = [table[h[i]] for i in range(64)]
             for i in range(64):
-                if wr[i]: table[h[i]] = pos[i]      # race winner: any; emulate "last lane wins"
-            grp = [0] * 64
-            for i in range(64):
-                g = 0
-                for k in range(64):
-                    if wr[i] and wr[k] and h[k] == h[i]: g |= 1 << k
-                grp[i] = g if g else (1 << i)
-                if not wr[i]: grp[i] = 1 << i
-            old_ok = [wr[i] and old[i] > 0 and old[i] + 65535 >= pos[i] for i in range(64)]
+                table[h[i]] = pos[i]                # race winner: any; emulate "last lane wins"
+            by_hash = {}
+            for i in range(64): by_hash[h[i]] = by_hash.get(h[i], 0) | (1 << i)
+            grp = [by_hash[h[i]] for i in range(64)]    # the lanes of the window that share lane i's hash
+            old_ok = [old[i] > 0 and old[i] + 65535 >= pos[i] for i in range(64)]
             cold = [[rd32(src, old[i] + 4*k) for k in range(4)] if old_ok[i] else [0]*4 for i in range(64)]
             vo = [old_ok[i] and cold[i][0] == fwd[i][0] for i in range(64)]
             mlo = []
@@ -104,10 +106,9 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                 x1, x2, x3 = fwd[i][1]^cold[i][1], fwd[i][2]^cold[i][2], fwd[i][3]^cold[i][3]
                 mlo.append(ctz(x1)>>3 if x1 else (4+(ctz(x2)>>3) if x2 else (8+(ctz(x3)>>3) if x3 else 12)))
             single = [grp[i] == (1 << i) for i in range(64)]
-            wrmask = sum(1 << i for i in range(64) if wr[i])
             cfast = sum(1 << i for i in range(64) if vo[i] and mlo[i] < 12)
-            slow = sum(1 << i for i in range(64) if wr[i] and (((not single[i]) and not (vo[i] and mlo[i] < 12)) or (vo[i] and mlo[i] >= 12)))
-            nsing = sum(1 << i for i in range(64) if wr[i] and not single[i])
+            slow = sum(1 << i for i in range(64) if (((not single[i]) and not (vo[i] and mlo[i] < 12)) or (vo[i] and mlo[i] >= 12)))
+            nsing = sum(1 << i for i in range(64) if not single[i])
             def first_ge(mask, i):
                 m = mask >> i
                 return i + ctz(m) if m else 64
@@ -165,7 +166,7 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                     break
                 pm = 0
                 if (nsing >> x) & 1:
-                    pm = grp[x] & wrmask & ~cov_acc & ((1 << x) - 1)      # (no run is pending here)
+                    pm = grp[x] & ~cov_acc & ((1 << x) - 1)      # (no run is pending here)
                 if pm:
                     pr = msb(pm); ok = fwd[pr][0] == fwd[x][0]; m_cand = A + pr; c = fwd[pr]
                 else:
@@ -188,8 +189,8 @@ def compress(src, accel=1, dst_len=None, RESTART=48, trace=False):
                 f = e + 1
             anchor = A + a
             f_end = 64 if continue_generic else (64 if a >= 64 else a + 1)
-            ins = ins_mask(wrmask, cov_acc, f_end)
-            commit_one_write(table, h, pos, old, wr, grp, ins)
+            ins = ins_mask(M64, cov_acc, f_end)
+            commit_one_write(table, h, pos, old, ALL_LANES, grp, ins)
             if not continue_generic:
                 if anchor < L: has_ins, F0 = True, anchor + 1
                 else: has_ins, F0 = False, L

@@ -192,45 +192,42 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
             // position anchor + i; every sequence that begins in these 64 positions is resolved from registers (16
             // forward bytes per lane, one table read / speculative put / read-back, one candidate gather), then one
             // short loop iteration per sequence.  Positions are positions in V: the window itself always lies in the
-            // record, its candidates anywhere below.  It starts behind a pending put(anchor), so the record's first
-            // search (which PROBES position D) runs on the generic path; with D == 0 it also starts the block, where
-            // position 0 is neither probed nor put.
+            // record, its candidates anywhere below.  It only starts behind a pending put(anchor) (lane 0, has_ins), so
+            // the record's first search runs on the generic path: with a dictionary it PROBES position D, without one
+            // (D == 0) position 0 is neither probed nor put.
             // =====================================================================================
-            if (accel == 1u && F0 == anchor + 1u && (has_ins || (D == 0u && anchor == 0u)) && (uint64_t)anchor + 192u < L) {
+            if (accel == 1u && F0 == anchor + 1u && has_ins && (uint64_t)anchor + 192u < L) {
               bool moved = false;           // the last window of the run advanced the anchor ...
               bool to_generic = false;      // ... or handed its search over to the generic path
               for (;;) {                    // consecutive windows: the next one starts without re-deriving the entry test
                 const uint32_t A = anchor;
                 const uint32_t pos = A + lane;
-                const bool wr = has_ins || lane > 0;                    // position 0 of V is never put
                 const u32x4 fwd = pf_anchor == A ? fwd_pf : ld128(V.srcv + pos);     // (pos >= D: the record)
                 const uint32_t prod = fwd.x * kHashMul;
                 const uint32_t h = prod >> 20;                          // :653
                 const uint32_t mine = (uint32_t)(T)pos;                 // my table entry
-                uint32_t old = 0, rb = 0;
-                if (wr) old = table[h];                                 // :654
+                const uint32_t old = table[h];                          // :654
                 // pre-window candidates: the old table value passes `match > 0`, `match < ip` and the distance test
                 // (:656-658); its bytes (dictionary or record) are gathered once for the whole window, right away, so
                 // that the latency overlaps the speculative put / read-back below
                 // (written mask by mask: see the note at `losers` below)
-                const uint64_t wrmask = has_ins ? ~0ull : ~1ull;        // wr is wave-uniform: all lanes or all but lane 0
-                const uint64_t okm = wrmask & ballot(old > 0) & ballot(old < pos) & ballot(old + kMaxDist >= pos);
+                const uint64_t okm = ballot(old > 0) & ballot(old < pos) & ballot(old + kMaxDist >= pos);
                 const bool old_ok = in_mask(okm);
                 u32x4 cold = {0, 0, 0, 0};
                 if (old_ok) cold = V.ld128v(old);
                 u32x4 f2 = {0, 0, 0, 0}, c2 = f2, f3 = f2, c3 = f2;
-                if (wr) table[h] = (T)mine;                             // :661 (speculative)
+                table[h] = (T)mine;                                     // :661 (speculative)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                if (wr) rb = table[h];
+                const uint32_t rb = table[h];
                 // (a ballot is lowered to its compare only when its argument is one compare; a compound predicate goes
                 //  through v_cndmask and v_cmp_ne again.  So compound predicates are scalar combinations of one-compare
                 //  ballots, and a lane's own bit of such a mask is in_mask().)
-                uint64_t losers = wrmask & ballot(rb != mine);
+                uint64_t losers = ballot(rb != mine);
                 uint64_t grp = lane_bit;
                 while (losers) {                                        // one round per duplicate-hash group
                     const uint32_t l = first_lane(losers);
                     const uint32_t hh = rdlane(h, l);
-                    const uint64_t same = wrmask & ballot(h == hh);
+                    const uint64_t same = ballot(h == hh);
                     if (in_mask(same)) grp = same;
                     losers &= ~same;
                 }
@@ -266,8 +263,8 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                 const uint64_t lt44 = ballot(mlo < 44u);
                 const uint64_t cfast = vom & lt44;            // oldfast: the result against the pre-window value is complete in
                                                               // registers; usable if no in-window put precedes
-                const uint64_t nsing = wrmask & ~singm;
-                const uint64_t slow = (nsing & ~cfast) | (vom & ~lt44);   // wr && ((!single && !oldfast) || (vo && mlo >= 44)): exact step if reached
+                const uint64_t nsing = ~singm;
+                const uint64_t slow = (nsing & ~cfast) | (vom & ~lt44);   // (!single && !oldfast) || (vo && mlo >= 44): exact step if reached
                 // per lane i: J = first cfast lane >= i, S = first slow lane >= i (64 = none),
                 // E = lane of the new anchor if the search that starts at i ends with the match at J
                 uint32_t J, S;
@@ -413,7 +410,7 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                     uint64_t pm = 0;
                     if (xp >> 7) {
                         const uint64_t grp_x = (uint64_t)rdlane((uint32_t)grp, x) | ((uint64_t)rdlane((uint32_t)(grp >> 32), x) << 32);
-                        pm = grp_x & wrmask & ~covered_now() & ((1ull << x) - 1ull);
+                        pm = grp_x & ~covered_now() & ((1ull << x) - 1ull);
                     }
                     const uint32_t j = x;
                     const uint32_t m_pos = A + j;
@@ -493,7 +490,7 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                 anchor = A + a;
                 // lanes the serial loop put(): below the frontier and not strictly inside a match (no run is pending here)
                 const uint32_t f_end = continue_generic ? 64u : (a >= 64u ? 64u : a + 1u);
-                const uint64_t ins = wrmask & ~cov_acc & (f_end >= 64u ? ~0ull : (1ull << f_end) - 1ull);
+                const uint64_t ins = ~cov_acc & (f_end >= 64u ? ~0ull : (1ull << f_end) - 1ull);
                 if (failed) break;
                 // ---- leave the table as the serial loop would have ----
                 // One write per lane: the slot's final value depends only on gi, the group's lanes in `ins`.  None: every
@@ -501,7 +498,7 @@ __global__ __launch_bounds__(64) void k_compress_fast_dict(
                 // carry equal values).  Else the last `ins` lane of the group stores its entry and the others write nothing.
                 const uint64_t gi = grp & ins;
                 const bool put_mine = in_mask(ins) && (gi & ~lanes_below & ~lane_bit) == 0;
-                if (put_mine || (wr && gi == 0)) table[h] = (T)(put_mine ? mine : old);
+                if (put_mine || gi == 0) table[h] = (T)(put_mine ? mine : old);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 moved = anchor != A;
                 to_generic = continue_generic;

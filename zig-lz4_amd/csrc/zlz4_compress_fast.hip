@@ -312,14 +312,17 @@ __global__ __launch_bounds__(256) void k_compress_fast(
             // iteration per sequence.  `ins` = lanes the serial loop would have put() so far; a lane's
             // table read is its nearest earlier `ins` lane with the same hash, else the pre-window
             // value.  At the end lanes not in `ins` put their old value back.
+            // A window only starts behind a match: lane 0 is the anchor's pending put (has_ins), never a probe, and
+            // every lane reads, puts and reads back its slot.  The block's first search, where position 0 is neither
+            // probed nor put (Q1), runs on the generic path below (seeded builds too: they start with anchor 0 and
+            // has_ins false like the others); its match sets has_ins, and every window of a run hands it on.
             // =====================================================================================
-            if (accel == 1u && F0 == anchor + 1u && (has_ins || anchor == 0u) && (uint64_t)anchor + 192u < L) {
+            if (accel == 1u && F0 == anchor + 1u && has_ins && (uint64_t)anchor + 192u < L) {
               bool moved = false;           // the last window of the run advanced the anchor ...
               bool to_generic = false;      // ... or handed its search over to the generic path
               for (;;) {                    // consecutive windows: the next one starts without re-deriving the entry test
                 const uint32_t A = anchor;
                 const uint32_t pos = A + lane;
-                const bool wr = has_ins || lane > 0;                    // position 0 is never inserted (Q1)
                 if (kRing && pf_anchor != A) {
                     sel_pf = ring_sel(A, ja_pf);
                     fwd_pf = ring_fwd(sel_pf, ja_pf, A, hi4_pf);
@@ -332,19 +335,16 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 const uint32_t mine = kTag == 2 ? (pos | (tg << 24)) : (uint32_t)(T)pos;     // my table entry
                 STAMP(1);
                 STAMP_COUNT(16);
-                uint32_t old_e = 0, rb = 0, told = tg;
-                if (wr) {
-                    old_e = table[h];                                   // :342
-                    if (kTag == 1) told = tags[h];
-                }
+                uint32_t told = tg;
+                const uint32_t old_e = table[h];                        // :342
+                if (kTag == 1) told = tags[h];
                 if (kTag == 2) told = old_e >> 24;
                 const uint32_t old = old_e & kPosMask;
                 // pre-window candidates: the old table value passes `match > 0`, `match < ip` (always, unless seeded) and
                 // the distance test (:345-347); its bytes are gathered once for the whole window.  The gather is
                 // issued right away so that its latency overlaps the speculative put / read-back below.
                 // (written mask by mask: see the note at `losers` below)
-                const uint64_t wrmask = has_ins ? ~0ull : ~1ull;        // wr is wave-uniform: all lanes or all but lane 0
-                uint64_t okm = wrmask & ballot(old > 0) & ballot(old + kMaxDist >= pos);
+                uint64_t okm = ballot(old > 0) & ballot(old + kMaxDist >= pos);
                 if (kSeed) okm &= ballot(old < pos);
                 if (kTag != 0) okm &= ballot(told == tg);
                 const bool old_ok = in_mask(okm);
@@ -367,18 +367,18 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     c2 = ld128(src + old + 16u); c3 = ld128(src + old + 32u);
                 }
                 STAMP(3);
-                if (wr) table[h] = (T)mine;                             // :350 (speculative)
+                table[h] = (T)mine;                                     // :350 (speculative)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                if (wr) rb = table[h];
+                const uint32_t rb = table[h];
                 // (a ballot is lowered to its compare only when its argument is one compare; a compound predicate goes
                 //  through v_cndmask and v_cmp_ne again.  So compound predicates are scalar combinations of one-compare
                 //  ballots, and a lane's own bit of such a mask is in_mask().)
-                uint64_t losers = wrmask & ballot(rb != mine);
+                uint64_t losers = ballot(rb != mine);
                 uint64_t grp = lane_bit;
                 while (losers) {                                        // one round per duplicate-hash group
                     const uint32_t l = first_lane(losers);
                     const uint32_t hh = rdlane(h, l);
-                    const uint64_t same = wrmask & ballot(h == hh);
+                    const uint64_t same = ballot(h == hh);
                     if (in_mask(same)) grp = same;
                     losers &= ~same;
                 }
@@ -418,8 +418,8 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 const uint64_t lt44 = ballot(mlo < 44u);
                 const uint64_t cfast = vom & lt44;            // oldfast: the result against the pre-window value is complete in
                                                               // registers; usable if no in-window put precedes
-                const uint64_t nsing = wrmask & ~singm;
-                const uint64_t slow = (nsing & ~cfast) | (vom & ~lt44);   // wr && ((!single && !oldfast) || (vo && mlo >= 44)): exact step if reached
+                const uint64_t nsing = ~singm;
+                const uint64_t slow = (nsing & ~cfast) | (vom & ~lt44);   // (!single && !oldfast) || (vo && mlo >= 44): exact step if reached
                 // per lane i: J = first cfast lane >= i, S = first slow lane >= i (64 = none),
                 // E = lane of the new anchor if the search that starts at i ends with the match at J
                 uint32_t J, S;
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     uint64_t pm = 0;
                     if (xp >> 7) {
                         const uint64_t grp_x = (uint64_t)rdlane((uint32_t)grp, x) | ((uint64_t)rdlane((uint32_t)(grp >> 32), x) << 32);
-                        pm = grp_x & wrmask & ~covered_now() & ((1ull << x) - 1ull);
+                        pm = grp_x & ~covered_now() & ((1ull << x) - 1ull);
                     }
                     const uint32_t j = x;
                     const uint32_t m_pos = A + j;
@@ -659,7 +659,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 STAMP(4);
                 // lanes the serial loop put(): below the frontier and not strictly inside a match (no run is pending here)
                 const uint32_t f_end = continue_generic ? 64u : (a >= 64u ? 64u : a + 1u);
-                const uint64_t ins = wrmask & ~cov_acc & (f_end >= 64u ? ~0ull : (1ull << f_end) - 1ull);
+                const uint64_t ins = ~cov_acc & (f_end >= 64u ? ~0ull : (1ull << f_end) - 1ull);
                 if (failed) break;
                 // ---- leave the table as the serial loop would have ----
                 // One write per lane: the slot's final value depends only on gi, the group's lanes in `ins`.  None: every
@@ -667,7 +667,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 // carry equal values).  Else the last `ins` lane of the group stores its entry and the others write nothing.
                 const uint64_t gi = grp & ins;
                 const bool put_mine = in_mask(ins) && (gi & ~lanes_below & ~lane_bit) == 0;
-                if (put_mine || (wr && gi == 0)) table[h] = (T)(put_mine ? mine : old_e);
+                if (put_mine || gi == 0) table[h] = (T)(put_mine ? mine : old_e);
                 if (kTag == 1 && put_mine) tags[h] = (uint8_t)tg;       // (the speculative put left the old tag in place)
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 STAMP(5);
