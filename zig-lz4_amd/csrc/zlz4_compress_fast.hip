@@ -420,39 +420,36 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                                                               // registers; usable if no in-window put precedes
                 const uint64_t nsing = ~singm;
                 const uint64_t slow = (nsing & ~cfast) | (vom & ~lt44);   // (!single && !oldfast) || (vo && mlo >= 44): exact step if reached
-                // per lane i: J = first cfast lane >= i, S = first slow lane >= i (64 = none),
-                // E = lane of the new anchor if the search that starts at i ends with the match at J
+                // a search from lane i ends with the in-register match at the first fastm lane >= i iff that lane lies below the
+                // first stopm lane >= i: cfast lies in fastm | stopm and slow in stopm, so nothing that can match comes first
+                const uint64_t fastm = cfast & singm;
+                const uint64_t stopm = slow | (cfast & nsing);
+                // per lane i: J = first fastm lane >= i, S = first stopm lane >= i (64 = none)
                 uint32_t J, S;
                 {
-                    const uint64_t mj = cfast >> lane, ms = slow >> lane;
+                    const uint64_t mj = fastm >> lane, ms = stopm >> lane;
                     J = mj ? lane + (uint32_t)__builtin_ctzll(mj) : 64u;
                     S = ms ? lane + (uint32_t)__builtin_ctzll(ms) : 64u;
                 }
-                uint32_t v_end = lane + kMinMatch + mlo;                          // anchor lane after a match at this lane
+                const uint32_t v_end = lane + kMinMatch + mlo;                          // anchor lane after a match at this lane
                 uint32_t mlo_e = mlo, off_e = pos - old;                          // match length / offset the flush emits for a match lane
-                // fast-run step of a search that starts at lane f, precomputed for every f: PK = j | (v_end[j] << 6) when
-                // the search ends with the in-register match at j = J[f] (no slow lane first, j's hash unique in the
-                // window), else ~0.  (Exact steps only rewrite v_end of lanes the search has already passed.)
-                // for the exact step: XP = first lane >= f that can match at all (min(J, S), 64 = none) | its nsing bit << 7;
-                // Q = what a probe finds against the pre-window value: valid (:345-348) | matched extension bytes << 1
-                uint32_t XP, Q;
-                {
-                    const uint32_t xm = J < S ? J : S;
-                    XP = xm | ((uint32_t)((nsing >> (xm & 63u)) & 1ull) << 7);
-                    Q = (vo ? 1u : 0u) | (mlo << 1);
-                }
+                // fast-run step of a search that starts at lane f, precomputed for every f: PK = j | ((v_end[j] + 1) << 6), the
+                // match lane and the next probe lane, with bit 31 set if the step ends the window (v_end[j] >= 63), when
+                // the search ends with the in-register match at j = J[f] (J[f] < S[f]), else ~0.
+                // for the exact step: X = first lane >= f that can match at all (min(J, S), 64 = none); Q = the lane's own
+                // nsing bit << 1 | what a probe finds against the pre-window value: valid | matched extension bytes << 2
+                const uint32_t X = J < S ? J : S;
+                const uint32_t Q = (mlo << 2) | (in_mask(nsing) ? 2u : 0u) | (vo ? 1u : 0u);
                 uint32_t PK;
                 {
-                    const uint32_t jc = J & 63u;
-                    const uint32_t ve_j = shfl(v_end, jc);
-                    const bool fastok = J < 64u && S > J && !((nsing >> jc) & 1ull);
-                    PK = fastok ? (J | (ve_j << 6)) : 0xFFFFFFFFu;
+                    const uint32_t ve_j = shfl(v_end, J & 63u);
+                    const bool fastok = J < S;
+                    PK = fastok ? (J | ((ve_j + 1u) << 6) | (ve_j >= 63u ? 0x80000000u : 0u)) : 0xFFFFFFFFu;
                 }
 
                 STAMP(6);
                 uint32_t f = 1;          // next lane to probe
                 uint32_t a = 0;          // lane of the current anchor
-                uint32_t nseq = 0;
                 // lanes strictly inside a match that has been emitted (Q6: never put()): every flush and every immediate
                 // emission ORs in the lanes of its own matches.  Runs and immediate sequences are consecutive lane ranges and
                 // a match's end lane is final once it is emitted, so no later event changes what an earlier one covered.
@@ -460,30 +457,27 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                 bool continue_generic = false;
                 // with less than 512 bytes of room left every sequence takes the exact step, which checks the capacity
                 const bool tight = dst_len - op < 512u;
-                uint32_t a0 = a, op0 = op;   // anchor lane / output position at the start of the pending (unflushed) run
+                uint32_t a0 = a;             // anchor lane at the start of the pending (unflushed) run; op stays where it was then
                 uint64_t mm_run = 0;         // match lanes of the pending run
-                // lanes strictly inside a match so far, for an exact step: the emitted ones, and those of the pending run from
-                // its match lanes and their end lanes (mm_run is wave-uniform: shfl sees every lane, see zlz4_device.hpp)
-                auto covered_now = [&]() -> uint64_t {
-                    if (mm_run == 0) return cov_acc;
-                    const uint64_t mb = mm_run & lanes_below;
-                    const uint32_t pj = mb ? 63u - (uint32_t)__builtin_clzll(mb) : 0u;
-                    const uint32_t pe = shfl(v_end, pj);
-                    return cov_acc | ballot(mb != 0 && lane < pe);
-                };
+                // end lanes of the pending run's matches (those below 64), entered where mm_run gets its bit.  The matches of
+                // a run are disjoint, ordered lane ranges, so the lanes strictly inside them are E_run - (mm_run << 1)
+                // (mod 2^64): every match contributes 2^e - 2^(j+1) = lanes j+1 .. e-1, and a last match that ends at or past
+                // lane 64 has no bit in E_run, so that the wrap carries its range up to lane 63.
+                uint64_t E_run = 0;
+                // lanes strictly inside a match so far, for an exact step: the emitted ones and those of the pending run
+                auto covered_now = [&]() -> uint64_t { return cov_acc | (E_run - (mm_run << 1)); };
                 // flush of the pending run: every offset from popcounts, three stores for all its sequences
                 auto flush_run = [&]() {
                     STAMP(9); STAMP_COUNT(21);
-                    const uint64_t mb = mm_run & lanes_below;
-                    const bool has_prev = mb != 0;
-                    const uint32_t pj = has_prev ? 63u - (uint32_t)__builtin_clzll(mb) : 0u;   // previous match lane
-                    const uint32_t pend_all = shfl(v_end, pj);          // (unconditional: see zlz4_device.hpp)
-                    const uint32_t pend = has_prev ? pend_all : a0;     // first lane of my literal run
-                    const uint64_t covm = ballot(mb != 0) & ballot(lane < pend_all);   // strictly inside a match of this run
+                    const uint64_t covm = E_run - (mm_run << 1);        // strictly inside a match of this run
+                    // first lane of my literal run: the nearest end lane of the run at or below me, else the run's anchor
+                    // (a match that starts where the previous one ends finds that end at its own lane: no literals)
+                    const uint64_t ends = (E_run | (1ull << a0) | 1ull) & (lanes_below | lane_bit);
+                    const uint32_t pend = 63u - (uint32_t)__builtin_clzll(ends);
                     const bool is_m = in_mask(mm_run);
                     const uint32_t jlast = 63u - (uint32_t)__builtin_clzll(mm_run);
-                    // literals: lanes from a0 on that are neither past the last match lane, nor covered, nor a match lane
-                    const uint64_t litmask = ballot(lane >= a0) & ~(ballot(lane >= jlast) | covm | mm_run);
+                    // literals: lanes from a0 up to the last match lane that are neither covered nor a match lane
+                    const uint64_t litmask = ((1ull << jlast) - 1ull) & ~((1ull << a0) - 1ull) & ~(covm | mm_run);
                     const bool is_lit = in_mask(litmask);
                     const uint64_t extm = mm_run & ballot(mlo_e >= 15u);                // matches with one length-extension byte (:416-429)
                     // literal runs of 15..63 bytes carry one extension byte too (:368-382): a lane's sequence is the
@@ -496,7 +490,7 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     // (prefix popcounts as lane_rank: v_mbcnt_lo / _hi)
                     const uint32_t k = lane_rank(mm_run);                               // sequences completed before me
                     const uint32_t lb = lane_rank(litmask);                             // literal bytes before me
-                    const uint32_t o1 = op0 + 3u * k + lb + 1u + lane_rank(extm) + lane_rank(lextm) + own_l;
+                    const uint32_t o1 = op + 3u * k + lb + 1u + lane_rank(extm) + lane_rank(lextm) + own_l;
                     if (is_lit) dst[o1] = (uint8_t)fwd.x;               // literals (:390)
                     if (is_m) {
                         const uint32_t lit_k = lane - pend;             // :360
@@ -508,9 +502,10 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                         if (mlo_e >= 15u) dst[o1 + 2u] = (uint8_t)(mlo_e - 15u);         // < 255 (mlen < 270 in a run)
                     }
                     const uint32_t nm = (uint32_t)__popcll(mm_run);
-                    op = op0 + 3u * nm + (uint32_t)__popcll(litmask) + (uint32_t)__popcll(extm) + (uint32_t)__popcll(lextm);
+                    op += 3u * nm + (uint32_t)__popcll(litmask) + (uint32_t)__popcll(extm) + (uint32_t)__popcll(lextm);
                     cov_acc |= covm;
                     mm_run = 0;
+                    E_run = 0;
                     STAMP(10);
                 };
                 for (;;) {
@@ -518,25 +513,25 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     //      starts at f ends at J[f] when no slow lane comes first, the lane's hash is unique in the
                     //      window (its probe reads the pre-window value whatever was put before) and the literal
                     //      run fits the token nibble. ----
-                    if (mm_run == 0) { a0 = a; op0 = op; }
-                    if (!tight) {
+                    if (mm_run == 0) a0 = a;
+                    if (!tight && f < 64u) {
                         // hand-scheduled scalar loop (the compiler spends ~25 scalar instructions per trip on the
                         // boolean plumbing; the scalar unit is what bounds this kernel):
-                        //   while (f < 64) { pk = PK[f]; j = pk & 63; if (pk == ~0) break;
-                        //                    mm_run |= 1 << j; nseq++; a = pk >> 6; f = a + 1; }          (two trips per branch back)
+                        //   for (;;) { pk = PK[f]; if (pk < 0) break; f = pk >> 6; j = pk & 63;
+                        //              mm_run |= 1 << j; a = f - 1; E_run |= 1 << a; }                (two trips per branch back)
+                        // One exit test: bit 31 of pk is set in the sentinel and in the step that ends the window, so a trip
+                        // that goes on has a < 63 and f < 64.
                         uint32_t t_pk, t_j;
 #define ZLZ4_FAST_RUN_TRIP                                   \
-                            "s_cmp_gt_u32 %[f], 63\n\t"      \
-                            "s_cbranch_scc1 3f\n\t"          \
                             "v_readlane_b32 %[pk], %[PK], %[f]\n\t" \
-                            "s_cmp_eq_u32 %[pk], -1\n\t"     \
+                            "s_cmp_lt_i32 %[pk], 0\n\t"      \
                             "s_cbranch_scc1 3f\n\t"          \
-                            "s_lshr_b32 %[a], %[pk], 6\n\t"  \
-                            "s_add_u32 %[f], %[a], 1\n\t"    \
+                            "s_lshr_b32 %[f], %[pk], 6\n\t"  \
                             "s_and_b32 %[j], %[pk], 63\n\t"  \
                             "s_bitset1_b64 %[mm], %[j]\n\t"  \
-                            "s_add_u32 %[nseq], %[nseq], 1\n\t"
-                        // (five scalar instructions lie between the write of f and the v_readlane that uses it as its lane
+                            "s_sub_u32 %[a], %[f], 1\n\t"    \
+                            "s_bitset1_b64 %[er], %[a]\n\t"
+                        // (four scalar instructions lie between the write of f and the v_readlane that uses it as its lane
                         //  select: the ISA asks for four wait states there)
                         asm volatile(
                             "s_nop 3\n"
@@ -545,29 +540,36 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                             ZLZ4_FAST_RUN_TRIP
                             "s_branch 1b\n"
                             "3:\n"
-                            : [f] "+s"(f), [a] "+s"(a), [nseq] "+s"(nseq), [mm] "+s"(mm_run), [pk] "=&s"(t_pk), [j] "=&s"(t_j)
+                            : [f] "+s"(f), [a] "+s"(a), [mm] "+s"(mm_run), [er] "+s"(E_run), [pk] "=&s"(t_pk), [j] "=&s"(t_j)
                             : [PK] "v"(PK)
                             : "scc");
 #undef ZLZ4_FAST_RUN_TRIP
+                        if (t_pk != 0xFFFFFFFFu) {
+                            // the step that ends the window, consumed once: its end lane is 63 or beyond
+                            mm_run |= 1ull << (t_pk & 63u);
+                            f = (t_pk >> 6) & 127u;
+                            a = f - 1u;
+                            if (a == 63u) E_run |= 1ull << 63;
+                        }
                     }
                     STAMP(8);
                     if (f >= 64u) {      // window done (a = last anchor lane, possibly >= 64)
-                        if (nseq == 0u) continue_generic = true;    // every lane probed, no match
+                        if (a == 0u) continue_generic = true;    // every lane probed, no match
                         break;
                     }
 
                     // ---- exact step for the probe at the first lane >= f that can match at all ----
-                    const uint32_t xp = rdlane(XP, f);
-                    const uint32_t x = xp & 127u;
+                    const uint32_t x = rdlane(X, f);
                     if (x >= 64u) {
-                        if (nseq == 0u) continue_generic = true;   // the search goes on past the window -> generic batches
+                        if (a == 0u) continue_generic = true;   // the search goes on past the window -> generic batches
                         // else: restart a fresh window at the current anchor (its lanes > a are re-probed there)
                         break;
                     }
                     // earlier put()s of this window with the same hash (only lanes of duplicate-hash groups can have one):
                     // every lane below x that is not strictly inside a match has been put
+                    const uint32_t q = rdlane(Q, x);
                     uint64_t pm = 0;
-                    if (xp >> 7) {
+                    if (q & 2u) {
                         const uint64_t grp_x = (uint64_t)rdlane((uint32_t)grp, x) | ((uint64_t)rdlane((uint32_t)(grp >> 32), x) << 32);
                         pm = grp_x & ~covered_now() & ((1ull << x) - 1ull);
                     }
@@ -587,15 +589,14 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                         else mlen = extend_match(src, m_pos, m_cand, 12u, match_limit, src_size, lane);
                     } else {
                         // the probe reads the pre-window value: the vector code has already compared up to 48 bytes
-                        const uint32_t q = rdlane(Q, x);
                         if (!(q & 1u)) { STAMP_COUNT(19); STAMP(9); f = x + 1u; continue; }      // probed, put, no match: next probe
                         STAMP_COUNT(18);
-                        mlen = q >> 1;
+                        mlen = q >> 2;
                         if (mlen < 44u && !tight) {
-                            // v_end / mlo_e / off_e of lane j already describe this sequence: it just joins the run
+                            // mlo_e / off_e of lane j already describe this sequence: it just joins the run
                             mm_run |= 1ull << j;
-                            nseq++;
                             a = j + kMinMatch + mlen;
+                            if (a < 64u) E_run |= 1ull << a;
                             STAMP(9);
                             if (a >= 64u) break;                            // the next window inserts it as its lane 0
                             f = a + 1u;
@@ -609,11 +610,10 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                     const uint32_t e = j + kMinMatch + mlen;                // lane of the new anchor (may be >= 64)
                     if (!tight && mlen < 270u) {
                         // simple sequence: joins the pending run, emitted by the flush
-                        v_end = wrlane(e, j, v_end);
                         mlo_e = wrlane(mlen, j, mlo_e);
                         off_e = wrlane(offset, j, off_e);
                         mm_run |= 1ull << j;
-                        nseq++;
+                        if (e < 64u) E_run |= 1ull << e;
                         a = e;
                         STAMP(9);
                         if (e >= 64u) break;                                // the next window inserts it as its lane 0
@@ -638,7 +638,6 @@ __global__ __launch_bounds__(256) void k_compress_fast(
                         const uint64_t upto_e = e >= 64u ? ~0ull : (1ull << e) - 1ull;
                         cov_acc |= upto_e & ~((2ull << j) - 1ull);          // lanes j+1 .. e-1
                     }
-                    nseq++;
                     a = e;
                     if (e >= 64u) break;                                    // the next window inserts it as its lane 0
                     f = e + 1u;
