@@ -61,6 +61,8 @@ def lib():
         L.zo_decompress_safe_partial.argtypes = [u8p, sz, u8p, sz, sz]
         L.zo_hc_reference_ub.restype = i64
         L.zo_hc_reference_ub.argtypes = [C.c_int]
+        L.zo_hc_opt_stats.restype = C.c_int
+        L.zo_hc_opt_stats.argtypes = [C.POINTER(C.c_int64), C.c_int]
         L.zo_xxh32.restype = C.c_uint32
         L.zo_xxh32.argtypes = [u8p, sz, C.c_uint32]
         L.zo_compress_frame_bound.restype = sz
@@ -132,6 +134,32 @@ def compress_hc_expected(src, level, cap=None):
 def hc_reference_ub(reset=True):
     """number of times compress_hc met the reference's u32 underflow (lz4hc.zig:636) since the last reset"""
     return lib().zo_hc_reference_ub(1 if reset else 0)
+
+
+# Event counters of compressOptimal (levels 10-12), in the order of lz4_oracle.c's ZS_* enum.  SPLIT = 1000 is the record
+# index from which k_hc_opt_parse_wave keeps opt[] in HBM: hi_* count accesses at or above it, x_* single steps whose
+# accesses lie on both sides of it (lit / match: the update passes at one position; trail: the three trailing literals;
+# back: the opt[cur - ll] read; hop: the reverse traversal).
+OPT_SPLIT = 1000
+OPT_STATS = ("windows", "max_window", "first_sufficient", "exit_sufficient", "exit_optnum", "min_optnum_sum",
+             "max_noexit_sum", "ties", "lit_updates", "hi_lit", "hi_match", "hi_trail", "hi_back", "hi_hop",
+             "x_lit", "x_match", "x_trail", "x_back", "x_hop", "max_llen", "max_optnum_llen", "mflimit_breaks",
+             "max_price", "max_window_llen", "max_break_cur")
+
+
+def hc_opt_stats():
+    """the counters of the last compress_hc call at a level 10-12 (the call resets them) -> {name: value}"""
+    v = (C.c_int64 * len(OPT_STATS))()
+    n = lib().zo_hc_opt_stats(v, len(OPT_STATS))
+    assert n == len(OPT_STATS), "OPT_STATS is out of step with lz4_oracle.c"
+    return dict(zip(OPT_STATS, (int(x) for x in v)))
+
+
+def compress_hc_stats(src, level, cap=None):
+    """-> (compress_hc's result, the counters of that call)"""
+    assert level >= 10
+    r = compress_hc(src, level, cap)
+    return r, hc_opt_stats()
 
 
 def decompress_safe(src, cap):

@@ -868,6 +868,31 @@ static inline int32_t sequencePrice(int32_t litlen, int32_t mlen) {      /* :476
     return price;
 }
 
+/* Event counters of the last zo_compress_hc call, all zero below level 10 (test infrastructure: tests/optgen.py builds
+ * blocks on the parser's edges and tests/test_opt_corpus_cpu.py witnesses them here).  ZO_OPT_SPLIT is the record index
+ * from which k_hc_opt_parse_wave keeps opt[] in HBM; "hi" counts accesses at or above it, "x" accesses of one step that
+ * lie on both sides of it.  Nothing here feeds back into the parse. */
+#define ZO_OPT_SPLIT 1000
+enum { ZS_WINDOWS, ZS_MAX_WINDOW, ZS_FIRST_SUFFICIENT, ZS_EXIT_SUFFICIENT, ZS_EXIT_OPTNUM, ZS_MIN_OPTNUM_SUM,
+       ZS_MAX_NOEXIT_SUM, ZS_TIES, ZS_LIT_UPDATES, ZS_HI_LIT, ZS_HI_MATCH, ZS_HI_TRAIL, ZS_HI_BACK, ZS_HI_HOP,
+       ZS_X_LIT, ZS_X_MATCH, ZS_X_TRAIL, ZS_X_BACK, ZS_X_HOP, ZS_MAX_LLEN, ZS_MAX_OPTNUM_LLEN, ZS_MFLIMIT_BREAKS,
+       ZS_MAX_PRICE, ZS_MAX_WINDOW_LLEN, ZS_MAX_BREAK_CUR, ZS_COUNT };
+static int64_t zo_opt_stats[ZS_COUNT];
+int zo_hc_opt_stats(int64_t *out, int n) {
+    for (int i = 0; i < n && i < ZS_COUNT; i++) out[i] = zo_opt_stats[i];
+    return ZS_COUNT;
+}
+static inline void zs_max(int which, int64_t v) { if (v > zo_opt_stats[which]) zo_opt_stats[which] = v; }
+static void zs_window(int64_t last_match_pos, int32_t llen) {       /* a window's final size, and the llen it began with */
+    if (last_match_pos > zo_opt_stats[ZS_MAX_WINDOW]) { zo_opt_stats[ZS_MAX_WINDOW] = last_match_pos; zo_opt_stats[ZS_MAX_WINDOW_LLEN] = llen; }
+}
+static void zs_trailing(size_t last_match_pos) {
+    if (last_match_pos + TRAILING_LITERALS >= ZO_OPT_SPLIT) {
+        zo_opt_stats[ZS_HI_TRAIL] += 1;
+        if (last_match_pos + 1 < ZO_OPT_SPLIT) zo_opt_stats[ZS_X_TRAIL] += 1;
+    }
+}
+
 static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize, uint8_t *dst, size_t dstLen,
                                int32_t nbSearches, size_t sufficientLen) {
     opt_match *opt = (opt_match *)malloc((LZ4_OPT_NUM + TRAILING_LITERALS) * sizeof(opt_match));   /* :1079 */
@@ -894,9 +919,12 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
         const hc_match firstMatch = insertAndGetWiderMatch(ctx, ip, ip, matchlimit, MINMATCH - 1, nbSearches, 1);
         if (firstMatch.len == 0) { ip += 1; continue; }                  /* :1127 (never true: len starts at 3) */
         if ((size_t)firstMatch.len > sufficient_len) {                   /* :1133 */
+            zo_opt_stats[ZS_FIRST_SUFFICIENT] += 1;
             if (encodeSequence(&ip, &op, &anchor, firstMatch.len, firstMatch.off, 1, oend) != 0) { free(opt); return ZO_ERR_OUTPUT_TOO_SMALL; }
             continue;
         }
+        zo_opt_stats[ZS_WINDOWS] += 1;
+        zs_max(ZS_MAX_LLEN, llen);
         for (size_t rPos = 0; rPos < MINMATCH; rPos++) {                 /* :1150-1157 */
             const int32_t cost = literalsPrice(llen + (int32_t)rPos);
             opt[rPos].mlen = 1; opt[rPos].off = 0; opt[rPos].litlen = llen + (int32_t)rPos; opt[rPos].price = cost;
@@ -908,6 +936,7 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
             opt[mlen].mlen = (int32_t)mlen; opt[mlen].off = offset; opt[mlen].litlen = llen; opt[mlen].price = cost;
         }
         size_t last_match_pos = matchML;                                 /* :1171 */
+        zs_trailing(last_match_pos);
         for (size_t addLit = 1; addLit <= TRAILING_LITERALS; addLit++) { /* :1174-1180 */
             opt[last_match_pos + addLit].mlen = 1; opt[last_match_pos + addLit].off = 0;
             opt[last_match_pos + addLit].litlen = (int32_t)addLit;
@@ -917,7 +946,7 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
         size_t cur;
         for (cur = 1; cur < last_match_pos; cur++) {                     /* :1183-1312 */
             const uint8_t *curPtr = ip + cur;
-            if (curPtr > mflimit) break;                                 /* :1187 */
+            if (curPtr > mflimit) { zo_opt_stats[ZS_MFLIMIT_BREAKS] += 1; zs_max(ZS_MAX_BREAK_CUR, (int64_t)cur); break; }   /* :1187 */
             if (opt[cur + 1].price <= opt[cur].price) continue;          /* :1190 */
             insertHC(ctx, curPtr);                                       /* :1193 */
             const hc_match newMatch = insertAndGetWiderMatch(ctx, curPtr, curPtr, matchlimit, MINMATCH - 1, nbSearches, 1);
@@ -925,6 +954,14 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
             if (((size_t)newMatch.len > sufficient_len) || (newMatch.len + (int32_t)cur >= (int32_t)LZ4_OPT_NUM)) {   /* :1208 */
                 const int32_t best_mlen = newMatch.len, best_off = newMatch.off;
                 size_t rp = 0;
+                if ((size_t)newMatch.len > sufficient_len) zo_opt_stats[ZS_EXIT_SUFFICIENT] += 1;
+                else {
+                    const int64_t sum = (int64_t)newMatch.len + (int64_t)cur;
+                    zo_opt_stats[ZS_EXIT_OPTNUM] += 1;
+                    if (zo_opt_stats[ZS_MIN_OPTNUM_SUM] == 0 || sum < zo_opt_stats[ZS_MIN_OPTNUM_SUM]) zo_opt_stats[ZS_MIN_OPTNUM_SUM] = sum;
+                    zs_max(ZS_MAX_OPTNUM_LLEN, llen);
+                }
+                zs_window((int64_t)last_match_pos, llen);
                 while (rp < cur) {                                       /* :1217-1238 */
                     const int32_t ml = opt[rp].mlen, off = opt[rp].off;
                     if (ml == 1) { ip += 1; rp += 1; continue; }
@@ -935,15 +972,25 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
                 encoded_early = 1;                                       /* :1255 continue :outer */
                 break;
             }
+            zs_max(ZS_MAX_NOEXIT_SUM, (int64_t)newMatch.len + (int64_t)cur);
             const int32_t baseLitlen = opt[cur].litlen;                  /* :1259 */
+            if (cur + 1 < ZO_OPT_SPLIT && cur + 3 >= ZO_OPT_SPLIT) zo_opt_stats[ZS_X_LIT] += 1;
             for (size_t litlen = 1; litlen < MINMATCH; litlen++) {       /* :1260-1270 */
                 const int32_t price = opt[cur].price - literalsPrice(baseLitlen) + literalsPrice(baseLitlen + (int32_t)litlen);
                 const size_t pos = cur + litlen;
                 if (price < opt[pos].price) {
+                    zo_opt_stats[ZS_LIT_UPDATES] += 1;
+                    if (pos >= ZO_OPT_SPLIT) zo_opt_stats[ZS_HI_LIT] += 1;
                     opt[pos].mlen = 1; opt[pos].off = 0; opt[pos].litlen = baseLitlen + (int32_t)litlen; opt[pos].price = price;
                 }
             }
             const size_t newMatchML = (size_t)newMatch.len;              /* :1273 */
+            if (newMatchML >= MINMATCH && cur + MINMATCH < ZO_OPT_SPLIT && cur + newMatchML >= ZO_OPT_SPLIT) zo_opt_stats[ZS_X_MATCH] += 1;
+            if (newMatchML >= MINMATCH && opt[cur].mlen == 1 && cur > (size_t)opt[cur].litlen) {
+                const size_t back = cur - (size_t)opt[cur].litlen;      /* the opt[cur - ll] read of :1280 */
+                if (back >= ZO_OPT_SPLIT) zo_opt_stats[ZS_HI_BACK] += 1;
+                else if (cur >= ZO_OPT_SPLIT) zo_opt_stats[ZS_X_BACK] += 1;
+            }
             for (size_t ml = MINMATCH; ml <= newMatchML; ml++) {         /* :1274-1302 */
                 const size_t pos = cur + ml;
                 const int32_t newOffset = newMatch.off;
@@ -957,6 +1004,9 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
                     price = opt[cur].price + sequencePrice(0, (int32_t)ml);
                 }
                 if (pos > last_match_pos + TRAILING_LITERALS || price <= opt[pos].price) {   /* :1293 */
+                    if (pos <= last_match_pos + TRAILING_LITERALS && price == opt[pos].price) zo_opt_stats[ZS_TIES] += 1;
+                    if (pos >= ZO_OPT_SPLIT) zo_opt_stats[ZS_HI_MATCH] += 1;
+                    zs_max(ZS_MAX_PRICE, price);
                     if ((ml == newMatchML) && (last_match_pos < pos)) last_match_pos = pos;
                     opt[pos].mlen = (int32_t)ml; opt[pos].off = newOffset; opt[pos].litlen = ll; opt[pos].price = price;
                 }
@@ -966,15 +1016,26 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
                 opt[last_match_pos + addLit].litlen = (int32_t)addLit;
                 opt[last_match_pos + addLit].price = opt[last_match_pos].price + literalsPrice((int32_t)addLit);
             }
+            zs_trailing(last_match_pos);
         }
         if (encoded_early) continue;
+        zs_window((int64_t)last_match_pos, llen);
         {   /* backtrack :1315-1332 */
             const int32_t best_mlen = opt[last_match_pos].mlen, best_off = opt[last_match_pos].off;
             cur = last_match_pos - (size_t)best_mlen;
             size_t candidate_pos = cur;
+            if (last_match_pos >= ZO_OPT_SPLIT) {
+                zo_opt_stats[ZS_HI_HOP] += 1;
+                if (cur < ZO_OPT_SPLIT) zo_opt_stats[ZS_X_HOP] += 1;
+            }
             int32_t selected_matchLength = best_mlen, selected_offset = best_off;
             for (;;) {
                 const int32_t next_matchLength = opt[candidate_pos].mlen, next_offset = opt[candidate_pos].off;
+                if (candidate_pos >= ZO_OPT_SPLIT) {
+                    zo_opt_stats[ZS_HI_HOP] += 1;
+                    if (next_matchLength <= (int32_t)candidate_pos && candidate_pos - (size_t)next_matchLength < ZO_OPT_SPLIT)
+                        zo_opt_stats[ZS_X_HOP] += 1;
+                }
                 opt[candidate_pos].mlen = selected_matchLength;
                 opt[candidate_pos].off = selected_offset;
                 selected_matchLength = next_matchLength;
@@ -1015,6 +1076,7 @@ static int64_t compressOptimal(hc_ctx *ctx, const uint8_t *src, size_t inputSize
 /* src/lz4hc.zig:1440-1453 + :1457-1489 */
 #define ZO_UNSUPPORTED_LEVEL (-1005)
 int64_t zo_compress_hc(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, int32_t compressionLevel) {
+    memset(zo_opt_stats, 0, sizeof(zo_opt_stats));                       /* the counters are those of the last call */
     if (n > LZ4_MAX_INPUT_SIZE) return ZO_ERR_INPUT_TOO_LARGE;           /* :1442 */
     if (n == 0) return 0;                                                /* :1443 */
     int32_t level = compressionLevel < LZ4HC_CLEVEL_MIN ? LZ4HC_CLEVEL_DEFAULT

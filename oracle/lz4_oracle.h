@@ -89,6 +89,10 @@ int64_t zo_compress_hc(const uint8_t *src, size_t n, uint8_t *dst,
  * levels 9-12; the reference has no defined output there, see lz4_oracle.c) */
 int64_t zo_hc_reference_ub(int reset);
 
+/* event counters of the last level 10-12 compress (compressOptimal): copies up to n of them to out, in the order of
+ * oracle/binding.py OPT_STATS, and returns how many there are.  Test infrastructure only. */
+int zo_hc_opt_stats(int64_t *out, int n);
+
 uint32_t zo_xxh32(const uint8_t *p, size_t n, uint32_t seed);          /* std.hash.XxHash32 */
 
 size_t  zo_compress_frame_bound(size_t n, const zo_prefs *prefs);      /* lz4f.zig:274-301 */

@@ -384,7 +384,22 @@ def _seq_price(litlen, mlen):                         # :473-483
     return p
 
 
-def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-1391
+OPT_SPLIT = 1000                                      # k_hc_opt_parse_wave keeps the records from here on in HBM
+OPT_TRACE_KEYS = ("windows", "max_window", "first_sufficient", "exit_sufficient", "exit_optnum", "min_optnum_sum",
+                  "max_noexit_sum", "ties", "lit_updates", "hi_lit", "hi_match", "hi_trail", "hi_back", "hi_hop",
+                  "x_lit", "x_match", "x_trail", "x_back", "x_hop", "max_llen", "max_optnum_llen", "mflimit_breaks",
+                  "max_price", "max_window_llen", "max_break_cur")
+
+
+def _optimal(src, nb_searches, sufficient_len, trace=None):   # compressOptimal :1068-1391
+    """`trace`, a dict, receives the event counters oracle/lz4_oracle.c keeps (same names, same definitions: hi_* are
+    accesses at record OPT_SPLIT or above, x_* steps whose accesses lie on both sides of it); filled even if the call
+    raises"""
+    t = dict.fromkeys(OPT_TRACE_KEYS, 0)
+    if trace is not None:
+        trace.clear()
+        trace.update(t)
+        t = trace
     n = len(src)
     if n < MFLIMIT + 1:
         return _encode_literals(src)
@@ -398,7 +413,15 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
     if sufficient_len >= OPT_NUM:
         sufficient_len = OPT_NUM - 1
 
+    def window(lmp, llen):
+        if lmp > t["max_window"]:
+            t["max_window"], t["max_window_llen"] = lmp, llen
+
     def trailing(lmp):
+        if lmp + TRAIL >= OPT_SPLIT:
+            t["hi_trail"] += 1
+            if lmp + 1 < OPT_SPLIT:
+                t["x_trail"] += 1
         for add in range(1, TRAIL + 1):
             e = opt[lmp + add]
             e[MLEN], e[OFF], e[LITLEN] = 1, 0, add
@@ -412,8 +435,11 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
             ip += 1
             continue
         if f_len > sufficient_len:                    # :1133
+            t["first_sufficient"] += 1
             ip = anchor = _encode_sequence(out, src, ip, anchor, f_len, f_off)
             continue
+        t["windows"] += 1
+        t["max_llen"] = max(t["max_llen"], llen)
         for r in range(MINMATCH):                     # :1150-1157
             opt[r][MLEN], opt[r][OFF], opt[r][LITLEN], opt[r][PRICE] = 1, 0, llen + r, _lit_price(llen + r)
         for ml in range(MINMATCH, f_len + 1):         # :1160-1169
@@ -425,6 +451,8 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
         while cur < last:                             # :1183
             cur_ptr = ip + cur
             if cur_ptr > mflimit:
+                t["mflimit_breaks"] += 1
+                t["max_break_cur"] = max(t["max_break_cur"], cur)
                 break
             if opt[cur + 1][PRICE] <= opt[cur][PRICE]:
                 cur += 1
@@ -435,6 +463,14 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
                 cur += 1
                 continue
             if n_len > sufficient_len or n_len + cur >= OPT_NUM:     # :1207-1256 (forward walk, as written)
+                if n_len > sufficient_len:
+                    t["exit_sufficient"] += 1
+                else:
+                    t["exit_optnum"] += 1
+                    if t["min_optnum_sum"] == 0 or n_len + cur < t["min_optnum_sum"]:
+                        t["min_optnum_sum"] = n_len + cur
+                    t["max_optnum_llen"] = max(t["max_optnum_llen"], llen)
+                window(last, llen)
                 rp = 0
                 while rp < cur:
                     ml, off = opt[rp][MLEN], opt[rp][OFF]
@@ -447,12 +483,25 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
                 ip = anchor = _encode_sequence(out, src, ip, anchor, n_len, n_off)
                 restart = True
                 break
+            t["max_noexit_sum"] = max(t["max_noexit_sum"], n_len + cur)
             base = opt[cur][LITLEN]                   # :1259-1270
+            if cur + 1 < OPT_SPLIT <= cur + 3:
+                t["x_lit"] += 1
             for litlen in range(1, MINMATCH):
                 price = opt[cur][PRICE] - _lit_price(base) + _lit_price(base + litlen)
                 pos = cur + litlen
                 if price < opt[pos][PRICE]:
+                    t["lit_updates"] += 1
+                    if pos >= OPT_SPLIT:
+                        t["hi_lit"] += 1
                     opt[pos][MLEN], opt[pos][OFF], opt[pos][LITLEN], opt[pos][PRICE] = 1, 0, base + litlen, price
+            if n_len >= MINMATCH and cur + MINMATCH < OPT_SPLIT <= cur + n_len:
+                t["x_match"] += 1
+            if n_len >= MINMATCH and opt[cur][MLEN] == 1 and cur > opt[cur][LITLEN]:
+                if cur - opt[cur][LITLEN] >= OPT_SPLIT:
+                    t["hi_back"] += 1
+                elif cur >= OPT_SPLIT:
+                    t["x_back"] += 1
             for ml in range(MINMATCH, n_len + 1):     # :1273-1302
                 pos = cur + ml
                 if opt[cur][MLEN] == 1:
@@ -463,6 +512,11 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
                     ll = 0
                     price = opt[cur][PRICE] + _seq_price(0, ml)
                 if pos > last + TRAIL or price <= opt[pos][PRICE]:
+                    if pos <= last + TRAIL and price == opt[pos][PRICE]:
+                        t["ties"] += 1
+                    if pos >= OPT_SPLIT:
+                        t["hi_match"] += 1
+                    t["max_price"] = max(t["max_price"], price)
                     if ml == n_len and last < pos:
                         last = pos
                     opt[pos][MLEN], opt[pos][OFF], opt[pos][LITLEN], opt[pos][PRICE] = ml, n_off, ll, price
@@ -470,11 +524,20 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
             cur += 1
         if restart:
             continue
+        window(last, llen)
         best_mlen, best_off = opt[last][MLEN], opt[last][OFF]       # :1315-1332
         cand = last - best_mlen
+        if last >= OPT_SPLIT:
+            t["hi_hop"] += 1
+            if cand < OPT_SPLIT:
+                t["x_hop"] += 1
         sel_ml, sel_off = best_mlen, best_off
         while True:
             nxt_ml, nxt_off = opt[cand][MLEN], opt[cand][OFF]
+            if cand >= OPT_SPLIT:
+                t["hi_hop"] += 1
+                if nxt_ml <= cand and cand - nxt_ml < OPT_SPLIT:
+                    t["x_hop"] += 1
             opt[cand][MLEN], opt[cand][OFF] = sel_ml, sel_off
             sel_ml, sel_off = nxt_ml, nxt_off
             if nxt_ml > cand:
@@ -495,9 +558,12 @@ def _optimal(src, nb_searches, sufficient_len):       # compressOptimal :1068-13
     return bytes(out)
 
 
-def compress_hc(src, level):
+def compress_hc(src, level, trace=None):
     """compressHC src/lz4hc.zig:1440-1453 -> compressHCExtState :1457-1489, level table :72-86."""
     src = bytes(src)
+    if trace is not None:                             # `trace`: the event counters of a level 10-12 parse, see _optimal
+        trace.clear()
+        trace.update(dict.fromkeys(OPT_TRACE_KEYS, 0))
     if len(src) == 0:
         return b""
     level = 9 if level < 2 else (12 if level > 12 else level)
@@ -506,4 +572,4 @@ def compress_hc(src, level):
     if level <= 9:
         return _hash_chain(src, 1 << (level - 1))
     nb, target = {10: (96, 64), 11: (512, 128), 12: (16384, OPT_NUM)}[level]
-    return _optimal(src, nb, target)
+    return _optimal(src, nb, target, trace)
