@@ -838,8 +838,9 @@ int64_t zlz4f_decompress_frame_prefix(const uint8_t *src, size_t src_len, uint8_
 int64_t zlz4f_decompress_frame_prefix_using_dict(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                                  const uint8_t *dict, size_t dict_len);
 
-/* ---- frame index and range decoding: bytes [a, b) of frames whose blocks decode on their own (no counterpart in the
- * reference).  A frame is a chain of blocks; the INDEX says where block k lies and at which decoded
+/* ---- frame index and range decoding: bytes [a, b) of single frames whose blocks decode on their own (no counterpart in
+ * the reference).  Every item is ONE frame (a multiframe buffer, below, is not served: index and
+ * range see its first frame only).  A frame is a chain of blocks; the INDEX says where block k lies and at which decoded
  * offset it starts, the RANGE DECODE decodes only the blocks that overlap [a, b), one wavefront per block.
  *
  * zlz4f_batch_frame_index: frame f with nb blocks in its chain gets nb + 1 entries at d_index + d_idx_off[f] (offsets and
@@ -978,6 +979,84 @@ int32_t zlz4f_batch_compress_frame_using_dict_ex(void *stream,
                                                  void *d_workspace, size_t workspace_bytes);
 int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                            const zlz4f_prefs *prefs, const uint8_t *dict, size_t dict_len);
+
+/* ---- multiframe buffers: concatenated and skippable frames (what a .lz4 file is; no counterpart in the reference;
+ * DESIGN.md section 4.4h).  A MULTIFRAME is a buffer that holds zero or more frames back to back, each of them a MEMBER.
+ * Every other zlz4f_* decode call takes exactly one frame per item and ignores what follows its end mark.
+ *
+ * zlz4f_batch_multiframe_split walks buffer s (d_src + d_src_off[s], d_src_len[s] = n bytes) from position 0.  At pos < n:
+ *   - 4 bytes remain and (magic & 0xFFFFFFF0) == 0x184D2A50: a skippable frame.  sz = the u32 LE at pos + 4; the member is
+ *     { pos, 8 + sz, ZLZ4F_MEMBER_SKIPPABLE | (magic & 15) << 8 }.  Fewer than 8 bytes remain, or pos + 8 + sz > n: the kind
+ *     is ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED (| nibble << 8), the member reaches to n and is the last one.
+ *   - anything else is a frame member { pos, len, ZLZ4F_MEMBER_FRAME }: the header (up to 19 bytes), then the block chain
+ *     (header word w, sz = w & 0x7FFFFFFF, + 4 with FLG 0x10) up to and including the end mark, then the 4-byte content
+ *     checksum word with FLG 0x04.
+ *   - WHATEVER CANNOT BE DELIMITED IS THE LAST MEMBER AND REACHES TO n: a header error (unknown magic, the legacy magic
+ *     0x184C2102, fewer than 7 bytes, ...), a chain that runs off the buffer, a missing end mark, a missing checksum word.
+ *     The split never judges a frame: the frame calls give that member its error -- or, for a chain that merely lacks its
+ *     end mark at the end of the buffer, its content -- exactly as they do for a frame that stands alone.  So a multiframe
+ *     of one frame answers what the frame call answers for it, byte for byte and code for code.
+ *   kind & 0xFF is the ZLZ4F_MEMBER_* kind, (kind >> 8) & 15 the low nibble of a skippable magic.
+ *   COUNT MODE (d_member == NULL; every argument behind it is ignored): d_count[s] = the members of buffer s, d_totals =
+ *     { members of all buffers, blocks of all frame members' chains (the max_blocks of the frame calls) }: one 16-byte
+ *     read-back sizes everything that follows.
+ *   RECORD MODE: the count again (d_count and d_totals as above), then d_item_first = the exclusive scan of d_count, nbuf + 1
+ *     entries; member k of buffer s is item i = d_item_first[s] + k and is written to d_member[d_mem_off[s] + k] (offsets
+ *     and capacities count entries), with the item arrays of the frame batch calls: d_item_off[i] = d_src_off[s] + pos,
+ *     d_item_len[i] = len for a frame member and 0 for a skippable one.  An item of length 0 is answered by the frame calls
+ *     with ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE without a byte read or written; the calls below know from `kind` to ignore
+ *     that answer.  d_count[s] > d_mem_cap[s]: d_result[s] = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL, no entry of that buffer is
+ *     written and its items keep their room with length 0; otherwise d_result[s] = d_count[s].
+ *   Null or 8-byte-misaligned arrays: ZLZ4_ERR_INVALID_STATE, nothing launched; the device check is the last refusal.
+ *   nbuf == 0 returns 0 and stores two zeros.
+ *
+ * zlz4f_batch_multiframe_plan: d_size[i] = what zlz4f_batch_frame_decompressed_size_ex answered for item i (over d_item_off /
+ *   d_item_len, with the caller's decode_flags).  d_dst_cap[i] = d_size[i], or 0 for an item whose query failed -- every
+ *   skippable item among them; d_out_size[s] = the sum over the items of buffer s; d_out_off[s] = the exclusive scan of
+ *   d_out_size rounded up to `align` (0, 1 or a power of two up to 4096, as zlz4_batch_plan_outputs); d_dst_off[i] =
+ *   d_out_off[s] + the capacities of the buffer's earlier items: the decoded members of a buffer form ONE RUN of bytes in
+ *   member order.  d_totals = { arena bytes, the sum of d_out_size }.  The member table is not read: the query's answer
+ *   says all the plan needs.  Refusals as above; nbuf == 0 stores two zeros.
+ *
+ * The decode is zlz4f_batch_decompress_frame_ex over the item arrays with d_dst_off / d_dst_cap of the plan, nframes =
+ *   d_totals[0] of the split and max_blocks = d_totals[1] of the split.
+ *
+ * zlz4f_batch_multiframe_finish folds the items into d_result[s]: a split result < 0 is the result; else the first member
+ *   in member order that is not OK decides -- a frame member's d_size[i] when negative, else its d_item_result[i] when
+ *   negative; ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED: ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE when fewer than 8 bytes remained, else
+ *   ZLZ4F_ERR_FRAME_SIZE_WRONG -- otherwise the sum of the frame members' d_item_result, which equals d_out_size[s].  An
+ *   empty buffer and a buffer of skippable frames give 0.  On an error nothing of the buffer's slot is promised; no byte
+ *   outside [d_out_off[s], d_out_off[s] + d_out_size[s]) is ever written.  The item results stay the caller's to read: the
+ *   members in front of a defect are decoded and can be salvaged.  (With d_item_result = d_size the call folds the size
+ *   query alone: what the decode answers apart from the content checksums.)
+ * All three: asynchronous on `stream`, a fixed launch sequence per mode, nothing allocated, nothing read back.
+ *
+ * zlz4f_multiframe_decompressed_size / zlz4f_decompress_multiframe: one buffer in HOST memory, staged and run as a batch
+ *   of one: count (read-back), record, size query, plan (read-back), decode, finish.  An unknown decode_flags bit:
+ *   ZLZ4F_ERR_PARAMETER_INVALID, then a null pointer with a length: ZLZ4_ERR_INVALID_STATE, both before the device check.
+ *   The planned total above dst_cap: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.
+ *
+ * NOT SERVED: a dictionary per member (a member with a dictID decodes as the plain frame call decodes it); prefix and
+ *   range decoding of a multiframe; the legacy frame format (magic 0x184C2102 is a member that cannot be delimited:
+ *   ZLZ4F_ERR_FRAME_TYPE_UNKNOWN); writing multiframes (they are the concatenation of what the compress calls return). */
+#define ZLZ4F_MEMBER_FRAME               1u
+#define ZLZ4F_MEMBER_SKIPPABLE           2u
+#define ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED 3u
+typedef struct { uint64_t pos; uint64_t len; uint32_t kind; uint32_t buf; } zlz4f_member;    /* 24 bytes */
+int32_t zlz4f_batch_multiframe_split(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                     const uint64_t *d_src_len, uint32_t nbuf, uint64_t *d_count, uint64_t *d_totals,
+                                     zlz4f_member *d_member, const uint64_t *d_mem_off, const uint64_t *d_mem_cap,
+                                     uint64_t *d_item_first, uint64_t *d_item_off, uint64_t *d_item_len,
+                                     int64_t *d_result);
+int32_t zlz4f_batch_multiframe_plan(void *stream, const int64_t *d_size, const uint64_t *d_item_first, uint32_t nbuf,
+                                    uint32_t align, uint64_t *d_dst_off, uint64_t *d_dst_cap, uint64_t *d_out_off,
+                                    uint64_t *d_out_size, uint64_t *d_totals);
+int32_t zlz4f_batch_multiframe_finish(void *stream, const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                                      const int64_t *d_split_result, const uint64_t *d_item_first, const int64_t *d_size,
+                                      const int64_t *d_item_result, uint32_t nbuf, int64_t *d_result);
+int64_t zlz4f_multiframe_decompressed_size(const uint8_t *src, size_t src_len, uint32_t decode_flags);
+int64_t zlz4f_decompress_multiframe(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                    uint32_t decode_flags);
 
 /* ======================================================================
  * 4. Introspection

@@ -148,6 +148,11 @@ SYMBOLS = {
     "zlz4f_batch_decompress_frame_range_workspace": (_SZ, [_U32, _U32]),
     "zlz4f_batch_decompress_frame_range": (_I32, [_VP] * 7 + [_U32] + [_VP] * 6 + [_U32, _U32, _VP, _SZ]),
     "zlz4f_decompress_frame_range": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ]),
+    "zlz4f_batch_multiframe_split": (_I32, [_VP] * 4 + [_U32] + [_VP] * 9),
+    "zlz4f_batch_multiframe_plan": (_I32, [_VP] * 3 + [_U32, _U32] + [_VP] * 5),
+    "zlz4f_batch_multiframe_finish": (_I32, [_VP] * 7 + [_U32, _VP]),
+    "zlz4f_multiframe_decompressed_size": (_I64, [_VP, _SZ, _U32]),
+    "zlz4f_decompress_multiframe": (_I64, [_VP, _SZ, _VP, _SZ, _U32]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -1051,6 +1056,137 @@ class lz4f:
         d = (C.c_uint8 * max(1, cap))()
         r = _check(lib().zlz4f_decompress_frame_range(C.addressof(s), n, a, b, C.addressof(d), cap))
         return bytes(d[:r])
+
+    # multiframe buffers: concatenated and skippable frames (include/zlz4_amd.h)
+    MEMBER_FRAME, MEMBER_SKIPPABLE, MEMBER_SKIPPABLE_TRUNCATED = 1, 2, 3
+
+    @staticmethod
+    def multiframeSplitBatch(d_src, src_off, src_len, count, totals, member=None, mem_off=None, mem_cap=None,
+                             item_first=None, item_off=None, item_len=None, result=None):
+        """zlz4f_batch_multiframe_split on torch CUDA tensors: count int64 [nbuf], totals int64 [2] = (members, chain blocks).
+        member None: count mode.  Else member int64 [entries, 3] = (pos, len, kind | buf << 32) per entry, mem_off / mem_cap
+        int64 [nbuf] in entries, item_first int64 [nbuf + 1], item_off / item_len int64 [members], result int64 [nbuf]."""
+        _check(lib().zlz4f_batch_multiframe_split(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), src_len.numel(),
+                                                  _ptr(count), _ptr(totals), _ptr(member), _ptr(mem_off), _ptr(mem_cap),
+                                                  _ptr(item_first), _ptr(item_off), _ptr(item_len), _ptr(result)))
+
+    @staticmethod
+    def multiframePlanBatch(size, item_first, dst_off, dst_cap, out_off, out_size, totals, align=0):
+        """zlz4f_batch_multiframe_plan: size / dst_off / dst_cap int64 per item, out_off / out_size int64 per buffer, totals
+        int64 [2] = (arena bytes, decoded bytes)."""
+        _check(lib().zlz4f_batch_multiframe_plan(_stream(), _ptr(size), _ptr(item_first), out_size.numel(), align,
+                                                 _ptr(dst_off), _ptr(dst_cap), _ptr(out_off), _ptr(out_size), _ptr(totals)))
+
+    @staticmethod
+    def multiframeFinishBatch(member, mem_off, split_result, item_first, size, item_result, result):
+        """zlz4f_batch_multiframe_finish: result int64 [nbuf] = the decoded size of buffer s or the code of its first member
+        that is not OK."""
+        _check(lib().zlz4f_batch_multiframe_finish(_stream(), _ptr(member), _ptr(mem_off), _ptr(split_result),
+                                                   _ptr(item_first), _ptr(size), _ptr(item_result), result.numel(),
+                                                   _ptr(result)))
+
+    class MultiframeSplit:
+        """What splitMultiframes returns: the staged buffers (d_src, src_off, src_len), the member table (member, mem_off,
+        count), the item arrays of the frame batch calls (item_first, item_off, item_len), the split results on the device
+        (result) and on the host (results), and the totals (nitems, max_blocks)."""
+
+    class MultiframeDecode:
+        """What decodeMultiframes returns: per item size, dst_off, dst_cap and item_result, per buffer out_off, out_size and
+        result, and the arena d_dst; all on the device."""
+
+    @staticmethod
+    def splitMultiframes(buffers, device="cuda"):
+        """Stage `buffers` and delimit their members: count mode, one read-back of the totals, record mode."""
+        import torch
+        sp = lz4f.MultiframeSplit()
+        nbuf = len(buffers)
+        sp.d_src, sp.src_off, sp.src_len = _stage(buffers, device)
+
+        def i64(n):
+            return torch.zeros(max(1, n), dtype=torch.int64, device=device)[:n]
+
+        sp.count, totals = i64(nbuf), i64(2)
+        lz4f.multiframeSplitBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals)
+        sp.nitems, sp.max_blocks = totals.cpu().tolist()
+        sp.member = torch.zeros((max(1, sp.nitems), 3), dtype=torch.int64, device=device)
+        sp.item_first, sp.item_off, sp.item_len, sp.result = i64(nbuf + 1), i64(sp.nitems), i64(sp.nitems), i64(nbuf)
+        lz4f.multiframeSplitBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals, sp.member, sp.item_first[:nbuf],
+                                  sp.count, sp.item_first, sp.item_off, sp.item_len, sp.result)
+        sp.mem_off = sp.item_first[:nbuf]             # the member table is laid out as the items are
+        sp.results = sp.result.cpu().tolist()
+        return sp
+
+    @staticmethod
+    def multiframeMembers(buffers, device="cuda"):
+        """Per buffer the list of its members (pos, len, kind, nibble) -- kind one of lz4f.MEMBER_*, nibble the low four
+        bits of a skippable magic -- or the split's error code."""
+        if not len(buffers):
+            return []
+        sp = lz4f.splitMultiframes(buffers, device)
+        rows = sp.member.cpu().tolist()
+        first = sp.item_first.cpu().tolist()
+        out = []
+        for s, r in enumerate(sp.results):
+            if r < 0:
+                out.append(r)
+                continue
+            out.append([(pos, ln, kb & 0xFF, (kb >> 8) & 15) for pos, ln, kb in rows[first[s]:first[s] + r]])
+        return out
+
+    @staticmethod
+    def decodeMultiframes(sp, flags=0, align=0, d_dst=None):
+        """Size query, plan, one read-back of the arena size, decode and finish over a MultiframeSplit -> MultiframeDecode.
+        d_dst: an arena of the caller's (at least the planned bytes), else one is allocated."""
+        import torch
+        dev = sp.d_src.device
+        nbuf, ni = sp.src_len.numel(), sp.nitems
+        dd = lz4f.MultiframeDecode()
+
+        def i64(n):
+            return torch.zeros(max(1, n), dtype=torch.int64, device=dev)[:n]
+
+        dd.size, dd.dst_off, dd.dst_cap, dd.item_result = i64(ni), i64(ni), i64(ni), i64(ni)
+        dd.out_off, dd.out_size, dd.result, totals = i64(nbuf), i64(nbuf), i64(nbuf), i64(2)
+        if ni:
+            lz4f.frameDecompressedSizeBatch(sp.d_src, sp.item_off, sp.item_len, dd.size, max_blocks=sp.max_blocks,
+                                            flags=flags)
+        lz4f.multiframePlanBatch(dd.size, sp.item_first, dd.dst_off, dd.dst_cap, dd.out_off, dd.out_size, totals, align)
+        dd.arena_bytes, dd.decoded_bytes = totals.cpu().tolist()
+        if d_dst is None:
+            d_dst = torch.empty(max(1, dd.arena_bytes), dtype=torch.uint8, device=dev)
+        elif d_dst.numel() < dd.arena_bytes:
+            raise ValueError("d_dst holds %d bytes, the plan needs %d" % (d_dst.numel(), dd.arena_bytes))
+        dd.d_dst = d_dst
+        if ni:
+            lz4f.decompressFrameBatch(sp.d_src, sp.item_off, sp.item_len, d_dst, dd.dst_off, dd.dst_cap, dd.item_result,
+                                      max_blocks=sp.max_blocks, flags=flags)
+        if nbuf:
+            lz4f.multiframeFinishBatch(sp.member, sp.mem_off, sp.result, sp.item_first, dd.size, dd.item_result, dd.result)
+        return dd
+
+    @staticmethod
+    def decompressMultiframes(buffers, flags=0, align=0, device="cuda"):
+        """Every buffer of `buffers` -- frames and skippable frames back to back, what a .lz4 file holds -- decoded in one
+        batch: -> list of contents (the members' contents concatenated) or the code of the first member that is not OK."""
+        if flags & ~lz4f.DECODE_LINKED:
+            _check(lib().zlz4f_decompress_multiframe(None, 0, None, 0, flags))
+        if not len(buffers):
+            return []
+        dd = lz4f.decodeMultiframes(lz4f.splitMultiframes(buffers, device), flags, align)
+        return _unstage(dd.d_dst, dd.out_off.cpu().tolist(), dd.result)
+
+    @staticmethod
+    def multiframeDecompressedSize(src, flags=0):
+        """zlz4f_multiframe_decompressed_size: what decompressMultiframe returns for `src` into a destination that is large
+        enough (content checksums are not verified); errors raise Lz4Error.  Nothing is decoded."""
+        s, n = _in(src)
+        return _check(lib().zlz4f_multiframe_decompressed_size(C.addressof(s), n, flags))
+
+    @staticmethod
+    def decompressMultiframe(src, flags=0, dst_cap=None):
+        """zlz4f_decompress_multiframe: one buffer in host memory.  dst_cap None: the size is queried first."""
+        cap = lz4f.multiframeDecompressedSize(src, flags) if dst_cap is None else dst_cap
+        return _run(lib().zlz4f_decompress_multiframe, src, cap, flags)
 
 
 def _offsets(lens):

@@ -426,6 +426,40 @@ inline Result decompressFrameRange(const std::uint8_t *src, std::size_t n, std::
                                    std::size_t cap) {
     return wrap(zlz4f_decompress_frame_range(src, n, a, b, dst, cap));
 }
+// multiframe buffers (include/zlz4_amd.h; no counterpart in the reference): frames and skippable frames back to back, as in
+// a .lz4 file.  multiframeSplitBatch delimits the members of every buffer (t.member == nullptr: count mode) and writes them
+// as the items of the frame batch calls; multiframePlanBatch packs a buffer's items into one run of bytes;
+// multiframeFinishBatch folds the item results: the first member that is not OK decides, else the decoded size.  Whatever
+// the split cannot delimit is the last member and reaches to the end of its buffer.
+using Member = zlz4f_member;
+struct Multiframes { const std::uint8_t *src; const std::uint64_t *src_off, *src_len; std::uint32_t nbuf; };
+struct MemberTable {
+    Member *member; const std::uint64_t *mem_off, *mem_cap;
+    std::uint64_t *item_first, *item_off, *item_len; std::int64_t *result;
+};
+inline Result multiframeSplitBatch(void *stream, const Multiframes &m, std::uint64_t *d_count, std::uint64_t *d_totals,
+                                   const MemberTable &t) {
+    return wrap(zlz4f_batch_multiframe_split(stream, m.src, m.src_off, m.src_len, m.nbuf, d_count, d_totals, t.member, t.mem_off,
+                                             t.mem_cap, t.item_first, t.item_off, t.item_len, t.result));
+}
+inline Result multiframePlanBatch(void *stream, const std::int64_t *d_size, const std::uint64_t *d_item_first, std::uint32_t nbuf,
+                                  std::uint32_t align, std::uint64_t *d_dst_off, std::uint64_t *d_dst_cap,
+                                  std::uint64_t *d_out_off, std::uint64_t *d_out_size, std::uint64_t *d_totals) {
+    return wrap(zlz4f_batch_multiframe_plan(stream, d_size, d_item_first, nbuf, align, d_dst_off, d_dst_cap, d_out_off, d_out_size,
+                                            d_totals));
+}
+inline Result multiframeFinishBatch(void *stream, const MemberTable &t, const std::int64_t *d_size,
+                                    const std::int64_t *d_item_result, std::uint32_t nbuf, std::int64_t *d_result) {
+    return wrap(zlz4f_batch_multiframe_finish(stream, t.member, t.mem_off, t.result, t.item_first, d_size, d_item_result, nbuf,
+                                              d_result));
+}
+inline Result multiframeDecompressedSize(const std::uint8_t *src, std::size_t n, std::uint32_t decode_flags = 0) {
+    return wrap(zlz4f_multiframe_decompressed_size(src, n, decode_flags));
+}
+inline Result decompressMultiframe(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                                   std::uint32_t decode_flags = 0) {
+    return wrap(zlz4f_decompress_multiframe(src, n, dst, cap, decode_flags));
+}
 }  // namespace lz4f
 
 }  // namespace zlz4

@@ -110,6 +110,13 @@ extern "c" fn zlz4f_batch_plan_frame_ranges(stream: ?*anyopaque, d_index: [*]con
 extern "c" fn zlz4f_batch_decompress_frame_range_workspace(nranges: u32, max_items: u32) usize;
 extern "c" fn zlz4f_batch_decompress_frame_range(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_index: [*]const IndexEntry, d_idx_off: [*]const u64, d_idx_n: [*]const i64, nframes: u32, d_range: [*]const Range, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_skip: [*]u64, d_result: [*]i64, nranges: u32, max_items: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_decompress_frame_range(src: [*]const u8, src_len: usize, a: u64, b: u64, dst: [*]u8, dst_cap: usize) i64;
+extern "c" fn zlz4f_batch_multiframe_split(stream: ?*anyopaque, d_src: ?[*]const u8, d_src_off: ?[*]const u64, d_src_len: ?[*]const u64, nbuf: u32, d_count: ?[*]u64, d_totals: [*]u64, d_member: ?[*]Member, d_mem_off: ?[*]const u64, d_mem_cap: ?[*]const u64, d_item_first: ?[*]u64, d_item_off: ?[*]u64, d_item_len: ?[*]u64, d_result: ?[*]i64) i32;
+extern "c" fn zlz4f_batch_multiframe_plan(stream: ?*anyopaque, d_size: ?[*]const i64, d_item_first: ?[*]const u64, nbuf: u32, alignment: u32, d_dst_off: ?[*]u64, d_dst_cap: ?[*]u64, d_out_off: ?[*]u64, d_out_size: ?[*]u64, d_totals: [*]u64) i32;
+extern "c" fn zlz4f_batch_multiframe_finish(stream: ?*anyopaque, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_item_first: ?[*]const u64, d_size: ?[*]const i64, d_item_result: ?[*]const i64, nbuf: u32, d_result: ?[*]i64) i32;
+extern "c" fn zlz4f_multiframe_decompressed_size(src: [*]const u8, src_len: usize, decode_flags: u32) i64;
+extern "c" fn zlz4f_decompress_multiframe(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
+/// zlz4f_member of include/zlz4_amd.h: kind & 0xFF is a MEMBER_* kind, (kind >> 8) & 15 the nibble of a skippable magic
+pub const Member = extern struct { pos: u64, len: u64, kind: u32, buf: u32 };
 /// zlz4f_index_entry / zlz4f_range of include/zlz4_amd.h
 pub const IndexEntry = extern struct { pos: u64, dec: u64 };
 pub const Range = extern struct { frame: u32, reserved: u32 = 0, a: u64, b: u64 };
@@ -859,6 +866,30 @@ pub const lz4f = struct {
     /// bytes [a, b) of one frame in host memory (both clamped to the frame's size) at dst[0..]; builds the index on every call
     pub fn decompressFrameRange(src: []const u8, a: u64, b: u64, dst: []u8) Error!usize {
         return mapFrame(zlz4f_decompress_frame_range(src.ptr, src.len, a, b, dst.ptr, dst.len));
+    }
+    /// No counterpart in the reference: multiframe buffers, frames and skippable frames back to back as in a .lz4 file
+    /// (include/zlz4_amd.h).  multiframeSplitBatch delimits the members of every buffer (member == null: count mode) and
+    /// writes them as the items of frameDecompressedSizeBatchEx / decompressFrameBatchEx; multiframePlanBatch packs a
+    /// buffer's items into one run of bytes; multiframeFinishBatch folds the item results: the first member that is not OK
+    /// decides, else the decoded size.  Whatever the split cannot delimit is the last member and reaches to the end.
+    pub const MEMBER_FRAME: u32 = 1;
+    pub const MEMBER_SKIPPABLE: u32 = 2;
+    pub const MEMBER_SKIPPABLE_TRUNCATED: u32 = 3;
+    pub fn multiframeSplitBatch(stream: ?*anyopaque, src: ?[*]const u8, src_off: ?[*]const u64, src_len: ?[*]const u64, nbuf: u32, count: ?[*]u64, totals: [*]u64, member: ?[*]Member, mem_off: ?[*]const u64, mem_cap: ?[*]const u64, item_first: ?[*]u64, item_off: ?[*]u64, item_len: ?[*]u64, result: ?[*]i64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_multiframe_split(stream, src, src_off, src_len, nbuf, count, totals, member, mem_off, mem_cap, item_first, item_off, item_len, result));
+    }
+    pub fn multiframePlanBatch(stream: ?*anyopaque, size: ?[*]const i64, item_first: ?[*]const u64, nbuf: u32, alignment: u32, dst_off: ?[*]u64, dst_cap: ?[*]u64, out_off: ?[*]u64, out_size: ?[*]u64, totals: [*]u64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_multiframe_plan(stream, size, item_first, nbuf, alignment, dst_off, dst_cap, out_off, out_size, totals));
+    }
+    pub fn multiframeFinishBatch(stream: ?*anyopaque, member: ?[*]const Member, mem_off: ?[*]const u64, split_result: ?[*]const i64, item_first: ?[*]const u64, size: ?[*]const i64, item_result: ?[*]const i64, nbuf: u32, result: ?[*]i64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_multiframe_finish(stream, member, mem_off, split_result, item_first, size, item_result, nbuf, result));
+    }
+    /// one buffer in host memory: the sum of its members' decoded sizes (content checksums set aside) / its content at dst
+    pub fn multiframeDecompressedSize(src: []const u8, decode_flags: u32) Error!usize {
+        return mapFrame(zlz4f_multiframe_decompressed_size(src.ptr, src.len, decode_flags));
+    }
+    pub fn decompressMultiframe(src: []const u8, dst: []u8, decode_flags: u32) Error!usize {
+        return mapFrame(zlz4f_decompress_multiframe(src.ptr, src.len, dst.ptr, dst.len, decode_flags));
     }
     pub fn frameDecompressedSizeUsingDict(src: []const u8, dict_len: usize) Error!usize {
         return mapFrame(zlz4f_frame_decompressed_size_using_dict(src.ptr, src.len, dict_len));
