@@ -135,9 +135,8 @@ __global__ void k_block_xxh32(const uint8_t *__restrict__ src, const uint64_t *_
                               const uint32_t *__restrict__ hdr, uint32_t nblocks, uint32_t *__restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nblocks) return;
-    const uint32_t h = hdr[i];
-    const uint8_t *p = (h & 0x80000000u) ? src + src_off[i] : slots + slot_off[i];
-    out[i] = xxh32(p, h & 0x7FFFFFFFu, 0);
+    const BlockWord w = block_word(hdr[i]);
+    out[i] = xxh32(w.stored ? src + src_off[i] : slots + slot_off[i], w.size, 0);
 }
 
 // one workgroup per block: header word, payload (compressed slot or raw source), optional checksum
@@ -147,8 +146,9 @@ __device__ __forceinline__ void scatter_block(uint32_t i, const uint8_t *__restr
                                               const uint32_t *__restrict__ cks, uint32_t block_checksum,
                                               uint8_t *__restrict__ dst) {
     const uint32_t t = threadIdx.x;
-    const uint32_t n = h & 0x7FFFFFFFu;
-    const uint8_t *p = (h & 0x80000000u) ? src + src_off[i] : slots + slot_off[i];
+    const BlockWord w = block_word(h);
+    const uint32_t n = w.size;
+    const uint8_t *p = w.stored ? src + src_off[i] : slots + slot_off[i];
     uint8_t *o = dst + dst_off[i];
     if (t < 4) o[t] = (uint8_t)(h >> (8u * t));                                   // :418
     o += 4;
@@ -205,10 +205,7 @@ __global__ void k_frame_walk(const uint8_t *__restrict__ src, uint64_t src_len, 
     uint64_t bs = bs_in;
     walk[0] = 0; walk[1] = 0; walk[2] = 0; walk[3] = 0;
     if (seg & 1u) {
-        uint8_t head[19];
-        const size_t have = src_len < sizeof head ? (size_t)src_len : sizeof head;
-        for (size_t k = 0; k < have; k++) head[k] = src[k];
-        const ParsedHeader ph = parse_header(head, have);                               // :547
+        const ParsedHeader ph = frame_header(src, src_len);                             // :547
         walk[3] = ph.size;
         if (ph.size < 0) { walk[4] = 0; walk[5] = 0; return; }
         src_pos = (uint64_t)ph.size;
@@ -216,29 +213,13 @@ __global__ void k_frame_walk(const uint8_t *__restrict__ src, uint64_t src_len, 
         bs = ph.block_size;
     }
     walk[4] = flg; walk[5] = (int64_t)bs;
-    const uint32_t block_checksum = (flg & 0x10u) ? 1u : 0u;
-    uint64_t nb = 0;
-    int64_t err = 0;
-    while (src_pos < src_len) {                                       // :563
-        if (src_pos + 4 > src_len) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }        // :565
-        const uint32_t h = zx_rd32(src + src_pos);
-        src_pos += 4;
-        if (h == 0) break;                                            // :573
-        const uint32_t sz = h & 0x7FFFFFFFu;
-        if (src_pos + sz > src_len) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }       // :582
-        const uint64_t off = src_pos;
-        src_pos += sz;
-        uint32_t fl = (h >> 31);
-        uint64_t co = 0;
-        if (block_checksum) {                                         // :590
-            if (src_pos + 4 > src_len) fl |= 2u;                      // FrameSizeWrong when this block is reached
-            else { co = src_pos; src_pos += 4; }
-        }
-        if (nb < max_blocks) { data_off[nb] = off; data_len[nb] = sz; flags[nb] = fl; cks_off[nb] = co; }
-        nb++;
-        if (fl & 2u) break;
-    }
-    walk[0] = (int64_t)nb; walk[1] = (int64_t)src_pos; walk[2] = err;
+    uint64_t nb;
+    const bool bc = (flg & 0x10u) != 0;
+    const ChainEnd end = chain_walk(src, src_len, bc, src_pos, ~0ull, nb, [&](uint64_t k, const ChainBlock &c) {
+        if (k >= max_blocks) return;
+        data_off[k] = c.off; data_len[k] = c.size; flags[k] = c.flags & (kBlkStored | kBlkNoCks); cks_off[k] = c.cks_off;
+    });
+    walk[0] = (int64_t)nb; walk[1] = (int64_t)src_pos; walk[2] = chain_error(end);
 }
 
 // one lane per block: verify the stored XXH32 of the block payload (:594-598); ok[i] = 1 / 0
@@ -832,8 +813,9 @@ __global__ void k_bfd_init(uint32_t *__restrict__ data_len, uint32_t *__restrict
     }
 }
 
-// one lane per frame: k_frame_walk's header parse (:547) and chain walk (:563-600).  The first pass counts (kRecord false),
-// the second records the blocks of every frame that fits the table at its base.
+// one lane per frame: the header parse (:547, frame_header) and the chain walk (:563-600, chain_walk) that k_frame_walk, the
+// multiframe split and the host calls run too.  The first pass counts (kRecord false), the second records the blocks of
+// every frame that fits the table at its base.
 template <bool kRecord>
 __global__ void k_bfd_walk(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
                            const uint64_t *__restrict__ src_len, uint32_t nframes, uint32_t max_blocks,
@@ -852,10 +834,7 @@ __global__ void k_bfd_walk(const uint8_t *__restrict__ src, const uint64_t *__re
         flg = F.flg;
         entry = F.base;
     } else {
-        uint8_t head[19];
-        const uint32_t have = n < sizeof head ? (uint32_t)n : (uint32_t)sizeof head;
-        for (uint32_t k = 0; k < have; k++) head[k] = s[k];
-        const ParsedHeader ph = parse_header(head, have);
+        const ParsedHeader ph = frame_header(s, n);
         BFrame F = {};
         F.status = ph.size;
         F.flg = ph.flg;
@@ -865,33 +844,14 @@ __global__ void k_bfd_walk(const uint8_t *__restrict__ src, const uint64_t *__re
         pos = (uint64_t)ph.size;
         flg = ph.flg;
     }
-    const bool bc = (flg & 0x10u) != 0;
     const uint64_t nb_max = kRecord ? fr[f].nb : ~0ull;               // (the record pass never leaves the frame's range)
-    uint64_t nb = 0;
-    int64_t err = 0;
-    while (pos < n && nb < nb_max) {                                  // :563
-        if (pos + 4 > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }             // :565
-        const uint32_t h = zx_rd32(s + pos);
-        pos += 4;
-        if (h == 0) break;                                            // :573
-        const uint32_t sz = h & 0x7FFFFFFFu;
-        if (pos + sz > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }            // :582
-        const uint64_t off = pos;
-        pos += sz;
-        uint32_t fl = (h >> 31);
-        uint64_t co = 0;
-        if (bc) {                                                     // :590
-            if (pos + 4 > n) fl |= kBlkNoCks;                         // FrameSizeWrong when this block is reached
-            else { co = pos; pos += 4; fl |= kBlkCks; }
-        }
-        if (kRecord) {
-            const uint64_t i = entry + nb;
-            data_off[i] = so + off; data_len[i] = sz; flags[i] = fl; cks_off[i] = so + co; fidx[i] = f;
-        }
-        nb++;
-        if (fl & kBlkNoCks) break;
-    }
-    if (!kRecord) { fr[f].nb = nb; fr[f].end = pos; fr[f].err = err; }
+    uint64_t nb;
+    const ChainEnd end = chain_walk(s, n, (flg & 0x10u) != 0, pos, nb_max, nb, [&](uint64_t k, const ChainBlock &c) {
+        if (!kRecord) return;
+        const uint64_t i = entry + k;
+        data_off[i] = so + c.off; data_len[i] = c.size; flags[i] = c.flags; cks_off[i] = so + c.cks_off; fidx[i] = f;
+    });
+    if (!kRecord) { fr[f].nb = nb; fr[f].end = pos; fr[f].err = chain_error(end); }
 }
 
 // one lane per entry of a frame whose FLG asks for block checksums: k_block_verify (:594-598)
@@ -1887,22 +1847,13 @@ int64_t zlz4f_frame_decompressed_size_ex(const uint8_t *src, size_t n, uint32_t 
 
 // what zlz4f_decompress_frame returns into a destination that is large enough (the content checksum aside), host
 // pointers: the frame is staged and queried as a batch of one; the block count for the table comes from a host walk of
-// the chain (k_bfd_walk's)
+// the chain (chain_blocks)
 int64_t zlz4f_frame_decompressed_size(const uint8_t *src, size_t n) {
     if (!src && n) return ZLZ4_ERR_INVALID_STATE;
     const ParsedHeader ph = parse_header(src, n);      // header errors need no device
     if (ph.size < 0) return ph.size;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const bool bc = (ph.flg & 0x10u) != 0;
-    uint64_t pos = (uint64_t)ph.size, nb = 0;
-    while (pos + 4 <= n) {
-        const uint32_t h = zx_rd32(src + pos);
-        const uint64_t sz = h & 0x7FFFFFFFu;
-        if (h == 0 || pos + 4 + sz > n) break;
-        pos += 4 + sz;
-        nb++;
-        if (bc) { if (pos + 4 > n) break; pos += 4; }
-    }
+    const uint64_t nb = chain_blocks(src, n, ph);
     if (nb > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const uint32_t max_blocks = (uint32_t)nb;
     const size_t ws = zlz4f_batch_frame_decompressed_size_workspace(1, max_blocks);
@@ -1935,13 +1886,9 @@ __global__ void k_bf_dict_id(const uint8_t *__restrict__ src, const uint64_t *__
     const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nframes) return;
     const uint8_t *s = src + src_off[f];
-    const uint64_t n = src_len[f];
-    uint8_t head[19];
-    const uint32_t have = n < sizeof head ? (uint32_t)n : (uint32_t)sizeof head;
-    for (uint32_t k = 0; k < have; k++) head[k] = s[k];
-    const ParsedHeader ph = parse_header(head, have);
+    const ParsedHeader ph = frame_header(s, src_len[f]);
     if (ph.size < 0) { dict_id[f] = ph.size; return; }
-    dict_id[f] = (ph.flg & 0x01u) ? (int64_t)zx_rd32(head + 6 + ((ph.flg & 0x08u) ? 8 : 0)) : 0;
+    dict_id[f] = (ph.flg & 0x01u) ? (int64_t)zx_rd32(s + 6 + ((ph.flg & 0x08u) ? 8 : 0)) : 0;   // (inside the header)
 }
 
 // the host-pointer call of both entry points: the refusals are host arithmetic and come before the device check
@@ -2417,9 +2364,9 @@ __global__ void k_bfr_expand(const BRange *__restrict__ rg, uint32_t nranges, ui
                 const uint64_t k = G.k0 + j;
                 const zlz4f_index_entry E = e[k], N = e[k + 1u];
                 const uint64_t so = src_off[f];
-                const uint32_t w = zx_rd32(src + so + E.pos);
-                const uint32_t sz = w & 0x7FFFFFFFu;
-                if (w == 0 || E.pos + 4u + sz + (G.bc ? 4u : 0u) != N.pos) ierr = kItemChain;      // (0: the end mark, no block)
+                const BlockWord w = block_word(zx_rd32(src + so + E.pos));
+                const uint32_t sz = w.size;
+                if (w.end_mark || E.pos + 4u + sz + (G.bc ? 4u : 0u) != N.pos) ierr = kItemChain;  // (the end mark is no block)
                 else {
                     const uint32_t step = (uint32_t)(N.dec - E.dec);             // <= the block size (k_bfr_range)
                     const uint64_t left = G.b - E.dec;                           // > 0: dec[k] <= dec[k1] < b'
@@ -2428,7 +2375,7 @@ __global__ void k_bfr_expand(const BRange *__restrict__ rg, uint32_t nranges, ui
                     d_len = sz;
                     o_off = dst_off[r] + (E.dec - G.d0);
                     if (G.bc) { fl |= kBlkCks; c_off = d_off + sz; }
-                    if (w >> 31) {
+                    if (w.stored) {
                         fl |= kBlkStored;
                         if (sz != step) ierr = kItemStored; else c_len = want;
                     } else if (want == step) { f_len = sz; f_cap = step; }
@@ -2614,16 +2561,7 @@ int64_t zlz4f_decompress_frame_range(const uint8_t *src, size_t n, uint64_t a, u
     if (ph.size < 0) return ph.size;
     if (a > b) return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
-    const bool bc = (ph.flg & 0x10u) != 0;
-    uint64_t pos = (uint64_t)ph.size, nb = 0;           // the block count for the table: k_bfd_walk's chain on the host
-    while (pos + 4 <= n) {
-        const uint32_t h = zx_rd32(src + pos);
-        const uint64_t sz = h & 0x7FFFFFFFu;
-        if (h == 0 || pos + 4 + sz > n) break;
-        pos += 4 + sz;
-        nb++;
-        if (bc) { if (pos + 4 > n) break; pos += 4; }
-    }
+    const uint64_t nb = chain_blocks(src, n, ph);        // the block count for the table
     if (nb >= 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const uint32_t max_blocks = (uint32_t)nb;
     const size_t iws = zlz4f_batch_frame_index_workspace(1, max_blocks);
@@ -2656,7 +2594,7 @@ int64_t zlz4f_decompress_frame_range(const uint8_t *src, size_t n, uint64_t a, u
         hipMemcpyAsync(&last, index + nb, sizeof last, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync())
         return ZLZ4_ERR_DEVICE;
     if (idx_n < 0) return idx_n;
-    if ((uint64_t)idx_n != nb) return ZLZ4_ERR_DEVICE;           // cannot happen
+    if ((uint64_t)idx_n != nb) return ZLZ4_ERR_DEVICE;           // (both counts are chain_walk's, here and in k_bfd_walk)
     const uint64_t S = last.dec, a1 = a < S ? a : S, b1 = b < S ? b : S;
     if (cap < b1 - a1) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
     if (totals[1] > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;

@@ -1,6 +1,8 @@
-// zlz4_frame_batch.hpp -- the per-frame record and the block flags of the batch frame calls,
-// XXH32 and the frame header parse, shared by zlz4_frame.hip (the pipeline) and zlz4_frame_linked.hip (the linked-block
-// kernels of section 4.4c, the frame prefix decoder of section 4.4f).
+// zlz4_frame_batch.hpp -- what the lz4f kernels and host calls share: the per-frame record and the block flags of the batch
+// frame calls, XXH32, the frame header parse, and the block chain: the
+// decode of a block word and the one step of the chain walk that every walker is written on.  Included by zlz4_frame.hip
+// (the pipelines), zlz4_frame_linked.hip (the linked-block kernels of section 4.4c, the frame prefix decoder of section 4.4f)
+// and zlz4_frame_multi.hip (the multiframe split of section 4.4h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,6 +93,85 @@ __host__ __device__ inline ParsedHeader parse_header(const uint8_t *src, size_t 
     r.size = (int64_t)pos;
     r.flg = flg;
     return r;
+}
+
+// the header of the frame at s, n bytes available: staged so that parse_header reads no global byte twice
+__device__ __forceinline__ ParsedHeader frame_header(const uint8_t *__restrict__ s, uint64_t n) {
+    uint8_t head[19];
+    const uint32_t have = n < sizeof head ? (uint32_t)n : (uint32_t)sizeof head;
+    for (uint32_t k = 0; k < have; k++) head[k] = s[k];
+    return parse_header(head, have);
+}
+
+// ------------------------------------------------------------------ block chain (src/lz4f.zig:563-600)
+// A block word: 0 is the end mark, bit 31 means stored, the low 31 bits are the payload size (:573, :578-579).
+struct BlockWord { uint32_t size; bool stored, end_mark; };
+__host__ __device__ __forceinline__ BlockWord block_word(uint32_t h) { return {h & 0x7FFFFFFFu, (h >> 31) != 0, h == 0}; }
+
+// What a step finds: a block (the first two) or how the walk ends without one.
+enum ChainEnd : uint32_t {
+    kChainBlock,        // a block; the cursor stands behind it and behind its checksum word when the frame has them
+    kChainCksCut,       // :591 a block whose checksum word is cut (kBlkNoCks): the cursor stands behind the payload, the walk
+                        // ends after this block, and decoding it is FrameSizeWrong
+    kChainBoundary,     // :563 the input ends at a block boundary; the cursor has not moved
+    kChainWordCut,      // :565 the input ends inside a block word; the cursor has not moved
+    kChainEndMark,      // :573 the cursor stands behind the mark
+    kChainDataCut,      // :582 the input ends inside the payload; the cursor stands behind the block word
+};
+struct ChainBlock {
+    uint64_t off;       // payload offset
+    uint64_t cks_off;   // 0 without a checksum word
+    uint32_t size;      // payload bytes
+    uint32_t flags;     // kBlkStored; with block checksums kBlkCks (the word is at cks_off) or kBlkNoCks
+};
+struct Rd32 { __host__ __device__ __forceinline__ uint32_t operator()(const uint8_t *p) const { return zx_rd32(p); } };
+
+// One step of the chain of the n bytes at s from the cursor `pos` on; bc = the frame has block checksums; rd reads a
+// 32-bit word (the prefix decoder's is wave-uniform).  b is written only when a block is found.
+template <class Rd = Rd32>
+__host__ __device__ __forceinline__ ChainEnd chain_step(const uint8_t *s, uint64_t n, bool bc, uint64_t &pos, ChainBlock &b,
+                                                        Rd rd = Rd()) {
+    if (pos >= n) return kChainBoundary;                              // :563
+    if (pos + 4 > n) return kChainWordCut;                            // :565
+    const BlockWord w = block_word(rd(s + pos));
+    pos += 4;
+    if (w.end_mark) return kChainEndMark;                             // :573
+    if (pos + w.size > n) return kChainDataCut;                       // :582
+    b.off = pos; b.cks_off = 0; b.size = w.size; b.flags = w.stored ? kBlkStored : 0u;
+    pos += w.size;
+    if (bc) {                                                         // :590
+        if (pos + 4 > n) { b.flags |= kBlkNoCks; return kChainCksCut; }             // :591
+        b.cks_off = pos; pos += 4; b.flags |= kBlkCks;
+    }
+    return kChainBlock;
+}
+
+// the walk's own error: the two places where the input ends inside a block (:565, :582)
+__host__ __device__ __forceinline__ int64_t chain_error(ChainEnd e) {
+    return e == kChainWordCut || e == kChainDataCut ? (int64_t)ZLZ4F_ERR_FRAME_SIZE_WRONG : 0;
+}
+
+// The walk: each(k, block) for block k = 0, 1, .. of at most nb_max (~0: no bound) -> how it ended (kChainBlock: at
+// nb_max); nb = the blocks found, pos = the cursor after the walk.
+template <class Each>
+__host__ __device__ __forceinline__ ChainEnd chain_walk(const uint8_t *s, uint64_t n, bool bc, uint64_t &pos, uint64_t nb_max,
+                                                        uint64_t &nb, Each each) {
+    for (nb = 0; nb_max == ~0ull || nb < nb_max;) {
+        ChainBlock b;
+        const ChainEnd e = chain_step(s, n, bc, pos, b);
+        if (e > kChainCksCut) return e;
+        each(nb++, b);
+        if (e == kChainCksCut) return e;
+    }
+    return kChainBlock;
+}
+
+// blocks the chain of a frame holds from its parsed header on: the count of the device walks, for the host calls that size
+// a block table before the device fills it
+inline uint64_t chain_blocks(const uint8_t *s, uint64_t n, const ParsedHeader &ph) {
+    uint64_t pos = (uint64_t)ph.size, nb;
+    chain_walk(s, n, (ph.flg & 0x10u) != 0, pos, ~0ull, nb, [](uint64_t, const ChainBlock &) {});
+    return nb;
 }
 
 __device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { return F.nb == 0 || F.base + F.nb <= max_blocks; }

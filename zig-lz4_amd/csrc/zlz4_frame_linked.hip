@@ -101,9 +101,10 @@ __global__ __launch_bounds__(256) void k_bfl_decode(BFrame *__restrict__ fr, uin
 
 // Frame prefix decoding, FP(frame, n, T) of DESIGN.md section 4.4f: the first n = dst_cap[f] bytes of frame f.  One
 // wavefront per frame, four per workgroup, and the wavefront does all of it in one serial walk that ends at the cut: the
-// header (:547), the chain (:563-600, k_bfd_walk's loop), a reached block's checksum (one lane hashes, the verdict is
-// broadcast), the stored copy, the history-aware decode cut at the bytes still wanted, and -- only when the chain ended
-// first -- the content checksum (:625-635).  No block table, no workspace; every scalar is wave-uniform (rfl / byte_at).
+// header (:547), the chain (:563-600, chain_step with a wave-uniform word reader), a reached block's checksum (one lane
+// hashes, the verdict is broadcast), the stored copy, the history-aware decode cut at the bytes still wanted, and --
+// only when the chain ended first -- the content checksum (:625-635).  No block table, no workspace; every scalar is
+// wave-uniform (rfl / byte_at).
 // The stop rule stands in front of the loop's own condition: once n bytes are out nothing more of the source is read.
 // kDict: frame f's dictionary is number dict_idx[f] (nullptr: 0) of ndicts; an index that names none gives InvalidState
 // in front of every other status.  The kDict == false instantiation never reads the dictionary arguments.
@@ -144,27 +145,24 @@ __global__ __launch_bounds__(256) void k_bfp_decode(const uint8_t *__restrict__ 
     uint64_t sp = (uint64_t)hs, pos = 0;
     int64_t err = 0;
     bool cut = false;
+    const auto rd = [](const uint8_t *p) {                             // a block word, wave-uniform
+        return byte_at(p) | (byte_at(p + 1) << 8) | (byte_at(p + 2) << 16) | (byte_at(p + 3) << 24);
+    };
     for (;;) {
         if (pos == want) { cut = true; break; }                        // the stop rule: nothing behind is read
-        if (sp >= n) break;                                            // :563
-        if (sp + 4 > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }   // :565
-        const uint32_t h = byte_at(s + sp) | (byte_at(s + sp + 1) << 8) | (byte_at(s + sp + 2) << 16) |
-                           (byte_at(s + sp + 3) << 24);
-        sp += 4;
-        if (h == 0) break;                                             // :573
-        const uint32_t sz = h & 0x7FFFFFFFu;
-        if (sp + sz > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }  // :582
-        const uint8_t *p = s + sp;
-        sp += sz;
-        if (bc) {                                                      // :590: over the whole block, in front of the decode
-            if (sp + 4 > n) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }            // :591
+        ChainBlock c;
+        const ChainEnd end = chain_step(s, n, bc, sp, c, rd);          // :563-591
+        if (end > kChainCksCut) { err = chain_error(end); break; }
+        if (end == kChainCksCut) { err = ZLZ4F_ERR_FRAME_SIZE_WRONG; break; }       // :591
+        const uint8_t *p = s + c.off;
+        const uint32_t sz = c.size;
+        if (c.flags & kBlkCks) {                                       // :590: over the whole block, in front of the decode
             uint32_t ok = 0;
-            if (lane == 0) ok = xxh32(p, sz, 0) == zx_rd32(s + sp) ? 1u : 0u;
+            if (lane == 0) ok = xxh32(p, sz, 0) == zx_rd32(s + c.cks_off) ? 1u : 0u;
             if (rfl(ok) == 0u) { err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID; break; }   // :596
-            sp += 4;
         }
         const uint64_t rem = want - pos;                               // >= 1
-        if (h >> 31) {                                                 // :603-608: the bytes that fit; history
+        if (c.flags & kBlkStored) {                                    // :603-608: the bytes that fit; history
             const uint32_t c = sz < rem ? sz : (uint32_t)rem;
             copy_bytes(out + pos, p, c, lane);
             pos += c;

@@ -19,9 +19,9 @@ inline bool mf_misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p
 // ------------------------------------------------------------------ split
 struct MfMember { uint64_t len; uint64_t nb; uint32_t kind; bool last; };
 
-// The member that starts at s[0] of the n bytes that remain (n >= 1).  A frame member is delimited by parse_header and
-// k_bfd_walk's chain rules; whatever they cannot delimit reaches to n and is the last member.  nb = the blocks
-// k_bfd_walk<false> counts for the member's bytes.
+// The member that starts at s[0] of the n bytes that remain (n >= 1).  A frame member is delimited by frame_header and
+// chain_walk up to the end mark; whatever they cannot delimit reaches to n and is the last member.  nb = the blocks of the
+// member's chain: chain_walk's count, as k_bfd_walk<false> takes it for the same bytes.
 __device__ MfMember mf_member(const uint8_t *__restrict__ s, uint64_t n) {
     MfMember m = {n, 0, ZLZ4F_MEMBER_FRAME, true};
     if (n >= 4) {
@@ -36,30 +36,11 @@ __device__ MfMember mf_member(const uint8_t *__restrict__ s, uint64_t n) {
             return m;
         }
     }
-    uint8_t head[19];
-    const uint32_t have = n < sizeof head ? (uint32_t)n : (uint32_t)sizeof head;
-    for (uint32_t k = 0; k < have; k++) head[k] = s[k];
-    const ParsedHeader ph = parse_header(head, have);
+    const ParsedHeader ph = frame_header(s, n);
     if (ph.size < 0) return m;
+    uint64_t pos = (uint64_t)ph.size;
     const bool bc = (ph.flg & 0x10u) != 0;
-    uint64_t pos = (uint64_t)ph.size, nb = 0;
-    bool ended = false;
-    while (pos < n) {
-        if (pos + 4 > n) break;
-        const uint32_t h = zx_rd32(s + pos);
-        pos += 4;
-        if (h == 0) { ended = true; break; }
-        const uint32_t sz = h & 0x7FFFFFFFu;
-        if (pos + sz > n) break;
-        pos += sz;
-        nb++;
-        if (bc) {
-            if (pos + 4 > n) break;
-            pos += 4;
-        }
-    }
-    m.nb = nb;
-    if (!ended) return m;
+    if (chain_walk(s, n, bc, pos, ~0ull, m.nb, [](uint64_t, const ChainBlock &) {}) != kChainEndMark) return m;
     if (ph.flg & 0x04u) {
         if (pos + 4 > n) return m;
         pos += 4;
