@@ -1037,8 +1037,10 @@ int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, u
  *   The planned total above dst_cap: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.
  *
  * NOT SERVED: a dictionary per member (a member with a dictID decodes as the plain frame call decodes it); prefix and
- *   range decoding of a multiframe; the legacy frame format (magic 0x184C2102 is a member that cannot be delimited:
- *   ZLZ4F_ERR_FRAME_TYPE_UNKNOWN); writing multiframes (they are the concatenation of what the compress calls return). */
+ *   range decoding of a multiframe; legacy frames through these calls (magic 0x184C2102 is a member that cannot be
+ *   delimited here: ZLZ4F_ERR_FRAME_TYPE_UNKNOWN; the legacy frame calls below read them, and their `consumed` is what
+ *   chains a legacy member to the next one); writing multiframes (they are the concatenation of what the compress calls
+ *   return). */
 #define ZLZ4F_MEMBER_FRAME               1u
 #define ZLZ4F_MEMBER_SKIPPABLE           2u
 #define ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED 3u
@@ -1057,6 +1059,97 @@ int32_t zlz4f_batch_multiframe_finish(void *stream, const zlz4f_member *d_member
 int64_t zlz4f_multiframe_decompressed_size(const uint8_t *src, size_t src_len, uint32_t decode_flags);
 int64_t zlz4f_decompress_multiframe(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                     uint32_t decode_flags);
+
+/* ---- legacy frames: what `lz4 -l` writes and the Linux kernel's unlz4 reads (vmlinuz.lz4, lz4 initramfs images); no
+ * counterpart in the reference; DESIGN.md section 4.4i.  The format, as lz4io.c's LZ4IO_compressFilename_Legacy and
+ * LZ4IO_decodeLegacyStream fix it: the 4-byte magic 0x184C2102, then { u32 LE size, block } repeated.  No checksums, no
+ * stored blocks, no end mark; every block is an independent LZ4 block that decodes to at most 8 MiB.
+ *
+ * READING frame f (d_src + d_src_off[f], d_src_len[f] = n bytes):
+ *   1. n < 4: ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE.  A first word that is not the legacy magic: ZLZ4F_ERR_FRAME_TYPE_UNKNOWN.
+ *      consumed = n in both cases.
+ *   2. pos = 4, then repeat:  pos == n: the frame ends, consumed = n.  1..3 bytes remain: ZLZ4F_ERR_FRAME_SIZE_WRONG (a torn
+ *      size word).  w = the u32 LE at pos.  w > ZLZ4F_LEGACY_BLOCK_BOUND: the frame ends in front of that word, consumed =
+ *      pos (the CLI's "maybe a new stream": every lz4 magic -- frame, skippable, legacy -- is larger than the bound, so the
+ *      next member of a concatenated file starts at consumed).  w == 0: ZLZ4F_ERR_DECOMPRESSION_FAILED (liblz4 fails an
+ *      empty block; the block calls of this library answer 0 for one).  pos + 4 + w > n: ZLZ4F_ERR_FRAME_SIZE_WRONG.
+ *      Otherwise { pos + 4, w } is a block and pos += 4 + w.  consumed = n after every defect of the walk.
+ *   3. Block k decodes as decompressSafe into a capacity of 8 MiB: its size is what zlz4_batch_decompressed_size answers;
+ *      a negative answer or a size above 8 MiB is ZLZ4F_ERR_DECOMPRESSION_FAILED.  A block of the single token 0x00
+ *      decodes to 0 bytes and is valid; blocks shorter than 8 MiB are valid anywhere in the chain.
+ *   4. THE FIRST DEFECT IN STREAM ORDER DECIDES (what a sequential reader meets first): a bad block in front of a torn
+ *      tail gives the block's code.  Block contents never move consumed: it is the walk's alone.
+ *   5. Without a defect the content is the blocks' outputs back to back, and its length is the result.
+ *   6. The decode call only: content above d_dst_cap[f] is ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL, decided from the sizes before a
+ *      byte of that frame is written.
+ *   7. A frame whose blocks do not all number below max_blocks gets ZLZ4_ERR_INVALID_STATE and nothing is written for it;
+ *      earlier frames are unaffected (the frame batch contract above; a frame without blocks needs no entries).
+ *
+ * WRITING frame f from n source bytes: the magic, then for every chunk of bs bytes (the last one shorter) the u32 LE
+ *   compressed size and the block; n == 0 writes the magic alone, as the CLI does.  bs = prefs->block_size: 0 means 8 MiB,
+ *   1 .. 8 MiB is taken as given (smaller blocks are still legal legacy frames -- `lz4 -d` and unlz4 take any block that
+ *   decodes to 8 MiB or less -- and are what lets one frame use more than a handful of wavefronts), anything larger is
+ *   ZLZ4F_ERR_MAX_BLOCK_SIZE_INVALID and nothing is launched.  The block is compressFast(chunk, acceleration 1) for
+ *   prefs->compression_level <= 0, else compressHC(chunk, level) with the level read as zlz4_batch_compress_hc reads it
+ *   (1 becomes 9, above 12 becomes 12; the HAZARD note of section 1 holds for 10..12).  The format has no stored blocks:
+ *   an incompressible chunk grows, up to zlz4_compress_bound(chunk).  A block whose compressor returns an error makes its
+ *   frame fail with that code.
+ *   zlz4f_legacy_compress_frame_bound(n, prefs) = 4 + the sum over the chunks of 4 + zlz4_compress_bound(chunk length): host
+ *   arithmetic; 0 for an invalid block_size.  n > ZLZ4_MAX_INPUT_SIZE: ZLZ4F_ERR_SRC_SIZE_TOO_LARGE; else d_dst_cap[f] below
+ *   the bound: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL; nothing is written for either.  A frame has ceil(n / bs) blocks.
+ *   The bytes differ from the CLI's (these are the reference's block algorithms); they decode everywhere.
+ *
+ * The batch calls keep the contract of zlz4f_batch_compress_frame / zlz4f_batch_decompress_frame: device pointers,
+ *   asynchronous on `stream`, a fixed launch sequence, nothing allocated, nothing read back; nframes == 0 returns 0.  A null
+ *   array, an array that is not 8-byte aligned, or a workspace that is null, not 16-byte aligned or smaller than its size
+ *   function says: ZLZ4_ERR_INVALID_STATE, nothing launched (d_consumed may be null: it is not written then).  The device
+ *   check is the last refusal.  No byte outside a frame's slot is ever written; bytes inside a failed frame's slot are
+ *   unspecified.
+ * zlz4f_batch_legacy_frame_count: the walk alone, no workspace.  d_nblocks[f] = the blocks of frame f's chain, d_consumed[f]
+ *   as above, d_totals[0] = the blocks of all frames (the max_blocks of the calls below): one 8-byte read-back sizes them.
+ * zlz4f_batch_legacy_frame_decompressed_size: d_size[f] = what the decode call stores in d_result[f] when d_dst_cap[f] is
+ *   large enough.  The walk (count, scan, record), the size kernel of zlz4_batch_decompressed_size over the block table,
+ *   one wavefront per frame for the fold.
+ * zlz4f_batch_decompress_legacy_frame: the same, the fold also places every block inside the frame's slot and empties the
+ *   table entries of every frame that fails; then the kernel of zlz4_batch_decompress_safe over the table, and a finish.
+ * zlz4f_batch_compress_legacy_frame: descriptors, the kernel of zlz4_batch_compress_fast / zlz4_batch_compress_hc over the
+ *   table with max_in_len = bs into compressBound-sized workspace slots, a prefix sum per frame, a scatter of size words
+ *   and blocks.  The workspace holds the table, the slots and, for compression_level > 0,
+ *   zlz4_batch_compress_hc_workspace(max_blocks, bs) bytes.
+ * The three host calls stage one frame and run the batch of one ("correct, not fast"); consumed may be null.  Before the
+ *   device check they answer: a null pointer with a length (ZLZ4_ERR_INVALID_STATE), an invalid block_size, then a source
+ *   above ZLZ4_MAX_INPUT_SIZE and a dst_cap below the bound (compress); step 1 above, and a defect of the walk in front of
+ *   the first block (decode and size query, which walk the host bytes to size the block table).
+ *
+ * NOT SERVED: legacy members inside the multiframe calls (chain them by consumed); prefix and range decoding of legacy
+ *   frames; dictionaries (the format has none); the segment calls. */
+#define ZLZ4F_LEGACY_MAGICNUMBER 0x184C2102u
+#define ZLZ4F_LEGACY_BLOCK_SIZE  (8u << 20)
+#define ZLZ4F_LEGACY_BLOCK_BOUND 8421520u        /* zlz4_compress_bound(ZLZ4F_LEGACY_BLOCK_SIZE) = LZ4_compressBound(8 MiB) */
+typedef struct { uint32_t block_size; int32_t compression_level; } zlz4f_legacy_prefs;      /* NULL = { 0, 0 } */
+size_t  zlz4f_legacy_compress_frame_bound(size_t src_size, const zlz4f_legacy_prefs *prefs);
+size_t  zlz4f_batch_compress_legacy_frame_workspace(uint32_t nframes, uint32_t max_blocks, const zlz4f_legacy_prefs *prefs);
+int32_t zlz4f_batch_compress_legacy_frame(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                          const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                          const uint64_t *d_dst_cap, int64_t *d_result, uint32_t nframes, uint32_t max_blocks,
+                                          const zlz4f_legacy_prefs *prefs, void *d_workspace, size_t workspace_bytes);
+int32_t zlz4f_batch_legacy_frame_count(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                       const uint64_t *d_src_len, uint32_t nframes, uint64_t *d_nblocks, uint64_t *d_consumed,
+                                       uint64_t *d_totals);
+size_t  zlz4f_batch_legacy_frame_decompressed_size_workspace(uint32_t nframes, uint32_t max_blocks);
+int32_t zlz4f_batch_legacy_frame_decompressed_size(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                   const uint64_t *d_src_len, int64_t *d_size, uint64_t *d_consumed,
+                                                   uint32_t nframes, uint32_t max_blocks, void *d_workspace,
+                                                   size_t workspace_bytes);
+size_t  zlz4f_batch_decompress_legacy_frame_workspace(uint32_t nframes, uint32_t max_blocks);
+int32_t zlz4f_batch_decompress_legacy_frame(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                            const uint64_t *d_src_len, uint8_t *d_dst, const uint64_t *d_dst_off,
+                                            const uint64_t *d_dst_cap, int64_t *d_result, uint64_t *d_consumed,
+                                            uint32_t nframes, uint32_t max_blocks, void *d_workspace, size_t workspace_bytes);
+int64_t zlz4f_compress_legacy_frame(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                    const zlz4f_legacy_prefs *prefs);
+int64_t zlz4f_legacy_frame_decompressed_size(const uint8_t *src, size_t src_len, size_t *consumed);
+int64_t zlz4f_decompress_legacy_frame(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *consumed);
 
 /* ======================================================================
  * 4. Introspection

@@ -50,9 +50,16 @@ class Prefs(C.Structure):
     ]
 
 
+class LegacyPrefs(C.Structure):
+    """zlz4f_legacy_prefs: block_size 0 = 8 MiB (what `lz4 -l` writes), 1 .. 8 MiB as given; compression_level <= 0 = fast,
+    else compressHC's level."""
+    _fields_ = [("block_size", C.c_uint32), ("compression_level", C.c_int32)]
+
+
 # every symbol include/zlz4_amd.h declares: name -> (restype, argtypes)
 _VP, _SZ, _I64, _I32, _U32 = C.c_void_p, C.c_size_t, C.c_int64, C.c_int32, C.c_uint32
 _PP = C.POINTER(Prefs)
+_LP = C.POINTER(LegacyPrefs)
 SYMBOLS = {
     "zlz4_compress_bound": (_SZ, [_SZ]),
     "zlz4_compress_default": (_I64, [_VP, _SZ, _VP, _SZ]),
@@ -153,6 +160,17 @@ SYMBOLS = {
     "zlz4f_batch_multiframe_finish": (_I32, [_VP] * 7 + [_U32, _VP]),
     "zlz4f_multiframe_decompressed_size": (_I64, [_VP, _SZ, _U32]),
     "zlz4f_decompress_multiframe": (_I64, [_VP, _SZ, _VP, _SZ, _U32]),
+    "zlz4f_legacy_compress_frame_bound": (_SZ, [_SZ, _LP]),
+    "zlz4f_batch_compress_legacy_frame_workspace": (_SZ, [_U32, _U32, _LP]),
+    "zlz4f_batch_compress_legacy_frame": (_I32, [_VP] * 8 + [_U32, _U32, _LP, _VP, _SZ]),
+    "zlz4f_batch_legacy_frame_count": (_I32, [_VP] * 4 + [_U32] + [_VP] * 3),
+    "zlz4f_batch_legacy_frame_decompressed_size_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_legacy_frame_decompressed_size": (_I32, [_VP] * 6 + [_U32, _U32, _VP, _SZ]),
+    "zlz4f_batch_decompress_legacy_frame_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_decompress_legacy_frame": (_I32, [_VP] * 9 + [_U32, _U32, _VP, _SZ]),
+    "zlz4f_compress_legacy_frame": (_I64, [_VP, _SZ, _VP, _SZ, _LP]),
+    "zlz4f_legacy_frame_decompressed_size": (_I64, [_VP, _SZ, C.POINTER(C.c_size_t)]),
+    "zlz4f_decompress_legacy_frame": (_I64, [_VP, _SZ, _VP, _SZ, C.POINTER(C.c_size_t)]),
     "zlz4_device_check": (_I32, []),
     "zlz4_version_string": (C.c_char_p, []),
     "zlz4_error_name": (C.c_char_p, [_I64]),
@@ -1187,6 +1205,147 @@ class lz4f:
         """zlz4f_decompress_multiframe: one buffer in host memory.  dst_cap None: the size is queried first."""
         cap = lz4f.multiframeDecompressedSize(src, flags) if dst_cap is None else dst_cap
         return _run(lib().zlz4f_decompress_multiframe, src, cap, flags)
+
+    # legacy frames: what `lz4 -l` writes (include/zlz4_amd.h, DESIGN.md section 4.4i)
+    LegacyPrefs = LegacyPrefs
+    LEGACY_MAGICNUMBER = 0x184C2102
+    LEGACY_BLOCK_SIZE = 8 << 20
+    LEGACY_BLOCK_BOUND = 8421520
+
+    @staticmethod
+    def _legacy_block_size(prefs):
+        return (prefs.block_size if prefs is not None else 0) or lz4f.LEGACY_BLOCK_SIZE
+
+    @staticmethod
+    def legacyCompressFrameBound(src_size, prefs=None):
+        return lib().zlz4f_legacy_compress_frame_bound(src_size, C.byref(prefs) if prefs is not None else None)
+
+    @staticmethod
+    def compressLegacyFrameBatchWorkspace(nframes, max_blocks, prefs=None):
+        return lib().zlz4f_batch_compress_legacy_frame_workspace(nframes, max_blocks,
+                                                                 C.byref(prefs) if prefs is not None else None)
+
+    @staticmethod
+    def legacyFrameDecompressedSizeBatchWorkspace(nframes, max_blocks):
+        return lib().zlz4f_batch_legacy_frame_decompressed_size_workspace(nframes, max_blocks)
+
+    @staticmethod
+    def decompressLegacyFrameBatchWorkspace(nframes, max_blocks):
+        return lib().zlz4f_batch_decompress_legacy_frame_workspace(nframes, max_blocks)
+
+    @staticmethod
+    def compressLegacyFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, prefs=None, max_blocks=None,
+                                 workspace=None):
+        """zlz4f_batch_compress_legacy_frame on torch CUDA tensors (layout as compressFrameBatch).  max_blocks defaults to
+        the block count of the lengths (read back once), workspace to a fresh buffer of the size the library asks for."""
+        import torch
+        pp = C.byref(prefs) if prefs is not None else None
+        if max_blocks is None:
+            bs = lz4f._legacy_block_size(prefs)
+            max_blocks = int(((src_len.cpu() + bs - 1) // bs).sum()) if src_len.numel() else 0
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_compress_legacy_frame_workspace(src_len.numel(), max_blocks, pp)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_compress_legacy_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                       _ptr(dst_off), _ptr(dst_cap), _ptr(result), src_len.numel(),
+                                                       max_blocks, pp, _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def legacyFrameCountBatch(d_src, src_off, src_len, nblocks, consumed, totals):
+        """zlz4f_batch_legacy_frame_count: nblocks / consumed int64 [nframes] (consumed may be None), totals int64 [1] = the
+        blocks of all frames."""
+        _check(lib().zlz4f_batch_legacy_frame_count(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), src_len.numel(),
+                                                    _ptr(nblocks), _ptr(consumed), _ptr(totals)))
+
+    @staticmethod
+    def legacyFrameDecompressedSizeBatch(d_src, src_off, src_len, size, consumed, max_blocks, workspace=None):
+        """zlz4f_batch_legacy_frame_decompressed_size: size int64 [nframes] = decoded size or the frame's error code;
+        max_blocks = totals[0] of legacyFrameCountBatch."""
+        import torch
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_legacy_frame_decompressed_size_workspace(src_len.numel(),
+                                                                                                       max_blocks)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_legacy_frame_decompressed_size(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len),
+                                                                _ptr(size), _ptr(consumed), src_len.numel(), max_blocks,
+                                                                _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def decompressLegacyFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, consumed, max_blocks,
+                                   workspace=None):
+        """zlz4f_batch_decompress_legacy_frame (layout as decompressFrameBatch, consumed int64 [nframes] or None)."""
+        import torch
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_decompress_legacy_frame_workspace(src_len.numel(), max_blocks)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_decompress_legacy_frame(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(d_dst),
+                                                         _ptr(dst_off), _ptr(dst_cap), _ptr(result), _ptr(consumed),
+                                                         src_len.numel(), max_blocks, _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def compressLegacyFrames(items, prefs=None, device="cuda"):
+        """Every byte string of `items` as its own legacy frame, in one batch call -> list of frames (bytes) or error
+        codes."""
+        import torch
+        if not len(items):
+            return []
+        caps = [lz4f.legacyCompressFrameBound(len(b), prefs) for b in items]
+        d_src, src_off, src_len = _stage(items, device)
+        dst_off = torch.tensor(_offsets(caps), dtype=torch.int64, device=device)
+        d_dst = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+        result = torch.empty(len(items), dtype=torch.int64, device=device)
+        lz4f.compressLegacyFrameBatch(d_src, src_off, src_len, d_dst, dst_off,
+                                      torch.tensor(caps, dtype=torch.int64, device=device), result, prefs)
+        return _unstage(d_dst, _offsets(caps), result)
+
+    @staticmethod
+    def decompressLegacyFrames(frames, device="cuda"):
+        """Every legacy frame of `frames` decoded in one batch -> list of (content or error code, consumed): count, one
+        read-back of the block total, size query, zlz4_batch_plan_outputs, one read-back of the arena size, decode.
+        frames[f][consumed:] is where the next member of a concatenated file starts."""
+        import torch
+        n = len(frames)
+        if n == 0:
+            return []
+        d_src, src_off, src_len = _stage(frames, device)
+
+        def i64(k):
+            return torch.empty(k, dtype=torch.int64, device=device)
+
+        nblocks, consumed, totals, size, dst_off, result = i64(n), i64(n), i64(1), i64(n), i64(n), i64(n)
+        lz4f.legacyFrameCountBatch(d_src, src_off, src_len, nblocks, consumed, totals)
+        max_blocks = int(totals.item())
+        lz4f.legacyFrameDecompressedSizeBatch(d_src, src_off, src_len, size, None, max_blocks)
+        cap32 = torch.empty(n, dtype=torch.int32, device=device)      # (a frame may hold more than 4 GiB: not used)
+        batch_plan_outputs(size, dst_off, cap32, totals)
+        dst_cap = size.clamp(min=0)
+        d_dst = torch.empty(max(1, int(totals.item())), dtype=torch.uint8, device=device)
+        lz4f.decompressLegacyFrameBatch(d_src, src_off, src_len, d_dst, dst_off, dst_cap, result, None, max_blocks)
+        sizes = size.cpu().tolist()
+        out = _unstage(d_dst, dst_off.cpu().tolist(), result)
+        # (a frame the query failed got no room: the query's code stands)
+        return [(o if s >= 0 else s, c) for o, s, c in zip(out, sizes, consumed.cpu().tolist())]
+
+    @staticmethod
+    def compressLegacyFrame(src, prefs=None, dst_cap=None):
+        """zlz4f_compress_legacy_frame: one frame in host memory; dst_cap defaults to the bound."""
+        cap = lz4f.legacyCompressFrameBound(len(src), prefs) if dst_cap is None else dst_cap
+        return _run(lib().zlz4f_compress_legacy_frame, src, cap, C.byref(prefs) if prefs is not None else None)
+
+    @staticmethod
+    def legacyFrameDecompressedSize(src):
+        """zlz4f_legacy_frame_decompressed_size -> (decoded size, consumed); errors raise Lz4Error."""
+        s, n = _in(src)
+        consumed = C.c_size_t(0)
+        r = _check(lib().zlz4f_legacy_frame_decompressed_size(C.addressof(s), n, C.byref(consumed)))
+        return r, consumed.value
+
+    @staticmethod
+    def decompressLegacyFrame(src, dst_cap=None):
+        """zlz4f_decompress_legacy_frame -> (content, consumed).  dst_cap None: the size is queried first."""
+        cap = lz4f.legacyFrameDecompressedSize(src)[0] if dst_cap is None else dst_cap
+        consumed = C.c_size_t(0)
+        return _run(lib().zlz4f_decompress_legacy_frame, src, cap, C.byref(consumed)), consumed.value
 
 
 def _offsets(lens):

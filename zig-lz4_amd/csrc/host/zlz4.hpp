@@ -460,6 +460,28 @@ inline Result decompressMultiframe(const std::uint8_t *src, std::size_t n, std::
                                    std::uint32_t decode_flags = 0) {
     return wrap(zlz4f_decompress_multiframe(src, n, dst, cap, decode_flags));
 }
+// legacy frames (include/zlz4_amd.h; no counterpart in the reference): what `lz4 -l` writes -- the magic 0x184C2102, then
+// { u32 size, block } repeated.  One frame in host memory per call; `consumed` (may be null) receives where the frame ends,
+// which is where the next member of a concatenated file starts.  The batch calls are those of the C header.
+namespace legacy {
+using Prefs = zlz4f_legacy_prefs;                 // block_size 0 = 8 MiB; compression_level <= 0 = fast
+constexpr std::uint32_t MAGICNUMBER = ZLZ4F_LEGACY_MAGICNUMBER, BLOCK_SIZE = ZLZ4F_LEGACY_BLOCK_SIZE,
+                        BLOCK_BOUND = ZLZ4F_LEGACY_BLOCK_BOUND;
+inline std::size_t compressFrameBound(std::size_t src_size, const Prefs *prefs = nullptr) {
+    return zlz4f_legacy_compress_frame_bound(src_size, prefs);
+}
+inline Result compressFrame(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                            const Prefs *prefs = nullptr) {
+    return wrap(zlz4f_compress_legacy_frame(src, n, dst, cap, prefs));
+}
+inline Result frameDecompressedSize(const std::uint8_t *src, std::size_t n, std::size_t *consumed = nullptr) {
+    return wrap(zlz4f_legacy_frame_decompressed_size(src, n, consumed));
+}
+inline Result decompressFrame(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                              std::size_t *consumed = nullptr) {
+    return wrap(zlz4f_decompress_legacy_frame(src, n, dst, cap, consumed));
+}
+}  // namespace legacy
 }  // namespace lz4f
 
 }  // namespace zlz4

@@ -1065,29 +1065,7 @@ __global__ __launch_bounds__(256) void k_bfq_total(const BFrame *__restrict__ fr
     if (lane == 0) result[f] = out;
 }
 
-// ------------------------------------------------------------------ workspace layout
-// A region of the caller's workspace: a typed pointer and `bytes`, the room it holds up to the next region.  A layout
-// function carves its regions in the order the workspace holds them, each rounded up to 256 bytes, and is the only place
-// that knows that order; the _workspace functions and the call itself both go through it.  A region the call's branch does
-// not have is never carved and stays null.
-template <typename T> struct Region {
-    T *p = nullptr;
-    size_t bytes = 0;
-    operator T *() const { return p; }
-};
-
-struct Carver {
-    uint8_t *ws;           // null: the _workspace functions, which want the total alone
-    size_t bytes = 0;
-    template <typename T> void one(size_t count, Region<T> &r) {
-        const size_t off = bytes;
-        bytes = (off + count * sizeof(T) + 255) & ~(size_t)255;
-        r.p = ws ? reinterpret_cast<T *>(ws + off) : nullptr;
-        r.bytes = bytes - off;
-    }
-    template <typename... R> void take(size_t count, R &...r) { (one(count, r), ...); }   // `count` elements each
-};
-
+// ------------------------------------------------------------------ workspace layout (Region, Carver: zlz4_frame_batch.hpp)
 int32_t bf_hc_level(const zlz4f_prefs &p) {   // compress_frame_impl's routing (:393-404, src/lz4hc.zig:1445)
     if (p.compression_level <= 0) return 0;
     return p.compression_level < 2 ? 9 : (p.compression_level > 12 ? 12 : p.compression_level);

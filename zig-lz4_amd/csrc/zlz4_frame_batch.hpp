@@ -1,8 +1,9 @@
 // zlz4_frame_batch.hpp -- what the lz4f kernels and host calls share: the per-frame record and the block flags of the batch
 // frame calls, XXH32, the frame header parse, and the block chain: the
-// decode of a block word and the one step of the chain walk that every walker is written on.  Included by zlz4_frame.hip
-// (the pipelines), zlz4_frame_linked.hip (the linked-block kernels of section 4.4c, the frame prefix decoder of section 4.4f)
-// and zlz4_frame_multi.hip (the multiframe split of section 4.4h).
+// decode of a block word and the one step of the chain walk that every walker is written on, the regions a call carves
+// out of its workspace, and the walk of a legacy frame (section 4.4i).  Included by zlz4_frame.hip (the pipelines), zlz4_frame_linked.hip (the linked-block kernels of
+// section 4.4c, the frame prefix decoder of section 4.4f), zlz4_frame_multi.hip (the multiframe split of section 4.4h) and
+// zlz4_frame_legacy.hip (the legacy frame calls of section 4.4i).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -172,6 +173,58 @@ inline uint64_t chain_blocks(const uint8_t *s, uint64_t n, const ParsedHeader &p
     uint64_t pos = (uint64_t)ph.size, nb;
     chain_walk(s, n, (ph.flg & 0x10u) != 0, pos, ~0ull, nb, [](uint64_t, const ChainBlock &) {});
     return nb;
+}
+
+// ------------------------------------------------------------------ workspace layout
+// A region of the caller's workspace: a typed pointer and `bytes`, the room it holds up to the next region.  A layout
+// function carves its regions in the order the workspace holds them, each rounded up to 256 bytes, and is the only place
+// that knows that order; the _workspace functions and the call itself both go through it.  A region the call's branch does
+// not have is never carved and stays null.
+template <typename T> struct Region {
+    T *p = nullptr;
+    size_t bytes = 0;
+    operator T *() const { return p; }
+};
+
+struct Carver {
+    uint8_t *ws;           // null: the _workspace functions, which want the total alone
+    size_t bytes = 0;
+    template <typename T> void one(size_t count, Region<T> &r) {
+        const size_t off = bytes;
+        bytes = (off + count * sizeof(T) + 255) & ~(size_t)255;
+        r.p = ws ? reinterpret_cast<T *>(ws + off) : nullptr;
+        r.bytes = bytes - off;
+    }
+    template <typename... R> void take(size_t count, R &...r) { (one(count, r), ...); }   // `count` elements each
+};
+
+// ------------------------------------------------------------------ legacy frames
+// The walk of a legacy frame (what `lz4 -l` writes; include/zlz4_amd.h): the magic, then { u32 LE size, block } up to the
+// end of the n bytes at s or up to a size word above ZLZ4F_LEGACY_BLOCK_BOUND, which is the next member of a concatenated
+// file (every lz4 magic is such a word).  each(k, off, size) for block k = 0, 1, .. of at most nb_max (~0: no bound) -> the
+// walk's own verdict: 0, the header error of bytes that are no legacy frame, FrameSizeWrong for a torn size word or a block
+// that runs off the input, DecompressionFailed for a size word of 0 (the block decoders answer 0 for an empty block; liblz4
+// fails it).  A defect ends the walk, so it stands behind all nb blocks in stream order.  consumed = where the frame ends:
+// n, or the position of the foreign word.
+template <class Each>
+__host__ __device__ __forceinline__ int64_t legacy_walk(const uint8_t *s, uint64_t n, uint64_t nb_max, uint64_t &nb,
+                                                        uint64_t &consumed, Each each) {
+    nb = 0;
+    consumed = n;
+    if (n < 4) return ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE;
+    if (zx_rd32(s) != ZLZ4F_LEGACY_MAGICNUMBER) return ZLZ4F_ERR_FRAME_TYPE_UNKNOWN;
+    uint64_t pos = 4;
+    while (nb_max == ~0ull || nb < nb_max) {
+        if (pos == n) return 0;
+        if (n - pos < 4) return ZLZ4F_ERR_FRAME_SIZE_WRONG;
+        const uint32_t w = zx_rd32(s + pos);
+        if (w > ZLZ4F_LEGACY_BLOCK_BOUND) { consumed = pos; return 0; }
+        if (w == 0) return ZLZ4F_ERR_DECOMPRESSION_FAILED;
+        if (w > n - pos - 4) return ZLZ4F_ERR_FRAME_SIZE_WRONG;
+        each(nb++, pos + 4, w);
+        pos += 4ull + w;
+    }
+    return 0;
 }
 
 __device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { return F.nb == 0 || F.base + F.nb <= max_blocks; }

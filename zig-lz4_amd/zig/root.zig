@@ -115,6 +115,12 @@ extern "c" fn zlz4f_batch_multiframe_plan(stream: ?*anyopaque, d_size: ?[*]const
 extern "c" fn zlz4f_batch_multiframe_finish(stream: ?*anyopaque, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_item_first: ?[*]const u64, d_size: ?[*]const i64, d_item_result: ?[*]const i64, nbuf: u32, d_result: ?[*]i64) i32;
 extern "c" fn zlz4f_multiframe_decompressed_size(src: [*]const u8, src_len: usize, decode_flags: u32) i64;
 extern "c" fn zlz4f_decompress_multiframe(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
+/// zlz4f_legacy_prefs of include/zlz4_amd.h: block_size 0 = 8 MiB, 1 .. 8 MiB as given; compression_level <= 0 = fast
+pub const LegacyPrefs = extern struct { block_size: u32 = 0, compression_level: i32 = 0 };
+extern "c" fn zlz4f_legacy_compress_frame_bound(src_size: usize, prefs: ?*const LegacyPrefs) usize;
+extern "c" fn zlz4f_compress_legacy_frame(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, prefs: ?*const LegacyPrefs) i64;
+extern "c" fn zlz4f_legacy_frame_decompressed_size(src: [*]const u8, src_len: usize, consumed: ?*usize) i64;
+extern "c" fn zlz4f_decompress_legacy_frame(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, consumed: ?*usize) i64;
 /// zlz4f_member of include/zlz4_amd.h: kind & 0xFF is a MEMBER_* kind, (kind >> 8) & 15 the nibble of a skippable magic
 pub const Member = extern struct { pos: u64, len: u64, kind: u32, buf: u32 };
 /// zlz4f_index_entry / zlz4f_range of include/zlz4_amd.h
@@ -891,6 +897,30 @@ pub const lz4f = struct {
     pub fn decompressMultiframe(src: []const u8, dst: []u8, decode_flags: u32) Error!usize {
         return mapFrame(zlz4f_decompress_multiframe(src.ptr, src.len, dst.ptr, dst.len, decode_flags));
     }
+    /// No counterpart in the reference: legacy frames, what `lz4 -l` writes and the Linux kernel's unlz4 reads -- the magic
+    /// 0x184C2102, then { u32 size, block } repeated (include/zlz4_amd.h).  One frame in host memory per call; `consumed`
+    /// receives where the frame ends, which is where the next member of a concatenated file starts.
+    pub const legacy = struct {
+        pub const MAGICNUMBER: u32 = 0x184C2102;
+        pub const BLOCK_SIZE: u32 = 8 << 20;
+        pub const BLOCK_BOUND: u32 = 8421520;
+        pub const Prefs = LegacyPrefs;
+        /// 0 for a block_size above 8 MiB
+        pub fn compressFrameBound(src_size: usize, prefs: ?Prefs) usize {
+            if (prefs) |p| return zlz4f_legacy_compress_frame_bound(src_size, &p);
+            return zlz4f_legacy_compress_frame_bound(src_size, null);
+        }
+        pub fn compressFrame(src: []const u8, dst: []u8, prefs: ?Prefs) Error!usize {
+            if (prefs) |p| return mapFrame(zlz4f_compress_legacy_frame(src.ptr, src.len, dst.ptr, dst.len, &p));
+            return mapFrame(zlz4f_compress_legacy_frame(src.ptr, src.len, dst.ptr, dst.len, null));
+        }
+        pub fn frameDecompressedSize(src: []const u8, consumed: ?*usize) Error!usize {
+            return mapFrame(zlz4f_legacy_frame_decompressed_size(src.ptr, src.len, consumed));
+        }
+        pub fn decompressFrame(src: []const u8, dst: []u8, consumed: ?*usize) Error!usize {
+            return mapFrame(zlz4f_decompress_legacy_frame(src.ptr, src.len, dst.ptr, dst.len, consumed));
+        }
+    };
     pub fn frameDecompressedSizeUsingDict(src: []const u8, dict_len: usize) Error!usize {
         return mapFrame(zlz4f_frame_decompressed_size_using_dict(src.ptr, src.len, dict_len));
     }
