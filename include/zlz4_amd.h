@@ -1037,10 +1037,54 @@ int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, u
  *   The planned total above dst_cap: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.
  *
  * NOT SERVED: a dictionary per member (a member with a dictID decodes as the plain frame call decodes it); prefix and
- *   range decoding of a multiframe; legacy frames through these calls (magic 0x184C2102 is a member that cannot be
- *   delimited here: ZLZ4F_ERR_FRAME_TYPE_UNKNOWN; the legacy frame calls below read them, and their `consumed` is what
- *   chains a legacy member to the next one); writing multiframes (they are the concatenation of what the compress calls
- *   return). */
+ *   range decoding of a multiframe; writing multiframes (they are the concatenation of what the compress calls return).
+ *   Legacy frames (magic 0x184C2102) are a member that cannot be delimited by THESE calls: ZLZ4F_ERR_FRAME_TYPE_UNKNOWN; the
+ *   _ex calls below with ZLZ4F_SPLIT_LEGACY serve them.
+ *
+ * ---- whole .lz4 files: legacy members in multiframe buffers.  What `lz4 -d` accepts is any
+ * sequence of modern frames, skippable frames and legacy frames (below).  The _ex calls take a SPLIT_FLAGS word; with
+ * split_flags == 0 every output equals that of the call without _ex on the same input.  An unknown split_flags bit:
+ * ZLZ4F_ERR_PARAMETER_INVALID, before any other refusal of the batch call; the host calls refuse an unknown decode_flags
+ * bit first, then an unknown split_flags bit, then a null pointer with a length, all before the device check.
+ *
+ * zlz4f_batch_multiframe_split_ex: the arguments of zlz4f_batch_multiframe_split, split_flags, and d_leg_len.  With
+ *   ZLZ4F_SPLIT_LEGACY, at a position where at least 4 bytes remain and the word is ZLZ4F_LEGACY_MAGICNUMBER the member is
+ *   { pos, consumed, ZLZ4F_MEMBER_LEGACY }, consumed as READING step 2 below says: the member ends at the end of the buffer
+ *   or in front of the first size word above ZLZ4F_LEGACY_BLOCK_BOUND.  It is not the last member (the walk ends on pos == n
+ *   anyway) unless the walk meets a defect -- a torn size word, a size word of 0, a block that runs off the buffer -- where
+ *   consumed = n: the same rule as every member that cannot be delimited.  The split never judges; the legacy call gives
+ *   the member its code.  The magic alone (then the end of the buffer or a foreign word) is a member of 0 blocks and 0 bytes
+ *   of content.  A foreign word that is no magic starts a frame member that cannot be delimited and gets what the frame
+ *   call answers (the CLI's "stream followed by undecodable data").
+ *   d_totals has FOUR entries: { members, blocks of the frame members' chains, legacy members, blocks of the legacy
+ *   members }: one 32-byte read-back sizes everything.  Legacy blocks are not counted into entry 1.
+ *   RECORD MODE: d_item_off as above; d_item_len[i] = len for a FRAME member, else 0; d_leg_len[i] = len for a LEGACY member,
+ *   else 0 (d_leg_len: 8-byte aligned, one entry per item, required in record mode, ignored in count mode); both are 0 for
+ *   every item of a buffer whose member table overflowed.  nbuf == 0 stores four zeros.
+ *
+ * zlz4f_batch_multiframe_select: d_out[i] = d_from_legacy[i] for the item of a LEGACY member, else d_from_frame[i]; the
+ *   items of a buffer whose split result is negative take d_from_frame.  d_out may be d_from_frame itself.  One wavefront
+ *   per buffer; refusals as the finish call; nbuf == 0 returns 0.
+ *
+ * zlz4f_batch_multiframe_finish reads a ZLZ4F_MEMBER_LEGACY member as it reads a frame member: a negative d_size[i]
+ *   decides, else d_item_result[i].
+ *
+ * THE SEQUENCE: split_ex (count mode), read back 32 bytes, split_ex (record mode);
+ *   zlz4f_batch_frame_decompressed_size_ex over (d_item_off, d_item_len) with max_blocks = totals[1];
+ *   zlz4f_batch_legacy_frame_decompressed_size over (d_item_off, d_leg_len) with max_blocks = totals[3]; select; plan, read
+ *   back; zlz4f_batch_decompress_frame_ex and zlz4f_batch_decompress_legacy_frame into the same arena with the plan's
+ *   d_dst_off / d_dst_cap (an item of length 0 is answered ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE by either family and writes
+ *   nothing whatever its capacity, so the two decodes never touch each other's slots); select; finish.  nframes =
+ *   totals[0] for both families.  WHEN totals[2] == 0 THE LEGACY CALLS AND BOTH SELECTS ARE SKIPPED and the sequence is
+ *   that of the calls above; otherwise the legacy calls' workspace, sized by their _workspace functions for (totals[0],
+ *   totals[3]), is never empty (it holds a record per item), also where totals[3] == 0.
+ *
+ * zlz4f_multiframe_decompressed_size_ex / zlz4f_decompress_multiframe_ex: one buffer in HOST memory, staged and run as a
+ *   batch of one through that sequence; with split_flags == 0 they make the calls of zlz4f_multiframe_decompressed_size /
+ *   zlz4f_decompress_multiframe.  zlz4f_decompress_multiframe_ex(.., ZLZ4F_DECODE_LINKED, ZLZ4F_SPLIT_LEGACY) returns what
+ *   `lz4 -dc` prints for the file, or the code of the first member that is not OK.
+ *
+ * NOT SERVED: a dictionary per member; prefix and range decoding of a multiframe. */
 #define ZLZ4F_MEMBER_FRAME               1u
 #define ZLZ4F_MEMBER_SKIPPABLE           2u
 #define ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED 3u
@@ -1059,6 +1103,21 @@ int32_t zlz4f_batch_multiframe_finish(void *stream, const zlz4f_member *d_member
 int64_t zlz4f_multiframe_decompressed_size(const uint8_t *src, size_t src_len, uint32_t decode_flags);
 int64_t zlz4f_decompress_multiframe(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                                     uint32_t decode_flags);
+#define ZLZ4F_SPLIT_LEGACY  1u      /* split_flags: delimit legacy frames as members */
+#define ZLZ4F_MEMBER_LEGACY 4u
+int32_t zlz4f_batch_multiframe_split_ex(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                        const uint64_t *d_src_len, uint32_t nbuf, uint64_t *d_count, uint64_t *d_totals,
+                                        zlz4f_member *d_member, const uint64_t *d_mem_off, const uint64_t *d_mem_cap,
+                                        uint64_t *d_item_first, uint64_t *d_item_off, uint64_t *d_item_len,
+                                        int64_t *d_result, uint32_t split_flags, uint64_t *d_leg_len);
+int32_t zlz4f_batch_multiframe_select(void *stream, const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                                      const int64_t *d_split_result, const uint64_t *d_item_first,
+                                      const int64_t *d_from_frame, const int64_t *d_from_legacy, uint32_t nbuf,
+                                      int64_t *d_out);
+int64_t zlz4f_multiframe_decompressed_size_ex(const uint8_t *src, size_t src_len, uint32_t decode_flags,
+                                              uint32_t split_flags);
+int64_t zlz4f_decompress_multiframe_ex(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                                       uint32_t decode_flags, uint32_t split_flags);
 
 /* ---- legacy frames: what `lz4 -l` writes and the Linux kernel's unlz4 reads (vmlinuz.lz4, lz4 initramfs images); no
  * counterpart in the reference; DESIGN.md section 4.4i.  The format, as lz4io.c's LZ4IO_compressFilename_Legacy and
@@ -1121,8 +1180,8 @@ int64_t zlz4f_decompress_multiframe(const uint8_t *src, size_t src_len, uint8_t 
  *   above ZLZ4_MAX_INPUT_SIZE and a dst_cap below the bound (compress); step 1 above, and a defect of the walk in front of
  *   the first block (decode and size query, which walk the host bytes to size the block table).
  *
- * NOT SERVED: legacy members inside the multiframe calls (chain them by consumed); prefix and range decoding of legacy
- *   frames; dictionaries (the format has none); the segment calls. */
+ * NOT SERVED: prefix and range decoding of legacy frames; dictionaries (the format has none); the segment calls.  Legacy
+ *   members of a concatenated file: the multiframe _ex calls above with ZLZ4F_SPLIT_LEGACY. */
 #define ZLZ4F_LEGACY_MAGICNUMBER 0x184C2102u
 #define ZLZ4F_LEGACY_BLOCK_SIZE  (8u << 20)
 #define ZLZ4F_LEGACY_BLOCK_BOUND 8421520u        /* zlz4_compress_bound(ZLZ4F_LEGACY_BLOCK_SIZE) = LZ4_compressBound(8 MiB) */

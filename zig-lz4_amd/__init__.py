@@ -160,6 +160,10 @@ SYMBOLS = {
     "zlz4f_batch_multiframe_finish": (_I32, [_VP] * 7 + [_U32, _VP]),
     "zlz4f_multiframe_decompressed_size": (_I64, [_VP, _SZ, _U32]),
     "zlz4f_decompress_multiframe": (_I64, [_VP, _SZ, _VP, _SZ, _U32]),
+    "zlz4f_batch_multiframe_split_ex": (_I32, [_VP] * 4 + [_U32] + [_VP] * 9 + [_U32, _VP]),
+    "zlz4f_batch_multiframe_select": (_I32, [_VP] * 7 + [_U32, _VP]),
+    "zlz4f_multiframe_decompressed_size_ex": (_I64, [_VP, _SZ, _U32, _U32]),
+    "zlz4f_decompress_multiframe_ex": (_I64, [_VP, _SZ, _VP, _SZ, _U32, _U32]),
     "zlz4f_legacy_compress_frame_bound": (_SZ, [_SZ, _LP]),
     "zlz4f_batch_compress_legacy_frame_workspace": (_SZ, [_U32, _U32, _LP]),
     "zlz4f_batch_compress_legacy_frame": (_I32, [_VP] * 8 + [_U32, _U32, _LP, _VP, _SZ]),
@@ -1103,18 +1107,43 @@ class lz4f:
                                                    _ptr(item_first), _ptr(size), _ptr(item_result), result.numel(),
                                                    _ptr(result)))
 
+    # whole .lz4 files: legacy members in multiframe buffers (include/zlz4_amd.h)
+    SPLIT_LEGACY = 1
+    MEMBER_LEGACY = 4
+
+    @staticmethod
+    def multiframeSplitBatchEx(d_src, src_off, src_len, count, totals, member=None, mem_off=None, mem_cap=None,
+                               item_first=None, item_off=None, item_len=None, result=None, split_flags=0, leg_len=None):
+        """zlz4f_batch_multiframe_split_ex: as multiframeSplitBatch with totals int64 [4] = (members, frame chain blocks,
+        legacy members, legacy blocks) and, in record mode, leg_len int64 [members]: the length of every legacy member's
+        item, 0 for the others (item_len: the other way round)."""
+        _check(lib().zlz4f_batch_multiframe_split_ex(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), src_len.numel(),
+                                                     _ptr(count), _ptr(totals), _ptr(member), _ptr(mem_off), _ptr(mem_cap),
+                                                     _ptr(item_first), _ptr(item_off), _ptr(item_len), _ptr(result),
+                                                     split_flags, _ptr(leg_len)))
+
+    @staticmethod
+    def multiframeSelectBatch(member, mem_off, split_result, item_first, from_frame, from_legacy, out):
+        """zlz4f_batch_multiframe_select: out[i] = from_legacy[i] for the item of a legacy member, else from_frame[i] (all
+        int64 per item; out may be from_frame)."""
+        _check(lib().zlz4f_batch_multiframe_select(_stream(), _ptr(member), _ptr(mem_off), _ptr(split_result),
+                                                   _ptr(item_first), _ptr(from_frame), _ptr(from_legacy),
+                                                   split_result.numel(), _ptr(out)))
+
     class MultiframeSplit:
         """What splitMultiframes returns: the staged buffers (d_src, src_off, src_len), the member table (member, mem_off,
         count), the item arrays of the frame batch calls (item_first, item_off, item_len), the split results on the device
-        (result) and on the host (results), and the totals (nitems, max_blocks)."""
+        (result) and on the host (results), and the totals (nitems, max_blocks).  For the legacy frame calls: leg_len (None
+        without legacy=True) and the totals nlegacy and legacy_blocks (0 without)."""
 
     class MultiframeDecode:
         """What decodeMultiframes returns: per item size, dst_off, dst_cap and item_result, per buffer out_off, out_size and
         result, and the arena d_dst; all on the device."""
 
     @staticmethod
-    def splitMultiframes(buffers, device="cuda"):
-        """Stage `buffers` and delimit their members: count mode, one read-back of the totals, record mode."""
+    def splitMultiframes(buffers, device="cuda", legacy=False):
+        """Stage `buffers` and delimit their members: count mode, one read-back of the totals, record mode.  legacy: legacy
+        frames are members too (the _ex split with SPLIT_LEGACY)."""
         import torch
         sp = lz4f.MultiframeSplit()
         nbuf = len(buffers)
@@ -1123,24 +1152,36 @@ class lz4f:
         def i64(n):
             return torch.zeros(max(1, n), dtype=torch.int64, device=device)[:n]
 
-        sp.count, totals = i64(nbuf), i64(2)
-        lz4f.multiframeSplitBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals)
-        sp.nitems, sp.max_blocks = totals.cpu().tolist()
+        sp.leg_len, sp.nlegacy, sp.legacy_blocks = None, 0, 0
+        if legacy:
+            sp.count, totals = i64(nbuf), i64(4)
+            lz4f.multiframeSplitBatchEx(sp.d_src, sp.src_off, sp.src_len, sp.count, totals, split_flags=lz4f.SPLIT_LEGACY)
+            sp.nitems, sp.max_blocks, sp.nlegacy, sp.legacy_blocks = totals.cpu().tolist()
+        else:
+            sp.count, totals = i64(nbuf), i64(2)
+            lz4f.multiframeSplitBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals)
+            sp.nitems, sp.max_blocks = totals.cpu().tolist()
         sp.member = torch.zeros((max(1, sp.nitems), 3), dtype=torch.int64, device=device)
         sp.item_first, sp.item_off, sp.item_len, sp.result = i64(nbuf + 1), i64(sp.nitems), i64(sp.nitems), i64(nbuf)
-        lz4f.multiframeSplitBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals, sp.member, sp.item_first[:nbuf],
-                                  sp.count, sp.item_first, sp.item_off, sp.item_len, sp.result)
+        if legacy:
+            sp.leg_len = i64(sp.nitems)
+            lz4f.multiframeSplitBatchEx(sp.d_src, sp.src_off, sp.src_len, sp.count, totals, sp.member, sp.item_first[:nbuf],
+                                        sp.count, sp.item_first, sp.item_off, sp.item_len, sp.result, lz4f.SPLIT_LEGACY,
+                                        sp.leg_len)
+        else:
+            lz4f.multiframeSplitBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals, sp.member, sp.item_first[:nbuf],
+                                      sp.count, sp.item_first, sp.item_off, sp.item_len, sp.result)
         sp.mem_off = sp.item_first[:nbuf]             # the member table is laid out as the items are
         sp.results = sp.result.cpu().tolist()
         return sp
 
     @staticmethod
-    def multiframeMembers(buffers, device="cuda"):
+    def multiframeMembers(buffers, device="cuda", legacy=False):
         """Per buffer the list of its members (pos, len, kind, nibble) -- kind one of lz4f.MEMBER_*, nibble the low four
-        bits of a skippable magic -- or the split's error code."""
+        bits of a skippable magic -- or the split's error code.  legacy: as splitMultiframes."""
         if not len(buffers):
             return []
-        sp = lz4f.splitMultiframes(buffers, device)
+        sp = lz4f.splitMultiframes(buffers, device, legacy)
         rows = sp.member.cpu().tolist()
         first = sp.item_first.cpu().tolist()
         out = []
@@ -1154,7 +1195,9 @@ class lz4f:
     @staticmethod
     def decodeMultiframes(sp, flags=0, align=0, d_dst=None):
         """Size query, plan, one read-back of the arena size, decode and finish over a MultiframeSplit -> MultiframeDecode.
-        d_dst: an arena of the caller's (at least the planned bytes), else one is allocated."""
+        d_dst: an arena of the caller's (at least the planned bytes), else one is allocated.  Where the split recorded
+        legacy members (sp.nlegacy) the legacy size query and decode run over the same items and multiframeSelectBatch
+        merges their answers into size and item_result."""
         import torch
         dev = sp.d_src.device
         nbuf, ni = sp.src_len.numel(), sp.nitems
@@ -1168,6 +1211,10 @@ class lz4f:
         if ni:
             lz4f.frameDecompressedSizeBatch(sp.d_src, sp.item_off, sp.item_len, dd.size, max_blocks=sp.max_blocks,
                                             flags=flags)
+        if sp.nlegacy:
+            from_legacy = i64(ni)
+            lz4f.legacyFrameDecompressedSizeBatch(sp.d_src, sp.item_off, sp.leg_len, from_legacy, None, sp.legacy_blocks)
+            lz4f.multiframeSelectBatch(sp.member, sp.mem_off, sp.result, sp.item_first, dd.size, from_legacy, dd.size)
         lz4f.multiframePlanBatch(dd.size, sp.item_first, dd.dst_off, dd.dst_cap, dd.out_off, dd.out_size, totals, align)
         dd.arena_bytes, dd.decoded_bytes = totals.cpu().tolist()
         if d_dst is None:
@@ -1178,33 +1225,60 @@ class lz4f:
         if ni:
             lz4f.decompressFrameBatch(sp.d_src, sp.item_off, sp.item_len, d_dst, dd.dst_off, dd.dst_cap, dd.item_result,
                                       max_blocks=sp.max_blocks, flags=flags)
+        if sp.nlegacy:
+            lz4f.decompressLegacyFrameBatch(sp.d_src, sp.item_off, sp.leg_len, d_dst, dd.dst_off, dd.dst_cap, from_legacy,
+                                            None, sp.legacy_blocks)
+            lz4f.multiframeSelectBatch(sp.member, sp.mem_off, sp.result, sp.item_first, dd.item_result, from_legacy,
+                                       dd.item_result)
         if nbuf:
             lz4f.multiframeFinishBatch(sp.member, sp.mem_off, sp.result, sp.item_first, dd.size, dd.item_result, dd.result)
         return dd
 
     @staticmethod
-    def decompressMultiframes(buffers, flags=0, align=0, device="cuda"):
+    def decompressMultiframes(buffers, flags=0, align=0, device="cuda", legacy=False):
         """Every buffer of `buffers` -- frames and skippable frames back to back, what a .lz4 file holds -- decoded in one
-        batch: -> list of contents (the members' contents concatenated) or the code of the first member that is not OK."""
+        batch: -> list of contents (the members' contents concatenated) or the code of the first member that is not OK.
+        legacy: legacy frames (`lz4 -l`) are members too."""
         if flags & ~lz4f.DECODE_LINKED:
             _check(lib().zlz4f_decompress_multiframe(None, 0, None, 0, flags))
         if not len(buffers):
             return []
-        dd = lz4f.decodeMultiframes(lz4f.splitMultiframes(buffers, device), flags, align)
+        dd = lz4f.decodeMultiframes(lz4f.splitMultiframes(buffers, device, legacy), flags, align)
         return _unstage(dd.d_dst, dd.out_off.cpu().tolist(), dd.result)
 
     @staticmethod
-    def multiframeDecompressedSize(src, flags=0):
+    def multiframeDecompressedSize(src, flags=0, legacy=False):
         """zlz4f_multiframe_decompressed_size: what decompressMultiframe returns for `src` into a destination that is large
-        enough (content checksums are not verified); errors raise Lz4Error.  Nothing is decoded."""
+        enough (content checksums are not verified); errors raise Lz4Error.  Nothing is decoded.  legacy: the _ex call with
+        SPLIT_LEGACY."""
         s, n = _in(src)
+        if legacy:
+            return _check(lib().zlz4f_multiframe_decompressed_size_ex(C.addressof(s), n, flags, lz4f.SPLIT_LEGACY))
         return _check(lib().zlz4f_multiframe_decompressed_size(C.addressof(s), n, flags))
 
     @staticmethod
-    def decompressMultiframe(src, flags=0, dst_cap=None):
-        """zlz4f_decompress_multiframe: one buffer in host memory.  dst_cap None: the size is queried first."""
-        cap = lz4f.multiframeDecompressedSize(src, flags) if dst_cap is None else dst_cap
+    def decompressMultiframe(src, flags=0, dst_cap=None, legacy=False):
+        """zlz4f_decompress_multiframe: one buffer in host memory.  dst_cap None: the size is queried first.  legacy: the _ex
+        calls with SPLIT_LEGACY."""
+        cap = lz4f.multiframeDecompressedSize(src, flags, legacy) if dst_cap is None else dst_cap
+        if legacy:
+            return _run(lib().zlz4f_decompress_multiframe_ex, src, cap, flags, lz4f.SPLIT_LEGACY)
         return _run(lib().zlz4f_decompress_multiframe, src, cap, flags)
+
+    @staticmethod
+    def decompressFiles(buffers, align=0, device="cuda"):
+        """Every buffer a whole .lz4 file -- modern frames (linked blocks too), skippable frames and legacy frames in any
+        order -- decoded in one batch: -> what `lz4 -dc` prints for each file, or the code of the first member that is not
+        OK.  decompressMultiframes(buffers, flags=DECODE_LINKED, legacy=True); a device that is no GPU raises DeviceError."""
+        import torch
+        if torch.device(device).type != "cuda":
+            _check(ERR_DEVICE)
+        return lz4f.decompressMultiframes(buffers, lz4f.DECODE_LINKED, align, device, legacy=True)
+
+    @staticmethod
+    def decompressFile(src):
+        """One whole .lz4 file in host memory: decompressMultiframe(src, flags=DECODE_LINKED, legacy=True)."""
+        return lz4f.decompressMultiframe(src, lz4f.DECODE_LINKED, legacy=True)
 
     # legacy frames: what `lz4 -l` writes (include/zlz4_amd.h, DESIGN.md section 4.4i)
     LegacyPrefs = LegacyPrefs

@@ -1,7 +1,8 @@
 // zlz4_frame_batch.hpp -- what the lz4f kernels and host calls share: the per-frame record and the block flags of the batch
 // frame calls, XXH32, the frame header parse, and the block chain: the
 // decode of a block word and the one step of the chain walk that every walker is written on, the regions a call carves
-// out of its workspace, and the walk of a legacy frame (section 4.4i).  Included by zlz4_frame.hip (the pipelines), zlz4_frame_linked.hip (the linked-block kernels of
+// out of its workspace, the walk of a legacy frame (section 4.4i) and the delimiter of a multiframe's members (sections
+// 4.4h, 4.4j).  Included by zlz4_frame.hip (the pipelines), zlz4_frame_linked.hip (the linked-block kernels of
 // section 4.4c, the frame prefix decoder of section 4.4f), zlz4_frame_multi.hip (the multiframe split of section 4.4h) and
 // zlz4_frame_legacy.hip (the legacy frame calls of section 4.4i).
 #pragma once
@@ -97,7 +98,7 @@ __host__ __device__ inline ParsedHeader parse_header(const uint8_t *src, size_t 
 }
 
 // the header of the frame at s, n bytes available: staged so that parse_header reads no global byte twice
-__device__ __forceinline__ ParsedHeader frame_header(const uint8_t *__restrict__ s, uint64_t n) {
+__host__ __device__ __forceinline__ ParsedHeader frame_header(const uint8_t *__restrict__ s, uint64_t n) {
     uint8_t head[19];
     const uint32_t have = n < sizeof head ? (uint32_t)n : (uint32_t)sizeof head;
     for (uint32_t k = 0; k < have; k++) head[k] = s[k];
@@ -225,6 +226,47 @@ __host__ __device__ __forceinline__ int64_t legacy_walk(const uint8_t *s, uint64
         pos += 4ull + w;
     }
     return 0;
+}
+
+// ------------------------------------------------------------------ multiframe members (DESIGN.md sections 4.4h, 4.4j)
+struct MfMember { uint64_t len; uint64_t nb; uint32_t kind; bool last; };
+
+// The member that starts at s[0] of the n bytes that remain (n >= 1).  A frame member is delimited by frame_header and
+// chain_walk up to the end mark; with ZLZ4F_SPLIT_LEGACY in split_flags the legacy magic starts a legacy member, delimited
+// by legacy_walk: it ends at the end of the bytes or in front of a foreign word, and is not the last one unless the walk
+// meets a defect.  Whatever cannot be delimited reaches to n and is the last member.  nb = the blocks of the member's
+// chain -- chain_walk's count, as k_bfd_walk<false> takes it for the same bytes, or legacy_walk's, as k_lf_walk<false>
+// does: the caller keeps the two apart by `kind`.
+__host__ __device__ inline MfMember mf_member(const uint8_t *__restrict__ s, uint64_t n, uint32_t split_flags) {
+    MfMember m = {n, 0, ZLZ4F_MEMBER_FRAME, true};
+    if (n >= 4) {
+        const uint32_t magic = zx_rd32(s);
+        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {
+            const uint32_t nib = (magic & 15u) << 8;
+            m.kind = ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED | nib;
+            if (n < 8) return m;
+            const uint64_t len = 8ull + zx_rd32(s + 4);
+            if (len > n) return m;
+            m.len = len; m.kind = ZLZ4F_MEMBER_SKIPPABLE | nib; m.last = false;
+            return m;
+        }
+        if ((split_flags & ZLZ4F_SPLIT_LEGACY) && magic == ZLZ4F_LEGACY_MAGICNUMBER) {
+            m.kind = ZLZ4F_MEMBER_LEGACY;
+            m.last = legacy_walk(s, n, ~0ull, m.nb, m.len, [](uint64_t, uint64_t, uint32_t) {}) < 0;    // (then len = n)
+            return m;
+        }
+    }
+    const ParsedHeader ph = frame_header(s, n);
+    if (ph.size < 0) return m;
+    uint64_t pos = (uint64_t)ph.size;
+    const bool bc = (ph.flg & 0x10u) != 0;
+    if (chain_walk(s, n, bc, pos, ~0ull, m.nb, [](uint64_t, const ChainBlock &) {}) != kChainEndMark) return m;
+    if (ph.flg & 0x04u) {
+        if (pos + 4 > n) return m;
+        pos += 4;
+    }
+    m.len = pos; m.last = false;
+    return m;
 }
 
 __device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { return F.nb == 0 || F.base + F.nb <= max_blocks; }

@@ -115,6 +115,10 @@ extern "c" fn zlz4f_batch_multiframe_plan(stream: ?*anyopaque, d_size: ?[*]const
 extern "c" fn zlz4f_batch_multiframe_finish(stream: ?*anyopaque, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_item_first: ?[*]const u64, d_size: ?[*]const i64, d_item_result: ?[*]const i64, nbuf: u32, d_result: ?[*]i64) i32;
 extern "c" fn zlz4f_multiframe_decompressed_size(src: [*]const u8, src_len: usize, decode_flags: u32) i64;
 extern "c" fn zlz4f_decompress_multiframe(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32) i64;
+extern "c" fn zlz4f_batch_multiframe_split_ex(stream: ?*anyopaque, d_src: ?[*]const u8, d_src_off: ?[*]const u64, d_src_len: ?[*]const u64, nbuf: u32, d_count: ?[*]u64, d_totals: [*]u64, d_member: ?[*]Member, d_mem_off: ?[*]const u64, d_mem_cap: ?[*]const u64, d_item_first: ?[*]u64, d_item_off: ?[*]u64, d_item_len: ?[*]u64, d_result: ?[*]i64, split_flags: u32, d_leg_len: ?[*]u64) i32;
+extern "c" fn zlz4f_batch_multiframe_select(stream: ?*anyopaque, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_item_first: ?[*]const u64, d_from_frame: ?[*]const i64, d_from_legacy: ?[*]const i64, nbuf: u32, d_out: ?[*]i64) i32;
+extern "c" fn zlz4f_multiframe_decompressed_size_ex(src: [*]const u8, src_len: usize, decode_flags: u32, split_flags: u32) i64;
+extern "c" fn zlz4f_decompress_multiframe_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32, split_flags: u32) i64;
 /// zlz4f_legacy_prefs of include/zlz4_amd.h: block_size 0 = 8 MiB, 1 .. 8 MiB as given; compression_level <= 0 = fast
 pub const LegacyPrefs = extern struct { block_size: u32 = 0, compression_level: i32 = 0 };
 extern "c" fn zlz4f_legacy_compress_frame_bound(src_size: usize, prefs: ?*const LegacyPrefs) usize;
@@ -896,6 +900,28 @@ pub const lz4f = struct {
     }
     pub fn decompressMultiframe(src: []const u8, dst: []u8, decode_flags: u32) Error!usize {
         return mapFrame(zlz4f_decompress_multiframe(src.ptr, src.len, dst.ptr, dst.len, decode_flags));
+    }
+    /// Whole .lz4 files: with SPLIT_LEGACY in split_flags a legacy frame is a member too (kind MEMBER_LEGACY).  The split
+    /// writes its length to leg_len (0 in item_len), totals has four entries (members, frame chain blocks, legacy members,
+    /// legacy blocks), the batch legacy frame calls run over (item_off, leg_len) beside the frame calls, and
+    /// multiframeSelectBatch takes the legacy call's answer for every legacy member's item.  split_flags 0: the calls above.
+    pub const SPLIT_LEGACY: u32 = 1;
+    pub const MEMBER_LEGACY: u32 = 4;
+    pub fn multiframeSplitBatchEx(stream: ?*anyopaque, src: ?[*]const u8, src_off: ?[*]const u64, src_len: ?[*]const u64, nbuf: u32, count: ?[*]u64, totals: [*]u64, member: ?[*]Member, mem_off: ?[*]const u64, mem_cap: ?[*]const u64, item_first: ?[*]u64, item_off: ?[*]u64, item_len: ?[*]u64, result: ?[*]i64, split_flags: u32, leg_len: ?[*]u64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_multiframe_split_ex(stream, src, src_off, src_len, nbuf, count, totals, member, mem_off, mem_cap, item_first, item_off, item_len, result, split_flags, leg_len));
+    }
+    pub fn multiframeSelectBatch(stream: ?*anyopaque, member: ?[*]const Member, mem_off: ?[*]const u64, split_result: ?[*]const i64, item_first: ?[*]const u64, from_frame: ?[*]const i64, from_legacy: ?[*]const i64, nbuf: u32, out: ?[*]i64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_multiframe_select(stream, member, mem_off, split_result, item_first, from_frame, from_legacy, nbuf, out));
+    }
+    pub fn multiframeDecompressedSizeEx(src: []const u8, decode_flags: u32, split_flags: u32) Error!usize {
+        return mapFrame(zlz4f_multiframe_decompressed_size_ex(src.ptr, src.len, decode_flags, split_flags));
+    }
+    pub fn decompressMultiframeEx(src: []const u8, dst: []u8, decode_flags: u32, split_flags: u32) Error!usize {
+        return mapFrame(zlz4f_decompress_multiframe_ex(src.ptr, src.len, dst.ptr, dst.len, decode_flags, split_flags));
+    }
+    /// what `lz4 -dc` prints for the .lz4 file `src`: linked-block frames, skippable frames and legacy frames included
+    pub fn decompressFile(src: []const u8, dst: []u8) Error!usize {
+        return decompressMultiframeEx(src, dst, DECODE_LINKED, SPLIT_LEGACY);
     }
     /// No counterpart in the reference: legacy frames, what `lz4 -l` writes and the Linux kernel's unlz4 reads -- the magic
     /// 0x184C2102, then { u32 size, block } repeated (include/zlz4_amd.h).  One frame in host memory per call; `consumed`
