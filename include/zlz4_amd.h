@@ -840,7 +840,7 @@ int64_t zlz4f_decompress_frame_prefix_using_dict(const uint8_t *src, size_t src_
 
 /* ---- frame index and range decoding: bytes [a, b) of single frames whose blocks decode on their own (no counterpart in
  * the reference).  Every item is ONE frame (a multiframe buffer, below, is not served: index and
- * range see its first frame only).  A frame is a chain of blocks; the INDEX says where block k lies and at which decoded
+ * range see its first frame only; the file index and range calls further below see every member).  A frame is a chain of blocks; the INDEX says where block k lies and at which decoded
  * offset it starts, the RANGE DECODE decodes only the blocks that overlap [a, b), one wavefront per block.
  *
  * zlz4f_batch_frame_index: frame f with nb blocks in its chain gets nb + 1 entries at d_index + d_idx_off[f] (offsets and
@@ -1036,8 +1036,8 @@ int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, u
  *   ZLZ4F_ERR_PARAMETER_INVALID, then a null pointer with a length: ZLZ4_ERR_INVALID_STATE, both before the device check.
  *   The planned total above dst_cap: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.
  *
- * NOT SERVED: a dictionary per member (a member with a dictID decodes as the plain frame call decodes it); prefix and
- *   range decoding of a multiframe; writing multiframes (they are the concatenation of what the compress calls return).
+ * NOT SERVED: a dictionary per member (a member with a dictID decodes as the plain frame call decodes it); writing
+ *   multiframes (they are the concatenation of what the compress calls return).
  *   Legacy frames (magic 0x184C2102) are a member that cannot be delimited by THESE calls: ZLZ4F_ERR_FRAME_TYPE_UNKNOWN; the
  *   _ex calls below with ZLZ4F_SPLIT_LEGACY serve them.
  *
@@ -1084,7 +1084,7 @@ int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, u
  *   zlz4f_decompress_multiframe.  zlz4f_decompress_multiframe_ex(.., ZLZ4F_DECODE_LINKED, ZLZ4F_SPLIT_LEGACY) returns what
  *   `lz4 -dc` prints for the file, or the code of the first member that is not OK.
  *
- * NOT SERVED: a dictionary per member; prefix and range decoding of a multiframe. */
+ * NOT SERVED: a dictionary per member.  Prefix and range decoding of a file: the file index and range calls below. */
 #define ZLZ4F_MEMBER_FRAME               1u
 #define ZLZ4F_MEMBER_SKIPPABLE           2u
 #define ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED 3u
@@ -1180,8 +1180,9 @@ int64_t zlz4f_decompress_multiframe_ex(const uint8_t *src, size_t src_len, uint8
  *   above ZLZ4_MAX_INPUT_SIZE and a dst_cap below the bound (compress); step 1 above, and a defect of the walk in front of
  *   the first block (decode and size query, which walk the host bytes to size the block table).
  *
- * NOT SERVED: prefix and range decoding of legacy frames; dictionaries (the format has none); the segment calls.  Legacy
- *   members of a concatenated file: the multiframe _ex calls above with ZLZ4F_SPLIT_LEGACY. */
+ * NOT SERVED: dictionaries (the format has none); the segment calls.  Legacy members of a concatenated file: the
+ *   multiframe _ex calls above with ZLZ4F_SPLIT_LEGACY.  Prefix and range decoding of a legacy frame: the file index and
+ *   range calls below, over the frame as a file of one member. */
 #define ZLZ4F_LEGACY_MAGICNUMBER 0x184C2102u
 #define ZLZ4F_LEGACY_BLOCK_SIZE  (8u << 20)
 #define ZLZ4F_LEGACY_BLOCK_BOUND 8421520u        /* zlz4_compress_bound(ZLZ4F_LEGACY_BLOCK_SIZE) = LZ4_compressBound(8 MiB) */
@@ -1209,6 +1210,101 @@ int64_t zlz4f_compress_legacy_frame(const uint8_t *src, size_t src_len, uint8_t 
                                     const zlz4f_legacy_prefs *prefs);
 int64_t zlz4f_legacy_frame_decompressed_size(const uint8_t *src, size_t src_len, size_t *consumed);
 int64_t zlz4f_decompress_legacy_frame(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *consumed);
+
+/* ---- file index and file range decoding: bytes [a, b) of whole .lz4 files (no counterpart in the reference; DESIGN.md
+ * section 4.4k).  A FILE is a buffer as the record-mode zlz4f_batch_multiframe_split_ex delimits it: frame, skippable and
+ * legacy members in any order.  The frame index and range calls above see one frame; these see every member, so a log that
+ * was appended to, `cat a.lz4 legacy.lz4 b.lz4` or an initramfs followed by modern frames can be read at any offset, and a
+ * file PREFIX is the range [0, n).
+ *
+ * zlz4f_batch_file_index.  INPUT: the buffers (d_src, d_src_off, d_src_len, nbuf), the outputs of the record-mode split over
+ *   them (d_member, d_mem_off, d_split_result = the split's d_result, d_item_first, d_item_off, d_item_len, d_leg_len) and
+ *   split_totals, a HOST pointer to the split's four totals as they were read back.  After a split with split_flags == 0
+ *   there is no legacy member (a legacy magic stays ZLZ4F_ERR_FRAME_TYPE_UNKNOWN, as everywhere); split_totals[2] == 0
+ *   skips the legacy kernels and d_leg_len may be null.
+ *   OUTPUT per buffer s with nb blocks: nb + 1 entries of zlz4f_index_entry at d_index + d_idx_off[s].  Entry k < nb is
+ *   block k of the file, counted across its frame and legacy members in member order: pos = the position of the block's
+ *   header word (frame) or size word (legacy) INSIDE THE BUFFER, dec = the offset at which the block starts INSIDE THE
+ *   FILE'S CONTENT.  Entry nb = { where the chain of the last frame or legacy member ended -- the end mark or the end of
+ *   the input for a frame, the member's end for a legacy frame; 0 for a file without such a member --, S = the file's
+ *   decoded size }.  Skippable members, frames without blocks and a legacy magic alone contribute no entry.
+ *   PACKING: the call writes d_idx_off itself, nbuf + 1 entries: the exclusive scan of every buffer's room, its chain blocks
+ *   plus one.  The room is the walks' count alone, so a buffer that fails keeps its room.  The caller sizes d_index from the
+ *   split's read-back: idx_cap = split_totals[1] + split_totals[3] + nbuf entries always suffice; a buffer whose room ends
+ *   behind idx_cap answers ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL and writes no entry.
+ *   d_result[s] = nb, or the code that zlz4f_batch_multiframe_finish gives the file when it folds the two size queries at
+ *   decode_flags == 0: a split result < 0, else the first member in member order that is not OK -- a frame member's size
+ *   query error (every block sized as an independent block, the content checksum set aside, as zlz4f_batch_frame_index: a
+ *   member whose blocks refer to earlier output is ZLZ4F_ERR_DECOMPRESSION_FAILED), a legacy member's, a truncated
+ *   skippable member's.  The index capacity is the last check.  On an error no entry of that buffer is promised.  A buffer
+ *   of one frame has exactly the entries and the result of zlz4f_batch_frame_index.
+ *   Workspace: zlz4f_batch_file_index_workspace(nbuf, split_totals) bytes, 16-byte aligned.  A null array, a misaligned (8
+ *   bytes) one, a null split_totals or one with a count above 2^32 - 1, or a refused workspace: ZLZ4_ERR_INVALID_STATE,
+ *   nothing launched; then the device.  nbuf == 0 returns 0.  Launches: the frame size query's sequence over the items up
+ *   to its fold; with legacy members the legacy walk (count, scan, record) and the size kernel over their blocks; the
+ *   rooms, their scan, and the fold -- one wavefront per buffer that walks the members, carries the decoded base and the
+ *   block count from member to member and writes the rebased entries, 64 blocks a step.
+ *
+ * THE PLAN is zlz4f_batch_plan_frame_ranges, unchanged: nframes = nbuf, zlz4f_range.frame names the buffer.
+ *
+ * zlz4f_batch_decompress_file_range: the arguments of zlz4f_batch_decompress_frame_range (nframes = nbuf) and the member
+ *   table, d_mem_off and the split results.  OUTPUT as there: slot r holds the decode from the start of block k0 to b', the
+ *   wanted bytes stand d_skip[r] bytes in, d_result[r] = b' - a', no byte outside [d_dst_off[r], d_dst_off[r] + b' - dec[k0])
+ *   is written.  A RANGE MAY SPAN MEMBERS: every item (one block of one range) finds its member by bisection over the
+ *   buffer's member table by pos and takes from it what the frame call takes from the one header -- for a frame member its
+ *   OWN FLG 0x10 (block checksum), the stored bit of the block word and the header's block size as the bound; for a legacy
+ *   member no checksum, no stored bit, a bound of 8 MiB and a size word that is neither 0 nor above
+ *   ZLZ4F_LEGACY_BLOCK_BOUND.  Two neighbouring blocks of one range may differ in all of these.
+ *   THE INDEX IS NOT TRUSTED; no position from it becomes an address before it is checked.  Per range, in this order:
+ *   1. ZLZ4_ERR_INVALID_STATE for frame >= nbuf, a > b, reserved != 0.  Then d_idx_n[buf] < 0: that code.
+ *   2. a' == b': 0, d_skip[r] = 0; nothing behind the tables (index, member table) is read.
+ *   3. ZLZ4_ERR_INVALID_STATE ("not this file's index") when the entries k0..k1+1 are no chain: k0 / k1 not found or k1 <
+ *      k0, dec[k0] > a', dec[k1] >= b', dec[k1+1] < b', the buffer has no member table (split result <= 0), or for a k in
+ *      k0..k1: no member starts at or in front of pos[k]; that member is neither FRAME nor LEGACY, does not lie inside the
+ *      buffer, or its header is none (a frame header error, a word that is not the legacy magic); pos[k] lies in front of
+ *      the end of that header or fewer than 4 bytes in front of the member's end; pos[k+1] <= pos[k]; dec[k+1] < dec[k];
+ *      dec[k+1] - dec[k] above the member's bound.
+ *   4. d_dst_cap[r] < b' - dec[k0]: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL.  5. max_items, as the frame call.
+ *   6. The first failing block in block order decides.  Block k with size sz from its word: ZLZ4_ERR_INVALID_STATE when the
+ *      word is an end mark (frame) or 0 or above the bound (legacy); when the block (+ 4 with a block checksum) runs past
+ *      its member's end; when pos[k+1] lies inside the member (at or in front of its end) and the block does not end exactly
+ *      there; when pos[k+1] lies behind the member and the block is not the member's last -- it ends on the frame member's
+ *      end mark, or at the member's end for a chain without one and for a legacy member.  Then the block checksum, the
+ *      stored block, zlz4_batch_decompress_safe for a block wanted in full and zlz4_batch_decompress_safe_prefix for the one
+ *      that b' cuts, with the codes of the frame call.
+ *   Nothing outside the touched blocks and their members' headers is read or validated; content checksums are never
+ *   checked.  Workspace: zlz4f_batch_decompress_file_range_workspace(nranges, max_items).  Refusals as the frame call,
+ *   with the three member arrays among the arrays.  The frame range kernels' scan, checksum, copy and finish are reused;
+ *   the frame calls themselves are unchanged.
+ * Both calls: asynchronous on `stream`, a fixed launch sequence (it depends on split_totals alone), nothing allocated,
+ *   nothing read back: graph-capturable.  The index stays valid for every later read of the same bytes.
+ *
+ * zlz4f_decompress_file_range: one file in HOST memory; exactly the b' - a' wanted bytes arrive at dst[0..).  Before the
+ *   device check: an unknown split_flags bit (ZLZ4F_ERR_PARAMETER_INVALID), then a null pointer with a length and a > b
+ *   (ZLZ4_ERR_INVALID_STATE).  Then split (count, record), index, plan and range as a batch of one.  An index error is the
+ *   result; dst_cap < b' - a' gives ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.  IT BUILDS THE INDEX ON EVERY
+ *   CALL (a size query of the whole file): a caller with several reads of one file keeps the index and uses the batch calls.
+ *
+ * NOT SERVED: dictionaries per member; history-aware ranges of linked members; a start offset inside one block; a
+ *   serialised index. */
+size_t  zlz4f_batch_file_index_workspace(uint32_t nbuf, const uint64_t *split_totals);
+int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                               uint32_t nbuf, const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                               const int64_t *d_split_result, const uint64_t *d_item_first, const uint64_t *d_item_off,
+                               const uint64_t *d_item_len, const uint64_t *d_leg_len, const uint64_t *split_totals,
+                               zlz4f_index_entry *d_index, uint64_t *d_idx_off, uint64_t idx_cap, int64_t *d_result,
+                               void *d_workspace, size_t workspace_bytes);
+size_t  zlz4f_batch_decompress_file_range_workspace(uint32_t nranges, uint32_t max_items);
+int32_t zlz4f_batch_decompress_file_range(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                          const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
+                                          const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nbuf,
+                                          const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                                          const int64_t *d_split_result, const zlz4f_range *d_range, uint8_t *d_dst,
+                                          const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_skip,
+                                          int64_t *d_result, uint32_t nranges, uint32_t max_items, void *d_workspace,
+                                          size_t workspace_bytes);
+int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t src_len, uint64_t a, uint64_t b, uint8_t *dst,
+                                    size_t dst_cap, uint32_t split_flags);
 
 /* ======================================================================
  * 4. Introspection

@@ -155,6 +155,11 @@ SYMBOLS = {
     "zlz4f_batch_decompress_frame_range_workspace": (_SZ, [_U32, _U32]),
     "zlz4f_batch_decompress_frame_range": (_I32, [_VP] * 7 + [_U32] + [_VP] * 6 + [_U32, _U32, _VP, _SZ]),
     "zlz4f_decompress_frame_range": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ]),
+    "zlz4f_batch_file_index_workspace": (_SZ, [_U32, _VP]),
+    "zlz4f_batch_file_index": (_I32, [_VP] * 4 + [_U32] + [_VP] * 10 + [C.c_uint64, _VP, _VP, _SZ]),
+    "zlz4f_batch_decompress_file_range_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_decompress_file_range": (_I32, [_VP] * 7 + [_U32] + [_VP] * 9 + [_U32, _U32, _VP, _SZ]),
+    "zlz4f_decompress_file_range": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ, _U32]),
     "zlz4f_batch_multiframe_split": (_I32, [_VP] * 4 + [_U32] + [_VP] * 9),
     "zlz4f_batch_multiframe_plan": (_I32, [_VP] * 3 + [_U32, _U32] + [_VP] * 5),
     "zlz4f_batch_multiframe_finish": (_I32, [_VP] * 7 + [_U32, _VP]),
@@ -1279,6 +1284,134 @@ class lz4f:
     def decompressFile(src):
         """One whole .lz4 file in host memory: decompressMultiframe(src, flags=DECODE_LINKED, legacy=True)."""
         return lz4f.decompressMultiframe(src, lz4f.DECODE_LINKED, legacy=True)
+
+    # file index and file range decoding (include/zlz4_amd.h, DESIGN.md section 4.4k)
+    @staticmethod
+    def _split_totals(totals):
+        t = [int(x) for x in totals]
+        if len(t) != 4:
+            raise ValueError("totals: the four totals of the record-mode split")
+        return (C.c_uint64 * 4)(*t)
+
+    @staticmethod
+    def fileIndexBatchWorkspace(nbuf, totals):
+        return lib().zlz4f_batch_file_index_workspace(nbuf, lz4f._split_totals(totals))
+
+    @staticmethod
+    def fileIndexBatch(d_src, src_off, src_len, member, mem_off, split_result, item_first, item_off, item_len, leg_len, totals,
+                       index, idx_off, result, idx_cap=None, workspace=None):
+        """zlz4f_batch_file_index on torch CUDA tensors: the buffers, the outputs of a record-mode split over them and its
+        four totals (host integers); index int64 [entries, 2] = (pos, dec), idx_off int64 [nbuf + 1] (written by the call),
+        result int64 [nbuf] = the file's block count or its code.  idx_cap None: the entries `index` holds."""
+        import torch
+        nbuf = src_len.numel()
+        t = lz4f._split_totals(totals)
+        if idx_cap is None:
+            idx_cap = index.shape[0]
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_file_index_workspace(nbuf, t)), dtype=torch.uint8,
+                                    device=d_src.device)
+        _check(lib().zlz4f_batch_file_index(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), nbuf, _ptr(member),
+                                            _ptr(mem_off), _ptr(split_result), _ptr(item_first), _ptr(item_off),
+                                            _ptr(item_len), _ptr(leg_len), t, _ptr(index), _ptr(idx_off), idx_cap,
+                                            _ptr(result), _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def decompressFileRangeBatchWorkspace(nranges, max_items):
+        return lib().zlz4f_batch_decompress_file_range_workspace(nranges, max_items)
+
+    @staticmethod
+    def decompressFileRangeBatch(d_src, src_off, src_len, index, idx_off, idx_n, member, mem_off, split_result, ranges, d_dst,
+                                 dst_off, dst_cap, skip, result, max_items, workspace=None):
+        """zlz4f_batch_decompress_file_range: range r's wanted bytes are d_dst[dst_off[r] + skip[r] ..][: result[r]]; the
+        range's first field names the buffer."""
+        import torch
+        nr = ranges.shape[0]
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_decompress_file_range_workspace(nr, max_items)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_decompress_file_range(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(index),
+                                                       _ptr(idx_off), _ptr(idx_n), idx_n.numel(), _ptr(member),
+                                                       _ptr(mem_off), _ptr(split_result), _ptr(ranges), _ptr(d_dst),
+                                                       _ptr(dst_off), _ptr(dst_cap), _ptr(skip), _ptr(result), nr, max_items,
+                                                       _ptr(workspace), workspace.numel()))
+
+    class FileIndex:
+        """What fileIndex returns: the staged buffers and their split (.split, a MultiframeSplit), the device index (index,
+        idx_off) and the per-file results: idx_n on the device, `results` on the host (a block count or a code per file)."""
+
+        def __init__(self, split, index, idx_off, idx_n, results):
+            self.split, self.index, self.idx_off, self.idx_n, self.results = split, index, idx_off, idx_n, results
+            self.d_src, self.src_off, self.src_len = split.d_src, split.src_off, split.src_len
+
+    @staticmethod
+    def fileIndex(buffers, device="cuda", legacy=True):
+        """Stage `buffers` -- whole .lz4 files -- split them and index them (zlz4f_batch_file_index) -> FileIndex, to be read
+        any number of times with decompressFileRanges.  A file whose size query fails keeps its code in .results.  legacy:
+        legacy frames are members (False: a legacy magic is FrameTypeUnknown)."""
+        import torch
+        if torch.device(device).type != "cuda":
+            _check(ERR_DEVICE)
+        nbuf = len(buffers)
+        sp = lz4f.splitMultiframes(buffers, device, legacy)
+        cap = sp.max_blocks + sp.legacy_blocks + nbuf
+        index = torch.zeros((max(1, cap), 2), dtype=torch.int64, device=device)
+        idx_off = torch.zeros(nbuf + 1, dtype=torch.int64, device=device)
+        idx_n = torch.zeros(nbuf, dtype=torch.int64, device=device)
+        if nbuf:
+            lz4f.fileIndexBatch(sp.d_src, sp.src_off, sp.src_len, sp.member, sp.mem_off, sp.result, sp.item_first, sp.item_off,
+                                sp.item_len, sp.leg_len, (sp.nitems, sp.max_blocks, sp.nlegacy, sp.legacy_blocks), index,
+                                idx_off, idx_n, cap)
+        return lz4f.FileIndex(sp, index, idx_off, idx_n, idx_n.cpu().tolist())
+
+    @staticmethod
+    def decompressFileRanges(indexed, ranges, align=0):
+        """Bytes [a, b) of file `buf` for every (buf, a, b) of `ranges` (both clamped to the file's size) -> list of bytes
+        or error codes.  Plan (planFrameRanges: the plan reads the index alone), one read-back of the totals, decode, one
+        read-back of the data."""
+        import torch
+        nr = len(ranges)
+        if nr == 0:
+            return []
+        sp = indexed.split
+        dev = sp.d_src.device
+        d_range = torch.from_numpy(lz4f.packRanges(ranges).view("int64")).to(dev)
+        dst_off = torch.empty(nr, dtype=torch.int64, device=dev)
+        dst_cap = torch.empty(nr, dtype=torch.int64, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        lz4f.planFrameRanges(indexed.index, indexed.idx_off, indexed.idx_n, d_range, dst_off, dst_cap, totals, align)
+        arena, items = totals.cpu().tolist()
+        d_dst = torch.empty(max(1, arena), dtype=torch.uint8, device=dev)
+        skip = torch.empty(nr, dtype=torch.int64, device=dev)
+        result = torch.empty(nr, dtype=torch.int64, device=dev)
+        lz4f.decompressFileRangeBatch(sp.d_src, sp.src_off, sp.src_len, indexed.index, indexed.idx_off, indexed.idx_n,
+                                      sp.member, sp.mem_off, sp.result, d_range, d_dst, dst_off, dst_cap, skip, result, items)
+        back = torch.stack((dst_off, skip, result)).cpu().tolist()
+        host = d_dst.cpu().numpy().tobytes()
+        return [host[o + s:o + s + r] if r >= 0 else r for o, s, r in zip(*back)]
+
+    @staticmethod
+    def decompressFilePrefixes(buffers, n, device="cuda", legacy=True):
+        """The first n bytes of every file (n: one int, or one per file): fileIndex plus the ranges (s, 0, n)."""
+        ns = [n] * len(buffers) if isinstance(n, int) else list(n)
+        if len(ns) != len(buffers):
+            raise ValueError("n: one int, or one per buffer")
+        if not len(buffers):
+            return []
+        return lz4f.decompressFileRanges(lz4f.fileIndex(buffers, device, legacy), [(s, 0, k) for s, k in enumerate(ns)])
+
+    @staticmethod
+    def decompressFileRange(src, a, b, legacy=True):
+        """zlz4f_decompress_file_range: bytes [a, b) of one file in host memory (both clamped to the file's size).  The
+        index is built on every call; several reads of one file: fileIndex + decompressFileRanges."""
+        s, n = _in(src)
+        flags = lz4f.SPLIT_LEGACY if legacy else 0
+        cap = max(0, min(b, 1 << 62) - a)
+        if cap > 1 << 20:                              # (b may lie far behind the file's end)
+            cap = min(cap, max(0, lz4f.multiframeDecompressedSize(src, 0, legacy) - a))
+        d = (C.c_uint8 * max(1, cap))()
+        r = _check(lib().zlz4f_decompress_file_range(C.addressof(s), n, a, b, C.addressof(d), cap, flags))
+        return bytes(d[:r])
 
     # legacy frames: what `lz4 -l` writes (include/zlz4_amd.h, DESIGN.md section 4.4i)
     LegacyPrefs = LegacyPrefs

@@ -460,6 +460,40 @@ inline Result decompressMultiframe(const std::uint8_t *src, std::size_t n, std::
                                    std::uint32_t decode_flags = 0) {
     return wrap(zlz4f_decompress_multiframe(src, n, dst, cap, decode_flags));
 }
+// file index and file range decoding (include/zlz4_amd.h; no counterpart in the reference): bytes [a, b) of whole .lz4 files.
+// fileIndexBatch is the frame index across the members of a record-mode split (split_totals: a HOST pointer to the split's
+// four totals): one run of (position in the buffer, offset in the file's content) per block in member order; it writes
+// idx_off itself.  The plan is planFrameRanges with nframes = the buffers.  decompressFileRangeBatch is
+// decompressFrameRangeBatch whose items each find their own member: a range may cross frame, skippable and legacy members.
+// decompressFileRange: one file from host memory, exactly [a, b) at dst; it builds the index on every call.
+struct FileSplit {
+    const Member *member; const std::uint64_t *mem_off; const std::int64_t *split_result;
+    const std::uint64_t *item_first, *item_off, *item_len, *leg_len; const std::uint64_t *split_totals;
+};
+inline std::size_t fileIndexBatchWorkspace(std::uint32_t nbuf, const std::uint64_t *split_totals) {
+    return zlz4f_batch_file_index_workspace(nbuf, split_totals);
+}
+inline Result fileIndexBatch(void *stream, const Multiframes &m, const FileSplit &s, IndexEntry *d_index, std::uint64_t *d_idx_off,
+                             std::uint64_t idx_cap, std::int64_t *d_idx_n, void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_file_index(stream, m.src, m.src_off, m.src_len, m.nbuf, s.member, s.mem_off, s.split_result,
+                                       s.item_first, s.item_off, s.item_len, s.leg_len, s.split_totals, d_index, d_idx_off,
+                                       idx_cap, d_idx_n, ws, ws_bytes));
+}
+inline std::size_t decompressFileRangeBatchWorkspace(std::uint32_t nranges, std::uint32_t max_items) {
+    return zlz4f_batch_decompress_file_range_workspace(nranges, max_items);
+}
+// f.dst, f.dst_off, f.dst_cap, f.result are per RANGE here (nranges of them), f.src* and f.nframes per buffer
+inline Result decompressFileRangeBatch(void *stream, const Frames &f, const FrameIndex &x, const FileSplit &s,
+                                       const Range *d_range, std::uint64_t *d_skip, std::uint32_t nranges,
+                                       std::uint32_t max_items, void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_decompress_file_range(stream, f.src, f.src_off, f.src_len, x.index, x.idx_off, x.idx_n, f.nframes,
+                                                  s.member, s.mem_off, s.split_result, d_range, f.dst, f.dst_off, f.dst_cap,
+                                                  d_skip, f.result, nranges, max_items, ws, ws_bytes));
+}
+inline Result decompressFileRange(const std::uint8_t *src, std::size_t n, std::uint64_t a, std::uint64_t b, std::uint8_t *dst,
+                                  std::size_t cap, std::uint32_t split_flags = ZLZ4F_SPLIT_LEGACY) {
+    return wrap(zlz4f_decompress_file_range(src, n, a, b, dst, cap, split_flags));
+}
 // legacy frames (include/zlz4_amd.h; no counterpart in the reference): what `lz4 -l` writes -- the magic 0x184C2102, then
 // { u32 size, block } repeated.  One frame in host memory per call; `consumed` (may be null) receives where the frame ends,
 // which is where the next member of a concatenated file starts.  The batch calls are those of the C header.

@@ -2079,47 +2079,43 @@ int64_t zlz4f_frame_decompressed_size_using_dict(const uint8_t *src, size_t n, s
 // k_bfr_expand check every entry they use against the frame before a position becomes an address.
 namespace {
 
-// one wavefront per frame: k_bfq_total's status over the same entries in the same order, then -- no error -- the nb + 1
-// index entries: 64 blocks per step with a shuffle prefix sum of their sizes (k_frame_plan's scan)
-__global__ __launch_bounds__(256) void k_bfi_index(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
-                                                   const uint64_t *__restrict__ data_off, const uint32_t *__restrict__ data_len,
-                                                   const uint32_t *__restrict__ flags, const int64_t *__restrict__ sizes,
-                                                   const uint32_t *__restrict__ cks_ok, const uint64_t *__restrict__ src_off,
-                                                   const uint64_t *__restrict__ src_len, zlz4f_index_entry *__restrict__ index,
-                                                   const uint64_t *__restrict__ idx_off, const uint64_t *__restrict__ idx_cap,
-                                                   int64_t *__restrict__ result) {
-    const uint32_t f = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
-    if (f >= nframes) return;
-    const BFrame F = fr[f];
+// k_bfq_total's status of frame F (n bytes long) over the same entries in the same order; wave-uniform, 0 = no error
+__device__ inline int64_t bfi_status(const BFrame &F, uint32_t max_blocks, uint32_t lane, const uint32_t *__restrict__ data_len,
+                                     const uint32_t *__restrict__ flags, const int64_t *__restrict__ sizes,
+                                     const uint32_t *__restrict__ cks_ok, uint64_t n) {
+    if (F.status < 0) return F.status;                                                 // :547
+    if (!bf_fits(F, max_blocks)) return ZLZ4_ERR_INVALID_STATE;
     int64_t out = 0;
-    if (F.status < 0) out = F.status;                                                  // :547
-    else if (!bf_fits(F, max_blocks)) out = ZLZ4_ERR_INVALID_STATE;
-    else {
-        const bool bc = (F.flg & 0x10u) != 0;
-        unsigned long long bad = ~0ull;                               // this lane's first failing block
-        int32_t code = 0;
-        for (uint64_t j = lane; j < F.nb && bad == ~0ull; j += 64u) {
-            const uint64_t i = F.base + j;
-            int32_t err = 0;
-            if (bc && cks_ok[i] == 2u) err = ZLZ4F_ERR_FRAME_SIZE_WRONG;               // :591
-            else if (bc && cks_ok[i] == 0u) err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID;    // :596
-            else if (!(flags[i] & kBlkStored) && data_len[i] != 0 && sizes[i] < 0) err = ZLZ4F_ERR_DECOMPRESSION_FAILED;   // :611
-            if (err) { bad = j; code = err; }
-        }
-        unsigned long long first = bad;
-        for (uint32_t d = 32u; d >= 1u; d >>= 1) {
-            const unsigned long long o = __shfl_xor(first, (int)d);
-            first = o < first ? o : first;
-        }
-        if (first != ~0ull) out = (int64_t)(int32_t)zlz4::rdlane((uint32_t)code, zlz4::first_lane(zlz4::ballot(bad == first)));
-        if (!out) out = F.err;
-        if (!out && (F.flg & 0x04u) && F.end + 4 > src_len[f]) out = ZLZ4F_ERR_FRAME_SIZE_WRONG;   // :626
-        if (!out && F.nb + 1u > idx_cap[f]) out = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+    const bool bc = (F.flg & 0x10u) != 0;
+    unsigned long long bad = ~0ull;                                   // this lane's first failing block
+    int32_t code = 0;
+    for (uint64_t j = lane; j < F.nb && bad == ~0ull; j += 64u) {
+        const uint64_t i = F.base + j;
+        int32_t err = 0;
+        if (bc && cks_ok[i] == 2u) err = ZLZ4F_ERR_FRAME_SIZE_WRONG;                   // :591
+        else if (bc && cks_ok[i] == 0u) err = ZLZ4F_ERR_BLOCK_CHECKSUM_INVALID;        // :596
+        else if (!(flags[i] & kBlkStored) && data_len[i] != 0 && sizes[i] < 0) err = ZLZ4F_ERR_DECOMPRESSION_FAILED;   // :611
+        if (err) { bad = j; code = err; }
     }
-    if (out) { if (lane == 0) result[f] = out; return; }
-    zlz4f_index_entry *e = index + idx_off[f];
-    const uint64_t so = src_off[f];
-    uint64_t run = 0, end_pos = (uint64_t)F.status;                   // (no block: the chain ends behind the header)
+    unsigned long long first = bad;
+    for (uint32_t d = 32u; d >= 1u; d >>= 1) {
+        const unsigned long long o = __shfl_xor(first, (int)d);
+        first = o < first ? o : first;
+    }
+    if (first != ~0ull) out = (int64_t)(int32_t)zlz4::rdlane((uint32_t)code, zlz4::first_lane(zlz4::ballot(bad == first)));
+    if (!out) out = F.err;
+    if (!out && (F.flg & 0x04u) && F.end + 4 > n) out = ZLZ4F_ERR_FRAME_SIZE_WRONG;    // :626
+    return out;
+}
+
+// The index entries of frame F's nb blocks, 64 per step with a shuffle prefix sum of their sizes (k_frame_plan's scan):
+// entry j = { the block's header word, counted from the byte `so` of d_src; run + the sizes in front of it }.  e == nullptr
+// writes nothing.  run advances by the frame's decoded size; -> where the chain ended (head for a frame without blocks).
+__device__ inline uint64_t bfi_entries(const BFrame &F, uint32_t lane, const uint64_t *__restrict__ data_off,
+                                       const uint32_t *__restrict__ data_len, const uint32_t *__restrict__ flags,
+                                       const int64_t *__restrict__ sizes, uint64_t so, uint64_t head,
+                                       zlz4f_index_entry *__restrict__ e, uint64_t &run) {
+    uint64_t end_pos = head;                                          // (no block: the chain ends behind the header)
     for (uint64_t b0 = 0; b0 < F.nb; b0 += 64u) {
         const uint64_t j = b0 + lane, i = F.base + j;
         uint64_t sz = 0;
@@ -2130,16 +2126,37 @@ __global__ __launch_bounds__(256) void k_bfi_index(const BFrame *__restrict__ fr
             if (lane >= d) incl += ((uint64_t)hi << 32) | lo;
         }
         if (j < F.nb) {
-            zlz4f_index_entry E;
-            E.pos = data_off[i] - so - 4u;
-            E.dec = run + incl - sz;
-            e[j] = E;
+            if (e) {
+                zlz4f_index_entry E;
+                E.pos = data_off[i] - so - 4u;
+                E.dec = run + incl - sz;
+                e[j] = E;
+            }
             if (j + 1u == F.nb) end_pos = data_off[i] - so + data_len[i] + ((flags[i] & kBlkCks) ? 4u : 0u);
         }
         run += ((uint64_t)zlz4::rdlane((uint32_t)(incl >> 32), 63) << 32) | zlz4::rdlane((uint32_t)incl, 63);
     }
     const uint32_t owner = F.nb ? (uint32_t)((F.nb - 1u) & 63u) : 0u;                  // the lane that saw the last block
-    end_pos = ((uint64_t)zlz4::rdlane((uint32_t)(end_pos >> 32), owner) << 32) | zlz4::rdlane((uint32_t)end_pos, owner);
+    return ((uint64_t)zlz4::rdlane((uint32_t)(end_pos >> 32), owner) << 32) | zlz4::rdlane((uint32_t)end_pos, owner);
+}
+
+// one wavefront per frame: the status, then -- no error -- the nb + 1 index entries
+__global__ __launch_bounds__(256) void k_bfi_index(const BFrame *__restrict__ fr, uint32_t nframes, uint32_t max_blocks,
+                                                   const uint64_t *__restrict__ data_off, const uint32_t *__restrict__ data_len,
+                                                   const uint32_t *__restrict__ flags, const int64_t *__restrict__ sizes,
+                                                   const uint32_t *__restrict__ cks_ok, const uint64_t *__restrict__ src_off,
+                                                   const uint64_t *__restrict__ src_len, zlz4f_index_entry *__restrict__ index,
+                                                   const uint64_t *__restrict__ idx_off, const uint64_t *__restrict__ idx_cap,
+                                                   int64_t *__restrict__ result) {
+    const uint32_t f = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (f >= nframes) return;
+    const BFrame F = fr[f];
+    int64_t out = bfi_status(F, max_blocks, lane, data_len, flags, sizes, cks_ok, src_len[f]);
+    if (!out && F.nb + 1u > idx_cap[f]) out = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+    if (out) { if (lane == 0) result[f] = out; return; }
+    zlz4f_index_entry *e = index + idx_off[f];
+    uint64_t run = 0;
+    const uint64_t end_pos = bfi_entries(F, lane, data_off, data_len, flags, sizes, src_off[f], (uint64_t)F.status, e, run);
     if (lane == 0) {
         zlz4f_index_entry E;
         E.pos = end_pos;
@@ -2590,6 +2607,559 @@ int64_t zlz4f_decompress_frame_range(const uint8_t *src, size_t n, uint64_t a, u
     if (hipMemcpyAsync(&skip, &r->skip, 8, hipMemcpyDeviceToHost, st) != hipSuccess || !read_result(dc, &r->rres, result))
         return ZLZ4_ERR_DEVICE;
     if (result > 0 && ((uint64_t)result > cap || skip + (uint64_t)result > totals[0] ||
+                       hipMemcpy(dst, d_dst.as<uint8_t>() + skip, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess))
+        return ZLZ4_ERR_DEVICE;
+    return result;
+}
+
+}  // extern "C"
+
+// ====================================================================== file index and range decoding
+// A FILE is a multiframe buffer as the record-mode split delimits it: frame, skippable and legacy members.  The file index
+// is the frame index across members -- one run of (position in the buffer, offset in the file's content) per block, in
+// member order -- and the file range decode is the frame range decode whose items each look up their own member: a
+// range may cross members, so block checksums, stored blocks and the block size bound change from item to item.
+namespace {
+
+// what the index keeps per item for a legacy member (an item of another kind has nb 0 and is never read)
+struct FfLeg {
+    uint64_t nb;        // blocks of the chain
+    uint64_t base;      // first entry of the legacy block table (exclusive scan of nb)
+    int64_t status;     // legacy_walk's verdict
+    uint64_t pad;
+};
+
+// one lane per item, k_lf_walk's two passes over (item_off, leg_len): count, then record the blocks at the item's base
+template <bool kRecord>
+__global__ __launch_bounds__(64) void k_ff_leg_walk(const uint8_t *__restrict__ src, const uint64_t *__restrict__ item_off,
+                                                    const uint64_t *__restrict__ leg_len, uint32_t nitems, uint32_t leg_blocks,
+                                                    FfLeg *__restrict__ lg, uint64_t *__restrict__ data_off,
+                                                    uint32_t *__restrict__ data_len) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nitems) return;
+    const uint64_t so = item_off[i], n = leg_len[i];
+    uint64_t nb = 0, end = 0;
+    if (kRecord) {
+        const FfLeg G = lg[i];
+        if (G.nb != 0 && G.base + G.nb <= leg_blocks)
+            (void)legacy_walk(src + so, n, G.nb, nb, end, [&](uint64_t k, uint64_t off, uint32_t size) {
+                data_off[G.base + k] = so + off;                      // (the record pass never leaves the item's range)
+                data_len[G.base + k] = size;
+            });
+    } else {
+        FfLeg G = {};
+        if (n != 0) {                                                 // (length 0: the item of a member that is not legacy)
+            G.status = legacy_walk(src + so, n, ~0ull, nb, end, [](uint64_t, uint64_t, uint32_t) {});
+            G.nb = nb;
+        }
+        lg[i] = G;
+    }
+}
+
+// k_bf_scan over the legacy records
+__global__ __launch_bounds__(1024) void k_ff_leg_scan(FfLeg *__restrict__ lg, uint32_t nitems) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (nitems + 1023u) / 1024u;
+    const uint64_t b0 = (uint64_t)t * chunk;
+    const uint32_t lo = b0 < nitems ? (uint32_t)b0 : nitems;
+    const uint32_t hi = b0 + chunk < nitems ? (uint32_t)(b0 + chunk) : nitems;
+    uint64_t s = 0, total;
+    for (uint32_t i = lo; i < hi; i++) s += lg[i].nb;
+    uint64_t run = bfr_wg_scan(s, part, total);
+    for (uint32_t i = lo; i < hi; i++) { lg[i].base = run; run += lg[i].nb; }
+}
+
+// one wavefront per buffer: its room in the index = the blocks of its items' chains, as the walks counted them, plus one
+__global__ __launch_bounds__(256) void k_ff_room(const BFrame *__restrict__ fr, const FfLeg *__restrict__ lg,
+                                                 const uint64_t *__restrict__ item_first, uint32_t nbuf,
+                                                 uint64_t *__restrict__ room) {
+    const uint32_t s = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (s >= nbuf) return;
+    const uint64_t i0 = item_first[s], i1 = item_first[s + 1];
+    unsigned long long sum = 0;
+    for (uint64_t i = i0 + lane; i < i1; i += 64u) sum += fr[i].nb + (lg ? lg[i].nb : 0u);
+    for (uint32_t d = 32u; d >= 1u; d >>= 1) sum += __shfl_xor(sum, (int)d);
+    if (lane == 0) room[s] = sum + 1u;
+}
+
+// one workgroup: out[0..n] = the exclusive scan of in[0..n), out[n] = the total
+__global__ __launch_bounds__(1024) void k_ff_scan(const uint64_t *__restrict__ in, uint32_t n, uint64_t *__restrict__ out) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (n + 1023u) / 1024u;
+    const uint64_t b0 = (uint64_t)t * chunk;
+    const uint32_t lo = b0 < n ? (uint32_t)b0 : n;
+    const uint32_t hi = b0 + chunk < n ? (uint32_t)(b0 + chunk) : n;
+    uint64_t s = 0, total;
+    for (uint32_t i = lo; i < hi; i++) s += in[i];
+    uint64_t run = bfr_wg_scan(s, part, total);
+    for (uint32_t i = lo; i < hi; i++) { out[i] = run; run += in[i]; }
+    if (t == 0) out[n] = total;
+}
+
+// the tables the fold reads: the frame size query's over the items, and the legacy walk's
+struct FfTables {
+    const BFrame *fr;
+    const uint64_t *data_off;
+    const uint32_t *data_len, *flags, *cks_ok;
+    const int64_t *sizes;
+    const FfLeg *lg;                  // null: the split found no legacy member
+    const uint64_t *leg_off;
+    const int64_t *leg_sizes;
+    uint32_t max_blocks, leg_blocks;
+};
+
+// The fold, one wavefront per buffer: k_mf_finish's verdict over the members in member order -- the first member that is
+// not OK decides -- while the decoded base `run`, the block count `kb` and the position base (the buffer's offset in d_src)
+// carry from member to member and every block's entry is written rebased: pos counts from the buffer's first byte, dec
+// from the file's first content byte.  Members and blocks are taken 64 at a step (blocks) or one at a time (members), so
+// neither count is bounded by the wavefront.  A buffer whose room does not fit idx_cap writes nothing.
+__global__ __launch_bounds__(256) void k_ff_fold(FfTables T, const zlz4f_member *__restrict__ member,
+                                                 const uint64_t *__restrict__ mem_off, const int64_t *__restrict__ split_result,
+                                                 const uint64_t *__restrict__ item_first, const uint64_t *__restrict__ item_len,
+                                                 const uint64_t *__restrict__ src_off, uint32_t nbuf,
+                                                 zlz4f_index_entry *__restrict__ index, const uint64_t *__restrict__ idx_off,
+                                                 uint64_t idx_cap, int64_t *__restrict__ result) {
+    const uint32_t s = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (s >= nbuf) return;
+    const int64_t sr = split_result[s];
+    if (sr < 0) { if (lane == 0) result[s] = sr; return; }
+    const uint64_t i0 = item_first[s], cnt = item_first[s + 1] - i0, so = src_off[s];
+    const uint64_t room = idx_off[s + 1] - idx_off[s];
+    const bool fits = idx_off[s + 1] <= idx_cap;
+    zlz4f_index_entry *e = fits ? index + idx_off[s] : nullptr;
+    const zlz4f_member *m = member + mem_off[s];
+    int64_t out = 0;
+    uint64_t kb = 0, run = 0, end_pos = 0;
+    for (uint64_t k = 0; k < cnt && !out; k++) {                      // (wave-uniform)
+        const zlz4f_member M = m[k];
+        const uint32_t kind = M.kind & 0xFFu;
+        const uint64_t i = i0 + k;
+        if (kind == ZLZ4F_MEMBER_FRAME) {
+            const BFrame F = T.fr[i];
+            out = bfi_status(F, T.max_blocks, lane, T.data_len, T.flags, T.sizes, T.cks_ok, item_len[i]);
+            if (!out && kb + F.nb + 1u > room) out = ZLZ4_ERR_INVALID_STATE;           // (tables that are not this split's)
+            if (out) break;
+            end_pos = bfi_entries(F, lane, T.data_off, T.data_len, T.flags, T.sizes, so, M.pos + (uint64_t)F.status,
+                                  e ? e + kb : nullptr, run);
+            kb += F.nb;
+        } else if (kind == ZLZ4F_MEMBER_LEGACY) {
+            if (!T.lg) { out = ZLZ4_ERR_INVALID_STATE; break; }
+            const FfLeg G = T.lg[i];
+            if ((G.nb != 0 && G.base + G.nb > T.leg_blocks) || kb + G.nb + 1u > room) { out = ZLZ4_ERR_INVALID_STATE; break; }
+            for (uint64_t b0 = 0; b0 < G.nb; b0 += 64u) {              // (wave-uniform trip count)
+                const uint64_t j = b0 + lane, ii = G.base + j;
+                const int64_t sz = j < G.nb ? T.leg_sizes[ii] : 0;
+                if (zlz4::ballot(sz < 0 || sz > (int64_t)ZLZ4F_LEGACY_BLOCK_SIZE) != 0) {
+                    out = ZLZ4F_ERR_DECOMPRESSION_FAILED;              // (a bad block stands in front of what ended the walk)
+                    break;
+                }
+                const uint32_t incl = zlz4::wave_incl_scan((uint32_t)sz);              // (64 blocks stay below 2^32)
+                if (e && j < G.nb) {
+                    zlz4f_index_entry E;
+                    E.pos = T.leg_off[ii] - so - 4u;
+                    E.dec = run + (incl - (uint32_t)sz);
+                    e[kb + j] = E;
+                }
+                run += zlz4::rdlane(incl, 63);
+            }
+            if (!out) out = G.status;
+            if (out) break;
+            kb += G.nb;
+            end_pos = M.pos + M.len;
+        } else if (kind == ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED) {
+            out = M.len < 8 ? ZLZ4F_ERR_FRAME_HEADER_INCOMPLETE : ZLZ4F_ERR_FRAME_SIZE_WRONG;
+        }
+    }
+    if (!out && !fits) out = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+    if (lane == 0) {
+        if (!out) {
+            zlz4f_index_entry E;
+            E.pos = end_pos;
+            E.dec = run;
+            e[kb] = E;
+        }
+        result[s] = out ? out : (int64_t)kb;
+    }
+}
+
+// ------------------------------------------------------------------ file ranges
+// what an item takes from its member
+struct FfMem {
+    uint64_t end;       // the member's end inside the buffer
+    uint32_t bound;     // the most a block decodes to
+    bool bc, legacy;    // block checksums (FLG 0x10); a legacy member: size words, no stored bit
+};
+
+// The member of buffer (s, n bytes; cnt members at m) that holds position pos, by bisection for the last member that
+// starts at or in front of pos.  false: pos is no place for a block word -- no such member, a member that is neither a
+// frame nor a legacy frame, that leaves the buffer or whose header is none, a position inside the header, or fewer than 4
+// bytes up to the member's end.  Reads the member table and the member's header, nothing else.
+__device__ inline bool ff_member_of(const zlz4f_member *__restrict__ m, uint64_t cnt, const uint8_t *__restrict__ s, uint64_t n,
+                                    uint64_t pos, FfMem &out) {
+    uint64_t lo = 0, hi = cnt;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2u;
+        if (m[mid].pos <= pos) lo = mid + 1u; else hi = mid;
+    }
+    if (lo == 0) return false;
+    const zlz4f_member M = m[lo - 1u];
+    if (M.len > n || M.pos > n - M.len) return false;
+    const uint32_t kind = M.kind & 0xFFu;
+    uint64_t first;
+    if (kind == ZLZ4F_MEMBER_FRAME) {
+        const ParsedHeader ph = frame_header(s + M.pos, M.len);
+        if (ph.size < 0) return false;
+        first = M.pos + (uint64_t)ph.size;
+        out.bound = (uint32_t)ph.block_size;
+        out.bc = (ph.flg & 0x10u) != 0;
+        out.legacy = false;
+    } else if (kind == ZLZ4F_MEMBER_LEGACY) {
+        if (M.len < 4 || zx_rd32(s + M.pos) != ZLZ4F_LEGACY_MAGICNUMBER) return false;
+        first = M.pos + 4u;
+        out.bound = ZLZ4F_LEGACY_BLOCK_SIZE;
+        out.bc = false;
+        out.legacy = true;
+    } else return false;
+    out.end = M.pos + M.len;
+    return pos >= first && pos <= out.end && out.end - pos >= 4u;
+}
+
+// k_bfr_range for files: the same statuses in the same order, with the chain check of every pair (k, k + 1) made against
+// the member that holds pos[k].  Nothing but the tables is read for a range with a' == b'.
+__global__ __launch_bounds__(256) void k_ffr_range(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                                   const uint64_t *__restrict__ src_len,
+                                                   const zlz4f_index_entry *__restrict__ index,
+                                                   const uint64_t *__restrict__ idx_off, const int64_t *__restrict__ idx_n,
+                                                   uint32_t nbuf, const zlz4f_member *__restrict__ member,
+                                                   const uint64_t *__restrict__ mem_off, const int64_t *__restrict__ split_result,
+                                                   const zlz4f_range *__restrict__ range, const uint64_t *__restrict__ dst_cap,
+                                                   uint32_t nranges, BRange *__restrict__ rg) {
+    const uint32_t r = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
+    if (r >= nranges) return;
+    const zlz4f_range R = range[r];
+    BRange G = {};
+    int64_t st = 0;
+    if (R.frame >= nbuf || R.a > R.b || R.reserved != 0) st = ZLZ4_ERR_INVALID_STATE;
+    else if (idx_n[R.frame] < 0) st = idx_n[R.frame];
+    else {
+        BfrSpan sp;
+        const zlz4f_index_entry *e = nullptr;
+        uint64_t nb = 0;
+        const bool found = bfr_span(R, index, idx_off, idx_n, nbuf, sp, e, nb);
+        G.a = sp.a; G.b = sp.b; G.d0 = sp.a;
+        if (sp.a != sp.b) {
+            const int64_t cnt = split_result[R.frame];
+            bool bad = !found || cnt <= 0;                            // (no member table: not this file's index)
+            if (!bad) {
+                const uint64_t n = src_len[R.frame];
+                const uint8_t *s = src + src_off[R.frame];
+                const zlz4f_member *m = member + mem_off[R.frame];
+                for (uint64_t k = sp.k0 + lane; k <= sp.k1; k += 64u) {
+                    const zlz4f_index_entry E = e[k], N = e[k + 1u];
+                    FfMem fm;
+                    if (!ff_member_of(m, (uint64_t)cnt, s, n, E.pos, fm) || N.pos <= E.pos || N.dec < E.dec ||
+                        N.dec - E.dec > fm.bound)
+                        bad = true;
+                }
+                if (e[sp.k1].dec >= sp.b || e[sp.k1 + 1u].dec < sp.b) bad = true;
+            }
+            if (zlz4::ballot(bad) != 0) st = ZLZ4_ERR_INVALID_STATE;
+            else if (dst_cap[r] < sp.b - e[sp.k0].dec) st = ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+            else { G.n = sp.k1 - sp.k0 + 1u; G.k0 = sp.k0; G.d0 = e[sp.k0].dec; }
+        }
+    }
+    G.status = st;
+    if (lane == 0) rg[r] = G;
+}
+
+// k_bfr_expand for files, one lane per item: the item's member again (k_ffr_range has accepted it), the block word as that
+// member reads it -- a frame's header word, or a legacy size word that is neither 0 nor above the bound -- and where the
+// block has to end: at pos[k + 1] when that lies in the same member, else on the frame member's end mark or, for a chain
+// without one and for a legacy member, at the member's end.  The block's bytes are used only when all of that holds.
+__global__ void k_ffr_expand(const BRange *__restrict__ rg, uint32_t nranges, uint32_t max_items,
+                             const zlz4f_range *__restrict__ range, const uint8_t *__restrict__ src,
+                             const uint64_t *__restrict__ src_off, const uint64_t *__restrict__ src_len,
+                             const zlz4f_index_entry *__restrict__ index, const uint64_t *__restrict__ idx_off,
+                             const zlz4f_member *__restrict__ member, const uint64_t *__restrict__ mem_off,
+                             const int64_t *__restrict__ split_result, const uint64_t *__restrict__ dst_off, BfrTables T) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_items; i += gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = nranges;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            if (rg[mid].base <= i) lo = mid + 1u; else hi = mid;
+        }
+        uint64_t d_off = 0, c_off = 0, o_off = 0;
+        uint32_t d_len = 0, fl = 0, f_len = 0, f_cap = 0, p_len = 0, p_cap = 0, c_len = 0, ierr = 0;
+        if (lo > 0) {
+            const uint32_t r = lo - 1u;
+            const BRange G = rg[r];
+            const uint64_t j = i - G.base;
+            if (j < G.n && G.status == 0 && bfr_fits(G, max_items)) {
+                const uint32_t f = range[r].frame;
+                const zlz4f_index_entry *e = index + idx_off[f];
+                const uint64_t k = G.k0 + j;
+                const zlz4f_index_entry E = e[k], N = e[k + 1u];
+                const uint64_t so = src_off[f];
+                const uint8_t *s = src + so;
+                const int64_t cnt = split_result[f];
+                FfMem fm;
+                bool ok = cnt > 0 && ff_member_of(member + mem_off[f], (uint64_t)cnt, s, src_len[f], E.pos, fm);
+                uint32_t sz = 0;
+                bool stored = false;
+                if (ok) {
+                    const uint32_t word = zx_rd32(s + E.pos);
+                    if (fm.legacy) { sz = word; ok = word != 0 && word <= ZLZ4F_LEGACY_BLOCK_BOUND; }
+                    else { const BlockWord w = block_word(word); sz = w.size; stored = w.stored; ok = !w.end_mark; }
+                }
+                if (ok) {
+                    const uint64_t q = E.pos + 4u + sz + (fm.bc ? 4u : 0u);             // where the block ends
+                    if (q > fm.end) ok = false;
+                    else if (N.pos <= fm.end) ok = q == N.pos;                           // k + 1 in the same member
+                    else if (fm.legacy) ok = q == fm.end;
+                    else ok = q == fm.end || (fm.end - q >= 4u && zx_rd32(s + q) == 0u);
+                }
+                if (!ok) ierr = kItemChain;
+                else {
+                    const uint32_t step = (uint32_t)(N.dec - E.dec);             // <= the member's bound (k_ffr_range)
+                    const uint64_t left = G.b - E.dec;                           // > 0: dec[k] <= dec[k1] < b'
+                    const uint32_t want = left < step ? (uint32_t)left : step;
+                    d_off = so + E.pos + 4u;
+                    d_len = sz;
+                    o_off = dst_off[r] + (E.dec - G.d0);
+                    if (fm.bc) { fl |= kBlkCks; c_off = d_off + sz; }
+                    if (stored) {
+                        fl |= kBlkStored;
+                        if (sz != step) ierr = kItemStored; else c_len = want;
+                    } else if (want == step) { f_len = sz; f_cap = step; }
+                    else { p_len = sz; p_cap = want; }
+                }
+            }
+        }
+        T.data_off[i] = d_off; T.cks_off[i] = c_off; T.out_off[i] = o_off;
+        T.data_len[i] = d_len; T.flags[i] = fl; T.f_len[i] = f_len; T.f_cap[i] = f_cap; T.p_len[i] = p_len;
+        T.p_cap[i] = p_cap; T.c_len[i] = c_len; T.ierr[i] = ierr;
+    }
+}
+
+// the file index's workspace: the frame size query's over the items, then the legacy walk's records and block table and
+// the rooms
+struct FfLayout {
+    BfdLayout q;
+    Region<FfLeg> leg;
+    Region<uint64_t> leg_off, room;
+    Region<uint32_t> leg_len;
+    Region<int64_t> leg_sizes;
+    size_t bytes = 0;
+};
+
+FfLayout ff_layout(uint32_t nbuf, uint32_t nitems, uint32_t max_blocks, uint32_t leg_blocks, void *ws = nullptr) {
+    FfLayout L;
+    L.q = bfd_layout(nitems, max_blocks, 0, false, kQuery, ws);
+    Carver c{static_cast<uint8_t *>(ws), L.q.bytes};
+    c.take(nitems, L.leg);
+    c.take(leg_blocks, L.leg_off, L.leg_len, L.leg_sizes);
+    c.take(nbuf, L.room);
+    L.bytes = c.bytes;
+    return L;
+}
+
+// the split's four totals as the 32-bit counts the kernels take; false: a null pointer or a count that is none
+bool ff_totals(const uint64_t *t, uint32_t &nitems, uint32_t &max_blocks, uint32_t &leg_blocks) {
+    if (!t || t[0] > 0xFFFFFFFFull || t[1] > 0xFFFFFFFFull || t[3] > 0xFFFFFFFFull) return false;
+    nitems = (uint32_t)t[0]; max_blocks = (uint32_t)t[1]; leg_blocks = (uint32_t)t[3];
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t zlz4f_batch_file_index_workspace(uint32_t nbuf, const uint64_t *split_totals) {
+    uint32_t nitems, mb, lb;
+    return ff_totals(split_totals, nitems, mb, lb) ? ff_layout(nbuf, nitems, mb, lb).bytes : 0;
+}
+
+// The frame size query's launch sequence over the items up to its fold, the legacy walk and size kernel over the same
+// items where the split found legacy members, the rooms and their scan, the fold.  The sequence depends on the totals alone.
+int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                               uint32_t nbuf, const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                               const int64_t *d_split_result, const uint64_t *d_item_first, const uint64_t *d_item_off,
+                               const uint64_t *d_item_len, const uint64_t *d_leg_len, const uint64_t *split_totals,
+                               zlz4f_index_entry *d_index, uint64_t *d_idx_off, uint64_t idx_cap, int64_t *d_result,
+                               void *d_workspace, size_t workspace_bytes) {
+    if (nbuf == 0) return 0;
+    uint32_t nitems, mb, lb;
+    if (!ff_totals(split_totals, nitems, mb, lb)) return ZLZ4_ERR_INVALID_STATE;
+    const bool legacy = split_totals[2] != 0;
+    if (!d_src || !d_src_off || !d_src_len || !d_mem_off || !d_split_result || !d_item_first || !d_index || !d_idx_off ||
+        !d_result || (nitems && (!d_member || !d_item_off || !d_item_len)) || (legacy && !d_leg_len))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) || bf_misaligned(d_member, 8) || bf_misaligned(d_mem_off, 8) ||
+        bf_misaligned(d_split_result, 8) || bf_misaligned(d_item_first, 8) || bf_misaligned(d_item_off, 8) ||
+        bf_misaligned(d_item_len, 8) || bf_misaligned(d_leg_len, 8) || bf_misaligned(d_index, 8) || bf_misaligned(d_idx_off, 8) ||
+        bf_misaligned(d_result, 8))
+        return ZLZ4_ERR_INVALID_STATE;
+    const FfLayout L = ff_layout(nbuf, nitems, mb, lb, d_workspace);
+    if (!d_workspace || workspace_bytes < L.bytes || bf_misaligned(d_workspace, 16)) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    const BfArrays a = {d_src, d_item_off, d_item_len, nullptr, nullptr, nullptr, nullptr, nitems, mb};
+    if (bfd_prelude(st, a, false, nullptr, L.q) != 0) return ZLZ4_ERR_DEVICE;
+    if (mb) {
+        hipLaunchKernelGGL(k_bfq_len, dim3(bf_grid(mb, 256, 4096)), dim3(256), 0, st, L.q.data_len, L.q.flags, mb, L.q.dec_len);
+        if (zlz4_launch_decompressed_size(st, d_src, L.q.data_off, L.q.dec_len, nullptr, L.q.sizes, mb) != 0)
+            return ZLZ4_ERR_DEVICE;
+    }
+    if (legacy) {
+        const uint32_t gi = bf_grid(nitems, 64);
+        hipLaunchKernelGGL(k_ff_leg_walk<false>, dim3(gi), dim3(64), 0, st, d_src, d_item_off, d_leg_len, nitems, lb, L.leg.p,
+                           (uint64_t *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(k_ff_leg_scan, dim3(1), dim3(1024), 0, st, L.leg.p, nitems);
+        if (lb) {
+            if (hipMemsetAsync(L.leg_len.p, 0, (size_t)lb * 4u, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+            hipLaunchKernelGGL(k_ff_leg_walk<true>, dim3(gi), dim3(64), 0, st, d_src, d_item_off, d_leg_len, nitems, lb, L.leg.p,
+                               L.leg_off.p, L.leg_len.p);
+            if (zlz4_launch_decompressed_size(st, d_src, L.leg_off, L.leg_len, nullptr, L.leg_sizes, lb) != 0)
+                return ZLZ4_ERR_DEVICE;
+        }
+    }
+    const FfLeg *lg = legacy ? L.leg.p : nullptr;
+    const uint32_t gs = bf_grid(nbuf, 4);
+    hipLaunchKernelGGL(k_ff_room, dim3(gs), dim3(256), 0, st, L.q.frames.p, lg, d_item_first, nbuf, L.room.p);
+    hipLaunchKernelGGL(k_ff_scan, dim3(1), dim3(1024), 0, st, L.room.p, nbuf, d_idx_off);
+    const FfTables T = {L.q.frames, L.q.data_off, L.q.data_len, L.q.flags, L.q.cks_ok, L.q.sizes, lg, L.leg_off, L.leg_sizes, mb, lb};
+    hipLaunchKernelGGL(k_ff_fold, dim3(gs), dim3(256), 0, st, T, d_member, d_mem_off, d_split_result, d_item_first, d_item_len,
+                       d_src_off, nbuf, d_index, d_idx_off, idx_cap, d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+size_t zlz4f_batch_decompress_file_range_workspace(uint32_t nranges, uint32_t max_items) {
+    return bfr_layout(nranges, max_items).bytes;
+}
+
+// zlz4f_batch_decompress_frame_range's launch sequence with k_ffr_range and k_ffr_expand in the places of k_bfr_range and
+// k_bfr_expand; scan, checksums, decoders, copy and finish are that call's
+int32_t zlz4f_batch_decompress_file_range(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                          const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
+                                          const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nbuf,
+                                          const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                                          const int64_t *d_split_result, const zlz4f_range *d_range, uint8_t *d_dst,
+                                          const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_skip,
+                                          int64_t *d_result, uint32_t nranges, uint32_t max_items, void *d_workspace,
+                                          size_t workspace_bytes) {
+    if (nranges == 0) return 0;
+    const BfrLayout L = bfr_layout(nranges, max_items, d_workspace);
+    if (!d_range || !d_dst_off || !d_dst_cap || !d_skip || !d_result || (max_items && !d_dst) ||
+        (nbuf && (!d_src || !d_src_off || !d_src_len || !d_index || !d_idx_off || !d_idx_n || !d_member || !d_mem_off ||
+                  !d_split_result)))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) || bf_misaligned(d_index, 8) || bf_misaligned(d_idx_off, 8) ||
+        bf_misaligned(d_idx_n, 8) || bf_misaligned(d_member, 8) || bf_misaligned(d_mem_off, 8) ||
+        bf_misaligned(d_split_result, 8) || bf_misaligned(d_range, 8) || bf_misaligned(d_dst_off, 8) ||
+        bf_misaligned(d_dst_cap, 8) || bf_misaligned(d_skip, 8) || bf_misaligned(d_result, 8))
+        return ZLZ4_ERR_INVALID_STATE;
+    if (!d_workspace || workspace_bytes < L.bytes || bf_misaligned(d_workspace, 16)) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t m = max_items, gr = bf_grid(nranges, 4);
+    const BfrTables T = {L.data_off, L.cks_off, L.out_off, L.data_len, L.flags, L.f_len, L.f_cap, L.p_len, L.p_cap, L.c_len, L.ierr};
+    hipLaunchKernelGGL(k_ffr_range, dim3(gr), dim3(256), 0, st, d_src, d_src_off, d_src_len, d_index, d_idx_off, d_idx_n, nbuf,
+                       d_member, d_mem_off, d_split_result, d_range, d_dst_cap, nranges, L.ranges);
+    hipLaunchKernelGGL(k_bfr_scan, dim3(1), dim3(1024), 0, st, L.ranges, nranges);
+    if (m) {
+        hipLaunchKernelGGL(k_ffr_expand, dim3(bf_grid(m, 256, 4096)), dim3(256), 0, st, L.ranges, nranges, m, d_range, d_src,
+                           d_src_off, d_src_len, d_index, d_idx_off, d_member, d_mem_off, d_split_result, d_dst_off, T);
+        hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(m, 64)), dim3(64), 0, st, d_src, L.data_off, L.data_len, L.flags,
+                           L.cks_off, m, L.cks_ok);
+        if (zlz4_launch_decompress_safe(st, d_src, L.data_off, L.f_len, d_dst, L.out_off, L.f_cap, L.sizes_f, m) != 0 ||
+            zlz4_launch_decompress_safe_prefix(st, d_src, L.data_off, L.p_len, d_dst, L.out_off, L.p_cap, L.sizes_p, m) != 0)
+            return ZLZ4_ERR_DEVICE;
+        hipLaunchKernelGGL(k_bfr_copy, dim3(m), dim3(256), 0, st, d_src, L.data_off, L.c_len, L.out_off, d_dst);
+    }
+    hipLaunchKernelGGL(k_bfr_finish, dim3(gr), dim3(256), 0, st, L.ranges, nranges, m, T, L.cks_ok, L.sizes_f, L.sizes_p, d_skip,
+                       d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+// One file from host memory: split (count, record), index, plan and range as a batch of one.  The index is built on every call.
+int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
+                                    uint32_t split_flags) {
+    if (split_flags & ~ZLZ4F_SPLIT_LEGACY) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if ((!src && n) || (!dst && cap) || a > b) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipStream_t st = nullptr;
+    DeviceCall dc(st);
+    struct Rec {
+        uint64_t src_off, src_len, count, totals[4], mem_off, mem_cap, item_first[2], idx_off[2], dst_off, dst_cap, skip,
+            plan_totals[2];
+        int64_t split_result, idx_n, rres;
+        zlz4f_range range;
+    };
+    DevBuf d_src(n, &dc);
+    Staged<Rec> rec(&dc, 256);
+    if (!d_src.p || !rec.d) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    rec.h.src_len = n;
+    rec.h.range.a = a; rec.h.range.b = b;
+    dc.launched();
+    if (!upload(d_src, src, n, st) || !rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    Rec *r = rec.d;
+    const uint8_t *s = d_src.as<uint8_t>();
+    int32_t rc = zlz4f_batch_multiframe_split_ex(st, s, &r->src_off, &r->src_len, 1, &r->count, r->totals, nullptr, nullptr,
+                                                 nullptr, nullptr, nullptr, nullptr, nullptr, split_flags, nullptr);
+    if (rc != 0) return rc;
+    uint64_t totals[4] = {0, 0, 0, 0};
+    if (hipMemcpyAsync(totals, r->totals, 32, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync()) return ZLZ4_ERR_DEVICE;
+    if (totals[0] == 0) return 0;                                      // the empty file: S == 0
+    if (totals[0] > 0xFFFFFFFFull || totals[1] > 0xFFFFFFFFull || totals[3] > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
+    const size_t nitems = (size_t)totals[0];
+    const uint64_t idx_cap = totals[1] + totals[3] + 1u;
+    const size_t iws = zlz4f_batch_file_index_workspace(1, totals);
+    DevBuf d_mem(nitems * sizeof(zlz4f_member), &dc), d_items(nitems * 24u, &dc), d_iws(iws, &dc),
+        d_index((size_t)idx_cap * sizeof(zlz4f_index_entry), &dc);
+    if (!d_mem.p || !d_items.p || !d_iws.p || !d_index.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    rec.h.mem_cap = nitems;
+    dc.launched();
+    if (hipMemcpyAsync(&r->mem_cap, &rec.h.mem_cap, 8, hipMemcpyHostToDevice, st) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    zlz4f_member *mem = d_mem.as<zlz4f_member>();
+    uint64_t *item_off = d_items.as<uint64_t>(), *item_len = item_off + nitems, *leg_len = item_len + nitems;
+    zlz4f_index_entry *index = d_index.as<zlz4f_index_entry>();
+    rc = zlz4f_batch_multiframe_split_ex(st, s, &r->src_off, &r->src_len, 1, &r->count, r->totals, mem, &r->mem_off, &r->mem_cap,
+                                         r->item_first, item_off, item_len, &r->split_result, split_flags, leg_len);
+    if (rc != 0) return rc;
+    rc = zlz4f_batch_file_index(st, s, &r->src_off, &r->src_len, 1, mem, &r->mem_off, &r->split_result, r->item_first, item_off,
+                                item_len, leg_len, totals, index, r->idx_off, idx_cap, &r->idx_n, d_iws.p, iws);
+    if (rc != 0) return rc;
+    rc = zlz4f_batch_plan_frame_ranges(st, index, r->idx_off, &r->idx_n, 1, &r->range, 1, 0, &r->dst_off, &r->dst_cap,
+                                       r->plan_totals);
+    if (rc != 0) return rc;
+    int64_t idx_n = 0;
+    uint64_t plan[2] = {0, 0};
+    if (hipMemcpyAsync(&idx_n, &r->idx_n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(plan, r->plan_totals, 16, hipMemcpyDeviceToHost, st) != hipSuccess || !dc.sync())
+        return ZLZ4_ERR_DEVICE;
+    if (idx_n < 0) return idx_n;
+    if ((uint64_t)idx_n >= idx_cap) return ZLZ4_ERR_DEVICE;          // (the fold's count is the walks', as the totals are)
+    zlz4f_index_entry last = {0, 0};
+    if (hipMemcpy(&last, index + idx_n, sizeof last, hipMemcpyDeviceToHost) != hipSuccess) return ZLZ4_ERR_DEVICE;
+    const uint64_t S = last.dec, a1 = a < S ? a : S, b1 = b < S ? b : S;
+    if (cap < b1 - a1) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+    if (plan[1] > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
+    const uint32_t max_items = (uint32_t)plan[1];
+    const size_t rws = zlz4f_batch_decompress_file_range_workspace(1, max_items);
+    DevBuf d_rws(rws, &dc), d_dst((size_t)plan[0], &dc);
+    if (!d_rws.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    dc.launched();
+    rc = zlz4f_batch_decompress_file_range(st, s, &r->src_off, &r->src_len, index, r->idx_off, &r->idx_n, 1, mem, &r->mem_off,
+                                           &r->split_result, &r->range, d_dst.as<uint8_t>(), &r->dst_off, &r->dst_cap, &r->skip,
+                                           &r->rres, 1, max_items, d_rws.p, rws);
+    if (rc != 0) return rc;
+    int64_t result = 0;
+    uint64_t skip = 0;
+    if (hipMemcpyAsync(&skip, &r->skip, 8, hipMemcpyDeviceToHost, st) != hipSuccess || !read_result(dc, &r->rres, result))
+        return ZLZ4_ERR_DEVICE;
+    if (result > 0 && ((uint64_t)result > cap || skip + (uint64_t)result > plan[0] ||
                        hipMemcpy(dst, d_dst.as<uint8_t>() + skip, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess))
         return ZLZ4_ERR_DEVICE;
     return result;

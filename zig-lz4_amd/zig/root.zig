@@ -119,6 +119,11 @@ extern "c" fn zlz4f_batch_multiframe_split_ex(stream: ?*anyopaque, d_src: ?[*]co
 extern "c" fn zlz4f_batch_multiframe_select(stream: ?*anyopaque, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_item_first: ?[*]const u64, d_from_frame: ?[*]const i64, d_from_legacy: ?[*]const i64, nbuf: u32, d_out: ?[*]i64) i32;
 extern "c" fn zlz4f_multiframe_decompressed_size_ex(src: [*]const u8, src_len: usize, decode_flags: u32, split_flags: u32) i64;
 extern "c" fn zlz4f_decompress_multiframe_ex(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, decode_flags: u32, split_flags: u32) i64;
+extern "c" fn zlz4f_batch_file_index_workspace(nbuf: u32, split_totals: ?[*]const u64) usize;
+extern "c" fn zlz4f_batch_file_index(stream: ?*anyopaque, d_src: ?[*]const u8, d_src_off: ?[*]const u64, d_src_len: ?[*]const u64, nbuf: u32, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_item_first: ?[*]const u64, d_item_off: ?[*]const u64, d_item_len: ?[*]const u64, d_leg_len: ?[*]const u64, split_totals: ?[*]const u64, d_index: ?[*]IndexEntry, d_idx_off: ?[*]u64, idx_cap: u64, d_result: ?[*]i64, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_decompress_file_range_workspace(nranges: u32, max_items: u32) usize;
+extern "c" fn zlz4f_batch_decompress_file_range(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_index: [*]const IndexEntry, d_idx_off: [*]const u64, d_idx_n: [*]const i64, nbuf: u32, d_member: [*]const Member, d_mem_off: [*]const u64, d_split_result: [*]const i64, d_range: [*]const Range, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_skip: [*]u64, d_result: [*]i64, nranges: u32, max_items: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_decompress_file_range(src: [*]const u8, src_len: usize, a: u64, b: u64, dst: [*]u8, dst_cap: usize, split_flags: u32) i64;
 /// zlz4f_legacy_prefs of include/zlz4_amd.h: block_size 0 = 8 MiB, 1 .. 8 MiB as given; compression_level <= 0 = fast
 pub const LegacyPrefs = extern struct { block_size: u32 = 0, compression_level: i32 = 0 };
 extern "c" fn zlz4f_legacy_compress_frame_bound(src_size: usize, prefs: ?*const LegacyPrefs) usize;
@@ -922,6 +927,27 @@ pub const lz4f = struct {
     /// what `lz4 -dc` prints for the .lz4 file `src`: linked-block frames, skippable frames and legacy frames included
     pub fn decompressFile(src: []const u8, dst: []u8) Error!usize {
         return decompressMultiframeEx(src, dst, DECODE_LINKED, SPLIT_LEGACY);
+    }
+    /// No counterpart in the reference: the file index and file range decoding, bytes [a, b) of whole .lz4 files
+    /// (include/zlz4_amd.h).  fileIndexBatch is the frame index across the members of a record-mode split (split_totals: a
+    /// host pointer to the split's four totals) and writes idx_off itself; the plan is planFrameRanges with nframes = the
+    /// buffers; decompressFileRangeBatch is decompressFrameRangeBatch whose items each find their own member, so a range may
+    /// cross frame, skippable and legacy members.  The index is the caller's data and is checked against the file.
+    pub fn fileIndexBatchWorkspace(nbuf: u32, split_totals: [*]const u64) usize {
+        return zlz4f_batch_file_index_workspace(nbuf, split_totals);
+    }
+    pub fn fileIndexBatch(stream: ?*anyopaque, src: ?[*]const u8, src_off: ?[*]const u64, src_len: ?[*]const u64, nbuf: u32, member: ?[*]const Member, mem_off: ?[*]const u64, split_result: ?[*]const i64, item_first: ?[*]const u64, item_off: ?[*]const u64, item_len: ?[*]const u64, leg_len: ?[*]const u64, split_totals: [*]const u64, index: ?[*]IndexEntry, idx_off: ?[*]u64, idx_cap: u64, idx_n: ?[*]i64, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_file_index(stream, src, src_off, src_len, nbuf, member, mem_off, split_result, item_first, item_off, item_len, leg_len, split_totals, index, idx_off, idx_cap, idx_n, workspace, workspace_bytes));
+    }
+    pub fn decompressFileRangeBatchWorkspace(nranges: u32, max_items: u32) usize {
+        return zlz4f_batch_decompress_file_range_workspace(nranges, max_items);
+    }
+    pub fn decompressFileRangeBatch(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, index: [*]const IndexEntry, idx_off: [*]const u64, idx_n: [*]const i64, nbuf: u32, member: [*]const Member, mem_off: [*]const u64, split_result: [*]const i64, ranges: [*]const Range, dst: [*]u8, dst_off: [*]const u64, dst_cap: [*]const u64, skip: [*]u64, result: [*]i64, nranges: u32, max_items: u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_file_range(stream, src, src_off, src_len, index, idx_off, idx_n, nbuf, member, mem_off, split_result, ranges, dst, dst_off, dst_cap, skip, result, nranges, max_items, workspace, workspace_bytes));
+    }
+    /// bytes [a, b) of one .lz4 file in host memory (both clamped to the file's size) at dst[0..]; builds the index on every call
+    pub fn decompressFileRange(src: []const u8, a: u64, b: u64, dst: []u8) Error!usize {
+        return mapFrame(zlz4f_decompress_file_range(src.ptr, src.len, a, b, dst.ptr, dst.len, SPLIT_LEGACY));
     }
     /// No counterpart in the reference: legacy frames, what `lz4 -l` writes and the Linux kernel's unlz4 reads -- the magic
     /// 0x184C2102, then { u32 size, block } repeated (include/zlz4_amd.h).  One frame in host memory per call; `consumed`
