@@ -1285,8 +1285,8 @@ int64_t zlz4f_decompress_legacy_frame(const uint8_t *src, size_t src_len, uint8_
  *   result; dst_cap < b' - a' gives ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.  IT BUILDS THE INDEX ON EVERY
  *   CALL (a size query of the whole file): a caller with several reads of one file keeps the index and uses the batch calls.
  *
- * NOT SERVED: dictionaries per member; history-aware ranges of linked members; a start offset inside one block; a
- *   serialised index. */
+ * NOT SERVED: dictionaries per member; history-aware ranges of linked members; a start offset inside one block.  (A
+ *   serialised index: the seek table, below.) */
 size_t  zlz4f_batch_file_index_workspace(uint32_t nbuf, const uint64_t *split_totals);
 int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
                                uint32_t nbuf, const zlz4f_member *d_member, const uint64_t *d_mem_off,
@@ -1305,6 +1305,107 @@ int32_t zlz4f_batch_decompress_file_range(void *stream, const uint8_t *d_src, co
                                           size_t workspace_bytes);
 int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t src_len, uint64_t a, uint64_t b, uint8_t *dst,
                                     size_t dst_cap, uint32_t split_flags);
+
+/* ---- seekable .lz4 files: a stored seek table, and a writer for such files (no counterpart in the reference; DESIGN.md
+ * section 4.4l).  The file index above is a size query of the whole file and the split in front of it a serial walk; both
+ * were computed by whoever wrote the file.  A SEEK TABLE stores them: it is one skippable frame, always the LAST MEMBER of
+ * its file, that holds the file's member rows and index entries.  Every lz4 decoder steps over it, the calls above
+ * included: to them it is a skippable member with nibble 0xC, and they answer for a file with a table exactly what they
+ * answer for any file.  (This closes "a serialised index" and "writing such files" of the NOT SERVED list above.)
+ *
+ * THE FORMAT, little-endian throughout.  A table over nm member rows and nb index blocks is T = 40 + 24*nm + 16*(nb + 1)
+ * bytes:
+ *   0          u32  0x184D2A5C                      ZLZ4F_SEEK_TABLE_MAGICNUMBER (a skippable magic, nibble 0xC)
+ *   4          u32  P = T - 8                       the skippable frame's payload size
+ *   8          nm     x { u64 pos, u64 len, u32 kind, u32 0 }   the members of the file in order, THIS ONE INCLUDED as the
+ *                                                   last row; kind as the record-mode split writes it: ZLZ4F_MEMBER_* |
+ *                                                   nibble << 8, so the last row's is ZLZ4F_MEMBER_SKIPPABLE | 0xC << 8
+ *   8 + 24*nm  nb + 1 x { u64 pos, u64 dec }        the entries of zlz4f_batch_file_index for the file
+ *   T - 32     u64 nm, u64 nb, u64 file_len (the file's length with this member), u32 version = 1, u32 0x4B53345A ("Z4SK")
+ *   The footer is the end of the file, so a reader finds the table from the tail.  The rows are zlz4f_member (buf is 0 in
+ *   the file) and zlz4f_index_entry as they stand in memory.  The table lists itself and its entries are those of the file
+ *   WITH the table: for a file G that ends in its table, the loaded tables equal, row for row, what the record-mode
+ *   zlz4f_batch_multiframe_split_ex and zlz4f_batch_file_index compute for G.  No checksum covers the table; it is not
+ *   trusted (below).
+ * zlz4f_seek_table_bound(nmembers, nblocks) = T for nmembers + 1 member rows (the file's members and the table's own row)
+ *   and nblocks + 1 entries; 0 when P does not fit 32 bits.
+ *
+ * zlz4f_batch_append_seek_table, the writer of the table.  INPUT: the buffers with room behind each one (buffer s is
+ *   d_buf_len[s] = n bytes at d_buf + d_buf_off[s], of a region of d_buf_cap[s] bytes from there), the record-mode split
+ *   over them (d_member, d_mem_off, d_split_result) and their file index (d_index, d_idx_off, d_idx_n).  OUTPUT: the table
+ *   at [n, n + T) of buffer s and d_result[s] = n + T.  Refusals per file, in this order, nothing written on any of them:
+ *   1. a split result < 0: that code.  2. d_idx_n[s] < 0: that code.  3. ZLZ4_ERR_INVALID_STATE when the last member is a
+ *   frame member whose chain lacks its end mark (entry[nb].pos + 4 > that member's end): appended bytes would be read as its
+ *   next block word.  4. ZLZ4_ERR_UNSUPPORTED when P does not fit 32 bits.  5. ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL when n + T >
+ *   d_buf_cap[s].  Bytes [0, n) are never touched, read or written, and no byte at or behind n + T is written.  A file that
+ *   already ends in a table gets a second one that lists the first as an ordinary member; the loader uses the last.  One
+ *   launch: the table is T / 8 64-bit fields that depend on their number alone, spread over lanes and, 256 at a time,
+ *   over the workgroups a file has; a table at an odd address is written as aligned words with its head and tail bytes
+ *   stored singly.
+ *
+ * zlz4f_batch_load_seek_table, the reader.  COUNT MODE (d_member == NULL): one lane per file reads the footer and the 8
+ *   bytes at n - T; d_count[s] = nm, or 0 for a file without a well-formed footer; d_totals = { the sum of nm, the sum of
+ *   the rooms }, a file's room being nb + 1, or 0 without such a footer: one 16-byte read-back sizes d_member and d_index.
+ *   RECORD MODE writes the member rows to d_member[d_mem_off[s] ..] with buf = s; d_idx_off itself, nbuf + 1 entries, the
+ *   exclusive scan of the rooms; the entries to d_index + d_idx_off[s]; d_split_result[s] = nm, or 0 (no table: n < 80 or
+ *   the tail magic is absent), or ZLZ4_ERR_INVALID_STATE (the tail magic is there and the table is MALFORMED), or
+ *   ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL (nm > d_mem_cap[s], or the room ends behind idx_cap; no row of that file is written);
+ *   d_idx_n[s] = nb when the split result is positive, else the negative split result, else ZLZ4_ERR_INVALID_STATE.  These
+ *   outputs are, unchanged, what zlz4f_batch_plan_frame_ranges and zlz4f_batch_decompress_file_range take.
+ *   MALFORMED: the footer's version != 1, T overflows or exceeds n, file_len != n, nm == 0, the word at n - T is not the
+ *   magic or the next one not P; a member row with pos[0] != 0, len == 0, pos[k] + len[k] != pos[k+1] (checked with
+ *   overflow), a last row that is not { n - T, T, ZLZ4F_MEMBER_SKIPPABLE | 0xC << 8 }, another row whose kind & 0xFF is not
+ *   FRAME, SKIPPABLE or LEGACY or that has bits outside 0xFFF, a reserved word that is set; an entry with pos > n - T, or
+ *   for k < nb pos[k+1] <= pos[k] or dec[k+1] < dec[k].  The rows of a malformed table are not promised.
+ *   THE LOADER CHECKS SHAPE ONLY; the range call stays the judge.  zlz4f_batch_decompress_file_range treats index and
+ *   member table as the caller's data and checks every position against the file before it becomes an address, so a
+ *   well-shaped table of ANOTHER file loads fine and is then refused (ZLZ4_ERR_INVALID_STATE) or answered correctly by
+ *   the range call, never with wrong bytes.
+ *   Launches: the footers (one lane per file), the scan of the rooms, the verdicts (one lane per file), the rows -- one
+ *   row per lane, 256 rows a slice, the slices of a file over the workgroups it has; each row is compared with its
+ *   neighbour and a slice that finds one out of shape lowers the file's verdict with one atomic.
+ *
+ * zlz4f_batch_concat, what a device-side file writer lacked: file s is its items d_item_first[s] .. d_item_first[s+1],
+ *   item i is d_item_len[i] bytes (int64: the compress call's d_result) at d_src + d_item_off[i]; the items are laid back
+ *   to back at d_dst + d_dst_off[s] and d_result[s] is the total -- or the first negative item length in item order, or
+ *   ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL against d_dst_cap[s]; nothing of that file is written then.  Source and destination do
+ *   not overlap.  Workspace: zlz4f_batch_concat_workspace(nitems) bytes, 8-byte aligned (every item's place).  One
+ *   wavefront per file places the items, 64 a step; one workgroup per item copies.
+ * All three: asynchronous on `stream`, a fixed launch sequence, nothing allocated, nothing read back.  A null or 8-byte
+ *   misaligned array: ZLZ4_ERR_INVALID_STATE, nothing launched; then the device.  nbuf == 0 returns 0.
+ *
+ * zlz4f_seek_table: one file in HOST memory; only the table member is written, to dst[0..T), and T returned -- the caller
+ *   appends it to the file.  Split (count, record), index and append as a batch of one; a refusal of the append is the
+ *   result.  zlz4f_decompress_file_range_ex: zlz4f_decompress_file_range with range_flags.  0: exactly that call.
+ *   ZLZ4F_RANGE_SEEK_TABLE: the tables are loaded when the file ends in a well-formed seek table, and the index is built as
+ *   before when it does not.  Both refuse, before the device check, an unknown flag bit (ZLZ4F_ERR_PARAMETER_INVALID),
+ *   then a null pointer with a length, and a > b (ZLZ4_ERR_INVALID_STATE).
+ *
+ * NOT SERVED: a dictionary per member; linked members with history; a table anywhere but at the file's end; any foreign
+ *   seekable format; a checksum over the table; partial staging in the host call -- zlz4f_decompress_file_range_ex still
+ *   copies the WHOLE file to the device, where the tail and the touched blocks would do. */
+#define ZLZ4F_SEEK_TABLE_MAGICNUMBER  0x184D2A5Cu
+#define ZLZ4F_SEEK_TABLE_FOOTER_MAGIC 0x4B53345Au
+#define ZLZ4F_SEEK_TABLE_VERSION      1u
+#define ZLZ4F_RANGE_SEEK_TABLE        1u     /* range_flags: take the tables from the file's seek table */
+size_t  zlz4f_seek_table_bound(uint64_t nmembers, uint64_t nblocks);
+int32_t zlz4f_batch_append_seek_table(void *stream, uint8_t *d_buf, const uint64_t *d_buf_off, const uint64_t *d_buf_len,
+                                      const uint64_t *d_buf_cap, uint32_t nbuf, const zlz4f_member *d_member,
+                                      const uint64_t *d_mem_off, const int64_t *d_split_result,
+                                      const zlz4f_index_entry *d_index, const uint64_t *d_idx_off, const int64_t *d_idx_n,
+                                      int64_t *d_result);
+int32_t zlz4f_batch_load_seek_table(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                                    uint32_t nbuf, uint64_t *d_count, uint64_t *d_totals, zlz4f_member *d_member,
+                                    const uint64_t *d_mem_off, const uint64_t *d_mem_cap, int64_t *d_split_result,
+                                    zlz4f_index_entry *d_index, uint64_t *d_idx_off, uint64_t idx_cap, int64_t *d_idx_n);
+size_t  zlz4f_batch_concat_workspace(uint32_t nitems);
+int32_t zlz4f_batch_concat(void *stream, const uint8_t *d_src, const uint64_t *d_item_off, const int64_t *d_item_len,
+                           const uint64_t *d_item_first, uint32_t nbuf, uint32_t nitems, uint8_t *d_dst,
+                           const uint64_t *d_dst_off, const uint64_t *d_dst_cap, int64_t *d_result, void *d_workspace,
+                           size_t workspace_bytes);
+int64_t zlz4f_seek_table(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t split_flags);
+int64_t zlz4f_decompress_file_range_ex(const uint8_t *src, size_t src_len, uint64_t a, uint64_t b, uint8_t *dst,
+                                       size_t dst_cap, uint32_t split_flags, uint32_t range_flags);
 
 /* ======================================================================
  * 4. Introspection

@@ -160,6 +160,13 @@ SYMBOLS = {
     "zlz4f_batch_decompress_file_range_workspace": (_SZ, [_U32, _U32]),
     "zlz4f_batch_decompress_file_range": (_I32, [_VP] * 7 + [_U32] + [_VP] * 9 + [_U32, _U32, _VP, _SZ]),
     "zlz4f_decompress_file_range": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ, _U32]),
+    "zlz4f_seek_table_bound": (_SZ, [C.c_uint64, C.c_uint64]),
+    "zlz4f_batch_append_seek_table": (_I32, [_VP] * 5 + [_U32] + [_VP] * 7),
+    "zlz4f_batch_load_seek_table": (_I32, [_VP] * 4 + [_U32] + [_VP] * 8 + [C.c_uint64, _VP]),
+    "zlz4f_batch_concat_workspace": (_SZ, [_U32]),
+    "zlz4f_batch_concat": (_I32, [_VP] * 5 + [_U32, _U32] + [_VP] * 5 + [_SZ]),
+    "zlz4f_seek_table": (_I64, [_VP, _SZ, _VP, _SZ, _U32]),
+    "zlz4f_decompress_file_range_ex": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ, _U32, _U32]),
     "zlz4f_batch_multiframe_split": (_I32, [_VP] * 4 + [_U32] + [_VP] * 9),
     "zlz4f_batch_multiframe_plan": (_I32, [_VP] * 3 + [_U32, _U32] + [_VP] * 5),
     "zlz4f_batch_multiframe_finish": (_I32, [_VP] * 7 + [_U32, _VP]),
@@ -1149,10 +1156,15 @@ class lz4f:
     def splitMultiframes(buffers, device="cuda", legacy=False):
         """Stage `buffers` and delimit their members: count mode, one read-back of the totals, record mode.  legacy: legacy
         frames are members too (the _ex split with SPLIT_LEGACY)."""
+        return lz4f.splitStaged(*_stage(buffers, device), legacy=legacy)
+
+    @staticmethod
+    def splitStaged(d_src, src_off, src_len, legacy=False):
+        """splitMultiframes over buffers that are on the device already: buffer s is src_len[s] bytes at d_src + src_off[s]."""
         import torch
         sp = lz4f.MultiframeSplit()
-        nbuf = len(buffers)
-        sp.d_src, sp.src_off, sp.src_len = _stage(buffers, device)
+        nbuf, device = src_len.numel(), d_src.device
+        sp.d_src, sp.src_off, sp.src_len = d_src, src_off, src_len
 
         def i64(n):
             return torch.zeros(max(1, n), dtype=torch.int64, device=device)[:n]
@@ -1352,8 +1364,13 @@ class lz4f:
         import torch
         if torch.device(device).type != "cuda":
             _check(ERR_DEVICE)
-        nbuf = len(buffers)
-        sp = lz4f.splitMultiframes(buffers, device, legacy)
+        return lz4f.indexSplit(lz4f.splitMultiframes(buffers, device, legacy))
+
+    @staticmethod
+    def indexSplit(sp):
+        """fileIndex over a MultiframeSplit (splitMultiframes, splitStaged) -> FileIndex."""
+        import torch
+        nbuf, device = sp.src_len.numel(), sp.d_src.device
         cap = sp.max_blocks + sp.legacy_blocks + nbuf
         index = torch.zeros((max(1, cap), 2), dtype=torch.int64, device=device)
         idx_off = torch.zeros(nbuf + 1, dtype=torch.int64, device=device)
@@ -1401,17 +1418,182 @@ class lz4f:
         return lz4f.decompressFileRanges(lz4f.fileIndex(buffers, device, legacy), [(s, 0, k) for s, k in enumerate(ns)])
 
     @staticmethod
-    def decompressFileRange(src, a, b, legacy=True):
+    def decompressFileRange(src, a, b, legacy=True, seek_table=False):
         """zlz4f_decompress_file_range: bytes [a, b) of one file in host memory (both clamped to the file's size).  The
-        index is built on every call; several reads of one file: fileIndex + decompressFileRanges."""
+        index is built on every call; several reads of one file: fileIndex + decompressFileRanges.  seek_table:
+        zlz4f_decompress_file_range_ex with RANGE_SEEK_TABLE -- the tables come from the file's seek table where it ends in
+        a well-formed one."""
         s, n = _in(src)
         flags = lz4f.SPLIT_LEGACY if legacy else 0
         cap = max(0, min(b, 1 << 62) - a)
         if cap > 1 << 20:                              # (b may lie far behind the file's end)
             cap = min(cap, max(0, lz4f.multiframeDecompressedSize(src, 0, legacy) - a))
         d = (C.c_uint8 * max(1, cap))()
-        r = _check(lib().zlz4f_decompress_file_range(C.addressof(s), n, a, b, C.addressof(d), cap, flags))
+        if seek_table:
+            r = _check(lib().zlz4f_decompress_file_range_ex(C.addressof(s), n, a, b, C.addressof(d), cap, flags,
+                                                            lz4f.RANGE_SEEK_TABLE))
+        else:
+            r = _check(lib().zlz4f_decompress_file_range(C.addressof(s), n, a, b, C.addressof(d), cap, flags))
         return bytes(d[:r])
+
+    # seekable files: a stored seek table and a writer for such files (include/zlz4_amd.h, DESIGN.md section 4.4l)
+    SEEK_TABLE_MAGICNUMBER = 0x184D2A5C
+    RANGE_SEEK_TABLE = 1
+
+    @staticmethod
+    def seekTableBound(nmembers, nblocks):
+        """zlz4f_seek_table_bound: the bytes of the table of a file of nmembers members and nblocks blocks (0: too large)."""
+        return lib().zlz4f_seek_table_bound(nmembers, nblocks)
+
+    @staticmethod
+    def appendSeekTableBatch(d_buf, buf_off, buf_len, buf_cap, member, mem_off, split_result, index, idx_off, idx_n, result):
+        """zlz4f_batch_append_seek_table on torch CUDA tensors: buffer s is buf_len[s] bytes at d_buf + buf_off[s] with
+        buf_cap[s] bytes of room from there; the record-mode split and the file index over the buffers; result int64 [nbuf]
+        = the file's length with its table, or the refusal's code."""
+        _check(lib().zlz4f_batch_append_seek_table(_stream(), _ptr(d_buf), _ptr(buf_off), _ptr(buf_len), _ptr(buf_cap),
+                                                   buf_len.numel(), _ptr(member), _ptr(mem_off), _ptr(split_result),
+                                                   _ptr(index), _ptr(idx_off), _ptr(idx_n), _ptr(result)))
+
+    @staticmethod
+    def loadSeekTableBatch(d_src, src_off, src_len, count, totals, member=None, mem_off=None, mem_cap=None, split_result=None,
+                           index=None, idx_off=None, idx_n=None, idx_cap=None):
+        """zlz4f_batch_load_seek_table: count int64 [nbuf], totals int64 [2] = (member rows, index entries).  member None:
+        count mode.  Else member int64 [rows, 3], mem_off / mem_cap / split_result / idx_n int64 [nbuf], index int64
+        [entries, 2], idx_off int64 [nbuf + 1] (written by the call).  idx_cap None: the entries `index` holds."""
+        if idx_cap is None:
+            idx_cap = index.shape[0] if index is not None else 0
+        _check(lib().zlz4f_batch_load_seek_table(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), src_len.numel(),
+                                                 _ptr(count), _ptr(totals), _ptr(member), _ptr(mem_off), _ptr(mem_cap),
+                                                 _ptr(split_result), _ptr(index), _ptr(idx_off), idx_cap, _ptr(idx_n)))
+
+    @staticmethod
+    def concatBatchWorkspace(nitems):
+        return lib().zlz4f_batch_concat_workspace(nitems)
+
+    @staticmethod
+    def concatBatch(d_src, item_off, item_len, item_first, d_dst, dst_off, dst_cap, result, workspace=None):
+        """zlz4f_batch_concat: file s is the items item_first[s] .. item_first[s + 1] (item_off / item_len int64 per item,
+        item_len as the compress call's result), laid back to back at d_dst + dst_off[s]; result int64 [nbuf] = the total,
+        the first negative item length, or DstMaxSizeTooSmall against dst_cap[s]."""
+        import torch
+        ni = item_len.numel()
+        if workspace is None:
+            workspace = torch.empty(max(8, lib().zlz4f_batch_concat_workspace(ni)), dtype=torch.uint8, device=d_dst.device)
+        _check(lib().zlz4f_batch_concat(_stream(), _ptr(d_src), _ptr(item_off), _ptr(item_len), _ptr(item_first),
+                                        result.numel(), ni, _ptr(d_dst), _ptr(dst_off), _ptr(dst_cap), _ptr(result),
+                                        _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def _appendTables(ix, d_buf, buf_off, buf_cap):
+        """the append over a FileIndex whose buffers stand in d_buf with room -> result tensor"""
+        import torch
+        sp = ix.split
+        result = torch.zeros(sp.src_len.numel(), dtype=torch.int64, device=d_buf.device)
+        lz4f.appendSeekTableBatch(d_buf, buf_off, sp.src_len, buf_cap, sp.member, sp.mem_off, sp.result, ix.index, ix.idx_off,
+                                  ix.idx_n, result)
+        return result
+
+    @staticmethod
+    def appendSeekTables(buffers, legacy=True, device="cuda"):
+        """Every file of `buffers` with its seek table appended -> list of files (bytes) or the refusal's code: fileIndex,
+        a copy of the files into slots with room (concatBatch, one item per file), the append, one read-back."""
+        import torch
+        if not len(buffers):
+            return []
+        ix = lz4f.fileIndex(buffers, device, legacy)
+        sp = ix.split
+        nbuf = len(buffers)
+        caps = [len(b) + lz4f.seekTableBound(max(0, nm), max(0, nb)) for b, nm, nb in zip(buffers, sp.results, ix.results)]
+        slots = [(c + 15) & ~15 for c in caps]
+        t = lambda v: torch.tensor(v, dtype=torch.int64, device=device)    # noqa: E731
+        buf_off, buf_cap = t(_offsets(slots)), t(caps)
+        d_buf = torch.zeros(max(1, sum(slots)), dtype=torch.uint8, device=device)
+        copied = torch.zeros(nbuf, dtype=torch.int64, device=device)
+        lz4f.concatBatch(sp.d_src, sp.src_off, sp.src_len, t(list(range(nbuf + 1))), d_buf, buf_off, buf_cap, copied)
+        return _unstage(d_buf, _offsets(slots), lz4f._appendTables(ix, d_buf, buf_off, buf_cap))
+
+    @staticmethod
+    def loadFileIndex(buffers, device="cuda"):
+        """Stage `buffers` -- files that end in a seek table -- and load their tables (zlz4f_batch_load_seek_table: count
+        mode, one read-back of the totals, record mode) -> FileIndex, which decompressFileRanges takes as it takes
+        fileIndex's.  No block header is walked.  A file without a table, or with one out of shape, keeps its code
+        (InvalidState) in .results.  The FileIndex's .split carries d_src, src_off, src_len, member, mem_off and result."""
+        import torch
+        if torch.device(device).type != "cuda":
+            _check(ERR_DEVICE)
+        nbuf = len(buffers)
+        sp = lz4f.MultiframeSplit()
+        sp.d_src, sp.src_off, sp.src_len = _stage(buffers, device)
+
+        def i64(n):
+            return torch.zeros(max(1, n), dtype=torch.int64, device=device)[:n]
+
+        sp.count, totals = i64(nbuf), i64(2)
+        lz4f.loadSeekTableBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals)
+        sp.nitems, rooms = totals.cpu().tolist()
+        sp.member = torch.zeros((max(1, sp.nitems), 3), dtype=torch.int64, device=device)
+        sp.mem_off = torch.cumsum(sp.count, 0) - sp.count if nbuf else i64(0)
+        sp.result = i64(nbuf)
+        index = torch.zeros((max(1, rooms), 2), dtype=torch.int64, device=device)
+        idx_off, idx_n = torch.zeros(nbuf + 1, dtype=torch.int64, device=device), i64(nbuf)
+        lz4f.loadSeekTableBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals, sp.member, sp.mem_off, sp.count, sp.result,
+                                index, idx_off, idx_n, rooms)
+        sp.results = sp.result.cpu().tolist()
+        return lz4f.FileIndex(sp, index, idx_off, idx_n, idx_n.cpu().tolist())
+
+    @staticmethod
+    def seekTable(src, legacy=True):
+        """zlz4f_seek_table: the seek table member of one file in host memory -> bytes; the caller appends them."""
+        s, n = _in(src)
+        flags = lz4f.SPLIT_LEGACY if legacy else 0
+        cap = 1 << 12
+        while True:
+            d = (C.c_uint8 * cap)()
+            r = lib().zlz4f_seek_table(C.addressof(s), n, C.addressof(d), cap, flags)
+            if r != -111 or cap >= 1 << 33:             # DstMaxSizeTooSmall: the table is larger
+                return bytes(d[:_check(r)])
+            cap *= 16
+
+    @staticmethod
+    def compressFiles(items, prefs=None, frame_size=4 << 20, seek_table=True, batch_flags=0, device="cuda"):
+        """Every byte string of `items` as one seekable .lz4 file -> list of files (bytes) or error codes.  An input becomes
+        ceil(len / frame_size) independent frames (an empty one: one empty frame), compressed in place as chunks of the
+        staged inputs by compressFrameBatch and laid back to back on the device (concatBatch); with seek_table the files
+        are split and indexed there (splitStaged, indexSplit) and their table is appended."""
+        import torch
+        if frame_size < 1:
+            raise ValueError("frame_size: at least 1")
+        nbuf = len(items)
+        if not nbuf:
+            return []
+        lens = [len(b) for b in items]
+        d_src, _, _ = _stage(items, device)
+        bs = lz4f.BLOCK_SIZES.get(prefs.block_size_id if prefs is not None else 0, 64 << 10)
+        c_off, c_len, first, blocks = [], [], [0], []
+        for o, n in zip(_offsets(lens), lens):
+            for j in range(max(1, -(-n // frame_size))):
+                c_off.append(o + j * frame_size)
+                c_len.append(min(frame_size, n - j * frame_size))
+            first.append(len(c_off))
+            blocks.append(sum(-(-k // bs) for k in c_len[first[-2]:]))
+        caps = [lz4f.compressFrameBound(n, prefs) for n in c_len]
+        t = lambda v: torch.tensor(v, dtype=torch.int64, device=device)    # noqa: E731
+        d_frames = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
+        f_off, f_len = t(_offsets(caps)), torch.zeros(len(caps), dtype=torch.int64, device=device)
+        lz4f.compressFrameBatch(d_src, t(c_off), t(c_len), d_frames, f_off, t(caps), f_len, prefs, batch_flags,
+                                max_blocks=sum(blocks))
+        room = [sum(caps[first[s]:first[s + 1]]) +
+                (lz4f.seekTableBound(first[s + 1] - first[s], blocks[s]) if seek_table else 0) for s in range(nbuf)]
+        slots = [(c + 15) & ~15 for c in room]
+        file_off, file_cap = t(_offsets(slots)), t(room)
+        d_files = torch.zeros(max(1, sum(slots)), dtype=torch.uint8, device=device)
+        joined = torch.zeros(nbuf, dtype=torch.int64, device=device)
+        lz4f.concatBatch(d_frames, f_off, f_len, t(first), d_files, file_off, file_cap, joined)
+        if not seek_table:
+            return _unstage(d_files, _offsets(slots), joined)
+        ix = lz4f.indexSplit(lz4f.splitStaged(d_files, file_off, torch.clamp(joined, min=0), legacy=True))
+        result = lz4f._appendTables(ix, d_files, file_off, file_cap)
+        return _unstage(d_files, _offsets(slots), torch.where(joined < 0, joined, result))
 
     # legacy frames: what `lz4 -l` writes (include/zlz4_amd.h, DESIGN.md section 4.4i)
     LegacyPrefs = LegacyPrefs

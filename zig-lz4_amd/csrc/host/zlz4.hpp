@@ -494,6 +494,46 @@ inline Result decompressFileRange(const std::uint8_t *src, std::size_t n, std::u
                                   std::size_t cap, std::uint32_t split_flags = ZLZ4F_SPLIT_LEGACY) {
     return wrap(zlz4f_decompress_file_range(src, n, a, b, dst, cap, split_flags));
 }
+// seekable files (include/zlz4_amd.h; no counterpart in the reference): a SEEK TABLE is the last, skippable member of a file
+// and stores the file's member rows and index entries.  appendSeekTableBatch writes it behind every buffer from the split
+// and the file index; loadSeekTableBatch reads both tables back from the file's tail (count mode: d_member null), checking
+// their shape only -- the range call stays the judge; concatBatch lays items back to back, file by file.  seekTable writes
+// the table member of one file in host memory to dst; decompressFileRangeEx takes the tables from the file's seek table
+// where range_flags asks for it and the file ends in a well-formed one.
+constexpr std::uint32_t SEEK_TABLE_MAGICNUMBER = ZLZ4F_SEEK_TABLE_MAGICNUMBER, RANGE_SEEK_TABLE = ZLZ4F_RANGE_SEEK_TABLE;
+inline std::size_t seekTableBound(std::uint64_t nmembers, std::uint64_t nblocks) {
+    return zlz4f_seek_table_bound(nmembers, nblocks);
+}
+inline Result appendSeekTableBatch(void *stream, std::uint8_t *d_buf, const std::uint64_t *d_buf_off,
+                                   const std::uint64_t *d_buf_len, const std::uint64_t *d_buf_cap, std::uint32_t nbuf,
+                                   const FileSplit &s, const FrameIndex &x, std::int64_t *d_result) {
+    return wrap(zlz4f_batch_append_seek_table(stream, d_buf, d_buf_off, d_buf_len, d_buf_cap, nbuf, s.member, s.mem_off,
+                                              s.split_result, x.index, x.idx_off, x.idx_n, d_result));
+}
+inline Result loadSeekTableBatch(void *stream, const Multiframes &m, std::uint64_t *d_count, std::uint64_t *d_totals,
+                                 Member *d_member, const std::uint64_t *d_mem_off, const std::uint64_t *d_mem_cap,
+                                 std::int64_t *d_split_result, IndexEntry *d_index, std::uint64_t *d_idx_off,
+                                 std::uint64_t idx_cap, std::int64_t *d_idx_n) {
+    return wrap(zlz4f_batch_load_seek_table(stream, m.src, m.src_off, m.src_len, m.nbuf, d_count, d_totals, d_member, d_mem_off,
+                                            d_mem_cap, d_split_result, d_index, d_idx_off, idx_cap, d_idx_n));
+}
+inline std::size_t concatBatchWorkspace(std::uint32_t nitems) { return zlz4f_batch_concat_workspace(nitems); }
+inline Result concatBatch(void *stream, const std::uint8_t *d_src, const std::uint64_t *d_item_off, const std::int64_t *d_item_len,
+                          const std::uint64_t *d_item_first, std::uint32_t nbuf, std::uint32_t nitems, std::uint8_t *d_dst,
+                          const std::uint64_t *d_dst_off, const std::uint64_t *d_dst_cap, std::int64_t *d_result, void *ws,
+                          std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_concat(stream, d_src, d_item_off, d_item_len, d_item_first, nbuf, nitems, d_dst, d_dst_off, d_dst_cap,
+                                   d_result, ws, ws_bytes));
+}
+inline Result seekTable(const std::uint8_t *src, std::size_t n, std::uint8_t *dst, std::size_t cap,
+                        std::uint32_t split_flags = ZLZ4F_SPLIT_LEGACY) {
+    return wrap(zlz4f_seek_table(src, n, dst, cap, split_flags));
+}
+inline Result decompressFileRangeEx(const std::uint8_t *src, std::size_t n, std::uint64_t a, std::uint64_t b, std::uint8_t *dst,
+                                    std::size_t cap, std::uint32_t split_flags = ZLZ4F_SPLIT_LEGACY,
+                                    std::uint32_t range_flags = ZLZ4F_RANGE_SEEK_TABLE) {
+    return wrap(zlz4f_decompress_file_range_ex(src, n, a, b, dst, cap, split_flags, range_flags));
+}
 // legacy frames (include/zlz4_amd.h; no counterpart in the reference): what `lz4 -l` writes -- the magic 0x184C2102, then
 // { u32 size, block } repeated.  One frame in host memory per call; `consumed` (may be null) receives where the frame ends,
 // which is where the next member of a concatenated file starts.  The batch calls are those of the C header.

@@ -277,3 +277,85 @@ __device__ __forceinline__ bool bf_fits(const BFrame &F, uint32_t max_blocks) { 
 __device__ __forceinline__ bool bfd_dict_serial(const BFrame &F) { return !(F.flg & 0x20u) && F.nb > 1; }
 
 }  // namespace
+
+// ------------------------------------------------------------------ seek tables
+// The last member of a seekable file (include/zlz4_amd.h states the format): a skippable frame of T bytes that holds the
+// file's member rows, its index entries and a 32-byte footer at the file's very end.  One statement of the footer parse
+// and of the per-row checks, for the loader's kernels (zlz4_frame_seek.hip) and the host check (tests/seek_table_check.cpp).
+// The checks are SHAPE ONLY: no position of a table becomes an address here.
+namespace {
+
+constexpr uint32_t kSeekFooterMagic = 0x4B53345Au;                    // "Z4SK"
+constexpr uint32_t kSeekSelfKind = ZLZ4F_MEMBER_SKIPPABLE | (ZLZ4F_SEEK_TABLE_MAGICNUMBER & 15u) << 8;
+
+__host__ __device__ inline uint64_t zx_rd64(const uint8_t *p) { return (uint64_t)zx_rd32(p) | ((uint64_t)zx_rd32(p + 4) << 32); }
+struct Rd64 { __host__ __device__ __forceinline__ uint64_t operator()(const uint8_t *p) const { return zx_rd64(p); } };
+
+// T for nm member rows (the table's own row included) and nb + 1 entries; false: T does not fit 64 bits
+__host__ __device__ inline bool seek_table_bytes(uint64_t nm, uint64_t nb, uint64_t &T) {
+    if (nm > (~0ull - 56u) / 24u) return false;
+    const uint64_t t = 56u + 24u * nm;
+    if (nb > (~0ull - t) / 16u) return false;
+    T = t + 16u * nb;
+    return true;
+}
+
+enum SeekVerdict : int32_t { kSeekNone = 0, kSeekOk = 1, kSeekMalformed = -1 };
+struct SeekFooter { uint64_t nm, nb, T; };
+
+// The footer of the n bytes at s: kSeekNone when n < 80 or the tail magic is absent, kSeekMalformed when it is there and
+// the version is not 1, T overflows or exceeds n, file_len is not n, there is no member row, or the 8 bytes at n - T are
+// not the skippable magic and P = T - 8.  Reads the last 32 bytes and those 8, byte by byte.
+__host__ __device__ inline SeekVerdict seek_footer(const uint8_t *s, uint64_t n, SeekFooter &F) {
+    F.nm = F.nb = F.T = 0;
+    if (n < 80u || zx_rd32(s + n - 4u) != kSeekFooterMagic) return kSeekNone;
+    if (zx_rd32(s + n - 8u) != 1u) return kSeekMalformed;
+    const uint64_t nm = zx_rd64(s + n - 32u), nb = zx_rd64(s + n - 24u), file_len = zx_rd64(s + n - 16u);
+    uint64_t T;
+    if (nm == 0 || !seek_table_bytes(nm, nb, T) || T > n || file_len != n) return kSeekMalformed;
+    if (zx_rd32(s + n - T) != ZLZ4F_SEEK_TABLE_MAGICNUMBER || (uint64_t)zx_rd32(s + n - T + 4u) != T - 8u) return kSeekMalformed;
+    F.nm = nm; F.nb = nb; F.T = T;
+    return kSeekOk;
+}
+
+// Member row k of the table of footer F that ends the n bytes at s, compared with its neighbour k + 1 -> the row is well
+// shaped; m = the row as it stands in the file (buf = the reserved word).  rd reads 8 bytes at any alignment.
+template <class Rd = Rd64>
+__host__ __device__ __forceinline__ bool seek_member_row(const uint8_t *s, uint64_t n, const SeekFooter &F, uint64_t k,
+                                                         zlz4f_member &m, Rd rd = Rd()) {
+    const uint8_t *row = s + (n - F.T) + 8u + 24u * k;
+    m.pos = rd(row); m.len = rd(row + 8);
+    const uint64_t w = rd(row + 16);
+    m.kind = (uint32_t)w; m.buf = (uint32_t)(w >> 32);
+    if (m.buf != 0 || m.len == 0 || (k == 0 && m.pos != 0)) return false;
+    if (k + 1u == F.nm) return m.pos == n - F.T && m.len == F.T && m.kind == kSeekSelfKind;
+    const uint32_t kind = m.kind & 0xFFu;
+    if ((m.kind & ~0xFFFu) || (kind != ZLZ4F_MEMBER_FRAME && kind != ZLZ4F_MEMBER_SKIPPABLE && kind != ZLZ4F_MEMBER_LEGACY))
+        return false;
+    return m.len <= ~0ull - m.pos && m.pos + m.len == rd(row + 24);
+}
+
+// Entry row k (0 .. nb) compared with its neighbour k + 1
+template <class Rd = Rd64>
+__host__ __device__ __forceinline__ bool seek_entry_row(const uint8_t *s, uint64_t n, const SeekFooter &F, uint64_t k,
+                                                        zlz4f_index_entry &e, Rd rd = Rd()) {
+    const uint8_t *row = s + (n - F.T) + 8u + 24u * F.nm + 16u * k;
+    e.pos = rd(row); e.dec = rd(row + 8);
+    if (e.pos > n - F.T) return false;
+    return k == F.nb || (rd(row + 16) > e.pos && rd(row + 24) >= e.dec);
+}
+
+// Why zlz4f_batch_append_seek_table refuses a file of n bytes with room for cap: 0 = it does not.  nm = the split's result,
+// last = the split's last member row (read only when nm > 0), nb = the index result, end_pos = entry[nb].pos.
+__host__ __device__ inline int64_t seek_append_refusal(int64_t nm, const zlz4f_member &last, int64_t nb, uint64_t end_pos,
+                                                       uint64_t n, uint64_t cap, uint64_t &T) {
+    T = 0;
+    if (nm < 0) return nm;
+    if (nb < 0) return nb;
+    if (nm > 0 && (last.kind & 0xFFu) == ZLZ4F_MEMBER_FRAME && end_pos + 4u > last.pos + last.len) return ZLZ4_ERR_INVALID_STATE;
+    if (!seek_table_bytes((uint64_t)nm + 1u, (uint64_t)nb, T) || T - 8u > 0xFFFFFFFFull) { T = 0; return ZLZ4_ERR_UNSUPPORTED; }
+    if (T > cap || n > cap - T) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
+    return 0;
+}
+
+}  // namespace

@@ -124,6 +124,13 @@ extern "c" fn zlz4f_batch_file_index(stream: ?*anyopaque, d_src: ?[*]const u8, d
 extern "c" fn zlz4f_batch_decompress_file_range_workspace(nranges: u32, max_items: u32) usize;
 extern "c" fn zlz4f_batch_decompress_file_range(stream: ?*anyopaque, d_src: [*]const u8, d_src_off: [*]const u64, d_src_len: [*]const u64, d_index: [*]const IndexEntry, d_idx_off: [*]const u64, d_idx_n: [*]const i64, nbuf: u32, d_member: [*]const Member, d_mem_off: [*]const u64, d_split_result: [*]const i64, d_range: [*]const Range, d_dst: [*]u8, d_dst_off: [*]const u64, d_dst_cap: [*]const u64, d_skip: [*]u64, d_result: [*]i64, nranges: u32, max_items: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_decompress_file_range(src: [*]const u8, src_len: usize, a: u64, b: u64, dst: [*]u8, dst_cap: usize, split_flags: u32) i64;
+extern "c" fn zlz4f_seek_table_bound(nmembers: u64, nblocks: u64) usize;
+extern "c" fn zlz4f_batch_append_seek_table(stream: ?*anyopaque, d_buf: ?[*]u8, d_buf_off: ?[*]const u64, d_buf_len: ?[*]const u64, d_buf_cap: ?[*]const u64, nbuf: u32, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_index: ?[*]const IndexEntry, d_idx_off: ?[*]const u64, d_idx_n: ?[*]const i64, d_result: ?[*]i64) i32;
+extern "c" fn zlz4f_batch_load_seek_table(stream: ?*anyopaque, d_src: ?[*]const u8, d_src_off: ?[*]const u64, d_src_len: ?[*]const u64, nbuf: u32, d_count: ?[*]u64, d_totals: [*]u64, d_member: ?[*]Member, d_mem_off: ?[*]const u64, d_mem_cap: ?[*]const u64, d_split_result: ?[*]i64, d_index: ?[*]IndexEntry, d_idx_off: ?[*]u64, idx_cap: u64, d_idx_n: ?[*]i64) i32;
+extern "c" fn zlz4f_batch_concat_workspace(nitems: u32) usize;
+extern "c" fn zlz4f_batch_concat(stream: ?*anyopaque, d_src: ?[*]const u8, d_item_off: ?[*]const u64, d_item_len: ?[*]const i64, d_item_first: ?[*]const u64, nbuf: u32, nitems: u32, d_dst: ?[*]u8, d_dst_off: ?[*]const u64, d_dst_cap: ?[*]const u64, d_result: ?[*]i64, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_seek_table(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, split_flags: u32) i64;
+extern "c" fn zlz4f_decompress_file_range_ex(src: [*]const u8, src_len: usize, a: u64, b: u64, dst: [*]u8, dst_cap: usize, split_flags: u32, range_flags: u32) i64;
 /// zlz4f_legacy_prefs of include/zlz4_amd.h: block_size 0 = 8 MiB, 1 .. 8 MiB as given; compression_level <= 0 = fast
 pub const LegacyPrefs = extern struct { block_size: u32 = 0, compression_level: i32 = 0 };
 extern "c" fn zlz4f_legacy_compress_frame_bound(src_size: usize, prefs: ?*const LegacyPrefs) usize;
@@ -948,6 +955,36 @@ pub const lz4f = struct {
     /// bytes [a, b) of one .lz4 file in host memory (both clamped to the file's size) at dst[0..]; builds the index on every call
     pub fn decompressFileRange(src: []const u8, a: u64, b: u64, dst: []u8) Error!usize {
         return mapFrame(zlz4f_decompress_file_range(src.ptr, src.len, a, b, dst.ptr, dst.len, SPLIT_LEGACY));
+    }
+    /// No counterpart in the reference: seekable files (include/zlz4_amd.h).  A SEEK TABLE is the last, skippable member of
+    /// a file (magic 0x184D2A5C) and stores the file's member rows and index entries.  appendSeekTableBatch writes it
+    /// behind every buffer from the split and the file index; loadSeekTableBatch reads both tables back from the file's
+    /// tail (count mode: member null) and checks their shape only -- the range call stays the judge; concatBatch lays items
+    /// back to back, file by file.
+    pub const SEEK_TABLE_MAGICNUMBER: u32 = 0x184D2A5C;
+    pub const RANGE_SEEK_TABLE: u32 = 1;
+    pub fn seekTableBound(nmembers: u64, nblocks: u64) usize {
+        return zlz4f_seek_table_bound(nmembers, nblocks);
+    }
+    pub fn appendSeekTableBatch(stream: ?*anyopaque, buf: ?[*]u8, buf_off: ?[*]const u64, buf_len: ?[*]const u64, buf_cap: ?[*]const u64, nbuf: u32, member: ?[*]const Member, mem_off: ?[*]const u64, split_result: ?[*]const i64, index: ?[*]const IndexEntry, idx_off: ?[*]const u64, idx_n: ?[*]const i64, result: ?[*]i64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_append_seek_table(stream, buf, buf_off, buf_len, buf_cap, nbuf, member, mem_off, split_result, index, idx_off, idx_n, result));
+    }
+    pub fn loadSeekTableBatch(stream: ?*anyopaque, src: ?[*]const u8, src_off: ?[*]const u64, src_len: ?[*]const u64, nbuf: u32, count: ?[*]u64, totals: [*]u64, member: ?[*]Member, mem_off: ?[*]const u64, mem_cap: ?[*]const u64, split_result: ?[*]i64, index: ?[*]IndexEntry, idx_off: ?[*]u64, idx_cap: u64, idx_n: ?[*]i64) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_load_seek_table(stream, src, src_off, src_len, nbuf, count, totals, member, mem_off, mem_cap, split_result, index, idx_off, idx_cap, idx_n));
+    }
+    pub fn concatBatchWorkspace(nitems: u32) usize {
+        return zlz4f_batch_concat_workspace(nitems);
+    }
+    pub fn concatBatch(stream: ?*anyopaque, src: ?[*]const u8, item_off: ?[*]const u64, item_len: ?[*]const i64, item_first: ?[*]const u64, nbuf: u32, nitems: u32, dst: ?[*]u8, dst_off: ?[*]const u64, dst_cap: ?[*]const u64, result: ?[*]i64, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_concat(stream, src, item_off, item_len, item_first, nbuf, nitems, dst, dst_off, dst_cap, result, workspace, workspace_bytes));
+    }
+    /// the seek table member of one .lz4 file in host memory at dst[0..]; the caller appends it to the file
+    pub fn seekTable(src: []const u8, dst: []u8) Error!usize {
+        return mapFrame(zlz4f_seek_table(src.ptr, src.len, dst.ptr, dst.len, SPLIT_LEGACY));
+    }
+    /// decompressFileRange that takes the tables from the file's seek table where it ends in a well-formed one
+    pub fn decompressFileRangeEx(src: []const u8, a: u64, b: u64, dst: []u8, range_flags: u32) Error!usize {
+        return mapFrame(zlz4f_decompress_file_range_ex(src.ptr, src.len, a, b, dst.ptr, dst.len, SPLIT_LEGACY, range_flags));
     }
     /// No counterpart in the reference: legacy frames, what `lz4 -l` writes and the Linux kernel's unlz4 reads -- the magic
     /// 0x184C2102, then { u32 size, block } repeated (include/zlz4_amd.h).  One frame in host memory per call; `consumed`
