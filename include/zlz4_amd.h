@@ -1036,8 +1036,9 @@ int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, u
  *   ZLZ4F_ERR_PARAMETER_INVALID, then a null pointer with a length: ZLZ4_ERR_INVALID_STATE, both before the device check.
  *   The planned total above dst_cap: ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.
  *
- * NOT SERVED: a dictionary per member (a member with a dictID decodes as the plain frame call decodes it); writing
- *   multiframes (they are the concatenation of what the compress calls return).
+ * NOT SERVED: a dictionary per MEMBER chosen by dictID (a member with a dictID decodes as the plain frame call decodes it;
+ *   one dictionary per buffer: zlz4f_batch_multiframe_item_dicts and the dictionary frame calls over the items, below);
+ *   writing multiframes (they are the concatenation of what the compress calls return).
  *   Legacy frames (magic 0x184C2102) are a member that cannot be delimited by THESE calls: ZLZ4F_ERR_FRAME_TYPE_UNKNOWN; the
  *   _ex calls below with ZLZ4F_SPLIT_LEGACY serve them.
  *
@@ -1084,7 +1085,8 @@ int64_t zlz4f_compress_frame_using_dict_ex(const uint8_t *src, size_t src_len, u
  *   zlz4f_decompress_multiframe.  zlz4f_decompress_multiframe_ex(.., ZLZ4F_DECODE_LINKED, ZLZ4F_SPLIT_LEGACY) returns what
  *   `lz4 -dc` prints for the file, or the code of the first member that is not OK.
  *
- * NOT SERVED: a dictionary per member.  Prefix and range decoding of a file: the file index and range calls below. */
+ * NOT SERVED: a dictionary per MEMBER chosen by dictID (a dictionary per FILE: the dictionary file calls below).  Prefix and
+ *   range decoding of a file: the file index and range calls below. */
 #define ZLZ4F_MEMBER_FRAME               1u
 #define ZLZ4F_MEMBER_SKIPPABLE           2u
 #define ZLZ4F_MEMBER_SKIPPABLE_TRUNCATED 3u
@@ -1285,8 +1287,8 @@ int64_t zlz4f_decompress_legacy_frame(const uint8_t *src, size_t src_len, uint8_
  *   result; dst_cap < b' - a' gives ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL in front of the decode.  IT BUILDS THE INDEX ON EVERY
  *   CALL (a size query of the whole file): a caller with several reads of one file keeps the index and uses the batch calls.
  *
- * NOT SERVED: dictionaries per member; history-aware ranges of linked members; a start offset inside one block.  (A
- *   serialised index: the seek table, below.) */
+ * NOT SERVED: a dictionary per MEMBER chosen by dictID (a dictionary per FILE: the _using_dict forms below); history-aware
+ *   ranges of linked members; a start offset inside one block.  (A serialised index: the seek table, below.) */
 size_t  zlz4f_batch_file_index_workspace(uint32_t nbuf, const uint64_t *split_totals);
 int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
                                uint32_t nbuf, const zlz4f_member *d_member, const uint64_t *d_mem_off,
@@ -1381,7 +1383,9 @@ int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t src_len, uint64_t
  *   before when it does not.  Both refuse, before the device check, an unknown flag bit (ZLZ4F_ERR_PARAMETER_INVALID),
  *   then a null pointer with a length, and a > b (ZLZ4_ERR_INVALID_STATE).
  *
- * NOT SERVED: a dictionary per member; linked members with history; a table anywhere but at the file's end; any foreign
+ * NOT SERVED: a dictionary per MEMBER chosen by dictID and zlz4f_seek_table with a dictionary (the table does not name a
+ *   dictionary; zlz4f_batch_append_seek_table takes the index of zlz4f_batch_file_index_using_dict as it takes any, and
+ *   the reader passes the dictionary again); linked members with history; a table anywhere but at the file's end; any foreign
  *   seekable format; a checksum over the table; partial staging in the host call -- zlz4f_decompress_file_range_ex still
  *   copies the WHOLE file to the device, where the tail and the touched blocks would do. */
 #define ZLZ4F_SEEK_TABLE_MAGICNUMBER  0x184D2A5Cu
@@ -1406,6 +1410,67 @@ int32_t zlz4f_batch_concat(void *stream, const uint8_t *d_src, const uint64_t *d
 int64_t zlz4f_seek_table(const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, uint32_t split_flags);
 int64_t zlz4f_decompress_file_range_ex(const uint8_t *src, size_t src_len, uint64_t a, uint64_t b, uint8_t *dst,
                                        size_t dst_cap, uint32_t split_flags, uint32_t range_flags);
+
+/* ---- dictionary .lz4 files: the file calls with ONE DICTIONARY PER FILE (no counterpart in the reference; DESIGN.md
+ * section 4.4m): what `lz4 -D dict` writes, and what zlz4f_batch_compress_frame_using_dict writes into a file.
+ * THE RULE.  File s uses dictionary d = d_dict_idx[s]; a NULL d_dict_idx means dictionary 0 for every file (the caller picks
+ *   the dictionary, as `lz4 -d -D dict file` does; the header's dictID stays informational).  T is the last D =
+ *   min(d_dict_len[d], 65536) bytes of the dictionary.  A legacy member's blocks never see T.  Every block of a frame member
+ *   whose FLG declares independent blocks (0x20) sees T.  Of a member that declares linked blocks, block 0 alone sees T --
+ *   the block whose word stands at the end of the member's header; its history is T alone -- and its blocks k >= 1 are
+ *   sized and decoded as independent blocks without a dictionary, exactly as the plain file calls do: one that refers to
+ *   earlier output or to T is ZLZ4F_ERR_DECOMPRESSION_FAILED in the index.  With D == 0 for every file each call answers
+ *   what its plain counterpart answers: bytes, statuses, index entries, d_skip.
+ * Dictionary arguments as in the dictionary frame calls, except that d_dict_idx has nbuf entries.  Dictionaries are
+ *   read-only and overlap no slot.  Workspace, alignment, null and refusal rules are the plain counterparts', with the
+ *   dictionary arrays among the arrays (d_dict_off 8-aligned, d_dict_len and d_dict_idx 4-aligned; with ndicts != 0
+ *   d_dict_len and, for the range call, d_dict_off not null); d_dict may be NULL only when every length is 0.
+ *   Asynchronous, a fixed launch sequence, nothing allocated, nothing read back.
+ * zlz4f_batch_file_index_using_dict: zlz4f_batch_file_index whose size pass gets a dictionary length per table entry, D
+ *   where the block sees T, else 0; no dictionary byte is read; the legacy family is unchanged.  d_dict_idx[s] >= ndicts
+ *   gives file s ZLZ4_ERR_INVALID_STATE in front of every other status of the file, the split's included; its room is
+ *   kept and the other files are unaffected.  Launches: the plain call's and two small kernels.
+ * zlz4f_batch_decompress_file_range_using_dict: zlz4f_batch_decompress_file_range where step 1 also refuses a range whose
+ *   file has d_dict_idx >= ndicts (ZLZ4_ERR_INVALID_STATE) and every item gets a dictionary descriptor, { d_dict_off[d] +
+ *   d_dict_len[d] - D, D } where its block sees T, else length 0.  A block wanted in full goes through the decoder of
+ *   zlz4_batch_decompress_safe_using_dict, the one that b' cuts through the prefix decoder with a dictionary; everything
+ *   else is unchanged.  INDEX, MEMBER TABLE AND DICTIONARY ARE THE CALLER'S DATA: a dictionary of another LENGTH than the
+ *   index was built with is answered per block by the decoder, right bytes or ZLZ4F_ERR_DECOMPRESSION_FAILED; other
+ *   CONTENT of the same length gives other bytes, as with liblz4.
+ * zlz4f_batch_multiframe_item_dicts: d_item_dict_idx[i] = d_dict_idx[s] for item i of buffer s (0 for a NULL index),
+ *   unchanged, so an out-of-range value gets the frame call's own refusal: what zlz4f_batch_decompress_frame_using_dict
+ *   and the _size_using_dict call take over the items of a split.  d_item_first: the split's, nbuf + 1 entries.  One
+ *   launch, one lane per item.  nbuf == 0 or nitems == 0 returns 0; a null or misaligned array: ZLZ4_ERR_INVALID_STATE.
+ * zlz4f_decompress_file_range_using_dict: zlz4f_decompress_file_range_ex with a dictionary, one file in HOST memory; the
+ *   dictionary's last 64 KiB alone are staged.  dict == NULL with dict_len > 0 is ZLZ4_ERR_INVALID_STATE among the other
+ *   null checks; dict_len == 0 is exactly the _ex call.
+ * NOT SERVED: a dictionary per MEMBER chosen by dictID; linked members with history; the frame range calls with a
+ *   dictionary; zlz4f_seek_table with a dictionary (the table does not name one); partial staging in the host call. */
+size_t  zlz4f_batch_file_index_using_dict_workspace(uint32_t nbuf, const uint64_t *split_totals);
+int32_t zlz4f_batch_file_index_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                          const uint64_t *d_src_len, uint32_t nbuf, const zlz4f_member *d_member,
+                                          const uint64_t *d_mem_off, const int64_t *d_split_result,
+                                          const uint64_t *d_item_first, const uint64_t *d_item_off, const uint64_t *d_item_len,
+                                          const uint64_t *d_leg_len, const uint64_t *split_totals, zlz4f_index_entry *d_index,
+                                          uint64_t *d_idx_off, uint64_t idx_cap, int64_t *d_result, const uint32_t *d_dict_len,
+                                          uint32_t ndicts, const uint32_t *d_dict_idx, void *d_workspace,
+                                          size_t workspace_bytes);
+size_t  zlz4f_batch_decompress_file_range_using_dict_workspace(uint32_t nranges, uint32_t max_items);
+int32_t zlz4f_batch_decompress_file_range_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                     const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
+                                                     const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nbuf,
+                                                     const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                                                     const int64_t *d_split_result, const zlz4f_range *d_range, uint8_t *d_dst,
+                                                     const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_skip,
+                                                     int64_t *d_result, uint32_t nranges, uint32_t max_items,
+                                                     const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                     const uint32_t *d_dict_len, uint32_t ndicts, const uint32_t *d_dict_idx,
+                                                     void *d_workspace, size_t workspace_bytes);
+int32_t zlz4f_batch_multiframe_item_dicts(void *stream, const uint64_t *d_item_first, uint32_t nbuf, uint32_t nitems,
+                                          const uint32_t *d_dict_idx, uint32_t *d_item_dict_idx);
+int64_t zlz4f_decompress_file_range_using_dict(const uint8_t *src, size_t src_len, uint64_t a, uint64_t b, uint8_t *dst,
+                                               size_t dst_cap, uint32_t split_flags, uint32_t range_flags,
+                                               const uint8_t *dict, size_t dict_len);
 
 /* ======================================================================
  * 4. Introspection

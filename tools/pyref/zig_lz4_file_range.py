@@ -115,15 +115,17 @@ def _legacy_block(data):
     return block_size(data)
 
 
-def file_index(buf, legacy=True, idx_cap=None):
+def file_index(buf, legacy=True, idx_cap=None, frame_member=None):
     """zlz4f_batch_file_index for one buffer -> (idx_n, entries).  The first member in member order that is not OK decides;
-    the capacity is the last check; an error writes no entry."""
+    the capacity is the last check; an error writes no entry.  frame_member: what indexes one frame member (body -> (n,
+    entries)); the dictionary model (zig_lz4_file_dict) passes its own."""
+    frame_member = frame_member or _frame_member
     buf = bytes(buf)
     entries, dec, end = [], 0, 0
     for pos, ln, kind in split(buf, legacy):
         body = buf[pos:pos + ln]
         if kind == FRAME:
-            n, ents = _frame_member(body)
+            n, ents = frame_member(body)
             if n < 0:
                 return n, []
             entries += [(pos + p, dec + d) for p, d in ents[:n]]
@@ -213,9 +215,11 @@ def range_items(buf, members, entries, idx_n, a, b, dst_cap=None, reserved=0, bu
     return 0 if go is None else go[3] - go[2] + 1
 
 
-def decompress_file_range(buf, members, entries, idx_n, a, b, dst_cap=None, reserved=0, buf_ok=True, fits=True):
+def decompress_file_range(buf, members, entries, idx_n, a, b, dst_cap=None, reserved=0, buf_ok=True, fits=True,
+                          block_dict=None):
     """zlz4f_batch_decompress_file_range for one range -> (result, skip, slot bytes).  dst_cap None: what the plan gives.
-    fits False: the range's items lie past max_items.  On an error skip is 0 and the slot is b""."""
+    fits False: the range's items lie past max_items.  On an error skip is 0 and the slot is b"".  block_dict: pos -> the
+    dictionary bytes the block at pos is decoded with (b"": none); the dictionary model (zig_lz4_file_dict) passes it."""
     buf = bytes(buf)
     st, go = _admit(buf, members, entries, idx_n, a, b, dst_cap, reserved, buf_ok)
     if go is None:
@@ -257,6 +261,12 @@ def decompress_file_range(buf, members, entries, idx_n, a, b, dst_cap=None, rese
             if sz != step:
                 return INVALID_STATE, 0, b""
             slot += data[:want]
+        elif block_dict is not None and block_dict(p):                 # the decoders that take a dictionary
+            T = block_dict(p)
+            r, out = fr.decompress_generic(data, step, step, T) if want == step else fr.decompress_prefix(data, want, T)
+            if r != want:
+                return F_DECOMPRESSION_FAILED, 0, b""
+            slot += out
         elif want == step:                                             # wanted in full: the safe decoder, exact capacity
             r, out = fr._full(data, step)
             if r != step:

@@ -167,6 +167,13 @@ SYMBOLS = {
     "zlz4f_batch_concat": (_I32, [_VP] * 5 + [_U32, _U32] + [_VP] * 5 + [_SZ]),
     "zlz4f_seek_table": (_I64, [_VP, _SZ, _VP, _SZ, _U32]),
     "zlz4f_decompress_file_range_ex": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ, _U32, _U32]),
+    "zlz4f_batch_file_index_using_dict_workspace": (_SZ, [_U32, _VP]),
+    "zlz4f_batch_file_index_using_dict": (_I32, [_VP] * 4 + [_U32] + [_VP] * 10 + [C.c_uint64, _VP, _VP, _U32, _VP, _VP, _SZ]),
+    "zlz4f_batch_decompress_file_range_using_dict_workspace": (_SZ, [_U32, _U32]),
+    "zlz4f_batch_decompress_file_range_using_dict": (_I32, [_VP] * 7 + [_U32] + [_VP] * 9 + [_U32, _U32] + [_VP] * 3 +
+                                                     [_U32, _VP, _VP, _SZ]),
+    "zlz4f_batch_multiframe_item_dicts": (_I32, [_VP, _VP, _U32, _U32, _VP, _VP]),
+    "zlz4f_decompress_file_range_using_dict": (_I64, [_VP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ, _U32, _U32, _VP, _SZ]),
     "zlz4f_batch_multiframe_split": (_I32, [_VP] * 4 + [_U32] + [_VP] * 9),
     "zlz4f_batch_multiframe_plan": (_I32, [_VP] * 3 + [_U32, _U32] + [_VP] * 5),
     "zlz4f_batch_multiframe_finish": (_I32, [_VP] * 7 + [_U32, _VP]),
@@ -1210,11 +1217,13 @@ class lz4f:
         return out
 
     @staticmethod
-    def decodeMultiframes(sp, flags=0, align=0, d_dst=None):
+    def decodeMultiframes(sp, flags=0, align=0, d_dst=None, dicts=None):
         """Size query, plan, one read-back of the arena size, decode and finish over a MultiframeSplit -> MultiframeDecode.
         d_dst: an arena of the caller's (at least the planned bytes), else one is allocated.  Where the split recorded
         legacy members (sp.nlegacy) the legacy size query and decode run over the same items and multiframeSelectBatch
-        merges their answers into size and item_result."""
+        merges their answers into size and item_result.  dicts (a FileDicts): one dictionary per buffer, spread over the
+        items by multiframeItemDictsBatch; the size query and the decode are then the _using_dict
+        frame calls (which decode linked frames with their history; `flags` is not used then).  Legacy items see none."""
         import torch
         dev = sp.d_src.device
         nbuf, ni = sp.src_len.numel(), sp.nitems
@@ -1225,7 +1234,12 @@ class lz4f:
 
         dd.size, dd.dst_off, dd.dst_cap, dd.item_result = i64(ni), i64(ni), i64(ni), i64(ni)
         dd.out_off, dd.out_size, dd.result, totals = i64(nbuf), i64(nbuf), i64(nbuf), i64(2)
-        if ni:
+        if ni and dicts is not None:
+            item_idx = torch.zeros(ni, dtype=torch.int32, device=dev)
+            lz4f.multiframeItemDictsBatch(sp.item_first, ni, dicts.idx, item_idx)
+            lz4f.frameDecompressedSizeUsingDictBatch(sp.d_src, sp.item_off, sp.item_len, dd.size, dicts.dict_len, item_idx,
+                                                     max_blocks=sp.max_blocks)
+        elif ni:
             lz4f.frameDecompressedSizeBatch(sp.d_src, sp.item_off, sp.item_len, dd.size, max_blocks=sp.max_blocks,
                                             flags=flags)
         if sp.nlegacy:
@@ -1239,7 +1253,11 @@ class lz4f:
         elif d_dst.numel() < dd.arena_bytes:
             raise ValueError("d_dst holds %d bytes, the plan needs %d" % (d_dst.numel(), dd.arena_bytes))
         dd.d_dst = d_dst
-        if ni:
+        if ni and dicts is not None:
+            lz4f.decompressFrameUsingDictBatch(sp.d_src, sp.item_off, sp.item_len, d_dst, dd.dst_off, dd.dst_cap,
+                                               dd.item_result, dicts.d_dict, dicts.dict_off, dicts.dict_len, item_idx,
+                                               max_blocks=sp.max_blocks)
+        elif ni:
             lz4f.decompressFrameBatch(sp.d_src, sp.item_off, sp.item_len, d_dst, dd.dst_off, dd.dst_cap, dd.item_result,
                                       max_blocks=sp.max_blocks, flags=flags)
         if sp.nlegacy:
@@ -1286,11 +1304,32 @@ class lz4f:
     def decompressFiles(buffers, align=0, device="cuda"):
         """Every buffer a whole .lz4 file -- modern frames (linked blocks too), skippable frames and legacy frames in any
         order -- decoded in one batch: -> what `lz4 -dc` prints for each file, or the code of the first member that is not
-        OK.  decompressMultiframes(buffers, flags=DECODE_LINKED, legacy=True); a device that is no GPU raises DeviceError."""
+        OK.  decompressMultiframes(buffers, flags=DECODE_LINKED, legacy=True); a device that is no GPU raises DeviceError.
+        Files written against a dictionary: decompressFilesUsingDict."""
         import torch
         if torch.device(device).type != "cuda":
             _check(ERR_DEVICE)
         return lz4f.decompressMultiframes(buffers, lz4f.DECODE_LINKED, align, device, legacy=True)
+
+    @staticmethod
+    def decompressFilesUsingDict(buffers, dicts, dict_index=None, align=0, device="cuda"):
+        """decompressFiles for files written against a dictionary: file s is decoded with dicts[dict_index[s]] (dict_index
+        None: dicts[0]) -> what `lz4 -dc -D dict` prints for each file, or the code of the first member that is not OK.
+        Linked members are decoded with their history behind the dictionary; legacy members see no dictionary.  A
+        dict_index outside dicts raises ValueError.  (A function of its own: decompressFiles keeps its three parameters.)"""
+        import torch
+        if torch.device(device).type != "cuda":
+            _check(ERR_DEVICE)
+        if dict_index is not None and (len(dict_index) != len(buffers) or
+                                       any(not 0 <= int(k) < len(dicts) for k in dict_index)):
+            raise ValueError("dict_index: one index into dicts per buffer")
+        if dict_index is None and len(buffers) and not len(dicts):
+            raise ValueError("dicts: at least one dictionary")
+        if not len(buffers):
+            return []
+        dd = lz4f.decodeMultiframes(lz4f.splitMultiframes(buffers, device, True), 0, align,
+                                    dicts=lz4f.stageFileDicts(dicts, dict_index, device))
+        return _unstage(dd.d_dst, dd.out_off.cpu().tolist(), dd.result)
 
     @staticmethod
     def decompressFile(src):
@@ -1348,43 +1387,120 @@ class lz4f:
                                                        _ptr(dst_off), _ptr(dst_cap), _ptr(skip), _ptr(result), nr, max_items,
                                                        _ptr(workspace), workspace.numel()))
 
-    class FileIndex:
-        """What fileIndex returns: the staged buffers and their split (.split, a MultiframeSplit), the device index (index,
-        idx_off) and the per-file results: idx_n on the device, `results` on the host (a block count or a code per file)."""
-
-        def __init__(self, split, index, idx_off, idx_n, results):
-            self.split, self.index, self.idx_off, self.idx_n, self.results = split, index, idx_off, idx_n, results
-            self.d_src, self.src_off, self.src_len = split.d_src, split.src_off, split.src_len
+    # dictionary .lz4 files: one dictionary per file (include/zlz4_amd.h)
+    @staticmethod
+    def fileIndexUsingDictBatchWorkspace(nbuf, totals):
+        return lib().zlz4f_batch_file_index_using_dict_workspace(nbuf, lz4f._split_totals(totals))
 
     @staticmethod
-    def fileIndex(buffers, device="cuda", legacy=True):
+    def fileIndexUsingDictBatch(d_src, src_off, src_len, member, mem_off, split_result, item_first, item_off, item_len,
+                                leg_len, totals, index, idx_off, result, dict_len, dict_idx=None, idx_cap=None, workspace=None):
+        """zlz4f_batch_file_index_using_dict: fileIndexBatch with the dictionary lengths (int32 [ndicts]) and the dictionary
+        of every buffer (dict_idx int32 [nbuf]; None: dictionary 0)."""
+        import torch
+        nbuf = src_len.numel()
+        t = lz4f._split_totals(totals)
+        if idx_cap is None:
+            idx_cap = index.shape[0]
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_file_index_using_dict_workspace(nbuf, t)), dtype=torch.uint8,
+                                    device=d_src.device)
+        _check(lib().zlz4f_batch_file_index_using_dict(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), nbuf,
+                                                       _ptr(member), _ptr(mem_off), _ptr(split_result), _ptr(item_first),
+                                                       _ptr(item_off), _ptr(item_len), _ptr(leg_len), t, _ptr(index),
+                                                       _ptr(idx_off), idx_cap, _ptr(result), _ptr(dict_len),
+                                                       dict_len.numel(), _ptr(dict_idx), _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def decompressFileRangeUsingDictBatchWorkspace(nranges, max_items):
+        return lib().zlz4f_batch_decompress_file_range_using_dict_workspace(nranges, max_items)
+
+    @staticmethod
+    def decompressFileRangeUsingDictBatch(d_src, src_off, src_len, index, idx_off, idx_n, member, mem_off, split_result,
+                                          ranges, d_dst, dst_off, dst_cap, skip, result, max_items, d_dict, dict_off,
+                                          dict_len, dict_idx=None, workspace=None):
+        """zlz4f_batch_decompress_file_range_using_dict: decompressFileRangeBatch with the dictionaries (layout as
+        compressFrameUsingDictBatch) and the dictionary of every buffer (dict_idx int32 [nbuf]; None: dictionary 0)."""
+        import torch
+        nr = ranges.shape[0]
+        if workspace is None:
+            workspace = torch.empty(max(16, lib().zlz4f_batch_decompress_file_range_using_dict_workspace(nr, max_items)),
+                                    dtype=torch.uint8, device=d_src.device)
+        _check(lib().zlz4f_batch_decompress_file_range_using_dict(
+            _stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), _ptr(index), _ptr(idx_off), _ptr(idx_n), idx_n.numel(),
+            _ptr(member), _ptr(mem_off), _ptr(split_result), _ptr(ranges), _ptr(d_dst), _ptr(dst_off), _ptr(dst_cap),
+            _ptr(skip), _ptr(result), nr, max_items, _ptr(d_dict), _ptr(dict_off), _ptr(dict_len), dict_len.numel(),
+            _ptr(dict_idx), _ptr(workspace), workspace.numel()))
+
+    @staticmethod
+    def multiframeItemDictsBatch(item_first, nitems, dict_idx, item_dict_idx):
+        """zlz4f_batch_multiframe_item_dicts: item_dict_idx (int32 [nitems]) = the dict_idx (int32 [nbuf]; None: 0) of every
+        item's buffer; item_first int64 [nbuf + 1]."""
+        _check(lib().zlz4f_batch_multiframe_item_dicts(_stream(), _ptr(item_first), item_first.numel() - 1, nitems,
+                                                       _ptr(dict_idx), _ptr(item_dict_idx)))
+
+    class FileDicts:
+        """Dictionaries staged for the file calls: d_dict, dict_off (int64), dict_len (int32) and idx (int32, one per file,
+        or None: dictionary 0 for every file)."""
+
+        def __init__(self, d_dict, dict_off, dict_len, idx):
+            self.d_dict, self.dict_off, self.dict_len, self.idx = d_dict, dict_off, dict_len, idx
+
+    @staticmethod
+    def stageFileDicts(dicts, dict_index=None, device="cuda"):
+        """`dicts` (byte strings) and the dictionary of every file (dict_index; None: dicts[0]) on the device -> FileDicts;
+        dicts None -> None.  A FileDicts passes through."""
+        if dicts is None or isinstance(dicts, lz4f.FileDicts):
+            return dicts
+        d_dict, dict_off, dict_len, idx, _ = lz4f._stage_dicts(dicts, dict_index, 0, device)
+        return lz4f.FileDicts(d_dict, dict_off, dict_len, idx)
+
+    class FileIndex:
+        """What fileIndex returns: the staged buffers and their split (.split, a MultiframeSplit), the device index (index,
+        idx_off) and the per-file results: idx_n on the device, `results` on the host (a block count or a code per file).
+        dicts: the staged dictionaries (a FileDicts) the index was built with, or None; decompressFileRanges uses them."""
+
+        def __init__(self, split, index, idx_off, idx_n, results, dicts=None):
+            self.split, self.index, self.idx_off, self.idx_n, self.results = split, index, idx_off, idx_n, results
+            self.d_src, self.src_off, self.src_len = split.d_src, split.src_off, split.src_len
+            self.dicts = dicts
+
+    @staticmethod
+    def fileIndex(buffers, device="cuda", legacy=True, dicts=None, dict_index=None):
         """Stage `buffers` -- whole .lz4 files -- split them and index them (zlz4f_batch_file_index) -> FileIndex, to be read
         any number of times with decompressFileRanges.  A file whose size query fails keeps its code in .results.  legacy:
-        legacy frames are members (False: a legacy magic is FrameTypeUnknown)."""
+        legacy frames are members (False: a legacy magic is FrameTypeUnknown).  dicts: file s was written against
+        dicts[dict_index[s]] (dict_index None: dicts[0]); the FileIndex keeps the staged dictionaries."""
         import torch
         if torch.device(device).type != "cuda":
             _check(ERR_DEVICE)
-        return lz4f.indexSplit(lz4f.splitMultiframes(buffers, device, legacy))
+        return lz4f.indexSplit(lz4f.splitMultiframes(buffers, device, legacy), dicts, dict_index)
 
     @staticmethod
-    def indexSplit(sp):
-        """fileIndex over a MultiframeSplit (splitMultiframes, splitStaged) -> FileIndex."""
+    def indexSplit(sp, dicts=None, dict_index=None):
+        """fileIndex over a MultiframeSplit (splitMultiframes, splitStaged) -> FileIndex.  dicts: as fileIndex, or a
+        FileDicts."""
         import torch
         nbuf, device = sp.src_len.numel(), sp.d_src.device
         cap = sp.max_blocks + sp.legacy_blocks + nbuf
         index = torch.zeros((max(1, cap), 2), dtype=torch.int64, device=device)
         idx_off = torch.zeros(nbuf + 1, dtype=torch.int64, device=device)
         idx_n = torch.zeros(nbuf, dtype=torch.int64, device=device)
-        if nbuf:
+        fd = lz4f.stageFileDicts(dicts, dict_index, device)
+        totals = (sp.nitems, sp.max_blocks, sp.nlegacy, sp.legacy_blocks)
+        if nbuf and fd is not None:
+            lz4f.fileIndexUsingDictBatch(sp.d_src, sp.src_off, sp.src_len, sp.member, sp.mem_off, sp.result, sp.item_first,
+                                         sp.item_off, sp.item_len, sp.leg_len, totals, index, idx_off, idx_n, fd.dict_len,
+                                         fd.idx, cap)
+        elif nbuf:
             lz4f.fileIndexBatch(sp.d_src, sp.src_off, sp.src_len, sp.member, sp.mem_off, sp.result, sp.item_first, sp.item_off,
-                                sp.item_len, sp.leg_len, (sp.nitems, sp.max_blocks, sp.nlegacy, sp.legacy_blocks), index,
-                                idx_off, idx_n, cap)
-        return lz4f.FileIndex(sp, index, idx_off, idx_n, idx_n.cpu().tolist())
+                                sp.item_len, sp.leg_len, totals, index, idx_off, idx_n, cap)
+        return lz4f.FileIndex(sp, index, idx_off, idx_n, idx_n.cpu().tolist(), fd)
 
     @staticmethod
     def decompressFileRanges(indexed, ranges, align=0):
         """Bytes [a, b) of file `buf` for every (buf, a, b) of `ranges` (both clamped to the file's size) -> list of bytes
-        or error codes.  Plan (planFrameRanges: the plan reads the index alone), one read-back of the totals, decode, one
+        or error codes.  An index that carries dictionaries (indexed.dicts) is read with them.  Plan (planFrameRanges: the plan reads the index alone), one read-back of the totals, decode, one
         read-back of the data."""
         import torch
         nr = len(ranges)
@@ -1401,33 +1517,53 @@ class lz4f:
         d_dst = torch.empty(max(1, arena), dtype=torch.uint8, device=dev)
         skip = torch.empty(nr, dtype=torch.int64, device=dev)
         result = torch.empty(nr, dtype=torch.int64, device=dev)
-        lz4f.decompressFileRangeBatch(sp.d_src, sp.src_off, sp.src_len, indexed.index, indexed.idx_off, indexed.idx_n,
-                                      sp.member, sp.mem_off, sp.result, d_range, d_dst, dst_off, dst_cap, skip, result, items)
+        fd = getattr(indexed, "dicts", None)
+        if fd is not None:
+            lz4f.decompressFileRangeUsingDictBatch(sp.d_src, sp.src_off, sp.src_len, indexed.index, indexed.idx_off,
+                                                   indexed.idx_n, sp.member, sp.mem_off, sp.result, d_range, d_dst, dst_off,
+                                                   dst_cap, skip, result, items, fd.d_dict, fd.dict_off, fd.dict_len, fd.idx)
+        else:
+            lz4f.decompressFileRangeBatch(sp.d_src, sp.src_off, sp.src_len, indexed.index, indexed.idx_off, indexed.idx_n,
+                                          sp.member, sp.mem_off, sp.result, d_range, d_dst, dst_off, dst_cap, skip, result,
+                                          items)
         back = torch.stack((dst_off, skip, result)).cpu().tolist()
         host = d_dst.cpu().numpy().tobytes()
         return [host[o + s:o + s + r] if r >= 0 else r for o, s, r in zip(*back)]
 
     @staticmethod
-    def decompressFilePrefixes(buffers, n, device="cuda", legacy=True):
-        """The first n bytes of every file (n: one int, or one per file): fileIndex plus the ranges (s, 0, n)."""
+    def decompressFilePrefixes(buffers, n, device="cuda", legacy=True, dicts=None, dict_index=None):
+        """The first n bytes of every file (n: one int, or one per file): fileIndex plus the ranges (s, 0, n).  dicts,
+        dict_index: as fileIndex."""
         ns = [n] * len(buffers) if isinstance(n, int) else list(n)
         if len(ns) != len(buffers):
             raise ValueError("n: one int, or one per buffer")
         if not len(buffers):
             return []
-        return lz4f.decompressFileRanges(lz4f.fileIndex(buffers, device, legacy), [(s, 0, k) for s, k in enumerate(ns)])
+        return lz4f.decompressFileRanges(lz4f.fileIndex(buffers, device, legacy, dicts, dict_index),
+                                         [(s, 0, k) for s, k in enumerate(ns)])
 
     @staticmethod
-    def decompressFileRange(src, a, b, legacy=True, seek_table=False):
+    def decompressFileRange(src, a, b, legacy=True, seek_table=False, dict=None):
         """zlz4f_decompress_file_range: bytes [a, b) of one file in host memory (both clamped to the file's size).  The
         index is built on every call; several reads of one file: fileIndex + decompressFileRanges.  seek_table:
         zlz4f_decompress_file_range_ex with RANGE_SEEK_TABLE -- the tables come from the file's seek table where it ends in
-        a well-formed one."""
+        a well-formed one.  dict: zlz4f_decompress_file_range_using_dict -- the file was written against `dict`."""
         s, n = _in(src)
         flags = lz4f.SPLIT_LEGACY if legacy else 0
         cap = max(0, min(b, 1 << 62) - a)
-        if cap > 1 << 20:                              # (b may lie far behind the file's end)
+        if cap > 1 << 20 and dict is None:             # (b may lie far behind the file's end)
             cap = min(cap, max(0, lz4f.multiframeDecompressedSize(src, 0, legacy) - a))
+        if dict is not None:                           # (no host size query takes a dictionary: the room grows on
+            dd, dn = _in(dict)                         # DstMaxSizeTooSmall, which the call answers in front of the decode)
+            want, cap = cap, min(cap, 1 << 20)
+            while True:
+                d = (C.c_uint8 * max(1, cap))()
+                r = lib().zlz4f_decompress_file_range_using_dict(C.addressof(s), n, a, b, C.addressof(d), cap, flags,
+                                                                 lz4f.RANGE_SEEK_TABLE if seek_table else 0,
+                                                                 C.addressof(dd) if dn else None, dn)
+                if r != -111 or cap >= want:
+                    return bytes(d[:_check(r)])
+                cap = min(want, cap * 16)
         d = (C.c_uint8 * max(1, cap))()
         if seek_table:
             r = _check(lib().zlz4f_decompress_file_range_ex(C.addressof(s), n, a, b, C.addressof(d), cap, flags,
@@ -1494,13 +1630,14 @@ class lz4f:
         return result
 
     @staticmethod
-    def appendSeekTables(buffers, legacy=True, device="cuda"):
+    def appendSeekTables(buffers, legacy=True, device="cuda", dicts=None, dict_index=None):
         """Every file of `buffers` with its seek table appended -> list of files (bytes) or the refusal's code: fileIndex,
-        a copy of the files into slots with room (concatBatch, one item per file), the append, one read-back."""
+        a copy of the files into slots with room (concatBatch, one item per file), the append, one read-back.  dicts,
+        dict_index: as fileIndex (the table does not name the dictionary; the reader passes it again)."""
         import torch
         if not len(buffers):
             return []
-        ix = lz4f.fileIndex(buffers, device, legacy)
+        ix = lz4f.fileIndex(buffers, device, legacy, dicts, dict_index)
         sp = ix.split
         nbuf = len(buffers)
         caps = [len(b) + lz4f.seekTableBound(max(0, nm), max(0, nb)) for b, nm, nb in zip(buffers, sp.results, ix.results)]
@@ -1513,11 +1650,13 @@ class lz4f:
         return _unstage(d_buf, _offsets(slots), lz4f._appendTables(ix, d_buf, buf_off, buf_cap))
 
     @staticmethod
-    def loadFileIndex(buffers, device="cuda"):
+    def loadFileIndex(buffers, device="cuda", dicts=None, dict_index=None):
         """Stage `buffers` -- files that end in a seek table -- and load their tables (zlz4f_batch_load_seek_table: count
         mode, one read-back of the totals, record mode) -> FileIndex, which decompressFileRanges takes as it takes
         fileIndex's.  No block header is walked.  A file without a table, or with one out of shape, keeps its code
-        (InvalidState) in .results.  The FileIndex's .split carries d_src, src_off, src_len, member, mem_off and result."""
+        (InvalidState) in .results.  The FileIndex's .split carries d_src, src_off, src_len, member, mem_off and result.
+        dicts, dict_index: the dictionaries the files were written against (the table does not name them); they are staged
+        and kept in the FileIndex, as fileIndex keeps them."""
         import torch
         if torch.device(device).type != "cuda":
             _check(ERR_DEVICE)
@@ -1539,7 +1678,7 @@ class lz4f:
         lz4f.loadSeekTableBatch(sp.d_src, sp.src_off, sp.src_len, sp.count, totals, sp.member, sp.mem_off, sp.count, sp.result,
                                 index, idx_off, idx_n, rooms)
         sp.results = sp.result.cpu().tolist()
-        return lz4f.FileIndex(sp, index, idx_off, idx_n, idx_n.cpu().tolist())
+        return lz4f.FileIndex(sp, index, idx_off, idx_n, idx_n.cpu().tolist(), lz4f.stageFileDicts(dicts, dict_index, device))
 
     @staticmethod
     def seekTable(src, legacy=True):
@@ -1555,20 +1694,29 @@ class lz4f:
             cap *= 16
 
     @staticmethod
-    def compressFiles(items, prefs=None, frame_size=4 << 20, seek_table=True, batch_flags=0, device="cuda"):
+    def compressFiles(items, prefs=None, frame_size=4 << 20, seek_table=True, batch_flags=0, device="cuda", dicts=None,
+                      dict_index=None):
         """Every byte string of `items` as one seekable .lz4 file -> list of files (bytes) or error codes.  An input becomes
         ceil(len / frame_size) independent frames (an empty one: one empty frame), compressed in place as chunks of the
         staged inputs by compressFrameBatch and laid back to back on the device (concatBatch); with seek_table the files
-        are split and indexed there (splitStaged, indexSplit) and their table is appended."""
+        are split and indexed there (splitStaged, indexSplit) and their table is appended.
+        dicts: file s is written against dicts[dict_index[s]] (dict_index None: dicts[0]): the chunks are compressed by
+        compressFrameUsingDictBatchEx (prefs.compression_level 3..9: the HC dictionary compressor; 2 and 10..12 keep its
+        refusal) and the index is built with the dictionary.  The seek table does not name the dictionary: the reader
+        passes it again (loadFileIndex(files, dicts=...)).  A small frame_size trades ratio -- every frame starts from the
+        dictionary alone and pays its header -- for less decoded per read.  prefs.block_mode == 0 (linked
+        blocks) with frame_size above the block size raises ValueError: a linked frame of several blocks cannot be indexed."""
         import torch
         if frame_size < 1:
             raise ValueError("frame_size: at least 1")
+        bs = lz4f.BLOCK_SIZES.get(prefs.block_size_id if prefs is not None else 0, 64 << 10)
+        if dicts is not None and (prefs is None or prefs.block_mode == 0) and frame_size > bs:
+            raise ValueError("linked blocks (prefs.block_mode 0) with frame_size above the block size: not indexable")
         nbuf = len(items)
         if not nbuf:
             return []
         lens = [len(b) for b in items]
         d_src, _, _ = _stage(items, device)
-        bs = lz4f.BLOCK_SIZES.get(prefs.block_size_id if prefs is not None else 0, 64 << 10)
         c_off, c_len, first, blocks = [], [], [0], []
         for o, n in zip(_offsets(lens), lens):
             for j in range(max(1, -(-n // frame_size))):
@@ -1580,8 +1728,21 @@ class lz4f:
         t = lambda v: torch.tensor(v, dtype=torch.int64, device=device)    # noqa: E731
         d_frames = torch.empty(max(1, sum(caps)), dtype=torch.uint8, device=device)
         f_off, f_len = t(_offsets(caps)), torch.zeros(len(caps), dtype=torch.int64, device=device)
-        lz4f.compressFrameBatch(d_src, t(c_off), t(c_len), d_frames, f_off, t(caps), f_len, prefs, batch_flags,
-                                max_blocks=sum(blocks))
+        fd = lz4f.stageFileDicts(dicts, dict_index, device)
+        if fd is not None:
+            c_idx = None
+            if fd.idx is not None:
+                per_file = fd.idx.cpu().tolist()
+                c_idx = torch.tensor([per_file[s] for s in range(nbuf) for _ in range(first[s + 1] - first[s])],
+                                     dtype=torch.int32, device=device)
+            # (the _ex call: at the fast level it is compressFrameUsingDictBatch)
+            lz4f.compressFrameUsingDictBatchEx(
+                d_src, t(c_off), t(c_len), d_frames, f_off, t(caps), f_len, fd.d_dict, fd.dict_off, fd.dict_len, c_idx, prefs,
+                batch_flags, max_blocks=sum(blocks), max_src_len=max(c_len),
+                max_dict_len=min(65536, int(fd.dict_len.max().item()) if fd.dict_len.numel() else 0))
+        else:
+            lz4f.compressFrameBatch(d_src, t(c_off), t(c_len), d_frames, f_off, t(caps), f_len, prefs, batch_flags,
+                                    max_blocks=sum(blocks))
         room = [sum(caps[first[s]:first[s + 1]]) +
                 (lz4f.seekTableBound(first[s + 1] - first[s], blocks[s]) if seek_table else 0) for s in range(nbuf)]
         slots = [(c + 15) & ~15 for c in room]
@@ -1591,7 +1752,7 @@ class lz4f:
         lz4f.concatBatch(d_frames, f_off, f_len, t(first), d_files, file_off, file_cap, joined)
         if not seek_table:
             return _unstage(d_files, _offsets(slots), joined)
-        ix = lz4f.indexSplit(lz4f.splitStaged(d_files, file_off, torch.clamp(joined, min=0), legacy=True))
+        ix = lz4f.indexSplit(lz4f.splitStaged(d_files, file_off, torch.clamp(joined, min=0), legacy=True), fd)
         result = lz4f._appendTables(ix, d_files, file_off, file_cap)
         return _unstage(d_files, _offsets(slots), torch.where(joined < 0, joined, result))
 

@@ -534,6 +534,41 @@ inline Result decompressFileRangeEx(const std::uint8_t *src, std::size_t n, std:
                                     std::uint32_t range_flags = ZLZ4F_RANGE_SEEK_TABLE) {
     return wrap(zlz4f_decompress_file_range_ex(src, n, a, b, dst, cap, split_flags, range_flags));
 }
+// dictionary files (include/zlz4_amd.h; no counterpart in the reference): the file calls with ONE DICTIONARY PER FILE.
+// FrameDicts here has one idx entry per buffer (nullptr: dictionary 0).  Every block of a member that declares independent
+// blocks sees the dictionary's last 64 KiB, block 0 of one that declares linked blocks, no block of a legacy member.  The
+// index call needs the lengths alone.  multiframeItemDictsBatch spreads the per-buffer index over the items of a split, for
+// the dictionary frame calls; decompressFileRangeUsingDict is decompressFileRangeEx with a dictionary.
+inline std::size_t fileIndexUsingDictBatchWorkspace(std::uint32_t nbuf, const std::uint64_t *split_totals) {
+    return zlz4f_batch_file_index_using_dict_workspace(nbuf, split_totals);
+}
+inline Result fileIndexUsingDictBatch(void *stream, const Multiframes &m, const FileSplit &s, IndexEntry *d_index,
+                                      std::uint64_t *d_idx_off, std::uint64_t idx_cap, std::int64_t *d_idx_n,
+                                      const FrameDicts &d, void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_file_index_using_dict(stream, m.src, m.src_off, m.src_len, m.nbuf, s.member, s.mem_off,
+                                                  s.split_result, s.item_first, s.item_off, s.item_len, s.leg_len, s.split_totals,
+                                                  d_index, d_idx_off, idx_cap, d_idx_n, d.len, d.ndicts, d.idx, ws, ws_bytes));
+}
+inline std::size_t decompressFileRangeUsingDictBatchWorkspace(std::uint32_t nranges, std::uint32_t max_items) {
+    return zlz4f_batch_decompress_file_range_using_dict_workspace(nranges, max_items);
+}
+inline Result decompressFileRangeUsingDictBatch(void *stream, const Frames &f, const FrameIndex &x, const FileSplit &s,
+                                                const Range *d_range, std::uint64_t *d_skip, std::uint32_t nranges,
+                                                std::uint32_t max_items, const FrameDicts &d, void *ws, std::size_t ws_bytes) {
+    return wrap(zlz4f_batch_decompress_file_range_using_dict(stream, f.src, f.src_off, f.src_len, x.index, x.idx_off, x.idx_n,
+                                                             f.nframes, s.member, s.mem_off, s.split_result, d_range, f.dst,
+                                                             f.dst_off, f.dst_cap, d_skip, f.result, nranges, max_items, d.dict,
+                                                             d.off, d.len, d.ndicts, d.idx, ws, ws_bytes));
+}
+inline Result multiframeItemDictsBatch(void *stream, const std::uint64_t *d_item_first, std::uint32_t nbuf, std::uint32_t nitems,
+                                       const std::uint32_t *d_dict_idx, std::uint32_t *d_item_dict_idx) {
+    return wrap(zlz4f_batch_multiframe_item_dicts(stream, d_item_first, nbuf, nitems, d_dict_idx, d_item_dict_idx));
+}
+inline Result decompressFileRangeUsingDict(const std::uint8_t *src, std::size_t n, std::uint64_t a, std::uint64_t b,
+                                           std::uint8_t *dst, std::size_t cap, const std::uint8_t *dict, std::size_t dict_len,
+                                           std::uint32_t split_flags = ZLZ4F_SPLIT_LEGACY, std::uint32_t range_flags = 0) {
+    return wrap(zlz4f_decompress_file_range_using_dict(src, n, a, b, dst, cap, split_flags, range_flags, dict, dict_len));
+}
 // legacy frames (include/zlz4_amd.h; no counterpart in the reference): what `lz4 -l` writes -- the magic 0x184C2102, then
 // { u32 size, block } repeated.  One frame in host memory per call; `consumed` (may be null) receives where the frame ends,
 // which is where the next member of a concatenated file starts.  The batch calls are those of the C header.

@@ -19,6 +19,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <optional>
 
 #include "../../include/zlz4_amd.h"
 #include "zlz4_device.hpp"
@@ -2440,10 +2441,13 @@ struct BfrLayout {
     Region<uint64_t> data_off, cks_off, out_off;
     Region<uint32_t> data_len, flags, cks_ok, f_len, f_cap, p_len, p_cap, c_len, ierr;
     Region<int64_t> sizes_f, sizes_p;
+    // the items' dictionary descriptors (the file range call with dictionaries)
+    Region<uint64_t> e_off;
+    Region<uint32_t> e_len;
     size_t bytes = 0;
 };
 
-BfrLayout bfr_layout(uint32_t nranges, uint32_t max_items, void *ws = nullptr) {
+BfrLayout bfr_layout(uint32_t nranges, uint32_t max_items, void *ws = nullptr, bool dict = false) {
     const size_t m = max_items;
     BfrLayout L;
     Carver c{static_cast<uint8_t *>(ws)};
@@ -2451,6 +2455,7 @@ BfrLayout bfr_layout(uint32_t nranges, uint32_t max_items, void *ws = nullptr) {
     c.take(m, L.data_off, L.cks_off, L.out_off);
     c.take(m, L.data_len, L.flags, L.cks_ok, L.f_len, L.f_cap, L.p_len, L.p_cap, L.c_len, L.ierr);
     c.take(m, L.sizes_f, L.sizes_p);
+    if (dict) { c.take(m, L.e_off); c.take(m, L.e_len); }
     L.bytes = c.bytes;
     return L;
 }
@@ -2788,8 +2793,10 @@ __global__ __launch_bounds__(256) void k_ff_fold(FfTables T, const zlz4f_member 
 // what an item takes from its member
 struct FfMem {
     uint64_t end;       // the member's end inside the buffer
+    uint64_t first;     // the end of the member's header: where the word of its block 0 stands
     uint32_t bound;     // the most a block decodes to
     bool bc, legacy;    // block checksums (FLG 0x10); a legacy member: size words, no stored bit
+    bool linked;        // a frame member whose FLG declares linked blocks (0x20 clear)
 };
 
 // The member of buffer (s, n bytes; cnt members at m) that holds position pos, by bisection for the last member that
@@ -2815,33 +2822,62 @@ __device__ inline bool ff_member_of(const zlz4f_member *__restrict__ m, uint64_t
         out.bound = (uint32_t)ph.block_size;
         out.bc = (ph.flg & 0x10u) != 0;
         out.legacy = false;
+        out.linked = (ph.flg & 0x20u) == 0;
     } else if (kind == ZLZ4F_MEMBER_LEGACY) {
         if (M.len < 4 || zx_rd32(s + M.pos) != ZLZ4F_LEGACY_MAGICNUMBER) return false;
         first = M.pos + 4u;
         out.bound = ZLZ4F_LEGACY_BLOCK_SIZE;
         out.bc = false;
         out.legacy = true;
+        out.linked = false;
     } else return false;
     out.end = M.pos + M.len;
+    out.first = first;
     return pos >= first && pos <= out.end && out.end - pos >= 4u;
 }
 
+// A FILE has at most one dictionary: buffer s uses dictionary dd.idx[s], dictionary 0 for a null
+// index.  false: the buffer names none.  T = the last D = min(len, 65536) bytes of the dictionary.
+__device__ __forceinline__ bool ff_dict_of(const BfDict &dd, uint32_t s, uint32_t &D, uint64_t &t_off) {
+    const uint32_t d = dd.idx ? dd.idx[s] : 0u;
+    D = 0; t_off = 0;
+    if (d >= dd.n) return false;
+    const uint32_t len = dd.len[d];
+    D = len < 65536u ? len : 65536u;
+    if (dd.off) t_off = dd.off[d] + (len - D);
+    return true;
+}
+
+// the buffer that holds item i: the last s < nbuf with item_first[s] <= i (buffers without items share their first)
+__device__ __forceinline__ uint32_t ff_buffer_of(const uint64_t *__restrict__ item_first, uint32_t nbuf, uint64_t i) {
+    uint32_t lo = 0, hi = nbuf;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (item_first[mid] <= i) lo = mid + 1u; else hi = mid;
+    }
+    return lo ? lo - 1u : 0u;
+}
+
 // k_bfr_range for files: the same statuses in the same order, with the chain check of every pair (k, k + 1) made against
-// the member that holds pos[k].  Nothing but the tables is read for a range with a' == b'.
-__global__ __launch_bounds__(256) void k_ffr_range(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
-                                                   const uint64_t *__restrict__ src_len,
-                                                   const zlz4f_index_entry *__restrict__ index,
-                                                   const uint64_t *__restrict__ idx_off, const int64_t *__restrict__ idx_n,
-                                                   uint32_t nbuf, const zlz4f_member *__restrict__ member,
-                                                   const uint64_t *__restrict__ mem_off, const int64_t *__restrict__ split_result,
-                                                   const zlz4f_range *__restrict__ range, const uint64_t *__restrict__ dst_cap,
-                                                   uint32_t nranges, BRange *__restrict__ rg) {
+// the member that holds pos[k].  Nothing but the tables is read for a range with a' == b'.  kDict: a range whose file names
+// no dictionary is refused with the first statuses.
+template <bool kDict>
+__device__ __forceinline__ void ffr_range(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                          const uint64_t *__restrict__ src_len, const zlz4f_index_entry *__restrict__ index,
+                                          const uint64_t *__restrict__ idx_off, const int64_t *__restrict__ idx_n,
+                                          uint32_t nbuf, const zlz4f_member *__restrict__ member,
+                                          const uint64_t *__restrict__ mem_off, const int64_t *__restrict__ split_result,
+                                          const zlz4f_range *__restrict__ range, const uint64_t *__restrict__ dst_cap,
+                                          uint32_t nranges, BRange *__restrict__ rg, const BfDict &dd) {
     const uint32_t r = blockIdx.x * 4u + threadIdx.x / 64u, lane = threadIdx.x & 63u;
     if (r >= nranges) return;
     const zlz4f_range R = range[r];
     BRange G = {};
     int64_t st = 0;
-    if (R.frame >= nbuf || R.a > R.b || R.reserved != 0) st = ZLZ4_ERR_INVALID_STATE;
+    uint32_t D;
+    uint64_t t_off;
+    if (R.frame >= nbuf || R.a > R.b || R.reserved != 0 || (kDict && !ff_dict_of(dd, R.frame, D, t_off)))
+        st = ZLZ4_ERR_INVALID_STATE;
     else if (idx_n[R.frame] < 0) st = idx_n[R.frame];
     else {
         BfrSpan sp;
@@ -2874,24 +2910,56 @@ __global__ __launch_bounds__(256) void k_ffr_range(const uint8_t *__restrict__ s
     if (lane == 0) rg[r] = G;
 }
 
+__global__ __launch_bounds__(256) void k_ffr_range(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                                   const uint64_t *__restrict__ src_len,
+                                                   const zlz4f_index_entry *__restrict__ index,
+                                                   const uint64_t *__restrict__ idx_off, const int64_t *__restrict__ idx_n,
+                                                   uint32_t nbuf, const zlz4f_member *__restrict__ member,
+                                                   const uint64_t *__restrict__ mem_off, const int64_t *__restrict__ split_result,
+                                                   const zlz4f_range *__restrict__ range, const uint64_t *__restrict__ dst_cap,
+                                                   uint32_t nranges, BRange *__restrict__ rg) {
+    ffr_range<false>(src, src_off, src_len, index, idx_off, idx_n, nbuf, member, mem_off, split_result, range, dst_cap, nranges,
+                     rg, BfDict{});
+}
+
+__global__ __launch_bounds__(256) void k_ffr_range_dict(const uint8_t *__restrict__ src, const uint64_t *__restrict__ src_off,
+                                                        const uint64_t *__restrict__ src_len,
+                                                        const zlz4f_index_entry *__restrict__ index,
+                                                        const uint64_t *__restrict__ idx_off, const int64_t *__restrict__ idx_n,
+                                                        uint32_t nbuf, const zlz4f_member *__restrict__ member,
+                                                        const uint64_t *__restrict__ mem_off,
+                                                        const int64_t *__restrict__ split_result,
+                                                        const zlz4f_range *__restrict__ range,
+                                                        const uint64_t *__restrict__ dst_cap, uint32_t nranges,
+                                                        BRange *__restrict__ rg, BfDict dd) {
+    ffr_range<true>(src, src_off, src_len, index, idx_off, idx_n, nbuf, member, mem_off, split_result, range, dst_cap, nranges,
+                    rg, dd);
+}
+
 // k_bfr_expand for files, one lane per item: the item's member again (k_ffr_range has accepted it), the block word as that
 // member reads it -- a frame's header word, or a legacy size word that is neither 0 nor above the bound -- and where the
 // block has to end: at pos[k + 1] when that lies in the same member, else on the frame member's end mark or, for a chain
 // without one and for a legacy member, at the member's end.  The block's bytes are used only when all of that holds.
-__global__ void k_ffr_expand(const BRange *__restrict__ rg, uint32_t nranges, uint32_t max_items,
-                             const zlz4f_range *__restrict__ range, const uint8_t *__restrict__ src,
-                             const uint64_t *__restrict__ src_off, const uint64_t *__restrict__ src_len,
-                             const zlz4f_index_entry *__restrict__ index, const uint64_t *__restrict__ idx_off,
-                             const zlz4f_member *__restrict__ member, const uint64_t *__restrict__ mem_off,
-                             const int64_t *__restrict__ split_result, const uint64_t *__restrict__ dst_off, BfrTables T) {
+// kDict: the item's dictionary descriptor (e_off, e_len) -- T of its file where the block sees it: every block of a frame
+// member that declares independent blocks, block 0 (the word at the header's end) of one that declares linked blocks, no
+// block of a legacy member; length 0 elsewhere.
+template <bool kDict>
+__device__ __forceinline__ void ffr_expand(const BRange *__restrict__ rg, uint32_t nranges, uint32_t max_items,
+                                           const zlz4f_range *__restrict__ range, const uint8_t *__restrict__ src,
+                                           const uint64_t *__restrict__ src_off, const uint64_t *__restrict__ src_len,
+                                           const zlz4f_index_entry *__restrict__ index, const uint64_t *__restrict__ idx_off,
+                                           const zlz4f_member *__restrict__ member, const uint64_t *__restrict__ mem_off,
+                                           const int64_t *__restrict__ split_result, const uint64_t *__restrict__ dst_off,
+                                           const BfrTables &T, const BfDict &dd, uint64_t *__restrict__ e_off,
+                                           uint32_t *__restrict__ e_len) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_items; i += gridDim.x * blockDim.x) {
         uint32_t lo = 0, hi = nranges;
         while (lo < hi) {
             const uint32_t mid = lo + (hi - lo) / 2u;
             if (rg[mid].base <= i) lo = mid + 1u; else hi = mid;
         }
-        uint64_t d_off = 0, c_off = 0, o_off = 0;
-        uint32_t d_len = 0, fl = 0, f_len = 0, f_cap = 0, p_len = 0, p_cap = 0, c_len = 0, ierr = 0;
+        uint64_t d_off = 0, c_off = 0, o_off = 0, x_off = 0;
+        uint32_t d_len = 0, fl = 0, f_len = 0, f_cap = 0, p_len = 0, p_cap = 0, c_len = 0, ierr = 0, x_len = 0;
         if (lo > 0) {
             const uint32_t r = lo - 1u;
             const BRange G = rg[r];
@@ -2934,33 +3002,92 @@ __global__ void k_ffr_expand(const BRange *__restrict__ rg, uint32_t nranges, ui
                         if (sz != step) ierr = kItemStored; else c_len = want;
                     } else if (want == step) { f_len = sz; f_cap = step; }
                     else { p_len = sz; p_cap = want; }
+                    if (kDict && !fm.legacy && (!fm.linked || E.pos == fm.first)) (void)ff_dict_of(dd, f, x_len, x_off);
                 }
             }
         }
         T.data_off[i] = d_off; T.cks_off[i] = c_off; T.out_off[i] = o_off;
         T.data_len[i] = d_len; T.flags[i] = fl; T.f_len[i] = f_len; T.f_cap[i] = f_cap; T.p_len[i] = p_len;
         T.p_cap[i] = p_cap; T.c_len[i] = c_len; T.ierr[i] = ierr;
+        if (kDict) { e_off[i] = x_off; e_len[i] = x_len; }
     }
 }
 
+__global__ void k_ffr_expand(const BRange *__restrict__ rg, uint32_t nranges, uint32_t max_items,
+                             const zlz4f_range *__restrict__ range, const uint8_t *__restrict__ src,
+                             const uint64_t *__restrict__ src_off, const uint64_t *__restrict__ src_len,
+                             const zlz4f_index_entry *__restrict__ index, const uint64_t *__restrict__ idx_off,
+                             const zlz4f_member *__restrict__ member, const uint64_t *__restrict__ mem_off,
+                             const int64_t *__restrict__ split_result, const uint64_t *__restrict__ dst_off, BfrTables T) {
+    ffr_expand<false>(rg, nranges, max_items, range, src, src_off, src_len, index, idx_off, member, mem_off, split_result, dst_off,
+                      T, BfDict{}, nullptr, nullptr);
+}
+
+__global__ void k_ffr_expand_dict(const BRange *__restrict__ rg, uint32_t nranges, uint32_t max_items,
+                                  const zlz4f_range *__restrict__ range, const uint8_t *__restrict__ src,
+                                  const uint64_t *__restrict__ src_off, const uint64_t *__restrict__ src_len,
+                                  const zlz4f_index_entry *__restrict__ index, const uint64_t *__restrict__ idx_off,
+                                  const zlz4f_member *__restrict__ member, const uint64_t *__restrict__ mem_off,
+                                  const int64_t *__restrict__ split_result, const uint64_t *__restrict__ dst_off, BfrTables T,
+                                  BfDict dd, uint64_t *__restrict__ e_off, uint32_t *__restrict__ e_len) {
+    ffr_expand<true>(rg, nranges, max_items, range, src, src_off, src_len, index, idx_off, member, mem_off, split_result, dst_off,
+                     T, dd, e_off, e_len);
+}
+
+// ------------------------------------------------------------------ the dictionary forms
+// the index, one lane per table entry: the dictionary length the size pass gives the entry's block -- D of its file where
+// the block sees T (every block of an independent-declared member, block 0 of a linked-declared one), else 0
+__global__ void k_ffd_entry_len(const BFrame *__restrict__ fr, const uint32_t *__restrict__ fidx, uint32_t max_blocks,
+                                const uint64_t *__restrict__ item_first, uint32_t nbuf, BfDict dd,
+                                uint32_t *__restrict__ e_len) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max_blocks; i += gridDim.x * blockDim.x) {
+        const uint32_t f = fidx[i];
+        uint32_t D = 0;
+        uint64_t t_off;
+        if (f != kNoFrame) {
+            const BFrame F = fr[f];
+            if ((F.flg & 0x20u) || i == F.base) (void)ff_dict_of(dd, ff_buffer_of(item_first, nbuf, f), D, t_off);
+        }
+        e_len[i] = D;
+    }
+}
+
+// the index, one lane per buffer, behind the fold: a file that names no dictionary is InvalidState in front of every other
+// status of the file, the split's included (its room stays: the room is the walks' count alone)
+__global__ void k_ffd_refuse(BfDict dd, uint32_t nbuf, int64_t *__restrict__ result) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t D;
+    uint64_t t_off;
+    if (s < nbuf && !ff_dict_of(dd, s, D, t_off)) result[s] = ZLZ4_ERR_INVALID_STATE;
+}
+
+// one lane per item: the dictionary index of its buffer, carried through unchanged
+__global__ void k_ffd_item_dicts(const uint64_t *__restrict__ item_first, uint32_t nbuf, uint32_t nitems,
+                                 const uint32_t *__restrict__ dict_idx, uint32_t *__restrict__ item_dict_idx) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nitems) item_dict_idx[i] = dict_idx ? dict_idx[ff_buffer_of(item_first, nbuf, i)] : 0u;
+}
+
 // the file index's workspace: the frame size query's over the items, then the legacy walk's records and block table and
-// the rooms
+// the rooms; with dictionaries the entries' dictionary lengths behind them
 struct FfLayout {
     BfdLayout q;
     Region<FfLeg> leg;
     Region<uint64_t> leg_off, room;
-    Region<uint32_t> leg_len;
+    Region<uint32_t> leg_len, e_len;
     Region<int64_t> leg_sizes;
     size_t bytes = 0;
 };
 
-FfLayout ff_layout(uint32_t nbuf, uint32_t nitems, uint32_t max_blocks, uint32_t leg_blocks, void *ws = nullptr) {
+FfLayout ff_layout(uint32_t nbuf, uint32_t nitems, uint32_t max_blocks, uint32_t leg_blocks, void *ws = nullptr,
+                   bool dict = false) {
     FfLayout L;
     L.q = bfd_layout(nitems, max_blocks, 0, false, kQuery, ws);
     Carver c{static_cast<uint8_t *>(ws), L.q.bytes};
     c.take(nitems, L.leg);
     c.take(leg_blocks, L.leg_off, L.leg_len, L.leg_sizes);
     c.take(nbuf, L.room);
+    if (dict) c.take(max_blocks, L.e_len);
     L.bytes = c.bytes;
     return L;
 }
@@ -2972,23 +3099,23 @@ bool ff_totals(const uint64_t *t, uint32_t &nitems, uint32_t &max_blocks, uint32
     return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t zlz4f_batch_file_index_workspace(uint32_t nbuf, const uint64_t *split_totals) {
-    uint32_t nitems, mb, lb;
-    return ff_totals(split_totals, nitems, mb, lb) ? ff_layout(nbuf, nitems, mb, lb).bytes : 0;
+// the dictionary arrays of a file call's _using_dict form are refused as the dictionary frame calls refuse theirs: with
+// ndicts != 0 a null length array (`bytes`: or a null offset array), and a misaligned array
+bool ff_dict_refused(const BfDict &dd, bool bytes) {
+    if (dd.n && (!dd.len || (bytes && !dd.off))) return true;
+    return bf_misaligned(dd.off, 8) || bf_misaligned(dd.len, 4) || bf_misaligned(dd.idx, 4);
 }
 
 // The frame size query's launch sequence over the items up to its fold, the legacy walk and size kernel over the same
 // items where the split found legacy members, the rooms and their scan, the fold.  The sequence depends on the totals alone.
-int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
-                               uint32_t nbuf, const zlz4f_member *d_member, const uint64_t *d_mem_off,
-                               const int64_t *d_split_result, const uint64_t *d_item_first, const uint64_t *d_item_off,
-                               const uint64_t *d_item_len, const uint64_t *d_leg_len, const uint64_t *split_totals,
-                               zlz4f_index_entry *d_index, uint64_t *d_idx_off, uint64_t idx_cap, int64_t *d_result,
-                               void *d_workspace, size_t workspace_bytes) {
+// dd (zlz4f_batch_file_index_using_dict): the size kernel gets a dictionary length per table entry, and the files that name
+// no dictionary are refused behind the fold.
+int32_t ff_index_impl(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len, uint32_t nbuf,
+                      const zlz4f_member *d_member, const uint64_t *d_mem_off, const int64_t *d_split_result,
+                      const uint64_t *d_item_first, const uint64_t *d_item_off, const uint64_t *d_item_len,
+                      const uint64_t *d_leg_len, const uint64_t *split_totals, zlz4f_index_entry *d_index, uint64_t *d_idx_off,
+                      uint64_t idx_cap, int64_t *d_result, void *d_workspace, size_t workspace_bytes,
+                      const BfDict *dd = nullptr) {
     if (nbuf == 0) return 0;
     uint32_t nitems, mb, lb;
     if (!ff_totals(split_totals, nitems, mb, lb)) return ZLZ4_ERR_INVALID_STATE;
@@ -2999,9 +3126,9 @@ int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_
     if (bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) || bf_misaligned(d_member, 8) || bf_misaligned(d_mem_off, 8) ||
         bf_misaligned(d_split_result, 8) || bf_misaligned(d_item_first, 8) || bf_misaligned(d_item_off, 8) ||
         bf_misaligned(d_item_len, 8) || bf_misaligned(d_leg_len, 8) || bf_misaligned(d_index, 8) || bf_misaligned(d_idx_off, 8) ||
-        bf_misaligned(d_result, 8))
+        bf_misaligned(d_result, 8) || (dd && ff_dict_refused(*dd, false)))
         return ZLZ4_ERR_INVALID_STATE;
-    const FfLayout L = ff_layout(nbuf, nitems, mb, lb, d_workspace);
+    const FfLayout L = ff_layout(nbuf, nitems, mb, lb, d_workspace, dd != nullptr);
     if (!d_workspace || workspace_bytes < L.bytes || bf_misaligned(d_workspace, 16)) return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     hipStream_t st = (hipStream_t)stream;
@@ -3009,7 +3136,10 @@ int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_
     if (bfd_prelude(st, a, false, nullptr, L.q) != 0) return ZLZ4_ERR_DEVICE;
     if (mb) {
         hipLaunchKernelGGL(k_bfq_len, dim3(bf_grid(mb, 256, 4096)), dim3(256), 0, st, L.q.data_len, L.q.flags, mb, L.q.dec_len);
-        if (zlz4_launch_decompressed_size(st, d_src, L.q.data_off, L.q.dec_len, nullptr, L.q.sizes, mb) != 0)
+        if (dd)
+            hipLaunchKernelGGL(k_ffd_entry_len, dim3(bf_grid(mb, 256, 4096)), dim3(256), 0, st, L.q.frames.p, L.q.fidx.p, mb,
+                               d_item_first, nbuf, *dd, L.e_len.p);
+        if (zlz4_launch_decompressed_size(st, d_src, L.q.data_off, L.q.dec_len, dd ? L.e_len.p : nullptr, L.q.sizes, mb) != 0)
             return ZLZ4_ERR_DEVICE;
     }
     if (legacy) {
@@ -3032,25 +3162,22 @@ int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_
     const FfTables T = {L.q.frames, L.q.data_off, L.q.data_len, L.q.flags, L.q.cks_ok, L.q.sizes, lg, L.leg_off, L.leg_sizes, mb, lb};
     hipLaunchKernelGGL(k_ff_fold, dim3(gs), dim3(256), 0, st, T, d_member, d_mem_off, d_split_result, d_item_first, d_item_len,
                        d_src_off, nbuf, d_index, d_idx_off, idx_cap, d_result);
+    if (dd) hipLaunchKernelGGL(k_ffd_refuse, dim3(bf_grid(nbuf, 256)), dim3(256), 0, st, *dd, nbuf, d_result);
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
-size_t zlz4f_batch_decompress_file_range_workspace(uint32_t nranges, uint32_t max_items) {
-    return bfr_layout(nranges, max_items).bytes;
-}
-
 // zlz4f_batch_decompress_frame_range's launch sequence with k_ffr_range and k_ffr_expand in the places of k_bfr_range and
-// k_bfr_expand; scan, checksums, decoders, copy and finish are that call's
-int32_t zlz4f_batch_decompress_file_range(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
-                                          const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
-                                          const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nbuf,
-                                          const zlz4f_member *d_member, const uint64_t *d_mem_off,
-                                          const int64_t *d_split_result, const zlz4f_range *d_range, uint8_t *d_dst,
-                                          const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_skip,
-                                          int64_t *d_result, uint32_t nranges, uint32_t max_items, void *d_workspace,
-                                          size_t workspace_bytes) {
+// k_bfr_expand; scan, checksums, decoders, copy and finish are that call's.  dd
+// (zlz4f_batch_decompress_file_range_using_dict): the _dict kernels, which also write every item's dictionary descriptor,
+// and the block decoders that take one.
+int32_t ff_range_impl(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                      const zlz4f_index_entry *d_index, const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nbuf,
+                      const zlz4f_member *d_member, const uint64_t *d_mem_off, const int64_t *d_split_result,
+                      const zlz4f_range *d_range, uint8_t *d_dst, const uint64_t *d_dst_off, const uint64_t *d_dst_cap,
+                      uint64_t *d_skip, int64_t *d_result, uint32_t nranges, uint32_t max_items, void *d_workspace,
+                      size_t workspace_bytes, const BfDict *dd = nullptr) {
     if (nranges == 0) return 0;
-    const BfrLayout L = bfr_layout(nranges, max_items, d_workspace);
+    const BfrLayout L = bfr_layout(nranges, max_items, d_workspace, dd != nullptr);
     if (!d_range || !d_dst_off || !d_dst_cap || !d_skip || !d_result || (max_items && !d_dst) ||
         (nbuf && (!d_src || !d_src_off || !d_src_len || !d_index || !d_idx_off || !d_idx_n || !d_member || !d_mem_off ||
                   !d_split_result)))
@@ -3058,23 +3185,38 @@ int32_t zlz4f_batch_decompress_file_range(void *stream, const uint8_t *d_src, co
     if (bf_misaligned(d_src_off, 8) || bf_misaligned(d_src_len, 8) || bf_misaligned(d_index, 8) || bf_misaligned(d_idx_off, 8) ||
         bf_misaligned(d_idx_n, 8) || bf_misaligned(d_member, 8) || bf_misaligned(d_mem_off, 8) ||
         bf_misaligned(d_split_result, 8) || bf_misaligned(d_range, 8) || bf_misaligned(d_dst_off, 8) ||
-        bf_misaligned(d_dst_cap, 8) || bf_misaligned(d_skip, 8) || bf_misaligned(d_result, 8))
+        bf_misaligned(d_dst_cap, 8) || bf_misaligned(d_skip, 8) || bf_misaligned(d_result, 8) ||
+        (dd && ff_dict_refused(*dd, true)))
         return ZLZ4_ERR_INVALID_STATE;
     if (!d_workspace || workspace_bytes < L.bytes || bf_misaligned(d_workspace, 16)) return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t m = max_items, gr = bf_grid(nranges, 4);
     const BfrTables T = {L.data_off, L.cks_off, L.out_off, L.data_len, L.flags, L.f_len, L.f_cap, L.p_len, L.p_cap, L.c_len, L.ierr};
-    hipLaunchKernelGGL(k_ffr_range, dim3(gr), dim3(256), 0, st, d_src, d_src_off, d_src_len, d_index, d_idx_off, d_idx_n, nbuf,
-                       d_member, d_mem_off, d_split_result, d_range, d_dst_cap, nranges, L.ranges);
+    if (dd)
+        hipLaunchKernelGGL(k_ffr_range_dict, dim3(gr), dim3(256), 0, st, d_src, d_src_off, d_src_len, d_index, d_idx_off, d_idx_n,
+                           nbuf, d_member, d_mem_off, d_split_result, d_range, d_dst_cap, nranges, L.ranges, *dd);
+    else
+        hipLaunchKernelGGL(k_ffr_range, dim3(gr), dim3(256), 0, st, d_src, d_src_off, d_src_len, d_index, d_idx_off, d_idx_n, nbuf,
+                           d_member, d_mem_off, d_split_result, d_range, d_dst_cap, nranges, L.ranges);
     hipLaunchKernelGGL(k_bfr_scan, dim3(1), dim3(1024), 0, st, L.ranges, nranges);
     if (m) {
-        hipLaunchKernelGGL(k_ffr_expand, dim3(bf_grid(m, 256, 4096)), dim3(256), 0, st, L.ranges, nranges, m, d_range, d_src,
-                           d_src_off, d_src_len, d_index, d_idx_off, d_member, d_mem_off, d_split_result, d_dst_off, T);
+        if (dd)
+            hipLaunchKernelGGL(k_ffr_expand_dict, dim3(bf_grid(m, 256, 4096)), dim3(256), 0, st, L.ranges, nranges, m, d_range,
+                               d_src, d_src_off, d_src_len, d_index, d_idx_off, d_member, d_mem_off, d_split_result, d_dst_off, T,
+                               *dd, L.e_off.p, L.e_len.p);
+        else
+            hipLaunchKernelGGL(k_ffr_expand, dim3(bf_grid(m, 256, 4096)), dim3(256), 0, st, L.ranges, nranges, m, d_range, d_src,
+                               d_src_off, d_src_len, d_index, d_idx_off, d_member, d_mem_off, d_split_result, d_dst_off, T);
         hipLaunchKernelGGL(k_bfd_verify, dim3(bf_grid(m, 64)), dim3(64), 0, st, d_src, L.data_off, L.data_len, L.flags,
                            L.cks_off, m, L.cks_ok);
-        if (zlz4_launch_decompress_safe(st, d_src, L.data_off, L.f_len, d_dst, L.out_off, L.f_cap, L.sizes_f, m) != 0 ||
-            zlz4_launch_decompress_safe_prefix(st, d_src, L.data_off, L.p_len, d_dst, L.out_off, L.p_cap, L.sizes_p, m) != 0)
+        if (dd ? zlz4_launch_decompress_safe_using_dict(st, d_src, L.data_off, L.f_len, d_dst, L.out_off, L.f_cap, L.sizes_f, m,
+                                                        dd->dict, L.e_off, L.e_len) != 0 ||
+                     zlz4_launch_decompress_safe_prefix_using_dict(st, d_src, L.data_off, L.p_len, d_dst, L.out_off, L.p_cap,
+                                                                   L.sizes_p, m, dd->dict, L.e_off, L.e_len) != 0
+               : zlz4_launch_decompress_safe(st, d_src, L.data_off, L.f_len, d_dst, L.out_off, L.f_cap, L.sizes_f, m) != 0 ||
+                     zlz4_launch_decompress_safe_prefix(st, d_src, L.data_off, L.p_len, d_dst, L.out_off, L.p_cap, L.sizes_p,
+                                                        m) != 0)
             return ZLZ4_ERR_DEVICE;
         hipLaunchKernelGGL(k_bfr_copy, dim3(m), dim3(256), 0, st, d_src, L.data_off, L.c_len, L.out_off, d_dst);
     }
@@ -3083,27 +3225,122 @@ int32_t zlz4f_batch_decompress_file_range(void *stream, const uint8_t *d_src, co
     return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
 }
 
-// One file from host memory: split (count, record), index, plan and range as a batch of one.  The index is built on every call.
-int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
-                                    uint32_t split_flags) {
-    if (split_flags & ~ZLZ4F_SPLIT_LEGACY) return ZLZ4F_ERR_PARAMETER_INVALID;
-    if ((!src && n) || (!dst && cap) || a > b) return ZLZ4_ERR_INVALID_STATE;
+}  // namespace
+
+extern "C" {
+
+size_t zlz4f_batch_file_index_workspace(uint32_t nbuf, const uint64_t *split_totals) {
+    uint32_t nitems, mb, lb;
+    return ff_totals(split_totals, nitems, mb, lb) ? ff_layout(nbuf, nitems, mb, lb).bytes : 0;
+}
+
+int32_t zlz4f_batch_file_index(void *stream, const uint8_t *d_src, const uint64_t *d_src_off, const uint64_t *d_src_len,
+                               uint32_t nbuf, const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                               const int64_t *d_split_result, const uint64_t *d_item_first, const uint64_t *d_item_off,
+                               const uint64_t *d_item_len, const uint64_t *d_leg_len, const uint64_t *split_totals,
+                               zlz4f_index_entry *d_index, uint64_t *d_idx_off, uint64_t idx_cap, int64_t *d_result,
+                               void *d_workspace, size_t workspace_bytes) {
+    return ff_index_impl(stream, d_src, d_src_off, d_src_len, nbuf, d_member, d_mem_off, d_split_result, d_item_first, d_item_off,
+                         d_item_len, d_leg_len, split_totals, d_index, d_idx_off, idx_cap, d_result, d_workspace, workspace_bytes);
+}
+
+size_t zlz4f_batch_decompress_file_range_workspace(uint32_t nranges, uint32_t max_items) {
+    return bfr_layout(nranges, max_items).bytes;
+}
+
+int32_t zlz4f_batch_decompress_file_range(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                          const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
+                                          const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nbuf,
+                                          const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                                          const int64_t *d_split_result, const zlz4f_range *d_range, uint8_t *d_dst,
+                                          const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_skip,
+                                          int64_t *d_result, uint32_t nranges, uint32_t max_items, void *d_workspace,
+                                          size_t workspace_bytes) {
+    return ff_range_impl(stream, d_src, d_src_off, d_src_len, d_index, d_idx_off, d_idx_n, nbuf, d_member, d_mem_off,
+                         d_split_result, d_range, d_dst, d_dst_off, d_dst_cap, d_skip, d_result, nranges, max_items, d_workspace,
+                         workspace_bytes);
+}
+
+// ---- the dictionary forms: a FILE has at most one dictionary, d_dict_idx has nbuf entries
+size_t zlz4f_batch_file_index_using_dict_workspace(uint32_t nbuf, const uint64_t *split_totals) {
+    uint32_t nitems, mb, lb;
+    return ff_totals(split_totals, nitems, mb, lb) ? ff_layout(nbuf, nitems, mb, lb, nullptr, true).bytes : 0;
+}
+
+int32_t zlz4f_batch_file_index_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                          const uint64_t *d_src_len, uint32_t nbuf, const zlz4f_member *d_member,
+                                          const uint64_t *d_mem_off, const int64_t *d_split_result,
+                                          const uint64_t *d_item_first, const uint64_t *d_item_off, const uint64_t *d_item_len,
+                                          const uint64_t *d_leg_len, const uint64_t *split_totals, zlz4f_index_entry *d_index,
+                                          uint64_t *d_idx_off, uint64_t idx_cap, int64_t *d_result, const uint32_t *d_dict_len,
+                                          uint32_t ndicts, const uint32_t *d_dict_idx, void *d_workspace,
+                                          size_t workspace_bytes) {
+    const BfDict dd = {nullptr, nullptr, d_dict_len, ndicts, d_dict_idx};
+    return ff_index_impl(stream, d_src, d_src_off, d_src_len, nbuf, d_member, d_mem_off, d_split_result, d_item_first, d_item_off,
+                         d_item_len, d_leg_len, split_totals, d_index, d_idx_off, idx_cap, d_result, d_workspace, workspace_bytes,
+                         &dd);
+}
+
+size_t zlz4f_batch_decompress_file_range_using_dict_workspace(uint32_t nranges, uint32_t max_items) {
+    return bfr_layout(nranges, max_items, nullptr, true).bytes;
+}
+
+int32_t zlz4f_batch_decompress_file_range_using_dict(void *stream, const uint8_t *d_src, const uint64_t *d_src_off,
+                                                     const uint64_t *d_src_len, const zlz4f_index_entry *d_index,
+                                                     const uint64_t *d_idx_off, const int64_t *d_idx_n, uint32_t nbuf,
+                                                     const zlz4f_member *d_member, const uint64_t *d_mem_off,
+                                                     const int64_t *d_split_result, const zlz4f_range *d_range, uint8_t *d_dst,
+                                                     const uint64_t *d_dst_off, const uint64_t *d_dst_cap, uint64_t *d_skip,
+                                                     int64_t *d_result, uint32_t nranges, uint32_t max_items,
+                                                     const uint8_t *d_dict, const uint64_t *d_dict_off,
+                                                     const uint32_t *d_dict_len, uint32_t ndicts, const uint32_t *d_dict_idx,
+                                                     void *d_workspace, size_t workspace_bytes) {
+    const BfDict dd = {d_dict, d_dict_off, d_dict_len, ndicts, d_dict_idx};
+    return ff_range_impl(stream, d_src, d_src_off, d_src_len, d_index, d_idx_off, d_idx_n, nbuf, d_member, d_mem_off,
+                         d_split_result, d_range, d_dst, d_dst_off, d_dst_cap, d_skip, d_result, nranges, max_items, d_workspace,
+                         workspace_bytes, &dd);
+}
+
+// One launch, one lane per item.  nbuf == 0 or nitems == 0 returns 0.
+int32_t zlz4f_batch_multiframe_item_dicts(void *stream, const uint64_t *d_item_first, uint32_t nbuf, uint32_t nitems,
+                                          const uint32_t *d_dict_idx, uint32_t *d_item_dict_idx) {
+    if (nbuf == 0 || nitems == 0) return 0;
+    if (!d_item_first || !d_item_dict_idx || bf_misaligned(d_item_first, 8) || bf_misaligned(d_dict_idx, 4) ||
+        bf_misaligned(d_item_dict_idx, 4))
+        return ZLZ4_ERR_INVALID_STATE;
     if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    hipLaunchKernelGGL(k_ffd_item_dicts, dim3(bf_grid(nitems, 256)), dim3(256), 0, (hipStream_t)stream, d_item_first, nbuf, nitems,
+                       d_dict_idx, d_item_dict_idx);
+    return hipGetLastError() == hipSuccess ? 0 : ZLZ4_ERR_DEVICE;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One file from host memory: split (count, record), index, plan and range as a batch of one.  The index is built on every
+// call.  d_dict: the staged tail T of the file's dictionary, D bytes (zlz4f_decompress_file_range_using_dict), else null.
+int64_t ff_host_range(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap, uint32_t split_flags,
+                      const uint8_t *tail, uint32_t D) {
     hipStream_t st = nullptr;
     DeviceCall dc(st);
     struct Rec {
         uint64_t src_off, src_len, count, totals[4], mem_off, mem_cap, item_first[2], idx_off[2], dst_off, dst_cap, skip,
-            plan_totals[2];
+            plan_totals[2], dict_off;
         int64_t split_result, idx_n, rres;
         zlz4f_range range;
+        uint32_t dict_len, pad;
     };
     DevBuf d_src(n, &dc);
+    std::optional<DevBuf> d_dict;                                       // (the plain call keeps its allocations)
+    if (tail) d_dict.emplace(D, &dc);
     Staged<Rec> rec(&dc, 256);
-    if (!d_src.p || !rec.d) return ZLZ4F_ERR_ALLOCATION_FAILED;
+    if (!d_src.p || !rec.d || (tail && !d_dict->p)) return ZLZ4F_ERR_ALLOCATION_FAILED;
     rec.h.src_len = n;
     rec.h.range.a = a; rec.h.range.b = b;
+    rec.h.dict_len = D;
     dc.launched();
-    if (!upload(d_src, src, n, st) || !rec.upload(st)) return ZLZ4_ERR_DEVICE;
+    if (!upload(d_src, src, n, st) || !rec.upload(st) || (tail && !upload(*d_dict, tail, D, st))) return ZLZ4_ERR_DEVICE;
     Rec *r = rec.d;
     const uint8_t *s = d_src.as<uint8_t>();
     int32_t rc = zlz4f_batch_multiframe_split_ex(st, s, &r->src_off, &r->src_len, 1, &r->count, r->totals, nullptr, nullptr,
@@ -3115,7 +3352,9 @@ int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t n, uint64_t a, ui
     if (totals[0] > 0xFFFFFFFFull || totals[1] > 0xFFFFFFFFull || totals[3] > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const size_t nitems = (size_t)totals[0];
     const uint64_t idx_cap = totals[1] + totals[3] + 1u;
-    const size_t iws = zlz4f_batch_file_index_workspace(1, totals);
+    const BfDict dd = {tail ? d_dict->as<uint8_t>() : nullptr, &r->dict_off, &r->dict_len, 1, nullptr};
+    const BfDict *ddp = tail ? &dd : nullptr;
+    const size_t iws = ff_layout(1, (uint32_t)totals[0], (uint32_t)totals[1], (uint32_t)totals[3], nullptr, ddp != nullptr).bytes;
     DevBuf d_mem(nitems * sizeof(zlz4f_member), &dc), d_items(nitems * 24u, &dc), d_iws(iws, &dc),
         d_index((size_t)idx_cap * sizeof(zlz4f_index_entry), &dc);
     if (!d_mem.p || !d_items.p || !d_iws.p || !d_index.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
@@ -3128,8 +3367,8 @@ int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t n, uint64_t a, ui
     rc = zlz4f_batch_multiframe_split_ex(st, s, &r->src_off, &r->src_len, 1, &r->count, r->totals, mem, &r->mem_off, &r->mem_cap,
                                          r->item_first, item_off, item_len, &r->split_result, split_flags, leg_len);
     if (rc != 0) return rc;
-    rc = zlz4f_batch_file_index(st, s, &r->src_off, &r->src_len, 1, mem, &r->mem_off, &r->split_result, r->item_first, item_off,
-                                item_len, leg_len, totals, index, r->idx_off, idx_cap, &r->idx_n, d_iws.p, iws);
+    rc = ff_index_impl(st, s, &r->src_off, &r->src_len, 1, mem, &r->mem_off, &r->split_result, r->item_first, item_off, item_len,
+                       leg_len, totals, index, r->idx_off, idx_cap, &r->idx_n, d_iws.p, iws, ddp);
     if (rc != 0) return rc;
     rc = zlz4f_batch_plan_frame_ranges(st, index, r->idx_off, &r->idx_n, 1, &r->range, 1, 0, &r->dst_off, &r->dst_cap,
                                        r->plan_totals);
@@ -3147,13 +3386,13 @@ int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t n, uint64_t a, ui
     if (cap < b1 - a1) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
     if (plan[1] > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const uint32_t max_items = (uint32_t)plan[1];
-    const size_t rws = zlz4f_batch_decompress_file_range_workspace(1, max_items);
+    const size_t rws = bfr_layout(1, max_items, nullptr, ddp != nullptr).bytes;
     DevBuf d_rws(rws, &dc), d_dst((size_t)plan[0], &dc);
     if (!d_rws.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     dc.launched();
-    rc = zlz4f_batch_decompress_file_range(st, s, &r->src_off, &r->src_len, index, r->idx_off, &r->idx_n, 1, mem, &r->mem_off,
-                                           &r->split_result, &r->range, d_dst.as<uint8_t>(), &r->dst_off, &r->dst_cap, &r->skip,
-                                           &r->rres, 1, max_items, d_rws.p, rws);
+    rc = ff_range_impl(st, s, &r->src_off, &r->src_len, index, r->idx_off, &r->idx_n, 1, mem, &r->mem_off, &r->split_result,
+                       &r->range, d_dst.as<uint8_t>(), &r->dst_off, &r->dst_cap, &r->skip, &r->rres, 1, max_items, d_rws.p, rws,
+                       ddp);
     if (rc != 0) return rc;
     int64_t result = 0;
     uint64_t skip = 0;
@@ -3163,6 +3402,25 @@ int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t n, uint64_t a, ui
                        hipMemcpy(dst, d_dst.as<uint8_t>() + skip, (size_t)result, hipMemcpyDeviceToHost) != hipSuccess))
         return ZLZ4_ERR_DEVICE;
     return result;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t zlz4f_decompress_file_range(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
+                                    uint32_t split_flags) {
+    if (split_flags & ~ZLZ4F_SPLIT_LEGACY) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if ((!src && n) || (!dst && cap) || a > b) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return ff_host_range(src, n, a, b, dst, cap, split_flags, nullptr, 0);
+}
+
+// zlz4f_decompress_file_range with the D > 0 bytes of a dictionary's tail: what zlz4f_decompress_file_range_using_dict
+// (zlz4_frame_seek.hip), which has made the refusals, runs where the file's seek table is not used
+int64_t zlz4_host_file_range_dict(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
+                                  uint32_t split_flags, const uint8_t *tail, uint32_t D) {
+    return ff_host_range(src, n, a, b, dst, cap, split_flags, tail, D);
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <optional>
+
 #include "zlz4_frame_batch.hpp"
 #include "zlz4_host.hpp"
 #include "zlz4_launch.hpp"
@@ -375,15 +377,16 @@ namespace {
 // what both host calls stage: the file, one record whose fields are the arrays of a batch of one, and the tables
 struct SkRec {
     uint64_t src_off, src_len, count, totals[4], mem_off, mem_cap, item_first[2], idx_off[2], dst_off, dst_cap, skip,
-        plan_totals[2], tab_off, tab_cap, load_count, load_totals[2];
+        plan_totals[2], tab_off, tab_cap, load_count, load_totals[2], dict_off;
     int64_t split_result, idx_n, rres, result;
     zlz4f_range range;
+    uint32_t dict_len, pad;           // the dictionary of zlz4f_decompress_file_range_using_dict: its staged tail
 };
 
 // plan, range decode and the copy of exactly the wanted bytes: the tail of zlz4f_decompress_file_range over tables that
-// are on the device already
+// are on the device already.  d_dict: the staged tail of the file's dictionary (r->dict_len bytes), else null.
 int64_t sk_range_tail(DeviceCall &dc, SkRec *r, const uint8_t *s, const zlz4f_member *mem, const zlz4f_index_entry *index,
-                      uint64_t idx_room, uint64_t a, uint64_t b, uint8_t *dst, size_t cap) {
+                      uint64_t idx_room, uint64_t a, uint64_t b, uint8_t *dst, size_t cap, const uint8_t *d_dict = nullptr) {
     hipStream_t st = dc.st;
     int32_t rc = zlz4f_batch_plan_frame_ranges(st, index, r->idx_off, &r->idx_n, 1, &r->range, 1, 0, &r->dst_off, &r->dst_cap,
                                                r->plan_totals);
@@ -401,13 +404,19 @@ int64_t sk_range_tail(DeviceCall &dc, SkRec *r, const uint8_t *s, const zlz4f_me
     if (cap < b1 - a1) return ZLZ4F_ERR_DST_MAX_SIZE_TOO_SMALL;
     if (plan[1] > 0xFFFFFFFFull) return ZLZ4F_ERR_SRC_SIZE_TOO_LARGE;
     const uint32_t max_items = (uint32_t)plan[1];
-    const size_t rws = zlz4f_batch_decompress_file_range_workspace(1, max_items);
+    const size_t rws = d_dict ? zlz4f_batch_decompress_file_range_using_dict_workspace(1, max_items)
+                              : zlz4f_batch_decompress_file_range_workspace(1, max_items);
     DevBuf d_rws(rws, &dc), d_dst((size_t)plan[0], &dc);
     if (!d_rws.p || !d_dst.p) return ZLZ4F_ERR_ALLOCATION_FAILED;
     dc.launched();
-    rc = zlz4f_batch_decompress_file_range(st, s, &r->src_off, &r->src_len, index, r->idx_off, &r->idx_n, 1, mem, &r->mem_off,
-                                           &r->split_result, &r->range, d_dst.as<uint8_t>(), &r->dst_off, &r->dst_cap, &r->skip,
-                                           &r->rres, 1, max_items, d_rws.p, rws);
+    rc = d_dict ? zlz4f_batch_decompress_file_range_using_dict(st, s, &r->src_off, &r->src_len, index, r->idx_off, &r->idx_n, 1,
+                                                               mem, &r->mem_off, &r->split_result, &r->range,
+                                                               d_dst.as<uint8_t>(), &r->dst_off, &r->dst_cap, &r->skip, &r->rres,
+                                                               1, max_items, d_dict, &r->dict_off, &r->dict_len, 1, nullptr,
+                                                               d_rws.p, rws)
+                : zlz4f_batch_decompress_file_range(st, s, &r->src_off, &r->src_len, index, r->idx_off, &r->idx_n, 1, mem,
+                                                    &r->mem_off, &r->split_result, &r->range, d_dst.as<uint8_t>(), &r->dst_off,
+                                                    &r->dst_cap, &r->skip, &r->rres, 1, max_items, d_rws.p, rws);
     if (rc != 0) return rc;
     int64_t result = 0;
     uint64_t skip = 0;
@@ -484,24 +493,28 @@ int64_t zlz4f_seek_table(const uint8_t *src, size_t n, uint8_t *dst, size_t cap,
     return T;
 }
 
-// zlz4f_decompress_file_range, with the tables taken from the file's tail where range_flags asks for it and the file
-// ends in a well-formed seek table.  The whole file is staged either way.
-int64_t zlz4f_decompress_file_range_ex(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
-                                       uint32_t split_flags, uint32_t range_flags) {
-    if ((split_flags & ~ZLZ4F_SPLIT_LEGACY) || (range_flags & ~ZLZ4F_RANGE_SEEK_TABLE)) return ZLZ4F_ERR_PARAMETER_INVALID;
-    if (range_flags == 0) return zlz4f_decompress_file_range(src, n, a, b, dst, cap, split_flags);
-    if ((!src && n) || (!dst && cap) || a > b) return ZLZ4_ERR_INVALID_STATE;
-    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+}  // extern "C"
+
+namespace {
+
+// zlz4f_decompress_file_range with ZLZ4F_RANGE_SEEK_TABLE, after the refusals: the tables are taken from the file's tail
+// where the file ends in a well-formed seek table.  The whole file is staged either way.  tail: the D > 0 last bytes
+// of the file's dictionary, else null.
+int64_t sk_host_range(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap, uint32_t split_flags,
+                      const uint8_t *tail, uint32_t D) {
     {
         hipStream_t st = nullptr;
         DeviceCall dc(st);
         DevBuf d_src(n, &dc);
+        std::optional<DevBuf> d_dict;                                   // (the plain call keeps its allocations)
+        if (tail) d_dict.emplace(D, &dc);
         Staged<SkRec> rec(&dc, 256);
-        if (!d_src.p || !rec.d) return ZLZ4F_ERR_ALLOCATION_FAILED;
+        if (!d_src.p || !rec.d || (tail && !d_dict->p)) return ZLZ4F_ERR_ALLOCATION_FAILED;
         rec.h.src_len = n;
         rec.h.range.a = a; rec.h.range.b = b;
+        rec.h.dict_len = D;
         dc.launched();
-        if (!upload(d_src, src, n, st) || !rec.upload(st)) return ZLZ4_ERR_DEVICE;
+        if (!upload(d_src, src, n, st) || !rec.upload(st) || (tail && !upload(*d_dict, tail, D, st))) return ZLZ4_ERR_DEVICE;
         SkRec *r = rec.d;
         const uint8_t *s = d_src.as<uint8_t>();
         int32_t rc = zlz4f_batch_load_seek_table(st, s, &r->src_off, &r->src_len, 1, &r->load_count, r->load_totals, nullptr,
@@ -522,10 +535,40 @@ int64_t zlz4f_decompress_file_range_ex(const uint8_t *src, size_t n, uint64_t a,
             if (rc != 0) return rc;
             int64_t loaded = 0;
             if (!read_result(dc, &r->split_result, loaded)) return ZLZ4_ERR_DEVICE;
-            if (loaded > 0) return sk_range_tail(dc, r, s, mem, index, lt[1], a, b, dst, cap);
+            if (loaded > 0)
+                return sk_range_tail(dc, r, s, mem, index, lt[1], a, b, dst, cap, tail ? d_dict->as<uint8_t>() : nullptr);
         }
     }
-    return zlz4f_decompress_file_range(src, n, a, b, dst, cap, split_flags);   // no table, or one out of shape: as today
+    // no table, or one out of shape: the index is built
+    return tail ? zlz4_host_file_range_dict(src, n, a, b, dst, cap, split_flags, tail, D)
+                     : zlz4f_decompress_file_range(src, n, a, b, dst, cap, split_flags);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t zlz4f_decompress_file_range_ex(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
+                                       uint32_t split_flags, uint32_t range_flags) {
+    if ((split_flags & ~ZLZ4F_SPLIT_LEGACY) || (range_flags & ~ZLZ4F_RANGE_SEEK_TABLE)) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if (range_flags == 0) return zlz4f_decompress_file_range(src, n, a, b, dst, cap, split_flags);
+    if ((!src && n) || (!dst && cap) || a > b) return ZLZ4_ERR_INVALID_STATE;
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    return sk_host_range(src, n, a, b, dst, cap, split_flags, nullptr, 0);
+}
+
+// The _ex call with a dictionary for the file: only the dictionary's last 64 KiB are staged.  dict_len == 0: the _ex call.
+int64_t zlz4f_decompress_file_range_using_dict(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
+                                               uint32_t split_flags, uint32_t range_flags, const uint8_t *dict,
+                                               size_t dict_len) {
+    if ((split_flags & ~ZLZ4F_SPLIT_LEGACY) || (range_flags & ~ZLZ4F_RANGE_SEEK_TABLE)) return ZLZ4F_ERR_PARAMETER_INVALID;
+    if ((!src && n) || (!dst && cap) || (!dict && dict_len) || a > b) return ZLZ4_ERR_INVALID_STATE;
+    if (dict_len == 0) return zlz4f_decompress_file_range_ex(src, n, a, b, dst, cap, split_flags, range_flags);
+    if (!device_ok()) return ZLZ4_ERR_DEVICE;
+    const uint32_t D = (uint32_t)dict_tail(dict_len);
+    const uint8_t *tail = dict + (dict_len - D);
+    return range_flags ? sk_host_range(src, n, a, b, dst, cap, split_flags, tail, D)
+                       : zlz4_host_file_range_dict(src, n, a, b, dst, cap, split_flags, tail, D);
 }
 
 }  // extern "C"

@@ -171,4 +171,8 @@ int zlz4_launch_bfl_hc_desc(hipStream_t st, const void *frames, uint32_t nframes
                             const uint64_t *in_off, const uint32_t *in_len, uint64_t *v_off, uint32_t *v_len,
                             uint32_t *v_pair);
 
+// zlz4_frame.hip, for zlz4_frame_seek.hip: zlz4f_decompress_file_range with the D > 0 last bytes of a dictionary (host memory)
+int64_t zlz4_host_file_range_dict(const uint8_t *src, size_t n, uint64_t a, uint64_t b, uint8_t *dst, size_t cap,
+                                  uint32_t split_flags, const uint8_t *tail, uint32_t D);
+
 }  // extern "C"

@@ -131,6 +131,12 @@ extern "c" fn zlz4f_batch_concat_workspace(nitems: u32) usize;
 extern "c" fn zlz4f_batch_concat(stream: ?*anyopaque, d_src: ?[*]const u8, d_item_off: ?[*]const u64, d_item_len: ?[*]const i64, d_item_first: ?[*]const u64, nbuf: u32, nitems: u32, d_dst: ?[*]u8, d_dst_off: ?[*]const u64, d_dst_cap: ?[*]const u64, d_result: ?[*]i64, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4f_seek_table(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, split_flags: u32) i64;
 extern "c" fn zlz4f_decompress_file_range_ex(src: [*]const u8, src_len: usize, a: u64, b: u64, dst: [*]u8, dst_cap: usize, split_flags: u32, range_flags: u32) i64;
+extern "c" fn zlz4f_batch_file_index_using_dict_workspace(nbuf: u32, split_totals: ?[*]const u64) usize;
+extern "c" fn zlz4f_batch_file_index_using_dict(stream: ?*anyopaque, d_src: ?[*]const u8, d_src_off: ?[*]const u64, d_src_len: ?[*]const u64, nbuf: u32, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_item_first: ?[*]const u64, d_item_off: ?[*]const u64, d_item_len: ?[*]const u64, d_leg_len: ?[*]const u64, split_totals: ?[*]const u64, d_index: ?[*]IndexEntry, d_idx_off: ?[*]u64, idx_cap: u64, d_result: ?[*]i64, d_dict_len: ?[*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_decompress_file_range_using_dict_workspace(nranges: u32, max_items: u32) usize;
+extern "c" fn zlz4f_batch_decompress_file_range_using_dict(stream: ?*anyopaque, d_src: ?[*]const u8, d_src_off: ?[*]const u64, d_src_len: ?[*]const u64, d_index: ?[*]const IndexEntry, d_idx_off: ?[*]const u64, d_idx_n: ?[*]const i64, nbuf: u32, d_member: ?[*]const Member, d_mem_off: ?[*]const u64, d_split_result: ?[*]const i64, d_range: ?[*]const Range, d_dst: ?[*]u8, d_dst_off: ?[*]const u64, d_dst_cap: ?[*]const u64, d_skip: ?[*]u64, d_result: ?[*]i64, nranges: u32, max_items: u32, d_dict: ?[*]const u8, d_dict_off: ?[*]const u64, d_dict_len: ?[*]const u32, ndicts: u32, d_dict_idx: ?[*]const u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+extern "c" fn zlz4f_batch_multiframe_item_dicts(stream: ?*anyopaque, d_item_first: ?[*]const u64, nbuf: u32, nitems: u32, d_dict_idx: ?[*]const u32, d_item_dict_idx: ?[*]u32) i32;
+extern "c" fn zlz4f_decompress_file_range_using_dict(src: [*]const u8, src_len: usize, a: u64, b: u64, dst: [*]u8, dst_cap: usize, split_flags: u32, range_flags: u32, dict: [*]const u8, dict_len: usize) i64;
 /// zlz4f_legacy_prefs of include/zlz4_amd.h: block_size 0 = 8 MiB, 1 .. 8 MiB as given; compression_level <= 0 = fast
 pub const LegacyPrefs = extern struct { block_size: u32 = 0, compression_level: i32 = 0 };
 extern "c" fn zlz4f_legacy_compress_frame_bound(src_size: usize, prefs: ?*const LegacyPrefs) usize;
@@ -985,6 +991,30 @@ pub const lz4f = struct {
     /// decompressFileRange that takes the tables from the file's seek table where it ends in a well-formed one
     pub fn decompressFileRangeEx(src: []const u8, a: u64, b: u64, dst: []u8, range_flags: u32) Error!usize {
         return mapFrame(zlz4f_decompress_file_range_ex(src.ptr, src.len, a, b, dst.ptr, dst.len, SPLIT_LEGACY, range_flags));
+    }
+    /// No counterpart in the reference: dictionary files (include/zlz4_amd.h) -- the file calls with ONE DICTIONARY PER
+    /// FILE: dict_idx has one entry per buffer (null: dictionary 0).  Every block of a member that declares independent
+    /// blocks sees the dictionary's last 64 KiB, block 0 of one that declares linked blocks, no block of a legacy member.
+    /// The index call needs the lengths alone; multiframeItemDictsBatch spreads the per-buffer index over the items of a
+    /// split, for the dictionary frame calls.
+    pub fn fileIndexUsingDictBatchWorkspace(nbuf: u32, split_totals: [*]const u64) usize {
+        return zlz4f_batch_file_index_using_dict_workspace(nbuf, split_totals);
+    }
+    pub fn fileIndexUsingDictBatch(stream: ?*anyopaque, src: ?[*]const u8, src_off: ?[*]const u64, src_len: ?[*]const u64, nbuf: u32, member: ?[*]const Member, mem_off: ?[*]const u64, split_result: ?[*]const i64, item_first: ?[*]const u64, item_off: ?[*]const u64, item_len: ?[*]const u64, leg_len: ?[*]const u64, split_totals: [*]const u64, index: ?[*]IndexEntry, idx_off: ?[*]u64, idx_cap: u64, idx_n: ?[*]i64, dict_len: ?[*]const u32, ndicts: u32, dict_idx: ?[*]const u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_file_index_using_dict(stream, src, src_off, src_len, nbuf, member, mem_off, split_result, item_first, item_off, item_len, leg_len, split_totals, index, idx_off, idx_cap, idx_n, dict_len, ndicts, dict_idx, workspace, workspace_bytes));
+    }
+    pub fn decompressFileRangeUsingDictBatchWorkspace(nranges: u32, max_items: u32) usize {
+        return zlz4f_batch_decompress_file_range_using_dict_workspace(nranges, max_items);
+    }
+    pub fn decompressFileRangeUsingDictBatch(stream: ?*anyopaque, src: [*]const u8, src_off: [*]const u64, src_len: [*]const u64, index: [*]const IndexEntry, idx_off: [*]const u64, idx_n: [*]const i64, nbuf: u32, member: [*]const Member, mem_off: [*]const u64, split_result: [*]const i64, ranges: [*]const Range, dst: [*]u8, dst_off: [*]const u64, dst_cap: [*]const u64, skip: [*]u64, result: [*]i64, nranges: u32, max_items: u32, dict: ?[*]const u8, dict_off: ?[*]const u64, dict_len: ?[*]const u32, ndicts: u32, dict_idx: ?[*]const u32, workspace: ?*anyopaque, workspace_bytes: usize) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_decompress_file_range_using_dict(stream, src, src_off, src_len, index, idx_off, idx_n, nbuf, member, mem_off, split_result, ranges, dst, dst_off, dst_cap, skip, result, nranges, max_items, dict, dict_off, dict_len, ndicts, dict_idx, workspace, workspace_bytes));
+    }
+    pub fn multiframeItemDictsBatch(stream: ?*anyopaque, item_first: ?[*]const u64, nbuf: u32, nitems: u32, dict_idx: ?[*]const u32, item_dict_idx: ?[*]u32) (Error || root.Error)!void {
+        return mapBatch(zlz4f_batch_multiframe_item_dicts(stream, item_first, nbuf, nitems, dict_idx, item_dict_idx));
+    }
+    /// decompressFileRangeEx for a file that was written against `dict` (only its last 64 KiB are staged)
+    pub fn decompressFileRangeUsingDict(src: []const u8, a: u64, b: u64, dst: []u8, range_flags: u32, dict: []const u8) Error!usize {
+        return mapFrame(zlz4f_decompress_file_range_using_dict(src.ptr, src.len, a, b, dst.ptr, dst.len, SPLIT_LEGACY, range_flags, dict.ptr, dict.len));
     }
     /// No counterpart in the reference: legacy frames, what `lz4 -l` writes and the Linux kernel's unlz4 reads -- the magic
     /// 0x184C2102, then { u32 size, block } repeated (include/zlz4_amd.h).  One frame in host memory per call; `consumed`
