@@ -15,6 +15,8 @@ the reference on its edge, and comes with a twin on the other side of it:
                (src/lz4hc.zig:571)
 * pos0         position 0 is never a match source (src/lz4hc.zig:571, `mi > 0`; src/lz4.zig: the empty table entry)
 
+Level 2 (lz4mid) runs through these blocks too, but its own decisions live in tests/midgen.py.
+
 `meta` names what the case is about: "probe" (lo, hi) is the region of the block where the decision shows, "twin" the
 name of the case on the other side of the edge, "accept" which side this one is on by construction (the CPU test
 witnesses it on the oracle, setting by setting), and the family's own parameters.  `rnd()` has no zero byte, so a zero
