@@ -10,7 +10,7 @@ HIPSRC  := $(CSRC)/zlz4_capi.hip $(CSRC)/zlz4_frame.hip $(CSRC)/zlz4_decompress.
            $(CSRC)/zlz4_dest_size.hip $(CSRC)/zlz4_stream_decode.hip $(CSRC)/zlz4_sizes.hip \
            $(CSRC)/zlz4_compress_dict.hip $(CSRC)/zlz4_compress_hc_dict.hip $(CSRC)/zlz4_frame_linked.hip \
            $(CSRC)/zlz4_frame_multi.hip $(CSRC)/zlz4_frame_legacy.hip $(CSRC)/zlz4_frame_seek.hip \
-           $(CSRC)/zlz4_host.hip
+           $(CSRC)/zlz4_train_dict.hip $(CSRC)/zlz4_host.hip
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude
 
 all: $(LIB) $(TUNELIB) oracle

@@ -462,6 +462,63 @@ int32_t zlz4_batch_compress_hc_using_dict(void *stream,
                                           int64_t *d_result, uint32_t nblocks, uint32_t max_in_len, uint32_t max_dict_len,
                                           int32_t compression_level, void *d_workspace, size_t workspace_bytes);
 
+/* Dictionary training (no counterpart in the reference, which takes dictionaries and makes none).
+ * A fastCover-style selection in integers only, so that the device and the model (tools/pyref/zig_lz4_train_dict.py)
+ * agree byte for byte.  One GROUP is a run of samples and yields one dictionary; the result is a raw lz4 dictionary (bytes
+ * to put in front of a record, no header), ready for every *_using_dict call.
+ *   - Parameters, for the whole call: d in {4, 6, 8} the d-mer length, k in 16..1024 with k >= d the segment length, f in
+ *     10..24 the log2 of the frequency table; m = k - d + 1.  `reserved` is not read.
+ *   - Per group a capacity C <= 65536 (lz4 never looks further back than 64 KiB).
+ *   - Buffer: B = the group's samples back to back in order, S bytes, S <= 2^27; d-mers may span sample boundaries.
+ *     nd = S - d + 1.  nd <= 0 or C == 0: the result is 0, nothing is written.
+ *   - Hash: v = the d bytes at p as a little-endian integer; h(p) = ((v << (64 - 8d)) * 0xCF1BBCDCB7A56463 mod 2^64)
+ *     >> (64 - f).
+ *   - Frequencies: freq[x] = the number of p in [0, nd) with h(p) == x.
+ *   - Epochs: nseg = ceil(C / k); E = max(1, min(nseg, nd / (8k))) (integer division); size = nd / E; epoch e is
+ *     [e * size, (e + 1) * size), the last epoch ends at nd.
+ *   - Steps: at most T = 2 * nseg.  tail = C, ep = 0, zero = 0.  A step
+ *       1. takes epoch ep as [b, e);
+ *       2. for every window start s in [b, e): score(s) = the sum of freq[h(p)] over p in [s, min(s + m, e)), where each
+ *          distinct hash value counts once per window (its first occurrence in the window counts, the rest do not);
+ *       3. the winner is the largest score, the lowest s on a tie;
+ *       4. ep = (ep + 1) % E;
+ *       5. score 0: zero += 1, stop when zero == E;
+ *       6. otherwise zero = 0; seg = min(k, tail, S - s); tail -= seg; out[tail .. tail + seg) = B[s .. s + seg);
+ *          freq[h(p)] = 0 for p in [s, min(s + m, e)); stop when tail == 0.
+ *   - Result: L = C - tail; the dictionary is out[tail .. C), moved to the front of the group's slot (bytes [L, C) of the
+ *     slot are not written).  The first segment picked stands last, nearest to the record.
+ *
+ * zlz4_batch_train_dict: sample i is d_src + d_src_off[i], d_src_len[i] bytes; group g is samples d_group_first[g] ..
+ * d_group_first[g + 1] - 1 (ngroups + 1 entries, non-decreasing, the last at most nsamples); its dictionary goes to d_dict
+ * + d_dict_off[g] (d_dict_cap[g] = C bytes) and d_result[g] = L.  A group with C > min(max_dict_cap, 65536), S > 2^27, a
+ * run of samples that is none, or more bytes than the workspace was sized for gets InvalidState and writes nothing; the
+ * other groups are unaffected.  max_dict_cap fixes the number of step launches (2 * ceil(min(max_dict_cap, 65536) / k)
+ * pairs of score and commit; a group that is done returns at once).  The workspace:
+ * zlz4_batch_train_dict_workspace(ngroups, total bytes of all samples, max_dict_cap, params) bytes, 16-byte aligned (per
+ * group a state record, an output buffer and a table of 2^f counters; per sample byte the byte, its hash and its reach
+ * distance: 7 bytes); the function returns 0 for parameters the call refuses.  ngroups == 0 returns 0 and reads nothing.
+ * A bad d, k or f, params == NULL, ngroups > 65535, null arrays (d_src, d_src_off and d_src_len may be NULL when nsamples
+ * == 0, d_dict when max_dict_cap == 0), a misaligned array (8 bytes for the 64-bit arrays, 4 for the 32-bit ones), a
+ * workspace that is null, misaligned or smaller than the one for no sample bytes return InvalidState and launch nothing.
+ * Asynchronous, no allocation, no read-back: samples in device memory in, dictionaries out. */
+typedef struct zlz4_train_params { uint32_t d, k, f, reserved; } zlz4_train_params;
+size_t  zlz4_batch_train_dict_workspace(uint32_t ngroups, uint64_t total_sample_bytes, uint32_t max_dict_cap,
+                                        const zlz4_train_params *params);
+int32_t zlz4_batch_train_dict(void *stream,
+                              const uint8_t *d_src, const uint64_t *d_src_off, const uint32_t *d_src_len, uint32_t nsamples,
+                              const uint32_t *d_group_first, uint32_t ngroups,
+                              uint8_t *d_dict, const uint64_t *d_dict_off, const uint32_t *d_dict_cap, int64_t *d_result,
+                              uint32_t max_dict_cap, const zlz4_train_params *params,
+                              void *d_workspace, size_t workspace_bytes);
+
+/* One dictionary from samples in host memory, as ZDICT_trainFromBuffer takes them: the samples lie back to back in
+ * `samples`, sample i has sample_sizes[i] bytes.  Returns L (the dictionary is dict[0 .. L)) or a code.  Decided on the
+ * host, in this order: a bad d, k or f, params == NULL, sample_sizes == NULL with nsamples > 0, dict == NULL with dict_cap >
+ * 0, dict_cap > 65536, more than 2^27 sample bytes, samples == NULL with sample bytes -> InvalidState; fewer than d sample
+ * bytes or dict_cap == 0 -> 0.  Otherwise the samples are staged and zlz4_batch_train_dict runs with one group. */
+int64_t zlz4_train_dict(const uint8_t *samples, const size_t *sample_sizes, uint32_t nsamples, uint8_t *dict, size_t dict_cap,
+                        const zlz4_train_params *params);
+
 /* lz4.compressDestSize (src/lz4.zig:551-616) per block: d_in_len[i] is *srcSizePtr on entry and d_out_cap[i] is dst.len.
  * d_result[i] and d_consumed[i] receive what zlz4_compress_dest_size returns and leaves in *src_size; bytes [0, result)
  * of the output slot hold compressDefault of the consumed prefix (the best probe, as in the single call), bytes

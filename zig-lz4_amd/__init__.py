@@ -50,6 +50,12 @@ class Prefs(C.Structure):
     ]
 
 
+class TrainParams(C.Structure):
+    """zlz4_train_params: d-mer length d in {4, 6, 8}, segment length k in 16..1024, log2 f of the frequency table in
+    10..24."""
+    _fields_ = [("d", C.c_uint32), ("k", C.c_uint32), ("f", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class LegacyPrefs(C.Structure):
     """zlz4f_legacy_prefs: block_size 0 = 8 MiB (what `lz4 -l` writes), 1 .. 8 MiB as given; compression_level <= 0 = fast,
     else compressHC's level."""
@@ -100,6 +106,9 @@ SYMBOLS = {
     "zlz4_compress_hc_using_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, _I32]),
     "zlz4_batch_compress_hc_using_dict_workspace": (_SZ, [_U32, _U32, _U32]),
     "zlz4_batch_compress_hc_using_dict": (_I32, [_VP] * 11 + [_U32, _U32, _U32, _I32, _VP, _SZ]),
+    "zlz4_batch_train_dict_workspace": (_SZ, [_U32, C.c_uint64, _U32, _VP]),
+    "zlz4_batch_train_dict": (_I32, [_VP] * 4 + [_U32, _VP, _U32] + [_VP] * 4 + [_U32, _VP, _VP, _SZ]),
+    "zlz4_train_dict": (_I64, [_VP, _VP, _U32, _VP, _SZ, _VP]),
     "zlz4_batch_compress_hc": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _I32, _VP, _SZ]),
     "zlz4_batch_compress_dest_size_workspace": (_SZ, [_U32, _U32]),
     "zlz4_batch_compress_dest_size": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _SZ]),
@@ -348,6 +357,21 @@ def compressHCUsingDict(src, dict, compression_level, dst_cap=None):
     dk, dn = _in(dict)
     return _run(lambda sp, n, dp, c: lib().zlz4_compress_hc_using_dict(sp, n, dp, c, C.addressof(dk), dn, compression_level),
                 src, cap)
+
+
+def trainDict(samples, dict_size=65536, d=8, k=256, f=20):
+    """zlz4_train_dict (no counterpart in the reference): one dictionary of at most dict_size (<= 65536) bytes from the
+    byte strings of `samples`, by the fastCover-style selection of include/zlz4_amd.h; a host call that stages the samples.
+    The result goes straight into compressFastUsingDict / compressHCUsingDict and the batch and frame calls with a
+    dictionary.  Too few sample bytes give b""; bad parameters raise InvalidState."""
+    items = [bytes(s) for s in samples]
+    s, _ = _in(b"".join(items))
+    sizes = (C.c_size_t * max(1, len(items)))(*[len(b) for b in items])
+    out = (C.c_uint8 * max(1, dict_size))()
+    p = TrainParams(d, k, f, 0)
+    r = _check(lib().zlz4_train_dict(C.addressof(s), C.addressof(sizes), len(items), C.addressof(out), dict_size,
+                                     C.addressof(p)))
+    return bytes(out[:r])
 
 
 def decompressedSize(src, dict_len=0):
@@ -2191,6 +2215,57 @@ def compressBlocksHCUsingDict(blocks, dicts, dict_index=None, level=9, device="c
                                  dict_off[sel].contiguous(), dict_len[sel].to(torch.int32).contiguous(), result, max_in,
                                  max_dict, level, ws)
     return _unstage(d_dst, _offsets(caps), result)
+
+
+def batch_train_dict_workspace(ngroups, total_sample_bytes, max_dict_cap, d=8, k=256, f=20):
+    """zlz4_batch_train_dict_workspace: bytes of workspace for ngroups groups with total_sample_bytes of samples in all;
+    0 for parameters the call refuses."""
+    p = TrainParams(d, k, f, 0)
+    return lib().zlz4_batch_train_dict_workspace(ngroups, total_sample_bytes, max_dict_cap, C.addressof(p))
+
+
+def batch_train_dict(d_src, src_off, src_len, group_first, d_dict, dict_off, dict_cap, result, max_dict_cap, workspace,
+                     d=8, k=256, f=20):
+    """zlz4_batch_train_dict on torch CUDA tensors: sample i is d_src[src_off[i] .. + src_len[i]) (int64 offsets / int32
+    lengths), group g is samples group_first[g] .. group_first[g + 1] - 1 (int32, result.numel() + 1 entries); its dictionary
+    goes to d_dict[dict_off[g] .. + dict_cap[g]) (int64 / int32) and result[g] (int64) = its length or InvalidState.
+    `workspace` is a uint8 tensor of at least batch_train_dict_workspace(...) bytes.  Asynchronous on the current stream."""
+    p = TrainParams(d, k, f, 0)
+    _check(lib().zlz4_batch_train_dict(_stream(), _ptr(d_src), _ptr(src_off), _ptr(src_len), src_len.numel(),
+                                       _ptr(group_first), result.numel(), _ptr(d_dict), _ptr(dict_off), _ptr(dict_cap),
+                                       _ptr(result), max_dict_cap, C.addressof(p), _ptr(workspace), workspace.numel()))
+
+
+def trainDicts(groups, dict_size=65536, d=8, k=256, f=20, device="cuda"):
+    """One dictionary per group of samples in one batch: groups[g] is a list of byte strings, dict_size one capacity for
+    all or one per group.  Packs the samples, trains every group in the same launches (batch_train_dict) and reads the
+    dictionaries back once.  -> list of dictionaries (bytes) or error codes, ready for compressBlocksUsingDict,
+    compressBlocksHCUsingDict, lz4f.compressFramesUsingDict and lz4f.compressFiles(..., dicts=)."""
+    import torch
+    ng = len(groups)
+    if ng == 0:
+        return []
+    caps = [int(dict_size)] * ng if isinstance(dict_size, int) else [int(c) for c in dict_size]
+    if len(caps) != ng or any(c < 0 or c > 0xFFFFFFFF for c in caps):
+        raise ValueError("dict_size: one capacity, or one per group, each in [0, 0xFFFFFFFF]")
+    samples = [bytes(s) for grp in groups for s in grp]
+    first = _offsets([len(grp) for grp in groups]) + [len(samples)]
+    d_src, src_off, src_len = _stage(samples, device)
+    slots = [min(c, 65536) for c in caps]             # (a capacity above 65536 is refused: its slot is never written)
+    offs = _offsets(slots)
+    d_dict = torch.empty(max(1, sum(slots)), dtype=torch.uint8, device=device)
+    dict_off = torch.tensor(offs, dtype=torch.int64, device=device)
+    dict_cap = torch.tensor([c - (1 << 32) if c >= (1 << 31) else c for c in caps], dtype=torch.int32, device=device)
+    group_first = torch.tensor(first, dtype=torch.int32, device=device)
+    result = torch.empty(ng, dtype=torch.int64, device=device)
+    max_cap = max(slots)
+    ws_bytes = batch_train_dict_workspace(ng, sum(len(s) for s in samples), max_cap, d, k, f)
+    if ws_bytes == 0:
+        raise Lz4Error(-5, error_name(-5))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    batch_train_dict(d_src, src_off, src_len.to(torch.int32), group_first, d_dict, dict_off, dict_cap, result, max_cap, ws,
+                     d, k, f)
+    return _unstage(d_dict, offs, result)
 
 
 def batch_compress_dest_size_workspace(nblocks, max_in_len):

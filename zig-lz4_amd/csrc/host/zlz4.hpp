@@ -146,6 +146,14 @@ inline Result compressHCUsingDict(const std::uint8_t *src, std::size_t n, std::u
     return wrap(zlz4_compress_hc_using_dict(src, n, dst, cap, dict, dict_len, level));
 }
 
+// Dictionary training (no counterpart in the reference): one dictionary of at most dict_cap (<= 65536) bytes from samples
+// that lie back to back, sample i having sample_sizes[i] bytes (include/zlz4_amd.h, zlz4_train_dict)
+using TrainParams = zlz4_train_params;
+inline Result trainDict(const std::uint8_t *samples, const std::size_t *sample_sizes, std::uint32_t nsamples, std::uint8_t *dict,
+                        std::size_t dict_cap, const TrainParams &params = TrainParams{8, 256, 20, 0}) {
+    return wrap(zlz4_train_dict(samples, sample_sizes, nsamples, dict, dict_cap, &params));
+}
+
 // lz4hc.sizeofStateHC / compressHCExtState, src/lz4hc.zig:1457-1494 (fresh context, passed as the bytes it occupies)
 inline std::size_t sizeofStateHC() { return zlz4_sizeof_state_hc(); }
 inline Result compressHCExtState(void *ctx, std::size_t ctx_len, const std::uint8_t *src, std::size_t n, std::uint8_t *dst,
@@ -245,6 +253,29 @@ inline Result compressHCUsingDictBatch(void *stream, const Blocks &b, const Dict
     return wrap(zlz4_batch_compress_hc_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict,
                                                   d.dict_off, d.dict_len, b.result, b.nblocks, max_in_len, max_dict_len, level,
                                                   ws, ws_bytes));
+}
+// one dictionary per group of samples: the arrays of zlz4_batch_train_dict
+struct TrainGroups {
+    const std::uint8_t *src;           // sample arena
+    const std::uint64_t *src_off;      // per sample: offset into `src`
+    const std::uint32_t *src_len;      // per sample: bytes
+    std::uint32_t nsamples;
+    const std::uint32_t *group_first;  // ngroups + 1: group g is samples group_first[g] .. group_first[g + 1] - 1
+    std::uint32_t ngroups;
+    std::uint8_t *dict;                // dictionary arena
+    const std::uint64_t *dict_off;     // per group: offset of its slot
+    const std::uint32_t *dict_cap;     // per group: capacity (<= 65536)
+    std::int64_t *result;              // per group: the dictionary's length or an error code
+};
+inline std::size_t trainDictWorkspace(std::uint32_t ngroups, std::uint64_t total_sample_bytes, std::uint32_t max_dict_cap,
+                                      const TrainParams &params) {
+    return zlz4_batch_train_dict_workspace(ngroups, total_sample_bytes, max_dict_cap, &params);
+}
+// trainDict per group; ws = device memory of trainDictWorkspace() bytes
+inline Result trainDictBatch(void *stream, const TrainGroups &g, std::uint32_t max_dict_cap, const TrainParams &params, void *ws,
+                             std::size_t ws_bytes) {
+    return wrap(zlz4_batch_train_dict(stream, g.src, g.src_off, g.src_len, g.nsamples, g.group_first, g.ngroups, g.dict,
+                                      g.dict_off, g.dict_cap, g.result, max_dict_cap, &params, ws, ws_bytes));
 }
 inline std::size_t compressDestSizeWorkspace(std::uint32_t nblocks, std::uint32_t max_in_len) {
     return zlz4_batch_compress_dest_size_workspace(nblocks, max_in_len);

@@ -45,6 +45,10 @@ extern "c" fn zlz4_batch_compress_hc_workspace(nblocks: u32, max_in_len: u32) us
 extern "c" fn zlz4_compress_hc_using_dict(src: [*]const u8, src_len: usize, dst: [*]u8, dst_cap: usize, dict: ?[*]const u8, dict_len: usize, level: i32) i64;
 extern "c" fn zlz4_batch_compress_hc_using_dict_workspace(nblocks: u32, max_in_len: u32, max_dict_len: u32) usize;
 extern "c" fn zlz4_batch_compress_hc_using_dict(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_dict: ?[*]const u8, d_dict_off: [*]const u64, d_dict_len: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, max_dict_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
+pub const TrainParams = extern struct { d: u32 = 8, k: u32 = 256, f: u32 = 20, reserved: u32 = 0 };
+extern "c" fn zlz4_train_dict(samples: ?[*]const u8, sample_sizes: ?[*]const usize, nsamples: u32, dict: ?[*]u8, dict_cap: usize, params: ?*const TrainParams) i64;
+extern "c" fn zlz4_batch_train_dict_workspace(ngroups: u32, total_sample_bytes: u64, max_dict_cap: u32, params: ?*const TrainParams) usize;
+extern "c" fn zlz4_batch_train_dict(stream: ?*anyopaque, d_src: ?[*]const u8, d_src_off: ?[*]const u64, d_src_len: ?[*]const u32, nsamples: u32, d_group_first: [*]const u32, ngroups: u32, d_dict: ?[*]u8, d_dict_off: [*]const u64, d_dict_cap: [*]const u32, d_result: [*]i64, max_dict_cap: u32, params: ?*const TrainParams, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_compress_hc(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, nblocks: u32, max_in_len: u32, level: i32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
 extern "c" fn zlz4_batch_compress_dest_size_workspace(nblocks: u32, max_in_len: u32) usize;
 extern "c" fn zlz4_batch_compress_dest_size(stream: ?*anyopaque, d_in: [*]const u8, d_in_off: [*]const u64, d_in_len: [*]const u32, d_out: [*]u8, d_out_off: [*]const u64, d_out_cap: [*]const u32, d_result: [*]i64, d_consumed: [*]u32, nblocks: u32, max_in_len: u32, d_workspace: ?*anyopaque, workspace_bytes: usize) i32;
@@ -249,6 +253,12 @@ pub fn compressDestSize(src: []const u8, dst: []u8, srcSizePtr: *usize) Error!us
 /// decompressSafeUsingDict(dst[0..n], out, dict).
 pub fn compressHCUsingDict(src: []const u8, dst: []u8, dict: []const u8, compressionLevel: i32) Error!usize {
     return mapBlock(zlz4_compress_hc_using_dict(src.ptr, src.len, dst.ptr, dst.len, dict.ptr, dict.len, compressionLevel));
+}
+/// Dictionary training (no counterpart in the reference): one dictionary of at most dict.len (<= 65536) bytes from samples
+/// that lie back to back in `samples`, sample i having sampleSizes[i] bytes; the fastCover-style selection specified in
+/// include/zlz4_amd.h.  Returns the dictionary's length; dict[0..len] goes into every ...UsingDict call.
+pub fn trainDict(samples: []const u8, sampleSizes: []const usize, dict: []u8, params: TrainParams) Error!usize {
+    return mapBlock(zlz4_train_dict(samples.ptr, sampleSizes.ptr, @intCast(sampleSizes.len), dict.ptr, dict.len, &params));
 }
 pub fn compressHC(src: []const u8, dst: []u8, compressionLevel: i32) Error!usize {
     return mapBlock(zlz4_compress_hc(src.ptr, src.len, dst.ptr, dst.len, compressionLevel));
@@ -464,6 +474,8 @@ pub const lz4hc = struct {
     pub const compressHC = root.compressHC;
     pub const compressHCExtState = root.compressHCExtState;
     pub const compressHCUsingDict = root.compressHCUsingDict;
+    pub const trainDict = root.trainDict;
+    pub const TrainParams = root.TrainParams;
     pub const sizeofStateHC = root.sizeofStateHC;
 };
 
@@ -555,6 +567,27 @@ pub const device = struct {
     /// compressHCUsingDictWorkspace() bytes, 16-byte aligned
     pub fn compressHCUsingDictBatch(stream: ?*anyopaque, b: Blocks, d: DictBlocks, max_in_len: u32, max_dict_len: u32, level: i32, workspace: ?*anyopaque, workspace_bytes: usize) Error!void {
         return mapLaunch(zlz4_batch_compress_hc_using_dict(stream, b.in, b.in_off, b.in_len, b.out, b.out_off, b.out_cap, d.dict, d.dict_off, d.dict_len, b.result, b.nblocks, max_in_len, max_dict_len, level, workspace, workspace_bytes));
+    }
+    /// one dictionary per group of samples (include/zlz4_amd.h, zlz4_batch_train_dict)
+    pub const TrainGroups = struct {
+        src: ?[*]const u8, // sample arena
+        src_off: ?[*]const u64, // per sample: offset into `src`
+        src_len: ?[*]const u32, // per sample: bytes
+        nsamples: u32,
+        group_first: [*]const u32, // ngroups + 1: group g is samples group_first[g] .. group_first[g + 1] - 1
+        ngroups: u32,
+        dict: ?[*]u8, // dictionary arena
+        dict_off: [*]const u64, // per group: offset of its slot
+        dict_cap: [*]const u32, // per group: capacity (<= 65536)
+        result: [*]i64, // per group: the dictionary's length or an error code
+    };
+    pub fn trainDictWorkspace(ngroups: u32, total_sample_bytes: u64, max_dict_cap: u32, params: TrainParams) usize {
+        return zlz4_batch_train_dict_workspace(ngroups, total_sample_bytes, max_dict_cap, &params);
+    }
+    /// batch form of trainDict: every group in the same launches; `workspace` = device memory of trainDictWorkspace()
+    /// bytes, 16-byte aligned
+    pub fn trainDictBatch(stream: ?*anyopaque, g: TrainGroups, max_dict_cap: u32, params: TrainParams, workspace: ?*anyopaque, workspace_bytes: usize) Error!void {
+        return mapLaunch(zlz4_batch_train_dict(stream, g.src, g.src_off, g.src_len, g.nsamples, g.group_first, g.ngroups, g.dict, g.dict_off, g.dict_cap, g.result, max_dict_cap, &params, workspace, workspace_bytes));
     }
     pub fn compressDestSizeWorkspace(nblocks: u32, max_in_len: u32) usize {
         return zlz4_batch_compress_dest_size_workspace(nblocks, max_in_len);
